@@ -8,13 +8,21 @@ round-robin over `--engines` executor engines per GPU (the reference's gpu_threa
 with its own HIP stream(s).
 
 ONE JSON line of at most 4 KB on rank 0 (kzero_amd/benchline.py: fixed key set; round 5's 27 KB line was not parsed by the
-driver) and the full record of everything measured in bench_full.json beside it (tools/show_bench.py prints it):
+driver) and the full record of everything measured in bench_full.json beside it (tools/show_bench.py prints it).
+
+A plain run (`--gpus 1 --steps K --warmup W`) does what `value` needs and nothing else: set-up, a quarter of a second of
+conditioning (`--prewarm`), W warm-up steps, ONE timed region of exactly K steps, the line.  `--full` adds everything
+below past `value` and `ms_per_step`: 7 timed regions (`--repeats`), HIP events around the launches and the roofline, the
+secondary timed regions, the sub-records, the seam, the CPU baseline and the finiteness checks of the outputs.
+`--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32): `values` [B, 5] and
+`move_probs` (every board's legal-move probabilities, in board order) on the decoded boundary, `scalars` and `policy` on
+the device-resident one.  The networks and boards are seeded, so the same arguments give the same inputs in every run.
   * `value`: the K timed steps THROUGH THE BOUNDARY A CALLER HAS — host boards + move lists in, decoded values + legal-move
     probabilities out (kz_engine_submit_packed_decoded -> kz_engine_wait_decoded: what kzero_amd/rust/hip.rs runs by
     default, replacing cudnn.rs:55-87 + common.rs:16-100), H2D of 284 B and D2H of 160 B per chess evaluation inside the
-    timed region.  The K-step region is timed `--repeats` times (default 7), each bracketed by barrier + device sync on both
-    sides; `value` is the MEDIAN region, `value_min` / `value_max` the slowest and fastest, `ms_per_step` x `steps` = the
-    median region;
+    timed region.  The K-step region is timed `--repeats` times (default 1, with --full 7), each bracketed by barrier +
+    device sync on both sides; `value` is the MEDIAN region, `value_min` / `value_max` the slowest and fastest,
+    `ms_per_step` x `steps` = the median region;
   * `value_device_resident`: the same K steps with the packed boards already in HBM and the raw outputs left in HBM — what
     `value` was in rounds 1-5 (1.00-1.015 x `value`; no caller of the Network trait can obtain it); `--boundary resident` makes
     it `value` for kernel A/B runs.  `value_host_boundary_raw`: host boards in, the raw 7.5 KB of policy rows out;
@@ -137,8 +145,16 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=None,
                     help="timed steps per region; default: about 1 s of the workload (chess 2000, ataxx 10000, go 400)")
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=7,
-                    help="timed regions of --steps steps each (every one bracketed by barrier + sync); value = the median region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: 7 timed regions, kernel timing and roofline, "
+                         "the device-resident and raw host-boundary regions, the other BASELINE configs, the seam, the CPU "
+                         "baseline, the output checks.  Without it a run times --steps steps once and prints the headline")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each (every one bracketed by barrier + sync); value = the median "
+                         "region; default: 1, with --full 7")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32; at most 64 MB, "
+                         "a fixed sample of rows beyond that)")
     ap.add_argument("--batch", type=int, default=None,
                     help="executor batch (gpu_batch_size); default: BASELINE.json's for the workload (256; Go 512)")
     ap.add_argument("--engines", type=int, default=None,
@@ -173,6 +189,8 @@ def parse_args(argv=None):
         args.batch = wl["batch"]
     if args.engines is None:
         args.engines = wl["engines"][args.dtype]
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
     args.is_default_line = args.workload == "chess-20x256" and args.dtype == "f16" and args.batch == 256
     return args
 
@@ -299,6 +317,24 @@ def committed_traffic(kernel: str, workload: str, batch: int):
     return None, None
 
 
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT):
+    """--dump-outputs: every array as out_dir/<name>.npy, float32 (float64 stays float64).  Should they hold more than
+    `limit` bytes together, each array keeps a fixed, seeded sample of its rows (leading axis), in order, that brings the
+    total under the limit."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > limit and a.ndim and len(a):
+            keep = max(1, len(a) * limit // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class Workload:
     """One (network, dtype, batch) on one device: engines, resident inputs, the two kinds of step."""
 
@@ -323,6 +359,7 @@ class Workload:
         self.stride = self.bits.shape[1]
         self.inflight = {}
         self.inflight_dec = set()
+        self.views = {}
         self.moves = None
         self.tower_path = self.engines[0].tower_path
         self.kernel = KERNEL_OF_PATH[self.tower_path]
@@ -361,15 +398,38 @@ class Workload:
         self.inflight_dec.add((e, slot))
 
     def sync(self):
+        # (the views of the last batch of every slot are kept: last_outputs() reads the timed path's final results from them)
         for (e, slot), n in list(self.inflight.items()):
-            self.host_engines[e].wait_view(slot, n)
+            self.views[(e, slot)] = self.host_engines[e].wait_view(slot, n)
         self.inflight.clear()
         for (e, slot) in list(self.inflight_dec):
-            self.host_engines[e].wait_decoded_view(slot)
+            self.views[(e, slot)] = self.host_engines[e].wait_decoded_view(slot)
         self.inflight_dec.clear()
         for e in self.engines:
             e.synchronize()
         self.capi.check(self.capi.load().kz_device_synchronize(self.device))
+
+    def last_outputs(self, step, steps):
+        """What a caller of `step` received from the last of `steps` timed steps (step index steps - 1), copied to host
+        float32 arrays, read after the closing sync: the decoded values [B, 5] and the legal-move probabilities of all
+        boards in board order (`move_probs`, the concatenation of the per-board lists) on the decoded boundary; the raw
+        scalars [B, 5] and policy rows [B, policy_len] on the raw host boundary and on the device-resident step."""
+        np, B, plen = self.np, self.B, self.info.policy_len
+        i = steps - 1
+        if step == self.step_resident:
+            e = i % len(self.engines)
+            return {"scalars": self.outs[e][0].to_host(np.float32, (B, 5)),
+                    "policy": self.outs[e][1].to_host(np.float32, (B, plen))}
+        n, S = len(self.host_engines), self.capi.KZ_ENGINE_SLOTS
+        view = self.views[(i % n, (i // n) % S)]
+        if step == self.step_host:
+            return {"scalars": np.array(view[0], np.float32), "policy": np.array(view[1], np.float32)}
+        import ctypes
+        fp = ctypes.POINTER(ctypes.c_float)
+        total = int(self.moves[0][-1])
+        return {"values": np.ctypeslib.as_array(ctypes.cast(view[0], fp), shape=(B, 5)).copy(),
+                "move_probs": np.ctypeslib.as_array(ctypes.cast(view[1], fp), shape=(total,)).copy() if total else
+                np.zeros(0, np.float32)}
 
     def profiling(self, on):
         if on and os.environ.get("KZ_BENCH_NO_KERNEL_TIMING") == "1":
@@ -772,12 +832,15 @@ def main():
     w = Workload(capi, synth, args.workload, args.dtype, args.batch, args.engines, device, benchlib.board_seed(rank))
     B = args.batch
 
-    def timed(step, own, profile=True, prewarm=args.prewarm):
-        """`--repeats` regions of K steps of `step`, each bracketed by barrier + device sync; with `profile`, HIP events
-        around every launch of the timed steps (per-layer paths: an instrumented pass of the same steps behind them)."""
+    def timed(step, own, profile=args.full, prewarm=args.prewarm, outputs=None):
+        """`--repeats` regions of K steps of `step`, each bracketed by barrier + device sync; with `profile` (--full), HIP
+        events around every launch of the timed steps (per-layer paths: an instrumented pass of the same steps behind them);
+        `outputs` (a dict) receives what the last timed step returned, read before anything else runs."""
         w.condition(step, prewarm)
         regs = benchlib.run_timed_regions(step, w.sync, args.steps, args.warmup, args.repeats, dist,
                                           on_timed_start=(lambda: w.profiling(True)) if profile and not w.per_layer else None, owns=own)
+        if outputs is not None:
+            outputs.update(w.last_outputs(step, args.steps))
         k = (0.0, 0)
         if profile:
             if w.per_layer:
@@ -795,25 +858,29 @@ def main():
     # by default, replacing cudnn.rs:55-87 + common.rs:16-100); H2D and D2H inside the timed region ----
     own, r_own, h_own = [], [], []
     decoded = args.boundary == "decoded"
-    main = timed(w.step_host_decoded if decoded else w.step_resident, own)
-    if decoded:
-        w.check_finite_decoded()
-    else:
-        w.check_finite()
+    outputs = {} if args.dump_outputs else None
+    main = timed(w.step_host_decoded if decoded else w.step_resident, own, outputs=outputs)
+    if outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
+    if args.full:
+        if decoded:
+            w.check_finite_decoded()
+        else:
+            w.check_finite()
     regions, elapsed, value, region_values, k_ms, k_n = (main[k] for k in ("regions", "elapsed", "value", "values", "k_ms", "k_n"))
     info = w.info
     peak = 157.3 if args.dtype == "f32" else 2500.0
 
     # ---- timed regions 2 (`value_device_resident`): packed boards already in HBM, raw outputs left in HBM ----
     res = main
-    if decoded and not args.no_host_io:
+    if args.full and decoded and not args.no_host_io:
         res = timed(w.step_resident, r_own, prewarm=min(args.prewarm, 0.1))
         w.check_finite()
 
     # ---- timed regions 3 (`value_host_boundary_raw`): host boards in, the raw (scalars, policy) rows out
     # (kz_engine_submit_packed -> kz_engine_wait_view: the reference's evaluate_batch alone, 7.5 KB D2H per chess eval) ----
     host = None
-    if decoded and not args.no_host_io:
+    if args.full and decoded and not args.no_host_io:
         raw = timed(w.step_host, h_own, prewarm=min(args.prewarm, 0.1))
         host = {"value": round(raw["value"], 1), "value_min": round(min(raw["values"]), 1), "value_max": round(max(raw["values"]), 1),
                 "unit": "evals/s", "steps": args.steps, "regions": len(raw["regions"]),
@@ -837,7 +904,7 @@ def main():
         "rank": rank, "device": device, "bus_id": devices_seen[rank], "numa_node": numa["numa_node"],
         "numa_bound": numa["bound"], "numa_bound_before_first_hip_call": numa.get("bound_before_first_hip_call", False),
         "host_cpus": numa["cpus"], "evals_s": round(args.steps * B / benchlib.median_region(own), 1),
-        "avg_launch_ms": round(k_ms / max(k_n, 1), 5),
+        "avg_launch_ms": round(k_ms / max(k_n, 1), 5) if args.full else None,
         "device_resident_evals_s": round(args.steps * B / benchlib.median_region(r_own), 1) if r_own else None})
     if rank != 0:
         w.close()
@@ -849,9 +916,10 @@ def main():
     wl = WORKLOADS[args.workload]
     metric = ("self-play NN evals/sec (node), Chess 20x256 ResNet b=256, 1/2/4/8 GPU" if args.is_default_line else
               f"self-play NN evals/sec (node), {wl['label'].rsplit(' b=', 1)[0]} b={B}, {world} GPU")
-    roof = w.roofline(k_ms, k_n, min(args.steps, 50) if w.per_layer else args.steps * len(regions), value / world,
-                      concurrent=None if decoded else len(w.engines))
-    roof["device_resident_frac"] = resident["chip_frac"]
+    if args.full:  # (the kernel timing behind it is only taken with --full)
+        roof = w.roofline(k_ms, k_n, min(args.steps, 50) if w.per_layer else args.steps * len(regions), value / world,
+                          concurrent=None if decoded else len(w.engines))
+        roof["device_resident_frac"] = resident["chip_frac"]
     n_moves = int(w.moves[0][-1]) / B if w.moves is not None else 0
     out = {
         "metric": metric,
@@ -863,7 +931,7 @@ def main():
         "regions": len(regions), "value_min": round(min(region_values), 1), "value_max": round(max(region_values), 1),
         "region_values": [round(v, 1) for v in region_values],
         # the same K steps with the packed boards already in HBM and the raw outputs left there (what `value` was up to round 5)
-        "value_device_resident": resident["value"] if decoded and not args.no_host_io else None,
+        "value_device_resident": resident["value"] if args.full and decoded and not args.no_host_io else None,
         # ... and through the raw host boundary (the reference's evaluate_batch alone: 7.5 KB of policy rows back per chess eval)
         "value_host_boundary_raw": host["value"] if host else None,
         "schema": "r6: value = the decoded host boundary (hip.rs's default entry points), median region; value_device_resident "
@@ -878,13 +946,14 @@ def main():
                    "legal_moves_per_board": round(n_moves, 1),
                    "h2d_bytes_per_eval": int(w.stride + 4 * info.input_scalar_channels + 8 + 4 * n_moves),
                    "d2h_bytes_per_eval": int(20 + 4 * n_moves),
-                   "device_resident_evals_s": resident["value"],
+                   "device_resident_evals_s": resident["value"] if args.full else None,
                    "host_boundary_raw_evals_s": host["value"] if host else None},
         "devices_seen": sorted(set(devices_seen)),
         "per_rank": per_rank,
-        "roofline": roof,
-        "device_resident": resident,
     }
+    if args.full:
+        out["roofline"] = roof
+        out["device_resident"] = resident
     if len(set(devices_seen)) < world:  # (only reachable with KZ_BENCH_ALLOW_SHARED_GPU=1)
         out["shared_gpu"] = True
         out["data"] = "synthetic; REHEARSAL: %d ranks share %d GPU(s) — not a scaling measurement" % (world, len(set(devices_seen)))
@@ -894,7 +963,7 @@ def main():
         out["hbm_bound_kernels"] = w.small
     blob, bits, scalars_in = w.blob, w.bits, w.scalars_in
     w.close()
-    if world == 1 and args.is_default_line and not args.no_others:
+    if args.full and world == 1 and args.is_default_line and not args.no_others:
         out["others"] = []
         for n, d in OTHERS:  # (a sub-record that fails says so in its place: it must not take the headline line with it)
             try:
@@ -917,13 +986,13 @@ def main():
             out["config"]["parity_default_dtype"] = "f32split16 (<= 1e-4 vs the oracle; hip.rs's default unless KZ_HIP_DTYPE=f16)"
             out["config"]["parity_default"] = ("KZ_DTYPE_F32_SPLIT16 (<= 1e-4 against the oracle; what the Rust binding runs unless "
                                                f"KZ_HIP_DTYPE=f16): {par[0]['value']} evals/s, frac {par[0]['roofline']['frac']}")
-    if world == 1 and args.is_default_line and not args.no_seam and not args.no_others:
+    if args.full and world == 1 and args.is_default_line and not args.no_seam and not args.no_others:
         out["seam"] = seam_record(blob, args.seam_seconds)
         # ... and at the arithmetic the Rust binding defaults to (KZ_HIP_DTYPE=parity -> split16 for this network)
         out["seam_parity"] = seam_record(blob, args.seam_seconds, dtype="f32split16", configs=SEAM_CONFIGS[:3] + SEAM_CONFIGS[4:5])
     if world > 1:
         dist.barrier()  # every rank has closed its engines
-        if args.is_default_line and not args.no_seam and not args.no_others:
+        if args.full and args.is_default_line and not args.no_seam and not args.no_others:
             # the topology the reference and the Rust drop-in use: ONE process, a thread set per device
             # (rust/kz-selfplay/src/server/server.rs:323-331) over exactly the GPUs the ranks of this run drove
             drove = [r["device"] for r in per_rank]
@@ -936,7 +1005,7 @@ def main():
             else:
                 out["seam_one_process"] = {"skipped": f"ranks see {ndev} GPU(s) each (masked visibility): rank 0 cannot drive "
                                                       f"the other ranks' devices from one process"}
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         try:
             out["cpu_baseline"] = cpu_baseline(blob, bits, scalars_in, args.cpu_seconds)
         except Exception as ex:  # noqa: BLE001 (the oracle library is test infrastructure: its absence must not cost the line)

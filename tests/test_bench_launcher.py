@@ -13,8 +13,10 @@ BENCH = os.path.join(REPO, "bench.py")
 
 
 def _clean_env():
+    # (the device masks too: the fake GPUs are whatever a test sets, not the visibility of the box the suite runs on)
     env = dict(os.environ)
-    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
+              "HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
         env.pop(k, None)
     return env
 

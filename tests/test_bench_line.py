@@ -96,7 +96,8 @@ def test_emit_writes_the_full_record_beside_the_line(tmp_path):
 
 @pytest.mark.timeout(180)
 def test_the_launchers_fake_step_line_goes_through_the_same_builder(tmp_path):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT",
+                                                            "HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
     env["KZ_BENCH_FULL_RECORD"] = str(tmp_path / "full.json")
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--repeats", "2",
                         "--fake-step", "5"], env=env, capture_output=True, text=True, timeout=170)
@@ -106,6 +107,123 @@ def test_the_launchers_fake_step_line_goes_through_the_same_builder(tmp_path):
     rec = json.loads(lines[0])
     assert rec["n_gpus"] == 2 and rec["full_record"] == "full.json" and len(rec["per_rank"]) == 2
     assert json.load(open(tmp_path / "full.json"))["value"] == rec["value"]
+
+
+def test_a_plain_run_times_steps_once_and_full_keeps_seven_regions():
+    sys.path.insert(0, REPO)
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and plain.repeats == 1 and plain.steps == 20 and plain.dump_outputs is None
+    assert bench.parse_args(["--full"]).repeats == 7
+    assert bench.parse_args(["--full", "--repeats", "3"]).repeats == 3
+
+
+def test_dump_outputs_writes_float32_and_a_fixed_sample_beyond_the_limit(tmp_path):
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    rng = np.random.default_rng(1)
+    small = {"values": rng.standard_normal((4, 5)).astype(np.float16), "move_probs": rng.random(9)}
+    bench.dump_outputs(str(tmp_path / "a"), small)
+    v = np.load(tmp_path / "a" / "values.npy")
+    assert v.dtype == np.float32 and np.array_equal(v, small["values"].astype(np.float32))
+    assert np.load(tmp_path / "a" / "move_probs.npy").dtype == np.float64
+    big = {"policy": rng.random((1000, 64), dtype=np.float32), "scalars": rng.random((1000, 5), dtype=np.float32)}
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, limit=100_000)
+    p = np.load(tmp_path / "b" / "policy.npy")
+    s = np.load(tmp_path / "b" / "scalars.npy")
+    assert p.nbytes + s.nbytes <= 100_000 and 0 < len(p) < 1000
+    assert np.array_equal(p, np.load(tmp_path / "c" / "policy.npy"))     # the same sample every run
+    assert any(np.array_equal(p[0], row) for row in big["policy"])        # rows of the output, not a resampling
+
+
+class _FakeEngine:
+    """Stands in for capi.Engine in bench.Workload's steps: every submission stamps its slot's staging (or the output
+    buffers it is given) with its sequence number over all engines, and a wait of a slot that has nothing in flight fails."""
+
+    def __init__(self, counter, B, plen):
+        import numpy as np
+        self.counter, self.busy = counter, {}
+        self.vals = [np.zeros((B, 5), np.float32) for _ in range(4)]
+        self.probs = [np.zeros(B * plen, np.float32) for _ in range(4)]
+        self.pol = [np.zeros((B, plen), np.float32) for _ in range(4)]
+
+    def _stamp(self, slot):
+        assert slot not in self.busy, "submit to a slot still in flight"
+        self.counter[0] += 1
+        self.busy[slot] = True
+        for a in (self.vals[slot], self.probs[slot], self.pol[slot]):
+            a[:] = self.counter[0]
+
+    def submit_packed_decoded_csr(self, slot, bits, scalars_in, offsets, idx):
+        self._stamp(slot)
+
+    def submit_packed(self, slot, bits, scalars_in):
+        self._stamp(slot)
+        return len(bits)
+
+    def wait_decoded_view(self, slot):
+        del self.busy[slot]
+        return self.vals[slot].ctypes.data, self.probs[slot].ctypes.data
+
+    def wait_view(self, slot, n):
+        del self.busy[slot]
+        return self.vals[slot], self.pol[slot]
+
+    def enqueue_packed_device(self, d_bits, stride, d_sin, batch, d_scalars, d_policy):
+        self.counter[0] += 1
+        d_scalars.data[:], d_policy.data[:] = self.counter[0], self.counter[0]
+
+    def synchronize(self):
+        pass
+
+
+class _FakeBuffer:
+    """Stands in for capi.DeviceBuffer: the host copy of what the fake engine wrote."""
+
+    def __init__(self, shape):
+        import numpy as np
+        self.data = np.zeros(shape, np.float32)
+
+    def to_host(self, dtype, shape):
+        return self.data.astype(dtype).reshape(shape)
+
+
+@pytest.mark.parametrize("kind", ["step_host_decoded", "step_host", "step_resident"])
+def test_last_outputs_are_what_the_last_timed_step_returned(kind):
+    """--dump-outputs reads the (engine, slot) or output buffers of the LAST timed step: over the real step functions and
+    timed-region loop, with two engines and step counts that end on every slot, the dumped arrays carry the number of
+    the last submission — not an earlier batch's."""
+    import numpy as np
+    from types import SimpleNamespace
+    sys.path.insert(0, REPO)
+    import bench
+    B, plen = 8, 64
+    for steps in (1, 2, 3, 5, 6, 8, 11):
+        counter = [0]
+        w = object.__new__(bench.Workload)
+        w.np, w.B, w.device, w.stride = np, B, 0, 3
+        w.capi = SimpleNamespace(KZ_ENGINE_SLOTS=4, check=lambda rc: None,
+                                 load=lambda: SimpleNamespace(kz_device_synchronize=lambda d: 0))
+        w.info = SimpleNamespace(policy_len=plen)
+        w.bits, w.scalars_in = np.zeros((B, 3), np.uint8), np.zeros((B, 1), np.float32)
+        w.d_bits = w.d_sin = None
+        w.engines = [_FakeEngine(counter, B, plen) for _ in range(2)]
+        w.host_engines = w.engines
+        w.outs = [(_FakeBuffer((B, 5)), _FakeBuffer((B, plen))) for _ in w.engines]
+        w.inflight, w.inflight_dec, w.views, w.moves = {}, set(), {}, None
+        step = getattr(w, kind)
+        benchlib.run_timed_regions(step, w.sync, steps, 3, 2)
+        out = w.last_outputs(step, steps)
+        last = counter[0]
+        if kind == "step_host_decoded":
+            assert set(out) == {"values", "move_probs"} and out["values"].shape == (B, 5)
+            assert len(out["move_probs"]) == int(w.moves[0][-1])
+        else:
+            assert set(out) == {"scalars", "policy"} and out["policy"].shape == (B, plen)
+        for name, a in out.items():
+            assert a.dtype == np.float32 and (a == last).all(), (kind, steps, name, a.ravel()[:2], last)
 
 
 # ------------------------------------------------------------------------------------------------------------------

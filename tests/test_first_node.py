@@ -38,7 +38,9 @@ def fake_sysfs(root, n_gpus=8):
 
 
 def _env(tmp_path, **extra):
-    env = dict(os.environ, FAKE="1", OUT=str(tmp_path / "out"), PYTHON=sys.executable, **extra)
+    # (without the box's own device masks: the fake GPUs are what `extra` sets)
+    env = {k: v for k, v in os.environ.items() if k not in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")}
+    env.update(FAKE="1", OUT=str(tmp_path / "out"), PYTHON=sys.executable, **extra)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     return env

@@ -1,6 +1,5 @@
 """N4: the packed position record format (rust/kz-selfplay/src/binary_output.rs:210-289)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -9,7 +8,31 @@ from kzero_amd import synth
 from kzero_amd.position_file import SCALAR_NAMES, PositionFile, PositionFileWriter, PositionRecord
 from tests import oracle_lib as O
 
-REF = "/root/reference/python"
+READER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "position_reader.npz")
+
+
+def _reference_read(path, case):
+    """What the reference's own consumer of this format (python/lib/data/file.py + position.py, `DataFile.open`) read from
+    the file at `path`: its reading of these very bytes, recorded with their SHA-256 by oracle/gen_position_reader_golden.py.
+    The file must be byte for byte the one it read; the positions and simulations come back with the attributes the
+    reference's `Position` / `Simulation` carry."""
+    import hashlib
+    from types import SimpleNamespace
+    z = np.load(READER)
+    got = [hashlib.sha256(open(path + ext, "rb").read()).hexdigest() for ext in (".bin", ".off", ".json")]
+    assert got == z[f"{case}_sha256"].tolist(), ("the writer no longer writes the bytes the reference's reader was recorded on; "
+                                                 "if the change is intended: python oracle/gen_position_reader_golden.py <reference>/python")
+    a = {k[len(case) + 1:]: z[k] for k in z.files if k.startswith(case + "_")}
+    off = a["policy_offsets"]
+    positions = [SimpleNamespace(move_index=int(a["move_index"][i]), available_mv_count=int(a["available_mv_count"][i]),
+                                 input_bools=a["input_bools"][i], input_scalars=a["input_scalars"][i],
+                                 policy_indices=a["policy_indices"][off[i]:off[i + 1]],
+                                 policy_values=a["policy_values"][off[i]:off[i + 1]],
+                                 zero_v=float(a["zero_v"][i]), is_final=bool(a["is_final"][i]))
+                 for i in range(len(a["move_index"]))]
+    simulations = [SimpleNamespace(start_file_pi=int(s), move_count=int(m))
+                   for s, m in zip(a["sim_start_file_pi"], a["sim_move_count"])]
+    return SimpleNamespace(positions=positions, simulations=simulations)
 
 
 def _games(rng, game="ataxx-7", n_games=3):
@@ -90,33 +113,25 @@ def test_round_trip(tmp_path):
     assert bits.shape == (2, 19) and scalars.shape == (2, 1) and len(moves[1]) == int(flat[5].scalars["available_mv_count"])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's own reader only exists in the build container")
 def test_reference_reader_accepts_our_files(tmp_path):
     """Pins the writer against the reference's own consumer of this format: python/lib/data/file.py + position.py."""
     games, shape, ns, pshape = _games(np.random.default_rng(2))
     path = str(tmp_path / "games_7")
     _write(path, games, shape, ns, pshape)
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, REF)
-    try:
-        from lib.data.file import DataFile
-        from lib.games import Game
-        df = DataFile.open(Game.find("ataxx-7"), path)
-        flat = [r for g in games for r in g]
-        assert len(df.positions) == len(flat) and len(df.simulations) == 3
-        for i, r in enumerate(flat):
-            p = df.positions[i]
-            assert p.move_index == int(r.scalars["pos_index"]) and p.available_mv_count == len(r.policy_indices)
-            unpacked = np.unpackbits(r.bits, bitorder="little")[:3 * 49].reshape(3, 7, 7)
-            assert np.array_equal(p.input_bools, unpacked)
-            assert np.array_equal(p.input_scalars, r.input_scalars)
-            assert np.array_equal(p.policy_indices, r.policy_indices.astype(np.int32))
-            assert np.array_equal(p.policy_values, r.policy_values)
-            assert p.zero_v == pytest.approx(0.5) and p.is_final == bool(r.scalars["is_final_position"])
-        sim = df.simulations[1]
-        assert sim.start_file_pi == 4 and sim.move_count == 4
-    finally:
-        sys.path.remove(REF)
+    df = _reference_read(path, "ours")
+    flat = [r for g in games for r in g]
+    assert len(df.positions) == len(flat) and len(df.simulations) == 3
+    for i, r in enumerate(flat):
+        p = df.positions[i]
+        assert p.move_index == int(r.scalars["pos_index"]) and p.available_mv_count == len(r.policy_indices)
+        unpacked = np.unpackbits(r.bits, bitorder="little")[:3 * 49].reshape(3, 7, 7)
+        assert np.array_equal(p.input_bools, unpacked)
+        assert np.array_equal(p.input_scalars, r.input_scalars)
+        assert np.array_equal(p.policy_indices, r.policy_indices.astype(np.int32))
+        assert np.array_equal(p.policy_values, r.policy_values)
+        assert p.zero_v == pytest.approx(0.5) and p.is_final == bool(r.scalars["is_final_position"])
+    sim = df.simulations[1]
+    assert sim.start_file_pi == 4 and sim.move_count == 4
 
 
 def test_recorded_boards_are_engine_inputs(tmp_path):
@@ -194,7 +209,6 @@ def test_cpp_writer_is_read_by_the_python_reader_and_back(tmp_path):
     assert bad.returncode == 1 and "error:" in bad.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's own reader only exists in the build container")
 def test_reference_reader_accepts_the_cpp_writers_files(tmp_path):
     """The reference's DataFile (python/lib/data/file.py) opens what the C++ writer wrote: chess-shaped records."""
     import subprocess
@@ -202,19 +216,12 @@ def test_reference_reader_accepts_the_cpp_writers_files(tmp_path):
     path = str(tmp_path / "games_9")
     subprocess.run([exe, "write", path, "5", "4"], capture_output=True, text=True, check=True)
     ours = PositionFile(path)
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, REF)
-    try:
-        from lib.data.file import DataFile
-        from lib.games import Game
-        df = DataFile.open(Game.find("chess"), path)
-        assert len(df.positions) == len(ours) and len(df.simulations) == 4
-        for i in range(len(ours)):
-            r, p = ours.position(i), df.positions[i]
-            assert p.available_mv_count == len(r.policy_indices)
-            assert np.array_equal(p.input_bools, np.unpackbits(r.bits, bitorder="little")[:13 * 64].reshape(13, 8, 8))
-            assert np.array_equal(p.input_scalars, r.input_scalars)
-            assert np.array_equal(p.policy_indices, r.policy_indices.astype(np.int32))
-            assert np.array_equal(p.policy_values, r.policy_values)
-    finally:
-        sys.path.remove(REF)
+    df = _reference_read(path, "cpp")
+    assert len(df.positions) == len(ours) and len(df.simulations) == 4
+    for i in range(len(ours)):
+        r, p = ours.position(i), df.positions[i]
+        assert p.available_mv_count == len(r.policy_indices)
+        assert np.array_equal(p.input_bools, np.unpackbits(r.bits, bitorder="little")[:13 * 64].reshape(13, 8, 8))
+        assert np.array_equal(p.input_scalars, r.input_scalars)
+        assert np.array_equal(p.policy_indices, r.policy_indices.astype(np.int32))
+        assert np.array_equal(p.policy_values, r.policy_values)

@@ -9,7 +9,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/r6_go_l2; mkdir -p $O
 for r in 1 2 3; do for v in _prev "" _l2; do
-  KZ_LIB_PATH=$PWD/kzero_amd/libkzhip$v.so python3 bench.py --workload go19-40x256 --dtype f16 --boundary resident --no-cpu-baseline --no-host-io --no-others --no-seam --repeats 3 --steps ${STEPS:-200} 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(\"go19-40x256 f16 lib$v\", d[\"value\"], d[\"value_min\"], d[\"value_max\"], d[\"roofline\"][\"avg_launch_ms\"])"
+  KZ_LIB_PATH=$PWD/kzero_amd/libkzhip$v.so python3 bench.py --full --workload go19-40x256 --dtype f16 --boundary resident --no-cpu-baseline --no-host-io --no-others --no-seam --repeats 3 --steps ${STEPS:-200} 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(\"go19-40x256 f16 lib$v\", d[\"value\"], d[\"value_min\"], d[\"value_max\"], d[\"roofline\"][\"avg_launch_ms\"])"
 done; done | tee $O/ab.txt
 for v in _prev "" _l2; do
   for set in clk sq; do

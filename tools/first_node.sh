@@ -27,7 +27,7 @@ if [ "$FAKE" = "1" ]; then
 else
   NDEV=$($PY -c "from kzero_amd import capi; print(capi.device_count())" 2>"$OUT/devices.err") || { echo "first_node: no HIP device / library (see $OUT/devices.err)"; exit 2; }
   $PY -c "from kzero_amd import capi; [print(d, capi.device_pci_bus_id(d)) for d in range(capi.device_count())]" | tee "$OUT/devices.txt"
-  BENCH_ARGS="${BENCH_ARGS:---steps 2000 --warmup 50}"
+  BENCH_ARGS="${BENCH_ARGS:---full --steps 2000 --warmup 50}"
   # 1. two devices in one process: bitwise what device 0 gives alone (f16 one-launch, split16, f32, board paths)
   if [ "$NDEV" -ge 2 ]; then
     $PY -m pytest tests -q -m gpu -k "two_devices" > "$OUT/pytest_two_devices.log" 2>&1 || { echo "first_node: FAILED pytest -k two_devices (see $OUT/pytest_two_devices.log)"; fail=1; }

@@ -24,8 +24,8 @@ r = json.loads(open(f"gpurun_out/power/{name}.json").read().strip().splitlines()
 print(f"{name:28s} value {r['value']:10.1f}  chip_frac {r['roofline']['chip_frac']:.3f}  power W mean {sum(p)/max(len(p),1):7.1f} max {max(p or [0]):7.1f}  sclk MHz {sorted(c)}")
 PY
 }
-run chess_f16        --workload chess-20x256 --dtype f16 --steps 24000 --warmup 50
-run chess_f32split16 --workload chess-20x256 --dtype f32split16 --steps 7000 --warmup 20
-run chess_f32        --workload chess-20x256 --dtype f32 --steps 2200 --warmup 10
-run ataxx_f32        --workload ataxx-8x128 --dtype f32 --steps 22000 --warmup 50
-run go19_f16         --workload go19-40x256 --dtype f16 --steps 700 --warmup 5
+run chess_f16        --full --workload chess-20x256 --dtype f16 --steps 24000 --warmup 50
+run chess_f32split16 --full --workload chess-20x256 --dtype f32split16 --steps 7000 --warmup 20
+run chess_f32        --full --workload chess-20x256 --dtype f32 --steps 2200 --warmup 10
+run ataxx_f32        --full --workload ataxx-8x128 --dtype f32 --steps 22000 --warmup 50
+run go19_f16         --full --workload go19-40x256 --dtype f16 --steps 700 --warmup 5

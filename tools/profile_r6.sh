@@ -17,11 +17,11 @@ STEPS=30 WARMUP=5 bash tools/pmc_traffic.sh chess-20x256 f32split16
 STEPS=60 WARMUP=10 bash tools/pmc_traffic.sh ataxx-8x128 f32
 STEPS=60 WARMUP=10 bash tools/pmc_traffic.sh ataxx-8x128 f32split16
 STEPS=30 WARMUP=5 bash tools/pmc_traffic.sh chess-20x256 f16
-python3 bench.py > $O/bench.json 2> $O/bench.err; cp bench_full.json $O/bench_full.json
+python3 bench.py --full > $O/bench.json 2> $O/bench.err; cp bench_full.json $O/bench_full.json
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; cp bench_full.json $O/bench_full_driver_cmd.json
 wc -c $O/bench.json $O/bench_driver_cmd.json
 rm -rf $O/stats
-KZ_BENCH_FULL_RECORD=$PWD/$O/stats_bench_full.json rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 bench.py --steps 2000 --repeats 3 --no-cpu-baseline --no-seam > $O/stats_bench.json 2> $O/stats.log
+KZ_BENCH_FULL_RECORD=$PWD/$O/stats_bench_full.json rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 bench.py --full --steps 2000 --repeats 3 --no-cpu-baseline --no-seam > $O/stats_bench.json 2> $O/stats.log
 f=$(ls -S $(find $O/stats -name "*kernel_stats.csv") | head -1)
 cp "$f" $O/kernel_stats_default_bench.csv
 rm -rf $O/stats

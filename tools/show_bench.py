@@ -6,7 +6,9 @@ r = json.load(open(path))
 
 
 def roof(x):
-    f = x["roofline"]
+    f = x.get("roofline")
+    if f is None:
+        return "(no roofline: a plain run; bench.py --full measures it)"
     return (f"frac {f['frac']} (launch_frac {f.get('launch_frac')}, {f.get('concurrent_launches')} at once) launch_ms {f['avg_launch_ms']} "
             f"traffic {f['traffic']} ratio {f.get('traffic_ratio')}" + (f" ERROR {f['error']}" if "error" in f else ""))
 
