@@ -327,7 +327,7 @@ struct DeviceWeights {
             const int cin_p = round_up(m.c_in, 32);
             const size_t stem_elems = (size_t)9 * 256 * cin_p, layer_elems = (size_t)9 * 256 * 256;
             const size_t head_elems = fused_heads ? kz::tower_heads_weight_elems() : 0;
-            std::vector<uint16_t> stem(stem_elems), rest(layer_elems * 2 * m.depth + head_elems);
+            std::vector<uint16_t> stem(stem_elems), rest(layer_elems * 2 * m.depth + head_elems + kz::tower_weight_pad_elems());
             kz::tower_pack_weights(m.tower[0].w.data(), C, m.c_in, cin_p, stem.data());
             for (int l = 0; l < 2 * m.depth; l++)
                 kz::tower_pack_weights(m.tower[1 + l].w.data(), C, C, 256, rest.data() + layer_elems * l);

@@ -236,6 +236,8 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
             e->fused_heads = false;
             e->path = "tower_resident_f16";
         }
+        const char *prev_env = getenv("KZ_TOWER_PREV");
+        e->tower_prev = e->resident && !e->nb4 && prev_env && prev_env[0] == '1';
         const char *t32b = getenv("KZ_T32_BOARDS");
         e->t32_dense3 = e->resident32 && !e->split16 && !e->pairs16 && t32b && atoi(t32b) == 3 &&
                         kz::tower32_dense3_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels, m.h, m.w,

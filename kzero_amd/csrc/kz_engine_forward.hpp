@@ -136,6 +136,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         if (dec && fused_heads) t.decode = *dec;
         prof.begin("kz_tower_resident_f16", stream);
 #ifdef KZ_EXPERIMENTS
+        t.prev = tower_prev;
         if (nb4) kz::launch_tower_resident4(t, xres, stream);
         else
 #endif

@@ -123,6 +123,7 @@ struct kz_engine {
     bool fused_split = false;  // the split-f16 launch with the scalar head and the policy head inside
     bool fused_pairs = false;  // the plain-f16 generic launch with the conv policy head and the scalar head inside
     bool nb4 = false;        // resident chess tower with four boards per workgroup (KZ_TOWER_NB=4)
+    bool tower_prev = false;  // resident chess tower: the round-6 address arithmetic (experiment build: KZ_TOWER_PREV=1)
     bool t32_dense3 = false;  // exact-f32 launch with three 7x7 boards per workgroup (experiment build: KZ_T32_BOARDS=3)
     void *xres = nullptr;    // its residual scratch
     std::string path;

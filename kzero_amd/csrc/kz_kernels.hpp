@@ -393,12 +393,14 @@ struct TowerArgs {
     int *nonfinite_flag;  // fused heads only: see ScalarHeadArgs
     int epoch;
     DecodeArgs decode;    // fused heads only; set: decode_output inside the launch, scalars / policy are not written
+    bool prev;            // experiment build only: the round-6 instance of the kernel (bit-identity reference)
 };
 bool tower_resident_supported(int dtype, int h, int w, int channels, int depth, int c_in);
 int tower_resident_boards_per_workgroup();  // 2 (1 with KZ_TOWER_NB=1)
 bool tower_heads_supported(int policy_kind, int query_channels, int policy_len, int sh_channels, int sh_size);
 size_t tower_packed_weight_elems(int cin_p, int depth);
 size_t tower_heads_weight_elems();
+size_t tower_weight_pad_elems();  // zero k-steps behind the weight stream (the ring's refills past its end)
 // heads part of the weight stream (appended after the tower layers) and its 5 x 256 bias rows
 void tower_pack_heads(const float *w_bulk, const float *b_bulk, const float *w_under, const float *b_under,
                       uint16_t *dst, float *bias5);

@@ -46,6 +46,7 @@ constexpr int URS = 3 * C * 2 + 16;  // row stride of the conv_under image (768 
 constexpr int KSTEPS = 72;      // 9 taps x 8 chunks of 32 channels
 constexpr int HEAD_KSTEPS = 5 * 8;  // conv_under as 3 passes of 256 channels, conv_bulk as 2: 8 k-steps each
 constexpr int POLICY = 1880, LOGIT_LD = 96;  // 64 x 88 attention logits, rows padded to 96
+constexpr int TOWER_PF_MAX = 8;  // deepest weight ring: the stream is padded by this many k-steps
 
 struct TowerDev {
     const h16 *x0;
@@ -101,17 +102,20 @@ struct Layout {
 };
 
 // LLVM SchedGroupMask bits for __builtin_amdgcn_sched_group_barrier
-constexpr int SG_MFMA = 0x8, SG_VMEM_READ = 0x20, SG_DS_READ = 0x100;
+constexpr int SG_VALU = 0x2, SG_SALU = 0x4, SG_MFMA = 0x8, SG_VMEM_READ = 0x20, SG_DS_READ = 0x100;
 
 // PF = weight prefetch distance in k-steps (register ring stages, a power of two <= 8); PF * 16 KB are in flight per
 // CU.  Measured at one board per workgroup: PF = 8 is SLOWER than PF = 4 (0.665 vs 0.611 ms per batch) — that
 // configuration is bound by L2->CU bandwidth (~80 GB/s per CU), not by latency.
 // WIDE: more than 32 input planes (the instance for up to 32 keeps its compile-time stem: a same-box A/B of a run-time
 // chunk count in the benchmark's instance cost 0.3 %)
-template <int NB, bool HEADS, int PF, bool WIDE = false>
+// PREV: the round-6 address arithmetic (per-lane 64-bit weight addresses with a clamp at the end of the stream, tap rows
+// through short-circuit conditions) — instantiated only in the experiment build, as the bit-identity reference
+template <int NB, bool HEADS, int PF, bool WIDE = false, bool PREV = false>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     using L = Layout<NB>;
     constexpr int M = L::M, MT = L::MT;
+    static_assert(PF <= TOWER_PF_MAX, "the refills past the end of the stream must land in its padding");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
     const int tid = threadIdx.x;
@@ -123,27 +127,47 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     const int total_ksteps = layers * KSTEPS + (HEADS ? HEAD_KSTEPS : 0);
     const int bias_rows = layers + (HEADS ? 5 : 0);  // last valid row of the bias table
 
-    // ---- weight stream: per k-step 16 KB = [wave 4][nt 4][lane 64] x 16 B; prime PF stages before anything else ----
-    const uint4 *wp = a.w_tower + wave * 256 + lane;
-    auto wload = [&](int gk, int nt) __attribute__((always_inline)) { return wp[(size_t)gk * 1024 + nt * 64]; };
+    // ---- weight stream: per k-step 16 KB = [wave 4][nt 4][lane 64] x 16 B; prime PF stages before anything else.
+    // A refill is global_load_dwordx4 v, v_lane, s[wk:wk+1] offset:1024*nt: the k-step's address is a wave-uniform
+    // running pointer (one 64-bit scalar add per k-step) plus the lane's 32-bit offset, and nt is the immediate.  The
+    // stream is padded by TOWER_PF_MAX k-steps (tower_weight_pad_elems), so the refills that run past its end read padding
+    // (never used) and need no clamp ----
+    const uint4 *wp = a.w_tower + wave * 256 + lane;  // (PREV)
+    auto wload_prev = [&](int gk, int nt) __attribute__((always_inline)) { return wp[(size_t)gk * 1024 + nt * 64]; };
+    typedef const __attribute__((address_space(1))) unsigned char *gptr;  // (global, so the loads stay global_load)
+    gptr wk = (gptr)a.w_tower + wave * 4096;
+    const unsigned wlane = lane * 16;
+    auto wload = [&](gptr k, int nt) __attribute__((always_inline)) {
+        typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+        return __builtin_bit_cast(uint4, *reinterpret_cast<const __attribute__((address_space(1))) u32x4 *>(k + wlane + nt * 1024));
+    };
     uint4 wreg[PF][4];
 #pragma unroll
     for (int s = 0; s < PF; s++) {
         const int g = s < total_ksteps ? s : total_ksteps - 1;
 #pragma unroll
-        for (int nt = 0; nt < 4; nt++) wreg[s][nt] = wload(g, nt);
+        for (int nt = 0; nt < 4; nt++) wreg[s][nt] = PREV ? wload_prev(g, nt) : wload(wk + s * 16384, nt);
     }
-    int g = 0;  // global k-step index into the weight stream
-    // take this k-step's fragments out of ring stage `stage` and refill the stage with k-step g + PF (clamped at the
-    // end of the stream; the surplus loads are never used)
+    wk += PF * 16384;
+    int g = 0;  // global k-step index into the weight stream (PREV)
+    // take this k-step's fragments out of ring stage `stage` and refill the stage with k-step g + PF
     auto ring_take = [&](int stage, h16x8 (&af)[4]) __attribute__((always_inline)) {
 #pragma unroll
         for (int nt = 0; nt < 4; nt++) af[nt] = *reinterpret_cast<const h16x8 *>(&wreg[stage][nt]);
 #ifndef KZ_TW_NO_WLOAD  // (timing experiments: a build without the weight stream)
-        const int gn = g + PF < total_ksteps ? g + PF : total_ksteps - 1;
+        if constexpr (PREV) {
+            const int gn = g + PF < total_ksteps ? g + PF : total_ksteps - 1;
 #pragma unroll
-        for (int nt = 0; nt < 4; nt++) wreg[stage][nt] = wload(gn, nt);
+            for (int nt = 0; nt < 4; nt++) wreg[stage][nt] = wload_prev(gn, nt);
+        } else {
+#pragma unroll
+            for (int nt = 0; nt < 4; nt++) wreg[stage][nt] = wload(wk, nt);
+        }
 #endif
+        wk += 16384;
+        // (opaque to the optimiser: otherwise strength reduction folds the lane offset into a per-lane 64-bit pointer and
+        // every k-step pays 64-bit VALU adds)
+        if constexpr (!PREV) asm("" : "+s"(wk));
     };
 
     // ---- zero rows and stem input.  Up to 32 input planes the stem input has its own rows of 64 B behind the zero rows;
@@ -297,6 +321,9 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     // board read zero row (q & 15), which keeps the same slot pattern.
     const int kq_off = 256 * (kq & 1) + 128 * (kq >> 1);
     const int frag_base = lane_row + kq_off;
+    // (The lane conditions are combined with bitwise operators: as short-circuit conditions the compiler turned every
+    // tile's choice into an exec-masked branch, ~100 instructions per tap outside any MFMA's shadow; this way they are
+    // eight v_cndmask.)
     auto tap_rows = [&](int tap, int src_off, int (&T)[MT]) __attribute__((always_inline)) {
         const int dy = tap / 3 - 1, dx = tap % 3 - 1;
         const int shifted = frag_base + src_off + (dy * 8 + dx) * RS;
@@ -304,8 +331,21 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
         // tiles differ by 8 rows
         const int zrow = L::Z_OFF + ((fr + dy * 8 + dx) & 15) * RS + kq_off;
         const int zrow_odd = L::LINE_TILES ? L::Z_OFF + ((fr + dy * 8 + dx + 8) & 15) * RS + kq_off : zrow;
+        if constexpr (PREV) {
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) T[mt] = tap_ok(mt, dy, dx) ? shifted + mt * L::TS : ((mt & 1) ? zrow_odd : zrow);
+            for (int mt = 0; mt < MT; mt++) T[mt] = tap_ok(mt, dy, dx) ? shifted + mt * L::TS : ((mt & 1) ? zrow_odd : zrow);
+        } else {
+            int z0 = zrow, z1 = zrow_odd;
+            asm("" : "+v"(z0), "+v"(z1));  // (computed for every lane: no exec-masked branch around them)
+            const bool kill_x = ((dx < 0) & x_is0) | ((dx > 0) & x_is7);
+#pragma unroll
+            for (int mt = 0; mt < MT; mt++) {
+                bool kill;
+                if constexpr (L::LINE_TILES) kill = kill_x | ((dy < 0) & (mt == 0)) | ((dy > 0) & (mt == MT - 1));
+                else kill = kill_x | (((mt & 3) == 0) & (dy < 0) & yo_is0) | (((mt & 3) == 3) & (dy > 0) & yo_is1);
+                T[mt] = kill ? ((mt & 1) ? z1 : z0) : shifted + mt * L::TS;
+            }
+        }
     };
 
     // One line of taps: acc += sum over taps (DY, dx in [dx_lo, dx_hi)) and all 256 input channels of W * image(src_off),
@@ -363,8 +403,21 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
                         __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
                     }
                 }
-                if (ch < 7) __builtin_amdgcn_sched_group_barrier(SG_MFMA, 4 * NT_ - (NT_ + 4), 0);
-                else __builtin_amdgcn_sched_group_barrier(SG_MFMA, 4 * NT_ - (NR_LAST + 4), 0);
+                // the first k-step of a tap also carries the next tap's row addresses (~35 VALU / SALU): two behind
+                // each of the following MFMAs instead of one block between two of them
+                constexpr int N_FREE = 4 * NT_ - (NT_ + 4), N_ALU = PREV ? 0 : N_FREE < 20 ? N_FREE : 20;
+                if (ch == 0) {
+#pragma unroll
+                    for (int i = 0; i < N_ALU; i++) {
+                        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 2, 0);
+                    }
+                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 4 * NT_ - (NT_ + 4) - N_ALU, 0);
+                } else if (ch < 7) {
+                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 4 * NT_ - (NT_ + 4), 0);
+                } else {
+                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 4 * NT_ - (NR_LAST + 4), 0);
+                }
                 __builtin_amdgcn_sched_barrier(0);
                 g++;
             }
@@ -647,6 +700,8 @@ size_t tower_packed_weight_elems(int cin_p, int depth) {
 
 size_t tower_heads_weight_elems() { return (size_t)HEAD_KSTEPS * 16 * 1024 / 2; }
 
+size_t tower_weight_pad_elems() { return (size_t)TOWER_PF_MAX * 16 * 1024 / 2; }
+
 // OIHW f32 -> [tap 9][chunk cin_p/32][wave 4][nt 4][lane 64][8] f16: element j of lane (fr, kq) of (wave, nt) is
 // W[oc = 64*wave + 16*nt + fr][channel][tap] — the A fragment of v_mfma_f32_16x16x32_f16 — where the k-step's channel
 // assignment is the kernel's: cin_p == 256: channel = 8*chunk + {0,128,64,192}[kq] + j (bank-conflict-free LDS reads);
@@ -728,6 +783,22 @@ void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
         }
         kernel<<<grid, 256, bytes, stream>>>(d);
     };
+#ifdef KZ_EXPERIMENTS
+    if (t.prev) {  // (the round-6 instances: tests/test_tower_overlap.py)
+        const int grid = (t.batch + 1) / 2;
+        if (t.cin_p > 32) {
+            if (heads) launch(kz_tower_resident<2, true, PF_NB2, true, true>, grid, Layout<2>::BYTES);
+            else launch(kz_tower_resident<2, false, PF_NB2, true, true>, grid, Layout<2>::BYTES);
+        } else if (boards_per_wg() == 1) {
+            if (heads) launch(kz_tower_resident<1, true, PF_NB1, false, true>, t.batch, Layout<1>::BYTES);
+            else launch(kz_tower_resident<1, false, PF_NB1, false, true>, t.batch, Layout<1>::BYTES);
+        } else {
+            if (heads) launch(kz_tower_resident<2, true, PF_NB2, false, true>, grid, Layout<2>::BYTES);
+            else launch(kz_tower_resident<2, false, PF_NB2, false, true>, grid, Layout<2>::BYTES);
+        }
+        return;
+    }
+#endif
     if (t.cin_p > 32) {  // (ChessHistoryMapper: 34 / 47 / 60 planes; always two boards per workgroup)
         const int grid = (t.batch + 1) / 2;
         if (heads) launch(kz_tower_resident<2, true, PF_NB2, true>, grid, Layout<2>::BYTES);
