@@ -1,11 +1,9 @@
-// kz_device_weights.hpp — device weights, shared by all engines of one (model, device, dtype): the packed weight streams of
-// whichever kernels kz_plan.hpp chose for the network, uploaded once and reference-counted.  Part of kz_engine.hip's
-// translation unit (included inside its anonymous namespace, after kz_engine_util.hpp).
+// kz_device_weights.hpp — device weights: the packed weight streams of the kernels a PathPlan (kz_plan.hpp) names, built by
+// DeviceWeights::build(model, plan) and shared, reference-counted, by all engines with the same WeightsKey — the model, the
+// device, the dtype and exactly the parts of the plan that build reads.  Part of kz_engine.hip's translation unit (included
+// inside its anonymous namespace, after kz_engine_util.hpp and kz_plan.hpp).
 #pragma once
 
-// ------------------------------------------------------------------------------------------------
-// Device weights, shared by all engines of one (model, device, dtype)
-// ------------------------------------------------------------------------------------------------
 struct DevConv {  // packed for kz_conv_igemm: [k*k][cout_p][cin_p] in T, bias f32 [cout_p]
     void *w = nullptr;
     float *b = nullptr;
@@ -24,9 +22,7 @@ struct DeviceWeights {
     float *post_scale = nullptr, *post_shift = nullptr;
 
     // resident tower
-    bool resident = false, fused_heads = false, resident32 = false, split16 = false, pairs16 = false;
-    bool fused_split = false;  // the split launch carries the heads (set before build)
-    bool fused_pairs = false;  // the plain-f16 generic launch carries the conv policy heads (set before build)
+    bool split16 = false;  // split_arithmetic(plan): upload_conv packs the 1x1 head convolutions in (hi, lo) pairs
     float *h32_small = nullptr;  // the fused f32 heads' small 1x1 convolutions (tower32_pack_small_weights)
     void *res32_w = nullptr;  // f32 resident launch (exact f32, or split f16 pairs): one packed weight stream
     void *res_w_stem = nullptr, *res_w_tower = nullptr;
@@ -179,8 +175,6 @@ struct DeviceWeights {
         return upload_f32(b, &d.b);
     }
 
-    bool use_board_conv = false;
-    bool use_board_split = false;  // split16 on a board too large for the resident launch: per-layer board-tile kernel
     int stem_cin_p = 0;  // != 0: the stem goes through the board-tile kernel and wants encoded rows of this many channels
     bool stem_split = false;  // split16 per layer: the stem too goes through kz_board_conv_split16 (<= 32 input planes)
     bool conv2 = false;  // the board-tile layers go through kz_board_conv2_f16
@@ -189,23 +183,17 @@ struct DeviceWeights {
     // DenseNetwork (kz_dense_network.hip)
     float *dn_w_in = nullptr, *dn_b_in = nullptr, *dn_blocks = nullptr, *dn_sf = nullptr, *dn_tf = nullptr, *dn_w_out = nullptr,
           *dn_b_out = nullptr;
-    bool att_heads = false;  // (set before build) ScalarHead + AttentionPolicyHead in one f16 launch (kz_att_heads.hip)
-    void *ah_w = nullptr;
+    void *ah_w = nullptr;  // PathPlan::att_heads: ScalarHead + AttentionPolicyHead in one f16 launch (kz_att_heads.hip)
     float *ah_bias = nullptr;
-    bool att_f16 = false;  // (set before build) the f16 launch's fragment streams instead of att_expand / att_layers
     void *att16_expand = nullptr, *att16_layers = nullptr;
     int *bc_rowmap = nullptr;  // (experiment build: kz_board_conv2_f16's tile-row map and halo-row list)
     unsigned short *bc_halo = nullptr;
     int bc_n_halo = 0;
-    int build(const Model &m, bool want_resident, bool want_fused, bool want_resident32, bool want_split16,
-              bool want_pairs16) {
-        resident32 = want_resident32;
-        split16 = want_split16;
-        pairs16 = want_pairs16;  // kz_tower_resident_split without the lo halves: plain f16, generic shapes
+    // (device and dtype set before: the engine's, KZ_DTYPE_F32 for split arithmetic)
+    int build(const Model &m, const PathPlan &p) {
+        split16 = split_arithmetic(p);
         const int C = m.channels, cp = round_up(C, 32), hw = m.h * m.w;
         HIP_TRY(hipSetDevice(device));
-        resident = want_resident;
-        fused_heads = want_resident && want_fused;
 
         if (m.tower_kind == kz::TOWER_DENSE_NET) {
             // dn_in's columns from the channel-major flatten (c * hw + p) to the encoded rows' order (p * cin_p + c)
@@ -230,7 +218,7 @@ struct DeviceWeights {
         }
         if (upload_f32(ps, &post_scale) || upload_f32(pt, &post_shift)) return 1;
 
-        if (m.tower_kind == kz::TOWER_ATTENTION && att_f16) {
+        if (p.tower == Tower::att_mfma) {
             const int cin_p = round_up(m.c_in, 32);
             const bool f32 = dtype == KZ_DTYPE_F32;
             const size_t esz = f32 ? 4 : 2;
@@ -244,7 +232,7 @@ struct DeviceWeights {
             if (upload(ex.data(), ex.size(), &att16_expand) || upload(all.data(), all.size(), &att16_layers) ||
                 upload_f32(m.att_embedding, &att_embedding))
                 return 1;
-        } else if (m.tower_kind == kz::TOWER_ATTENTION) {
+        } else if (p.tower == Tower::att_valu) {
             std::vector<float> all;
             all.reserve(kz::att_tower_layer_elems(C, m.att_heads, m.att_dk, m.att_dv, m.att_dff) * m.att_layers.size());
             for (auto &l : m.att_layers) {
@@ -254,11 +242,11 @@ struct DeviceWeights {
                 all.insert(all.end(), l.ff1.begin(), l.ff1.end());
             }
             if (upload_f32(m.att_expand, &att_expand) || upload_f32(m.att_embedding, &att_embedding) || upload_f32(all, &att_layers)) return 1;
-        } else if ((split16 && !use_board_split) || pairs16) {
+        } else if (p.tower == Tower::resident_split16 || p.tower == Tower::resident_f16g) {
             // f16 fragments — (hi, lo) pairs for split16 — in fragment order: 9 * ceil(c_in / 32) stem k-steps, then 9*C/32 per convolution
             // (+ the attention heads' five passes and bias rows when the split launch carries the heads)
-            const bool conv_heads = (split16 && fused_split && m.policy_kind != kz::POLICY_ATTENTION) || (pairs16 && fused_pairs);  // (Ataxx, Go 9x9)
-            const bool heads = split16 && fused_split && !conv_heads;
+            const bool conv_heads = p.heads && m.policy_kind != kz::POLICY_ATTENTION;  // (Ataxx, Go 9x9)
+            const bool heads = p.heads && !conv_heads;  // (the split launch only)
             const size_t tower_elems = kz::tower_split_weight_elems(C, m.depth, m.c_in, split16);
             std::vector<uint16_t> packed(tower_elems + (heads ? kz::tower_split_heads_weight_elems() : 0) +
                                          (conv_heads ? kz::tower_split_conv_heads_weight_elems(C, split16) : 0));
@@ -274,7 +262,7 @@ struct DeviceWeights {
             if (conv_heads) {  // the policy head's hidden layer as one more pass; the small convolutions as for the f32 launch
                 kz::tower_split_pack_conv_heads(m.p_conv0.w.data(), C, split16, packed.data() + tower_elems);
                 for (int o = 0; o < C; o++) bias[(size_t)(1 + 2 * m.depth) * C + o] = m.p_conv0.b[o];
-                if (pairs16) {  // the plain-f16 launch runs the two small convolutions as f16 MFMAs
+                if (!split16) {  // the plain-f16 launch runs the two small convolutions as f16 MFMAs
                     std::vector<uint16_t> small(kz::tower_split_small_weight16_elems(C));
                     kz::tower_split_pack_small_weights16(m.sh_conv.w.data(), m.sh_conv.cout,
                                                          m.policy_extra_moves ? m.p_extra_conv.w.data() : nullptr,
@@ -297,7 +285,7 @@ struct DeviceWeights {
             }
             if (upload(packed.data(), packed.size() * 2, &res32_w)) return 1;
             if (upload_f32(bias, &res_bias)) return 1;
-        } else if (resident32) {
+        } else if (p.tower == Tower::resident_f32) {
             // (the conv policy head's first 1x1 conv rides at the end of the stream whenever the launch can fuse the
             // heads; a launch without heads never reads it)
             const bool heads32 = kz::tower32_heads_supported((int)m.policy_kind, m.policy_extra_moves,
@@ -323,18 +311,18 @@ struct DeviceWeights {
             }
             if (upload(packed.data(), packed.size() * 4, &res32_w)) return 1;
             if (upload_f32(bias, &res_bias)) return 1;
-        } else if (resident) {
+        } else if (p.tower == Tower::resident_f16) {
             const int cin_p = round_up(m.c_in, 32);
             const size_t stem_elems = (size_t)9 * 256 * cin_p, layer_elems = (size_t)9 * 256 * 256;
-            const size_t head_elems = fused_heads ? kz::tower_heads_weight_elems() : 0;
+            const size_t head_elems = p.heads ? kz::tower_heads_weight_elems() : 0;
             std::vector<uint16_t> stem(stem_elems), rest(layer_elems * 2 * m.depth + head_elems + kz::tower_weight_pad_elems());
             kz::tower_pack_weights(m.tower[0].w.data(), C, m.c_in, cin_p, stem.data());
             for (int l = 0; l < 2 * m.depth; l++)
                 kz::tower_pack_weights(m.tower[1 + l].w.data(), C, C, 256, rest.data() + layer_elems * l);
-            std::vector<float> bias((size_t)(1 + 2 * m.depth + (fused_heads ? 5 : 0)) * 256);
+            std::vector<float> bias((size_t)(1 + 2 * m.depth + (p.heads ? 5 : 0)) * 256);
             for (int l = 0; l < 1 + 2 * m.depth; l++)
                 for (int o = 0; o < 256; o++) bias[(size_t)l * 256 + o] = m.tower[l].b[o];
-            if (fused_heads) {
+            if (p.heads) {
                 kz::tower_pack_heads(m.p_bulk.w.data(), m.p_bulk.b.data(), m.p_under.w.data(), m.p_under.b.data(),
                                      rest.data() + layer_elems * 2 * m.depth, bias.data() + (size_t)(1 + 2 * m.depth) * 256);
                 std::vector<int32_t> idx(m.flat_to_att.size());
@@ -345,25 +333,21 @@ struct DeviceWeights {
             if (upload(rest.data(), rest.size() * 2, &res_w_tower)) return 1;
             if (upload_f32(bias, &res_bias)) return 1;
         } else {
+            // per layer: board_conv_f16 / board_conv_split16 / conv_igemm (the stem and layers no board-tile kernel takes)
             tower.resize(m.tower.size());
-            const char *noboard = getenv("KZ_NO_BOARD_CONV");
+            const bool on = p.tower == Tower::board_conv_f16, use_board_split = p.tower == Tower::board_conv_split16;
 #ifdef KZ_EXPERIMENTS
-            if (use_board_conv && !(noboard && noboard[0] == '1')) {
-                const char *c2 = getenv("KZ_BOARD_CONV2");
-                // (experiment, opt-in: the second organisation measured 26.2k against 33.5k evals/s on Go-19 40x256)
-                conv2 = c2 && c2[0] == '1' && kz::board_conv2_supported(dtype, m.h, m.w, m.channels, m.channels);
-                if (conv2) {  // its tile-row map and halo-row list (the product kernel needs no tables)
-                    std::vector<int> rowmap;
-                    std::vector<unsigned short> halo;
-                    kz::board_conv2_tables(m.h, m.w, rowmap, halo);
-                    bc_n_halo = (int)halo.size();
-                    if (upload(rowmap.data(), rowmap.size() * sizeof(int), (void **)&bc_rowmap)) return 1;
-                    if (upload(halo.data(), halo.size() * sizeof(unsigned short), (void **)&bc_halo)) return 1;
-                }
+            conv2 = p.conv2;  // (the second organisation measured 26.2k against 33.5k evals/s on Go-19 40x256)
+            if (conv2) {  // its tile-row map and halo-row list (the product kernel needs no tables)
+                std::vector<int> rowmap;
+                std::vector<unsigned short> halo;
+                kz::board_conv2_tables(m.h, m.w, rowmap, halo);
+                bc_n_halo = (int)halo.size();
+                if (upload(rowmap.data(), rowmap.size() * sizeof(int), (void **)&bc_rowmap)) return 1;
+                if (upload(halo.data(), halo.size() * sizeof(unsigned short), (void **)&bc_halo)) return 1;
             }
 #endif
             for (size_t i = 0; i < m.tower.size(); i++) {
-                const bool on = use_board_conv && !(noboard && noboard[0] == '1');
                 // the stem joins the board-tile family with its input planes padded to one 64-channel chunk (the encode
                 // kernel then writes 64-channel rows): a quarter of a tower layer's work instead of an implicit GEMM
                 const bool stem64 = on && i == 0 && !conv2 && m.tower[0].cin <= 64 && m.tower[0].k == 3 &&
@@ -396,7 +380,7 @@ struct DeviceWeights {
             if (upload_f32(wt, &sh_w1t)) return 1;
         }
 
-        if (fused_heads) return 0;  // the policy head lives in the tower's weight stream
+        if (p.tower == Tower::resident_f16 && p.heads) return 0;  // the policy head lives in the tower's weight stream
         switch (m.policy_kind) {
             case kz::POLICY_ATAXX_CONV:
             case kz::POLICY_CONV:
@@ -427,7 +411,7 @@ struct DeviceWeights {
                 break;
             }
             case kz::POLICY_ATTENTION:
-                if (att_heads) {
+                if (p.att_heads) {
                     const int Q = m.policy_query_channels;
                     std::vector<uint16_t> packed(kz::att_heads_weight_elems(C, Q));
                     std::vector<float> bias((size_t)5 * Q + 16);
@@ -460,5 +444,21 @@ struct DeviceWeights {
     }
 };
 
+// what build reads: engines with equal keys share one DeviceWeights.  (The exact-f32 stream carries the conv heads wherever
+// the kernel can run them, whether the launch does or not.)
+struct WeightsKey {
+    const Model *model;
+    int device, dtype;
+    Tower tower;
+    bool heads, att_heads, conv2 = false;
+    WeightsKey(const Model *m, int device, int dtype, const PathPlan &p)
+        : model(m), device(device), dtype(dtype), tower(p.tower), heads(p.heads && p.tower != Tower::resident_f32), att_heads(p.att_heads) {
+#ifdef KZ_EXPERIMENTS
+        conv2 = p.conv2;
+#endif
+    }
+    auto fields() const { return std::tie(model, device, dtype, tower, heads, att_heads, conv2); }
+    bool operator<(const WeightsKey &o) const { return fields() < o.fields(); }
+};
 std::mutex g_cache_mutex;
-std::map<std::tuple<const Model *, int, int, bool, bool, bool>, std::weak_ptr<DeviceWeights>> g_cache;
+std::map<WeightsKey, std::weak_ptr<DeviceWeights>> g_cache;

@@ -27,10 +27,36 @@
 namespace {
 
 #include "kz_engine_util.hpp"     // g_err, fail, guarded, HIP_TRY
-#include "kz_device_weights.hpp"  // DevConv, DeviceWeights, the per-(model, device, dtype) cache
+#include "kz_plan.hpp"            // Tower, PathPlan, plan_path: which kernels run a network
+#include "kz_device_weights.hpp"  // DevConv, DeviceWeights::build(model, plan), the cache by WeightsKey
 
 #include "kz_engine_state.hpp"    // Prof, kz_model, effective_model, struct kz_engine: streams, slots, staging (closes the namespace itself)
 #include "kz_engine_forward.hpp"  // kz_engine::run_tower / run_heads / forward_*: the launches of a forward pass
+
+// The experiment build's switches (experiments/build.sh; the product reads none of them): the measured-and-rejected kernel
+// organisations, applied to the plan after plan_path.  Their hooks stay where they act: the tower4 / board_conv2 launches
+// (kz_engine_forward.hpp), the board_conv2 packing (kz_device_weights.hpp) and the graph replay (kz_engine_state.hpp).
+static void experiment_switches(const Model &m, int dtype, int cin_p, PathPlan &p) {
+#ifdef KZ_EXPERIMENTS
+    const auto env_int = [](const char *name) { return getenv(name) ? atoi(getenv(name)) : 0; };
+    if (env_on("KZ_NO_TOWER_F16") && p.tower == Tower::resident_f16) {  // (chess f16 through the generic one-launch f16 tower)
+        p.tower = kz::tower_split_supported(m.h, m.w, m.channels, m.depth, m.c_in, false) ? Tower::resident_f16g : Tower::conv_igemm;
+        p.heads = p.wide = false;
+    }
+    p.nb4 = p.tower == Tower::resident_f16 && env_int("KZ_TOWER_NB") == 4 && cin_p == 32;
+    if (p.nb4) p.heads = false;  // (the four-board launch has no fused heads yet)
+    p.tower_prev = p.tower == Tower::resident_f16 && !p.nb4 && env_on("KZ_TOWER_PREV");
+    p.t32_dense3 = p.tower == Tower::resident_f32 && env_int("KZ_T32_BOARDS") == 3 &&
+                   kz::tower32_dense3_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels, m.h, m.w, m.channels,
+                                                m.sh_conv.cout, m.sh_fc0.out, p.heads);
+    p.att_heads = !p.heads && att_heads_one_launch(m, dtype);
+    // (the opt-in board-conv organisation has its own weight packing)
+    p.conv2 = env_on("KZ_BOARD_CONV2") && p.tower == Tower::board_conv_f16 &&
+              kz::board_conv2_supported(dtype, m.h, m.w, m.channels, m.channels);
+    p.graph = env_on("KZ_HIP_GRAPH") && !p.heads;
+    p.no_zero_copy = env_on("KZ_NO_ZERO_COPY");  // (the staged-copy variant of the "+heads" launches, for A/B timing)
+#endif
+}
 
 
 // ------------------------------------------------------------------------------------------------
@@ -166,18 +192,18 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
     return guarded("kz_engine_create", [&]() -> int {
         if (!model || !out) return fail("kz_engine_create: null argument");
         if (max_batch <= 0) return fail("kz_engine_create: max_batch must be positive");
-        {
-            // every tensor of an engine is addressed with 32-bit byte offsets (buffer descriptors, int row indices): the
-            // largest one — an activation row set in f32, or the policy rows — must stay below 2 GiB.  This also keeps an
-            // absurd max_batch (a corrupted settings value) from reaching the allocator.
-            const Model &mm = *model->m;
-            const size_t per_board = (size_t)4 * std::max<size_t>((size_t)mm.h * mm.w * round_up(std::max(mm.channels, mm.c_in), 64),
-                                                                   (size_t)std::max(mm.policy_len, 1));
-            const size_t limit = (((size_t)1 << 31) - 1) / per_board;
-            if ((size_t)max_batch > limit)
-                return fail("kz_engine_create: max_batch " + std::to_string(max_batch) + " too large for this network: at most " +
-                            std::to_string(limit) + " boards (every engine tensor must stay below 2 GiB)");
-        }
+        // every tensor of an engine is addressed with 32-bit byte offsets (buffer descriptors, int row indices): max_batch times
+        // its bytes per board must stay below 2 GiB.  The largest one — an activation row set in f32, or the policy rows — is
+        // checked here, before any HIP call: this also keeps an absurd max_batch (a corrupted settings value) from the allocator
+        const auto too_large = [&](size_t per_board) {
+            const size_t limit = (((size_t)1 << 31) - 1) / std::max<size_t>(per_board, 1);
+            return (size_t)max_batch > limit && fail("kz_engine_create: max_batch " + std::to_string(max_batch) + " too large for this "
+                                                     "network: at most " + std::to_string(limit) + " boards (every engine tensor must stay below 2 GiB)");
+        };
+        const Model &mm = *model->m;
+        if (too_large((size_t)4 * std::max<size_t>((size_t)mm.h * mm.w * round_up(std::max(mm.channels, mm.c_in), 64),
+                                                   (size_t)std::max(mm.policy_len, 1))))
+            return 1;
         if (dtype != KZ_DTYPE_F32 && dtype != KZ_DTYPE_F16 && dtype != KZ_DTYPE_F32_SPLIT16)
             return fail("kz_engine_create: unknown dtype");
         // KZ_DTYPE_F32_SPLIT16 is the f32 engine with one kernel exchanged: everything below sees KZ_DTYPE_F32
@@ -200,110 +226,30 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
         e->esz = dtype == KZ_DTYPE_F32 ? 4 : 2;
         e->cin_p = round_up(m.c_in, 32);
         e->cp = round_up(m.channels, 32);
-        // which kernels run this network: plan_path (above) — the table of DESIGN.md §5.0 is printed from it
-        PathPlan plan;
-        {
-            std::string why;
-            if (!plan_path(m, max_batch, split16 ? KZ_DTYPE_F32_SPLIT16 : dtype, plan, why)) return fail("kz_engine_create: " + why);
-        }
-        e->dense_net = plan.dense_net;
-        e->att_tower = plan.att_tower;
-        e->att_f16 = plan.att_f16;
-        e->resident = plan.resident;
-        e->fused_heads = plan.fused_heads;
-        e->keep = plan.keep;
-        e->resident32 = plan.resident32;
-        e->split16 = plan.split16;
-        e->bsplit = plan.bsplit;
-        e->pairs16 = plan.pairs16;
-        e->wide = plan.wide;
-        e->fused_pairs = plan.fused_pairs;
-        e->fused32 = plan.fused32;
-        e->fused_split = plan.fused_split;
-        e->path = plan.path;
-        const bool board_conv = plan.board_conv;
-    #ifdef KZ_EXPERIMENTS
-        const char *notower = getenv("KZ_NO_TOWER_F16");  // (chess f16 through the generic one-launch f16 tower)
-        if (notower && notower[0] == '1' && e->resident) {
-            e->resident = e->fused_heads = false;
-            e->pairs16 = kz::tower_split_supported(m.h, m.w, m.channels, m.depth, m.c_in, false);
-            e->wide = false;
-            e->path = e->pairs16 ? "tower_resident_f16g" : "conv_igemm_f16";
-        }
-        const char *nb_env = getenv("KZ_TOWER_NB");
-        e->nb4 = e->resident && nb_env && atoi(nb_env) == 4 && e->cin_p == 32;
-        if (e->nb4) {  // (the four-board launch has no fused heads yet)
-            e->fused_heads = false;
-            e->path = "tower_resident_f16";
-        }
-        const char *prev_env = getenv("KZ_TOWER_PREV");
-        e->tower_prev = e->resident && !e->nb4 && prev_env && prev_env[0] == '1';
-        const char *t32b = getenv("KZ_T32_BOARDS");
-        e->t32_dense3 = e->resident32 && !e->split16 && !e->pairs16 && t32b && atoi(t32b) == 3 &&
-                        kz::tower32_dense3_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels, m.h, m.w,
-                                                     m.channels, m.sh_conv.cout, m.sh_fc0.out, e->fused32);
-    #endif
-
+        // which kernels run this network: plan_path (kz_plan.hpp) — the table of DESIGN.md §5 is printed from it
+        std::string why;
+        if (!plan_path(m, max_batch, split16 ? KZ_DTYPE_F32_SPLIT16 : dtype, e->plan, why)) return fail("kz_engine_create: " + why);
+        experiment_switches(m, dtype, e->cin_p, e->plan);
+        const PathPlan &plan = e->plan;
         {
             std::lock_guard<std::mutex> lock(g_cache_mutex);
-            int variant = 0;
-    #ifdef KZ_EXPERIMENTS
-            const char *c2 = getenv("KZ_BOARD_CONV2");  // (the opt-in board-conv organisation has its own weight packing)
-            variant = c2 && c2[0] == '1' ? 400 : 0;
-    #endif
-            const bool att_heads = !e->fused_heads && att_heads_one_launch(m, dtype, e->split16);
-            auto key = std::make_tuple(e->model.get(), device,
-                                       dtype + (e->split16 ? 100 : 0) + (e->pairs16 ? 200 : 0) + (e->att_f16 ? 800 : 0) + (att_heads ? 1600 : 0) + variant,
-                                       e->resident || e->resident32,
-                                       e->fused_heads || e->fused_split || e->fused_pairs, board_conv);
+            const WeightsKey key(e->model.get(), device, dtype, plan);
             auto it = g_cache.find(key);
             if (it != g_cache.end()) e->wts = it->second.lock();
             if (!e->wts) {
                 auto w = std::make_shared<DeviceWeights>();
                 w->device = device;
                 w->dtype = dtype;
-                w->use_board_conv = board_conv;
-                w->use_board_split = e->bsplit;
-                w->fused_split = e->fused_split;
-                w->fused_pairs = e->fused_pairs;
-                w->att_f16 = e->att_f16;
-                w->att_heads = att_heads;
-                if (w->build(m, e->resident, e->fused_heads, e->resident32, e->split16, e->pairs16)) return 1;
+                if (w->build(m, plan)) return 1;
                 g_cache[key] = w;
                 e->wts = w;
             }
         }
-
-    #ifdef KZ_EXPERIMENTS
-        {
-            const char *hg = getenv("KZ_HIP_GRAPH");
-            e->use_graph = hg && hg[0] == '1' && !e->fused_heads && !e->fused32 && !e->fused_split && !e->fused_pairs;
-        }
-    #endif
-        HIP_TRY(hipStreamCreateWithFlags(&e->slot_stream[0], hipStreamNonBlocking));
-        e->stream = e->slot_stream[0];
-        if (e->fused_heads || e->fused32 || e->fused_split || e->fused_pairs) {  // one launch per batch that touches nothing but its slot's buffers
-            HIP_TRY(hipStreamCreateWithFlags(&e->slot_stream[1], hipStreamNonBlocking));
-            for (int i = 2; i < KZ_ENGINE_SLOTS; i++) e->slot_stream[i] = e->slot_stream[i & 1];
-            e->zero_copy = true;
-    #ifdef KZ_EXPERIMENTS
-            const char *nzc = getenv("KZ_NO_ZERO_COPY");  // (the staged-copy variant of the one-launch paths, for A/B timing)
-            if (nzc && nzc[0] == '1') e->zero_copy = false;
-    #endif
-        }
-        if (e->wts->stem_cin_p) e->cin_p = e->wts->stem_cin_p;
+        // head temporaries, for run_heads' separate launches: the one tensor pair the check above does not bound
         const size_t hw = (size_t)m.h * m.w, rows = (size_t)max_batch * hw;
-        if (e->dmalloc(&e->x_in, rows * e->cin_p * e->esz)) return 1;
-    #ifdef KZ_EXPERIMENTS
-        if (e->nb4 && e->dmalloc(&e->xres, kz::tower4_scratch_bytes(max_batch))) return 1;
-    #endif
-        const int nact = (e->resident || e->resident32 || e->pairs16 || e->att_tower || e->dense_net) ? 1 : 3;
-        for (int i = 0; i < nact; i++)
-            if (e->dmalloc(&e->act[i], rows * e->cp * e->esz)) return 1;
-        // head temporaries
         size_t h0 = 0, h1 = 0;
         const DeviceWeights &w = *e->wts;
-        if (!e->fused_heads) switch (m.policy_kind) {
+        if (!plan.heads && !plan.att_heads) switch (m.policy_kind) {
             case kz::POLICY_ATAXX_CONV:
             case kz::POLICY_ARIMAA:
             case kz::POLICY_CONV: h0 = rows * w.p_conv0.cout_p; break;
@@ -317,6 +263,25 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
                 if (m.dense_hidden_size) h1 = (size_t)max_batch * w.p_fc0.cout_p;
                 break;
         }
+        if (too_large(std::max(h0, h1) * e->esz / max_batch)) return 1;
+
+        HIP_TRY(hipStreamCreateWithFlags(&e->slot_stream[0], hipStreamNonBlocking));
+        e->stream = e->slot_stream[0];
+        if (plan.heads) {  // one launch per batch that touches nothing but its slot's buffers
+            HIP_TRY(hipStreamCreateWithFlags(&e->slot_stream[1], hipStreamNonBlocking));
+            for (int i = 2; i < KZ_ENGINE_SLOTS; i++) e->slot_stream[i] = e->slot_stream[i & 1];
+            e->zero_copy = true;
+    #ifdef KZ_EXPERIMENTS
+            e->zero_copy = !plan.no_zero_copy;
+    #endif
+        }
+        if (e->wts->stem_cin_p) e->cin_p = e->wts->stem_cin_p;
+        if (e->dmalloc(&e->x_in, rows * e->cin_p * e->esz)) return 1;
+    #ifdef KZ_EXPERIMENTS
+        if (plan.nb4 && e->dmalloc(&e->xres, kz::tower4_scratch_bytes(max_batch))) return 1;
+    #endif
+        for (int i = 0; i < (per_layer(plan) ? 3 : 1); i++)
+            if (e->dmalloc(&e->act[i], rows * e->cp * e->esz)) return 1;
         if (e->dmalloc(&e->head0, h0 * e->esz) || e->dmalloc(&e->head1, h1 * e->esz)) return 1;
 
         const int nb_planes = m.n_bool < 0 ? 0 : m.n_bool, ns_planes = m.n_scalar < 0 ? 0 : m.n_scalar;
@@ -364,7 +329,7 @@ KZ_API int kz_model_plan(const kz_model *model, int max_batch, int dtype, kz_pat
         std::string why;
         if (!plan_path(*effective_model(model, dtype, max_batch), max_batch, dtype, plan, why)) return fail("kz_model_plan: " + why);
         memset(out, 0, sizeof *out);
-        snprintf(out->tower_path, sizeof out->tower_path, "%s", plan.path.c_str());
+        snprintf(out->tower_path, sizeof out->tower_path, "%s", path_name(plan, dtype));
         out->launches_per_batch = plan.launches;
         return 0;
     });
@@ -372,30 +337,35 @@ KZ_API int kz_model_plan(const kz_model *model, int max_batch, int dtype, kz_pat
 
 KZ_API int kz_engine_max_batch(const kz_engine *e) { return e ? e->max_batch : 0; }
 
-KZ_API const char *kz_engine_tower_path(const kz_engine *e) { return e ? e->path.c_str() : ""; }
+KZ_API const char *kz_engine_tower_path(const kz_engine *e) { return e ? path_name(e->plan, e->dtype) : ""; }
 
 KZ_API int kz_engine_launch_geometry(const kz_engine *e, int batch, int *workgroups, int *boards_per_workgroup) {
     return guarded("kz_engine_launch_geometry", [&]() -> int {
         if (!e || !workgroups || !boards_per_workgroup) return fail("kz_engine_launch_geometry: null argument");
         if ((batch < 0 || batch > e->max_batch ? fail("kz_engine_launch_geometry: batch out of range") : 0)) return 1;
         const Model &m = *e->model;
+        const PathPlan &p = e->plan;
         int per = 0, wgs = 0;
-        if (e->dense_net) per = 1;
-        else if (e->att_f16) per = kz::att_tower16_boards_per_workgroup(m.channels, m.att_dff, batch, e->dtype == KZ_DTYPE_F32);
-        else if (e->att_tower) per = 1;  // a workgroup is a board
-        else if (e->resident) per = e->nb4 ? 4 : e->cin_p > 32 ? 2 : kz::tower_resident_boards_per_workgroup();
-        else if ((e->split16 && !e->bsplit) || e->pairs16) per = kz::tower_split_boards_per_workgroup(m.h, m.w, m.channels, e->split16,
-                                                             e->wide ? batch : 0);  // (per launch: the widest level this batch fills the chip with)
-        else if (e->resident32) per = e->t32_dense3 ? 3 : kz::tower32_boards_per_workgroup(m.h, m.w, m.channels);
-        if (per) wgs = (batch + per - 1) / per;
-        else if (e->path == "board_conv_split16") wgs = kz::board_conv_workgroups(batch, m.h, m.w, m.channels);
-        else if (e->path == "board_conv_f16")
+        switch (p.tower) {
+            case Tower::dense_net:
+            case Tower::att_valu: per = 1; break;  // a workgroup is a board
+            case Tower::att_mfma: per = kz::att_tower16_boards_per_workgroup(m.channels, m.att_dff, batch, e->dtype == KZ_DTYPE_F32); break;
+            case Tower::resident_f16: per = e->cin_p > 32 ? 2 : kz::tower_resident_boards_per_workgroup(); break;
+            case Tower::resident_f32: per = kz::tower32_boards_per_workgroup(m.h, m.w, m.channels); break;
+            case Tower::resident_split16:
+            case Tower::resident_f16g:  // (per launch: the widest level this batch fills the chip with)
+                per = kz::tower_split_boards_per_workgroup(m.h, m.w, m.channels, e->split16(), p.wide ? batch : 0);
+                break;
+            case Tower::board_conv_f16:
+            case Tower::board_conv_split16: wgs = kz::board_conv_workgroups(batch, m.h, m.w, m.channels); break;
+            case Tower::conv_igemm: wgs = kz::conv_workgroups(e->dtype, batch * m.h * m.w, e->cp); break;
+        }
     #ifdef KZ_EXPERIMENTS
-            wgs = e->wts->conv2 ? kz::board_conv2_workgroups(batch, m.channels) : kz::board_conv_workgroups(batch, m.h, m.w, m.channels);
-    #else
-            wgs = kz::board_conv_workgroups(batch, m.h, m.w, m.channels);
+        if (p.nb4) per = 4;
+        if (p.t32_dense3) per = 3;
+        if (p.conv2) wgs = kz::board_conv2_workgroups(batch, m.channels);
     #endif
-        else wgs = kz::conv_workgroups(e->dtype, batch * m.h * m.w, e->cp);
+        if (per) wgs = (batch + per - 1) / per;
         *workgroups = wgs;
         *boards_per_workgroup = per;
         return 0;
@@ -575,7 +545,7 @@ KZ_API int kz_engine_submit_packed_decoded(kz_engine *e, int slot, const uint8_t
             ~StreamSwap() { e->stream = saved; }
         } swap{e, e->stream};
         if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
-        if (e->zero_copy && e->decode_in_launch()) {
+        if (e->zero_copy && e->plan.heads) {
             // ONE launch and no copy operation: it reads the packed boards and the move lists from the slot's pinned staging
             // and writes the decoded values and the available moves' probabilities there (0.2 KB per chess evaluation cross
             // PCIe); decode_output (common.rs:16-100) is the launch's last step.  The conv policy heads keep their logits in
@@ -806,8 +776,8 @@ KZ_API int kz_engine_read_activation(kz_engine *e, const char *name, int batch, 
         if (!e || !name || !out_nchw) return fail("kz_engine_read_activation: null argument");
         // "tower.out": the tower output of the last evaluation, on every path that materialises it (all but the fused-heads
         // launch)
-        const bool tower_out = std::string(name) == "tower.out" && !e->fused_heads && !e->fused32 && !e->fused_split && !e->fused_pairs;
-        if (!e->keep && !tower_out)
+        const bool tower_out = std::string(name) == "tower.out" && !e->plan.heads;
+        if (!e->plan.keep && !tower_out)
             return fail("kz_engine_read_activation: engine keeps no activations (create it with KZ_FORCE_GENERIC=1 and "
                         "KZ_KEEP_ACTIVATIONS=1; \"tower.out\" is available on every path without fused heads)");
         auto it = e->kept.find(name);

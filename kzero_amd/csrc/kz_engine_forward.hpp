@@ -1,5 +1,5 @@
-// kz_engine_forward.hpp — the forward pass of an engine: which kernels run for a network on its path (PathPlan, kz_plan.hpp),
-// in which order, on the engine's current stream.  Out-of-class definitions of the members kz_engine_state.hpp declares;
+// kz_engine_forward.hpp — the forward pass of an engine: which kernels run for its plan (kz_engine::plan, kz_plan.hpp: the
+// tower family, heads inside its launch or not), in which order, on the engine's current stream.  Out-of-class definitions of the members kz_engine_state.hpp declares;
 // included ONCE, by kz_engine.hip.
 #pragma once
 
@@ -37,7 +37,7 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
     }
     if (w.sw && y && !res && !post && !y32 && ldx >= w.cin_p) {  // 1x1 head convolution: split16 or any f16 path
         kz::Conv1x1SplitArgs c{};
-        c.split = split16;
+        c.split = split16();
         c.x = x; c.ldx = ldx; c.weights = w.sw; c.bias = w.b; c.y = y; c.ldy = ldy;
         c.M = M; c.cin_p = w.cin_p; c.cout_p = w.cout_p; c.relu = relu;
         c.group = group; c.src_group = src_group; c.src_off = src_off;
@@ -61,14 +61,14 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
     return 0;
 }
 
-// packed != nullptr (resident path only): the launch encodes the boards itself.  The one-launch networks ("...+heads") can
+// packed != nullptr (encodes_boards(plan) only): the launch encodes the boards itself.  The "+heads" launches (plan.heads) can
 // end in decode_output (kz_decode_dev.hpp): with `dec` nothing but the decoded values and the available moves' probabilities
 // leave the launch
 inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, const PackedIn *packed,
               const kz::DecodeArgs *dec) {
     const Model &m = *model;
     const int hw = m.h * m.w, M = batch * hw;
-    if (dense_net) {  // DenseNetwork: encoded planes in x_in -> scalars and policy, one launch
+    if (plan.tower == Tower::dense_net) {  // DenseNetwork: encoded planes in x_in -> scalars and policy, one launch
         kz::DenseNetArgs t{};
         t.x0 = x_in; t.in_f16 = dtype == KZ_DTYPE_F16; t.batch = batch; t.hw = hw; t.cin_p = cin_p; t.size = m.channels;
         t.depth = m.depth; t.res = m.dn_res ? 1 : 0; t.policy_len = m.policy_len;
@@ -82,7 +82,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         tower_out = 0;
         return 0;
     }
-    if (att_f16) {  // AttentionTower on the matrix cores, in the engine's arithmetic
+    if (plan.tower == Tower::att_mfma) {  // AttentionTower on the matrix cores, in the engine's arithmetic
         kz::AttTower16Args t{};
         t.f32 = dtype == KZ_DTYPE_F32;
         t.x0 = x_in; t.cin_p = cin_p; t.w_expand = wts->att16_expand; t.embedding = wts->att_embedding;
@@ -102,7 +102,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         tower_out = 0;
         return 0;
     }
-    if (att_tower) {  // AttentionTower: encoded planes in x_in -> tower output rows in act[0], one launch
+    if (plan.tower == Tower::att_valu) {  // AttentionTower: encoded planes in x_in -> tower output rows in act[0], one launch
         kz::AttTowerArgs t{};
         t.x0 = x_in; t.ldx0 = cin_p; t.in_f16 = dtype == KZ_DTYPE_F16; t.c_in = m.c_in;
         t.expand = wts->att_expand; t.embedding = wts->att_embedding; t.layers = wts->att_layers;
@@ -116,7 +116,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         tower_out = 0;
         return 0;
     }
-    if (resident) {
+    if (plan.tower == Tower::resident_f16) {
         kz::TowerArgs t{};
         if (packed) {
             t.bits = (const uint8_t *)packed->bits;
@@ -128,16 +128,16 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.x0 = x_in; t.cin_p = cin_p; t.w_stem = wts->res_w_stem; t.w_tower = wts->res_w_tower;
         t.bias = wts->res_bias; t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
         t.y = act[0]; t.batch = batch; t.h = m.h; t.w = m.w; t.depth = m.depth;
-        t.fused_heads = fused_heads;
+        t.fused_heads = plan.heads;
         t.sh_w0 = wts->sh_w0; t.sh_b0 = wts->sh_b0; t.sh_w1 = wts->sh_w1; t.sh_b1 = wts->sh_b1;
         t.sh_w2 = wts->sh_w2; t.sh_b2 = wts->sh_b2; t.att_idx = wts->att_idx;
         t.scalars = d_scalars; t.policy = d_policy;
         t.nonfinite_flag = nf_flag; t.epoch = nf_epoch;
-        if (dec && fused_heads) t.decode = *dec;
+        if (dec && plan.heads) t.decode = *dec;
         prof.begin("kz_tower_resident_f16", stream);
 #ifdef KZ_EXPERIMENTS
-        t.prev = tower_prev;
-        if (nb4) kz::launch_tower_resident4(t, xres, stream);
+        t.prev = plan.tower_prev;
+        if (plan.nb4) kz::launch_tower_resident4(t, xres, stream);
         else
 #endif
         kz::launch_tower_resident(t, stream);
@@ -146,7 +146,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         tower_out = 0;
         return 0;
     }
-    if (resident32 || pairs16) {
+    if (!per_layer(plan)) {  // resident_f32, resident_split16, resident_f16g
         kz::Tower32Args t{};
         t.x0 = (const float *)x_in; t.ldx0 = cin_p; t.c_in = m.c_in; t.weights = wts->res32_w; t.bias = wts->res_bias;
         t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
@@ -159,7 +159,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
             t.n_scalar = m.n_scalar;
             t.n_bool = m.n_bool;
         }
-        if (fused_split && m.policy_kind == kz::POLICY_ATTENTION) {
+        if (plan.heads && m.policy_kind == kz::POLICY_ATTENTION) {  // (the split launch only)
             kz::Tower32Args::Heads &hd = t.heads;
             hd.on = true;
             hd.sh_w0 = wts->sh_w0; hd.sh_b0 = wts->sh_b0; hd.sh_w1 = wts->sh_w1; hd.sh_b1 = wts->sh_b1;
@@ -168,7 +168,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
             hd.scalars = d_scalars; hd.policy = d_policy;
             hd.nonfinite_flag = nf_flag; hd.epoch = nf_epoch;
         }
-        if (fused32 || fused_pairs || (fused_split && m.policy_kind != kz::POLICY_ATTENTION)) {  // conv policy heads: the f32 tail
+        if (plan.heads && m.policy_kind != kz::POLICY_ATTENTION) {  // conv policy heads: the f32 tail
             kz::Tower32Args::Heads &hd = t.heads;
             hd.on = true;
             hd.hc = m.sh_conv.cout; hd.hs = m.sh_fc0.out;
@@ -184,18 +184,21 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
             hd.nonfinite_flag = nf_flag; hd.epoch = nf_epoch;
         }
         if (dec && t.heads.on) t.heads.decode = *dec;
-        t.dense3 = t32_dense3;
-        t.wide = wide;
-        prof.begin(split16 ? "kz_tower_resident_split" : pairs16 ? "kz_tower_resident_f16g" : "kz_tower_resident_f32", stream);
-        if (split16) kz::launch_tower_split(t, stream);
-        else if (pairs16) kz::launch_tower_pairs(t, false, stream);  // f16 tensors behind the same pointers
+#ifdef KZ_EXPERIMENTS
+        t.dense3 = plan.t32_dense3;
+#endif
+        t.wide = plan.wide;
+        const bool f16g = plan.tower == Tower::resident_f16g;
+        prof.begin(split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : "kz_tower_resident_f32", stream);
+        if (split16()) kz::launch_tower_split(t, stream);
+        else if (f16g) kz::launch_tower_pairs(t, false, stream);  // f16 tensors behind the same pointers
         else kz::launch_tower32(t, stream);
         prof.end(stream);
         HIP_TRY(hipGetLastError());
         tower_out = 0;
         return 0;
     }
-    if (bsplit) {
+    if (plan.tower == Tower::board_conv_split16) {
         // the stem in exact f32 (its inputs are f32 planes), its output split into (hi, lo) halves — an f32 tensor and a
         // (hi, lo) tensor of the same shape have the same size, so the three activation buffers serve both —, the
         // 2·depth tower convolutions in split arithmetic, the last one writing f32 for the heads
@@ -246,15 +249,15 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
 inline bool kz_engine::extra_in_scalar_head() const {
     const Model &m = *model;
     return m.policy_kind == kz::POLICY_CONV && m.policy_extra_moves > 0 && wts->sh_w0x &&
-           kz::scalar_head_takes_extra(dtype == KZ_DTYPE_F32 || split16 ? 0 : 1, cp, m.sh_conv.cout);
+           kz::scalar_head_takes_extra(dtype == KZ_DTYPE_F32 ? 0 : 1, cp, m.sh_conv.cout);
 }
 
 inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
-    if (fused_heads || fused32 || fused_split || fused_pairs || dense_net) return 0;  // written by the tower launch
+    if (plan.heads || plan.tower == Tower::dense_net) return 0;  // written by the tower launch
     const Model &m = *model;
     const int hw = m.h * m.w, M = batch * hw;
     const void *x = act[tower_out];
-    if (wts->att_heads) {  // ScalarHead + AttentionPolicyHead in one launch
+    if (plan.att_heads) {  // ScalarHead + AttentionPolicyHead in one launch
         kz::AttHeadsArgs a{};
         a.x = x; a.ldx = cp; a.batch = batch; a.channels = m.channels; a.q = m.policy_query_channels;
         a.hc = m.sh_conv.cout; a.hs = m.sh_fc0.out; a.policy_len = m.policy_len;
@@ -291,7 +294,7 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
                 kz::conv1x1_policy_epilogue_supported(c0.cin_p, c0.cout_p, c0.cout, pc)) {
                 // Conv1x1 C->C + ReLU + Conv1x1 C->1 in one launch: the hidden layer never goes to memory
                 kz::Conv1x1SplitArgs c{};
-                c.split = split16;
+                c.split = split16();
                 c.x = x; c.ldx = cp; c.weights = c0.sw; c.bias = c0.b; c.y = nullptr; c.ldy = 0;
                 c.M = M; c.cin_p = c0.cin_p; c.cout_p = c0.cout_p; c.relu = 1;
                 c.group = hw; c.src_group = hw; c.src_off = 0;
@@ -379,11 +382,11 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
     return 0;
 }
 
-// dec (decode_in_launch() engines only): the launch ends in decode_output and writes dec->values / dec->probs
+// dec (plan.heads only): the launch ends in decode_output and writes dec->values / dec->probs
 inline int kz_engine::forward_packed(const void *d_bits, size_t stride, const void *d_sin, int batch, void *d_sout, void *d_pol,
                    const kz::DecodeArgs *dec) {
     const Model &m = *model;
-    if (resident || resident32 || pairs16 || att_f16) {  // encode is fused into the tower launch
+    if (encodes_boards(plan)) {
         const PackedIn in{d_bits, stride, d_sin};
         if (run_tower(batch, (float *)d_sout, (float *)d_pol, &in, dec)) return 1;
         return run_heads(batch, (float *)d_sout, (float *)d_pol);

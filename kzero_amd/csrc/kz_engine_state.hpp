@@ -1,8 +1,9 @@
 // kz_engine_state.hpp — what an engine IS: the per-launch profiler, the model handle, and `struct kz_engine` with its
-// streams, slots (pinned staging + device buffers), range-check epochs and allocation bookkeeping.  The forward pass over
+// path (one PathPlan of kz_plan.hpp, asked whenever a kernel choice depends on it), streams, slots (pinned staging + device
+// buffers), range-check epochs and allocation bookkeeping.  The forward pass over
 // that state — which kernels run, in which order — is declared here and defined in kz_engine_forward.hpp; the `extern "C"`
 // entry points that drive both are kz_engine.hip.  Included ONCE, by kz_engine.hip, inside its anonymous namespace (the
-// first part) — the same arrangement as kz_engine_util.hpp / kz_device_weights.hpp / kz_plan.hpp.
+// first part) — the same arrangement as kz_engine_util.hpp / kz_plan.hpp / kz_device_weights.hpp.
 #pragma once
 
 struct Prof {
@@ -47,8 +48,6 @@ struct Prof {
 };
 
 
-#include "kz_plan.hpp"  // PathPlan, plan_path: which kernels run a network
-
 }  // namespace
 
 struct kz_model {
@@ -88,7 +87,7 @@ std::shared_ptr<Model> effective_model(const kz_model *model, int dtype_in, int 
     PathPlan pw, po;
     std::string why;
     if (!plan_path(*wide, max_batch, dtype_in, pw, why)) return model->m;
-    if (pw.path.compare(0, 10, "conv_igemm") == 0 && plan_path(m, max_batch, dtype_in, po, why)) return model->m;
+    if (pw.tower == Tower::conv_igemm && plan_path(m, max_batch, dtype_in, po, why)) return model->m;
     return wide;
 }
 }  // namespace
@@ -113,20 +112,9 @@ struct kz_engine {
         return 0;
     }
     std::vector<void *> allocs, pinned;
-    bool dense_net = false;  // DenseNetwork: kz_dense_network.hip runs the whole network
-    bool att_tower = false;  // AttentionTower network: kz_att_tower.hip runs the tower
-    bool att_f16 = false;    // ... kz_att_tower_f16.hip does
-    bool resident = false, fused_heads = false, resident32 = false, split16 = false, pairs16 = false;
-    bool bsplit = false;  // split16 per layer through kz_board_conv_split16 (Go-size boards)
-    bool wide = false;    // the plain-f16 one-launch tower with twice the boards per workgroup (PathPlan::wide)
-    bool fused32 = false;  // the exact-f32 resident launch with the conv policy head and the scalar head inside
-    bool fused_split = false;  // the split-f16 launch with the scalar head and the policy head inside
-    bool fused_pairs = false;  // the plain-f16 generic launch with the conv policy head and the scalar head inside
-    bool nb4 = false;        // resident chess tower with four boards per workgroup (KZ_TOWER_NB=4)
-    bool tower_prev = false;  // resident chess tower: the round-6 address arithmetic (experiment build: KZ_TOWER_PREV=1)
-    bool t32_dense3 = false;  // exact-f32 launch with three 7x7 boards per workgroup (experiment build: KZ_T32_BOARDS=3)
-    void *xres = nullptr;    // its residual scratch
-    std::string path;
+    PathPlan plan;  // which kernels run the network (plan_path, then the experiment build's switches)
+    bool split16() const { return split_arithmetic(plan); }
+    void *xres = nullptr;  // (experiment build, PathPlan::nb4: the four-board launch's residual scratch)
 
     // activations
     int cin_p = 0, cp = 0;
@@ -205,7 +193,7 @@ struct kz_engine {
 #ifndef KZ_EXPERIMENTS
     static constexpr bool graph_mode() { return false; }  // the replay is an experiment build's switch (no gain measured)
 #else
-    bool use_graph = false, graph_warm = false;
+    bool graph_warm = false;
     struct GraphEntry {
         int kind, batch;  // kind: slot index, or -1 for the device-resident entry point
         const void *bits;
@@ -215,7 +203,7 @@ struct kz_engine {
         hipGraphExec_t exec;
     };
     std::vector<GraphEntry> graphs;
-    bool graph_mode() const { return use_graph && graph_warm && !prof.on && !keep; }
+    bool graph_mode() const { return plan.graph && graph_warm && !prof.on && !plan.keep; }
     // runs `body` (which enqueues on `stream`) through the graph of this key: captured at first sight
     template <class Body>
     int replay(int kind, int batch, const void *bits, size_t stride, const void *sin, void *sout, void *pol, Body body) {
@@ -269,8 +257,7 @@ struct kz_engine {
                "and split-f16 paths overflow: evaluate this network with KZ_DTYPE_F32)";
     }
 
-    // debugging
-    bool keep = false;
+    // debugging (PathPlan::keep)
     std::map<std::string, void *> kept;
 
     Prof prof;
@@ -287,7 +274,7 @@ struct kz_engine {
     }
 
     int stash(const std::string &name, const void *src, int batch) {
-        if (!keep) return 0;
+        if (!plan.keep) return 0;
         const size_t bytes = (size_t)batch * model->h * model->w * cp * esz;
         auto it = kept.find(name);
         if (it == kept.end()) {
@@ -307,7 +294,6 @@ struct kz_engine {
     };
     int conv(const DevConv &w, const void *x, int ldx, void *y, int ldy, int M, int relu, const void *res, bool post,
              int h, int wd, int group, int src_group, int src_off, float *y32 = nullptr, int ldy32 = 0);
-    bool decode_in_launch() const { return fused_heads || fused32 || fused_split || fused_pairs; }
     int run_tower(int batch, float *d_scalars, float *d_policy, const PackedIn *packed = nullptr,
                   const kz::DecodeArgs *dec = nullptr);
     bool extra_in_scalar_head() const;

@@ -828,6 +828,19 @@ def test_large_batches_and_engine_churn(dev):
     assert np.array_equal(s3, s[:64])
 
 
+def test_head_temporaries_are_held_to_2gib(dev):
+    """The check in front of every HIP call bounds the tower's tensors and the policy rows; a head convolution wider than the
+    tower (conv_bulk: 256 channels behind a 32-channel tower) is bounded once the plan and the weights are known — refused
+    with the same message, before the engine allocates anything, instead of a 6.5 GB tensor behind 32-bit offsets."""
+    model = capi.Model(blob=synth.random_model("chess", 1, 32, "attention", query_channels=128, seed=63))
+    assert model.plan(100_000, capi.KZ_DTYPE_F32)[0] == "conv_igemm_f32"
+    with pytest.raises(capi.KzError, match="max_batch 100000 too large for this network: at most 32767 boards"):
+        capi.Engine(model, dev, 100_000, capi.KZ_DTYPE_F32)
+    bits, scalars_in = synth.random_boards("chess", 3, seed=64)
+    s, p = capi.Engine(model, dev, 8, capi.KZ_DTYPE_F32).eval_packed(bits, scalars_in)
+    assert np.isfinite(s).all() and np.isfinite(p).all()
+
+
 def test_go19_generic_path_vs_oracle(dev):
     """Large board (19x19, 13 input planes, conv head + pass move): the per-layer implicit-GEMM path."""
     blob = synth.random_model("go-19", 3, 64, "conv", seed=31)

@@ -20,6 +20,22 @@ def test_committed_path_table_is_what_the_selector_chooses():
     assert committed["lattice"] == fresh["lattice"], "lattice differs: regenerate with tools/gen_path_table.py"
 
 
+def test_committed_switch_table_is_what_the_selector_chooses():
+    """The environment switches' effect on the selector, every sweep case x arithmetic x max_batch x switch set."""
+    committed, fresh = json.load(open(gen_path_table.OUT))["switches"], gen_path_table.switches()
+    for key in ("dtypes", "max_batch", "sets"):
+        assert committed[key] == fresh[key], key
+    entries = [(d, mb, "+".join(s) or "none") for d in fresh["dtypes"] for mb in fresh["max_batch"] for s in fresh["sets"]]
+
+    def decode(table, case_id):
+        return [table["values"][gen_path_table.INDEX_CHARS.index(c)] for c in table["cases"][case_id]]
+
+    assert set(committed["cases"]) == set(fresh["cases"])
+    for case_id in fresh["cases"]:
+        diff = [(e, a, b) for e, a, b in zip(entries, decode(committed, case_id), decode(fresh, case_id)) if a != b]
+        assert not diff, f"{case_id}: (dtype, max_batch, switches), committed, now: {diff[:4]}"
+
+
 def test_every_sweep_case_has_a_one_launch_or_board_tile_path_at_128_channels_and_up():
     """No network with >= 128 tower channels in a multiple of 64 falls back to the generic implicit GEMM in f16 at the
     executor batch (VERDICT r3 #1): it takes a one-launch tower or the per-layer board-tile kernel."""

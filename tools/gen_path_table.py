@@ -7,6 +7,10 @@ build container.  It writes tests/golden/path_table.json:
   "paths":   {sweep case id: {"f32" | "f16" | "parity": tower path}}   for tests/test_shape_sweep.py (-m gpu)
   "lattice": rows (game, squares, c_in, channels, head) x (f32, f16, parity) -> tower path, launches per batch
              at max_batch 256, for the DESIGN table
+  "switches": every sweep case x (f32, f16, f32split16) x max_batch (1, 8, 256, 2048) x the environment switches that
+             steer the selector (none, or one of SWITCH_SETS) -> "path launches", or "refused".  Compact: the distinct
+             entries once ("values"), and per case one character per entry, an index into them, in the order
+             dtype, max_batch, switch set (the innermost)
 
 tests/test_path_table.py recomputes both from the built library and fails on any difference: a change of a support
 predicate has to come with a regenerated table (python tools/gen_path_table.py) and shows up in the diff.
@@ -29,6 +33,10 @@ from tests import sweep_cases  # noqa: E402
 OUT = os.path.join(REPO, "tests", "golden", "path_table.json")
 MAX_BATCH = 256
 DTYPES = {"f32": capi.KZ_DTYPE_F32, "f16": capi.KZ_DTYPE_F16, "f32split16": capi.KZ_DTYPE_F32_SPLIT16}
+SWITCH_BATCHES = (1, 8, 256, 2048)
+SWITCH_SETS = ((), ("KZ_FORCE_GENERIC",), ("KZ_NO_FUSED_HEADS",), ("KZ_NO_BOARD_CONV",), ("KZ_NO_RESIDENT_F16G",),
+               ("KZ_KEEP_ACTIVATIONS",), ("KZ_FORCE_GENERIC", "KZ_KEEP_ACTIVATIONS"))
+INDEX_CHARS = "".join(chr(c) for c in range(0x21, 0x7f) if chr(c) not in "\\\"")  # one JSON-safe character per entry
 CHANNELS = (32, 48, 64, 96, 128, 160, 192, 256, 320, 384, 512)
 LATTICE_GAMES = [  # (game, head): every board size the reference's server accepts a mapper for, with its usual head
     ("ataxx-4", "ataxx_conv"), ("ataxx-5", "ataxx_conv"), ("ataxx-6", "ataxx_conv"), ("ataxx-7", "ataxx_conv"),
@@ -59,7 +67,37 @@ def build():
             model = capi.Model(blob=synth.random_model(game, 2, ch, head, seed=1, **kw))
             lattice.append({"game": game, "squares": g["size"] ** 2, "c_in": g["n_scalar"] + g["n_bool"], "channels": ch,
                             "head": head, **plans(model)})
-    return {"max_batch": MAX_BATCH, "paths": paths, "lattice": lattice}
+    return {"max_batch": MAX_BATCH, "paths": paths, "lattice": lattice, "switches": switches()}
+
+
+def switches():
+    """The selector under each switch set; the switches are read per call (kz_model_plan), so setting them in this
+    process's environment is enough."""
+    saved = {k: os.environ.pop(k) for k in {k for ks in SWITCH_SETS for k in ks} if k in os.environ}
+    values, cases = [], {}
+    try:
+        for case in sweep_cases.CASES:
+            model = capi.Model(blob=synth.random_model(case.game, case.depth, case.channels, case.head, seed=11, **case.kw))
+            row = []
+            for dtype in DTYPES.values():
+                for mb in SWITCH_BATCHES:
+                    for keys in SWITCH_SETS:
+                        os.environ.update({k: "1" for k in keys})
+                        try:
+                            entry = "%s %d" % model.plan(mb, dtype)
+                        except capi.KzError:
+                            entry = "refused"
+                        finally:
+                            for k in keys:
+                                del os.environ[k]
+                        if entry not in values:
+                            values.append(entry)
+                        row.append(INDEX_CHARS[values.index(entry)])
+            cases[case.id] = "".join(row)
+    finally:
+        os.environ.update(saved)
+    return {"dtypes": list(DTYPES), "max_batch": list(SWITCH_BATCHES), "sets": [list(k) for k in SWITCH_SETS],
+            "values": values, "cases": cases}
 
 
 def markdown(table, rates, games=None):
