@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 
@@ -398,13 +399,7 @@ void launch_board_conv2(const BoardConvArgs &t, hipStream_t stream) {
     d.rowmap = t.rowmap; d.halo = t.halo; d.n_halo = t.n_halo;
     static const int ablate = getenv("KZ_BC_ABLATE") ? atoi(getenv("KZ_BC_ABLATE")) : 0;
     d.ablate = ablate;
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_board_conv2_f16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        done_mask |= 1ull << (dev & 63);
-    }
+    allow_dynamic_lds<kz_board_conv2_f16>(160 * 1024);
     const int grid = ((d.groups + 7) / 8) * 8 * d.nq;
 #ifdef KZ_BC2_STAMPS
     static unsigned long long *stamp_buf = nullptr;

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 
@@ -28,6 +29,8 @@ typedef h16 h16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
+
+#include "kz_encode_dev.hpp"  // encoded_plane: the board encode's one statement
 
 constexpr int C = 256;
 constexpr int RS = C * 2 + 16;   // LDS bytes per pixel row (512 B of channels + 16 B pad: 16 rows -> 16 different slots)
@@ -56,10 +59,7 @@ struct Tower4Dev {
     h16 *y;
     uint4 *xres;  // [grid][XCHUNKS][256] x 16 B
     int cin_p, batch, depth;
-    const uint8_t *bits;
-    size_t bits_stride;
-    const float *scalars_in;
-    int n_scalar, n_bool;
+    PackedBoards in;
 };
 
 // The 256 accumulator registers of a wave (64 output channels x 256 pixels) are the WHOLE accumulator file.  Left to the
@@ -113,21 +113,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident4(Tower4Dev a) {
         const int board = board0 + b;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (board < a.batch) {
-            if (a.bits) {  // encode_input_full (rust/kz-core/src/mapping/mod.rs:40-63), 8 channels of one square
-                const uint8_t *bb = a.bits + (size_t)board * a.bits_stride;
+            if (a.in.bits) {  // 8 channels of one square (kz_encode_dev.hpp)
                 h16x8 e;
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int ch = c * 8 + j;
-                    float f = 0.0f;
-                    if (ch < a.n_scalar) {
-                        f = a.scalars_in[(size_t)board * a.n_scalar + ch];
-                    } else if (ch < a.n_scalar + a.n_bool) {
-                        const unsigned bit = (unsigned)(ch - a.n_scalar) * 64 + p;
-                        f = (float)((bb[bit >> 3] >> (bit & 7)) & 1);
-                    }
-                    e[j] = (h16)f;
-                }
+                for (int j = 0; j < 8; j++) e[j] = (h16)encoded_plane(a.in, board, c * 8 + j, p, 64);
                 v = *reinterpret_cast<const uint4 *>(&e);
             } else {
                 v = *reinterpret_cast<const uint4 *>(a.x0 + ((size_t)board * 64 + p) * a.cin_p + c * 8);
@@ -432,16 +421,9 @@ void launch_tower_resident4(const TowerArgs &t, void *xres, hipStream_t stream) 
     d.y = static_cast<h16 *>(t.y);
     d.xres = static_cast<uint4 *>(xres);
     d.cin_p = t.cin_p; d.batch = t.batch; d.depth = t.depth;
-    d.bits = t.bits; d.bits_stride = t.bits_stride; d.scalars_in = t.scalars_in; d.n_scalar = t.n_scalar; d.n_bool = t.n_bool;
-    auto kernel = kz_tower_resident4<4, 8>;
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L4::BYTES);
-        done_mask |= 1ull << (dev & 63);
-    }
-    kernel<<<(t.batch + NB - 1) / NB, 256, L4::BYTES, stream>>>(d);
+    d.in = t.in;
+    allow_dynamic_lds<kz_tower_resident4<4, 8>>(L4::BYTES);
+    kz_tower_resident4<4, 8><<<(t.batch + NB - 1) / NB, 256, L4::BYTES, stream>>>(d);
 }
 
 }  // namespace kz

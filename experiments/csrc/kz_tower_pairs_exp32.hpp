@@ -72,21 +72,11 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split32(SplitDev a) 
         const int row = id >> 3, c4 = id & 7;
         const bool have = row < rows_valid && c4 * 4 < a.ldx0;
         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (a.bits) {
-            // encode_input_full (rust/kz-core/src/mapping/mod.rs:40-63): scalar planes first, then the bool planes
+        if (a.in.bits) {  // (kz_encode_dev.hpp)
             if (row < rows_valid) {
                 const int b = (int)(((unsigned)row * a.inv_hw) >> 16), q = row - b * a.hw;
-                const uint8_t *bb = a.bits + (size_t)(board0 + b) * a.bits_stride;
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int ch = c4 * 4 + j;
-                    if (ch < a.n_scalar) {
-                        v[j] = a.scalars_in[(size_t)(board0 + b) * a.n_scalar + ch];
-                    } else if (ch < a.n_scalar + a.n_bool) {
-                        const unsigned bit = (unsigned)(ch - a.n_scalar) * a.hw + q;
-                        v[j] = (float)((bb[bit >> 3] >> (bit & 7)) & 1);
-                    }
-                }
+                for (int j = 0; j < 4; j++) v[j] = encoded_plane(a.in, board0 + b, c4 * 4 + j, q, a.hw);
             }
         } else if constexpr (SPLIT) {
             if (have) v = *reinterpret_cast<const f32x4 *>(static_cast<const float *>(a.x0) + ((size_t)board0 * a.hw + row) * a.ldx0 + c4 * 4);
@@ -342,13 +332,6 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split32(SplitDev a) 
 
 template <bool SPLIT>
 void launch32(const SplitDev &d, int grid, hipStream_t stream) {
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_tower_resident_split32<SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  Geo<256, 4, SPLIT>::LDS_BYTES_OWN_STEM);
-        done_mask |= 1ull << (dev & 63);
-    }
+    allow_dynamic_lds<kz_tower_resident_split32<SPLIT>>(Geo<256, 4, SPLIT>::LDS_BYTES_OWN_STEM);
     kz_tower_resident_split32<SPLIT><<<grid, 256, Geo<256, 4, SPLIT>::LDS_BYTES_OWN_STEM, stream>>>(d);
 }

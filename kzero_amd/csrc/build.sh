@@ -27,12 +27,21 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -mcode-obj
 mkdir -p $B
 # a change of flags rebuilds everything
 if [ "$(cat $B/.flags 2>/dev/null)" != "$FLAGS" ]; then rm -f $B/*.o; echo "$FLAGS" > $B/.flags; fi
+# an object is rebuilt when its source, any header here or in experiments/csrc, or the C ABI header is newer than it
+stale() {
+  local obj=$1 src=$2 f
+  [ -f "$obj" ] || return 0
+  for f in "$src" *.hpp ../../experiments/csrc/*.hpp ../../include/kz_hip.h; do
+    if [ "$f" -nt "$obj" ]; then return 0; fi
+  done
+  return 1
+}
 pids=()
 objs=()
 for src in $HIP_SRCS; do
   obj=$B/$(basename ${src%.hip}).o
   objs+=("$obj")
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ kz_kernels.hpp -nt "$obj" ] || [ kz_conv_heads.hpp -nt "$obj" ] || [ kz_decode_dev.hpp -nt "$obj" ] || [ kz_tower_pairs.hpp -nt "$obj" ] || [ kz_tower_pairs_shapes.hpp -nt "$obj" ] || [ ../../experiments/csrc/kz_tower_pairs_exp32.hpp -nt "$obj" ] || [ kz_model.hpp -nt "$obj" ] || [ ../../include/kz_hip.h -nt "$obj" ] || { [ "$src" = kz_engine.hip ] && { [ kz_plan.hpp -nt "$obj" ] || [ kz_device_weights.hpp -nt "$obj" ] || [ kz_engine_util.hpp -nt "$obj" ] || [ kz_engine_state.hpp -nt "$obj" ] || [ kz_engine_forward.hpp -nt "$obj" ]; }; }; then
+  if stale "$obj" "$src"; then
     $HIPCC $FLAGS -c "$src" -o "$obj" &
     pids+=($!)
   fi
@@ -40,7 +49,7 @@ done
 for src in kz_model.cpp kz_onnx.cpp; do
   obj=$B/${src%.cpp}.o
   objs+=("$obj")
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ kz_model.hpp -nt "$obj" ] || [ kz_onnx_match.hpp -nt "$obj" ]; then
+  if stale "$obj" "$src"; then
     g++ -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -c "$src" -o "$obj" &
     pids+=($!)
   fi

@@ -12,6 +12,7 @@
 // of one token into the q_from / k_to rows; the logits are a second GEMM over those rows (24 tile pairs, three per wave).
 // conv_under's rows are stored r-major (row r Q + q = the reference's 3 q + r) so that a tile is 16 q of one r.
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 namespace {
@@ -261,13 +262,7 @@ void launch_att_heads(const AttHeadsArgs &t, hipStream_t stream) {
     d.nonfinite_flag = t.nonfinite_flag; d.epoch = t.epoch;
     d.inv_sqrt_q = 1.0f / sqrtf((float)t.q);
     const size_t bytes = ah_geo(cp, t.q, t.hc, t.hs).bytes;
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_att_heads_f16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        done_mask |= 1ull << (dev & 63);
-    }
+    allow_dynamic_lds<kz_att_heads_f16>(160 * 1024);
     kz_att_heads_f16<<<t.batch, AH_THREADS, bytes, stream>>>(d);
 }
 

@@ -10,6 +10,7 @@
 // All arithmetic is f32 FMA (this is the <= 1e-4 path, and the path of every shape the matrix-core kernel kz_att_tower_mfma.hip does not
 // take); the rows it reads and writes are f32 or f16 as the engine's other kernels expect them.
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 namespace {
@@ -290,13 +291,7 @@ void launch_att_tower(const AttTowerArgs &t, hipStream_t stream) {
     d.batch = t.batch; d.depth = t.depth; d.alpha = t.alpha; d.eps = t.eps;
     d.g = att_geo(t.h * t.w, t.c_in, t.d_model, t.heads, t.d_k, t.d_v, t.d_ff);
     const size_t lds = d.g.lds_floats * 4;
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_att_tower_f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AT_MAX_LDS);
-        done_mask |= 1ull << (dev & 63);
-    }
+    allow_dynamic_lds<kz_att_tower_f32>((int)AT_MAX_LDS);
     if (t.batch <= 0) return;
     kz_att_tower_f32<<<t.batch, AT_THREADS, lds, stream>>>(d);
 }

@@ -19,9 +19,12 @@
 // B operand of that product.  Softmax over the keys (attention.py:119, no scale factor :117): in-lane over 16 values, two
 // butterflies.
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 namespace {
+
+#include "kz_encode_dev.hpp"  // encoded_plane: the board encode's one statement
 
 typedef _Float16 h16;
 typedef h16 h16x8 __attribute__((ext_vector_type(8)));
@@ -70,11 +73,7 @@ struct AttTower16Dev {
     const float *embedding; // [64][D] f32
     const uint4 *w_layers;  // per layer: project_qkv | project_out | ff.0 | ff.2 fragments
     void *y;                // [batch * 64][D]
-    // fused board encode (F0, rust/kz-core/src/mapping/mod.rs:40-63): packed boards straight into the launch (bits == nullptr: x0)
-    const uint8_t *bits;
-    size_t bits_stride;
-    const float *scalars_in;
-    int n_scalar, n_bool;
+    PackedBoards in;        // fused board encode (F0): packed boards straight into the launch (in.bits == nullptr: x0)
     int batch, depth;
     float alpha, eps;
 };
@@ -269,26 +268,12 @@ __global__ __launch_bounds__(A16_THREADS) void kz_att_tower_mfma(AttTower16Dev a
         // ---- the boards' encoded planes -> LDS (a board past the batch's end repeats the last one and is not stored) ----
         __syncthreads();
         const int per_row = a.cin_p / FE;
-        if (a.bits) {
-            // scalar planes first, each broadcast over the board, then the bool planes: bool i of a board = bit i % 8 of byte
-            // i / 8 (bit_buffer.rs:73-75), i = plane * 64 + square
+        if (a.in.bits) {  // (kz_encode_dev.hpp)
             for (int i = tid; i < S::ROWS * per_row; i += A16_THREADS) {
                 const int c = i / S::ROWS, r = i - c * S::ROWS, board = min(board0 + r / A16_TOKENS, a.batch - 1), sq = r % A16_TOKENS;
-                const uint8_t *bb = a.bits + (size_t)board * a.bits_stride;
-                const float *sc = a.scalars_in + (size_t)board * a.n_scalar;
                 typename O::Frag v;
 #pragma unroll
-                for (int j = 0; j < FE; j++) {
-                    const int ch = c * FE + j;
-                    float f = 0.0f;
-                    if (ch < a.n_scalar) {
-                        f = sc[ch];
-                    } else if (ch < a.n_scalar + a.n_bool) {
-                        const unsigned bit = (unsigned)(ch - a.n_scalar) * A16_TOKENS + sq;
-                        f = (float)((bb[bit >> 3] >> (bit & 7)) & 1);
-                    }
-                    v[j] = (E)f;
-                }
+                for (int j = 0; j < FE; j++) v[j] = (E)encoded_plane(a.in, board, c * FE + j, sq, A16_TOKENS);
                 *reinterpret_cast<typename O::Frag *>(R + r * ldi + c * FE) = v;
             }
         } else {
@@ -447,13 +432,7 @@ __global__ __launch_bounds__(A16_THREADS) void kz_att_tower_mfma(AttTower16Dev a
 template <class O, int D, int DFF, int NB>
 void launch1(const AttTower16Dev &d, hipStream_t stream) {
     using S = A16Shape<O, D, DFF, NB>;
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_att_tower_mfma<O, D, DFF, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::LDS_BYTES);
-        done_mask |= 1ull << (dev & 63);
-    }
+    allow_dynamic_lds<kz_att_tower_mfma<O, D, DFF, NB>>((int)S::LDS_BYTES);
     kz_att_tower_mfma<O, D, DFF, NB><<<(d.batch + NB - 1) / NB, A16_THREADS, S::LDS_BYTES, stream>>>(d);
 }
 
@@ -547,7 +526,7 @@ void launch_att_tower16(const AttTower16Args &t, hipStream_t stream) {
     d.x0 = t.x0; d.cin_p = t.cin_p;
     d.w_expand = static_cast<const uint4 *>(t.w_expand); d.embedding = t.embedding;
     d.w_layers = static_cast<const uint4 *>(t.w_layers);
-    d.bits = t.bits; d.bits_stride = t.bits_stride; d.scalars_in = t.scalars_in; d.n_scalar = t.n_scalar; d.n_bool = t.n_bool;
+    d.in = t.in;
     d.y = t.y; d.batch = t.batch; d.depth = t.depth; d.alpha = t.alpha; d.eps = t.eps;
     if (t.f32) {
         if (t.d_model == 128 && t.d_ff == 128) launch1<OpsF32, 128, 128, 1>(d, stream);

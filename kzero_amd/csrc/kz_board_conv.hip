@@ -44,6 +44,7 @@
 #include <type_traits>
 
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 
@@ -833,19 +834,11 @@ void launch_board_conv_any(const BoardConvArgs &t, bool split, hipStream_t strea
     d.relu = t.relu;
     d.groups = (t.boards + d.bpw - 1) / d.bpw;
     d.nq = t.cout / OCW;
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
     d.inv_tpb = (65536u + (unsigned)geo.tpb - 1) / (unsigned)geo.tpb;
     d.inv_w = (65536u + (unsigned)t.w - 1) / (unsigned)t.w;
     const unsigned nhb = (unsigned)geo.line16 + 5 * ((unsigned)geo.pitch + 1) + 10 * (unsigned)t.h;  // halo slots per board and plane
     d.inv_nhb = (unsigned)(((1ull << 32) + nhb - 1) / nhb);  // __umulhi(id, inv) == id / nhb for id * nhb < 2^32
     d.inv_10 = (65536u + 9) / 10;
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_board_conv_f16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void *)kz_board_conv_split16, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        done_mask |= 1ull << (dev & 63);
-    }
     const int grid = ((d.groups + 7) / 8) * 8 * d.nq;
 #ifdef KZ_BC_STAMPS
 #ifdef KZ_BC_REALTIME
@@ -863,8 +856,13 @@ void launch_board_conv_any(const BoardConvArgs &t, bool split, hipStream_t strea
 #else
     d.stamps = nullptr;
 #endif
-    if (split) kz_board_conv_split16<<<grid, 256, geo.lds_bytes, stream>>>(d);
-    else kz_board_conv_f16<<<grid, 256, geo.lds_bytes, stream>>>(d);
+    if (split) {
+        allow_dynamic_lds<kz_board_conv_split16>(160 * 1024);
+        kz_board_conv_split16<<<grid, 256, geo.lds_bytes, stream>>>(d);
+    } else {
+        allow_dynamic_lds<kz_board_conv_f16>(160 * 1024);
+        kz_board_conv_f16<<<grid, 256, geo.lds_bytes, stream>>>(d);
+    }
 #ifdef KZ_BC_STAMPS
     if (launches++ == stamp_launch + KEPT - 1 && getenv("KZ_BC_STAMP_FILE")) {
         (void)hipStreamSynchronize(stream);

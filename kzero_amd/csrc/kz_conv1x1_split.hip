@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 
@@ -232,6 +233,14 @@ void conv1x1_split_pack_weights(const float *w, int cout, int cin, int cout_p, i
         }
 }
 
+namespace {
+template <auto Kernel>
+void go(const Conv1x1SplitDev &d, int grid, int lds_bytes, hipStream_t stream) {
+    allow_dynamic_lds<Kernel>(160 * 1024);
+    Kernel<<<grid, 256, lds_bytes, stream>>>(d);
+}
+}  // namespace
+
 void launch_conv1x1_split(const Conv1x1SplitArgs &t, hipStream_t stream) {
     Conv1x1SplitDev d{};
     d.x = t.x;
@@ -250,37 +259,27 @@ void launch_conv1x1_split(const Conv1x1SplitArgs &t, hipStream_t stream) {
     const int lds_bytes = (t.split ? 2 : 1) * 64 * (t.cin_p * 2 + 16);
     const int grid = (t.M + 63) / 64;
     const int ot = conv1x1_split_ot(t.cout_p);
-    auto go = [&](auto kernel) {
-        static thread_local unsigned long long done_mask = 0;  // per instantiation
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (!((done_mask >> (dev & 63)) & 1)) {
-            (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            done_mask |= 1ull << (dev & 63);
-        }
-        kernel<<<grid, 256, lds_bytes, stream>>>(d);
-    };
     if (t.policy) {  // (conv1x1_policy_epilogue_supported)
         d.pw1 = t.pw1; d.pb1 = t.pb1; d.policy = t.policy; d.policy_len = t.policy_len; d.hw = t.hw;
         if (t.split) {
-            if (ot == 4) go(kz_conv1x1_split<4, true, true>);
-            else if (ot == 2) go(kz_conv1x1_split<2, true, true>);
-            else go(kz_conv1x1_split<1, true, true>);
+            if (ot == 4) go<kz_conv1x1_split<4, true, true>>(d, grid, lds_bytes, stream);
+            else if (ot == 2) go<kz_conv1x1_split<2, true, true>>(d, grid, lds_bytes, stream);
+            else go<kz_conv1x1_split<1, true, true>>(d, grid, lds_bytes, stream);
         } else {
-            if (ot == 4) go(kz_conv1x1_split<4, false, true>);
-            else if (ot == 2) go(kz_conv1x1_split<2, false, true>);
-            else go(kz_conv1x1_split<1, false, true>);
+            if (ot == 4) go<kz_conv1x1_split<4, false, true>>(d, grid, lds_bytes, stream);
+            else if (ot == 2) go<kz_conv1x1_split<2, false, true>>(d, grid, lds_bytes, stream);
+            else go<kz_conv1x1_split<1, false, true>>(d, grid, lds_bytes, stream);
         }
         return;
     }
     if (t.split) {
-        if (ot == 4) go(kz_conv1x1_split<4, true>);
-        else if (ot == 2) go(kz_conv1x1_split<2, true>);
-        else go(kz_conv1x1_split<1, true>);
+        if (ot == 4) go<kz_conv1x1_split<4, true>>(d, grid, lds_bytes, stream);
+        else if (ot == 2) go<kz_conv1x1_split<2, true>>(d, grid, lds_bytes, stream);
+        else go<kz_conv1x1_split<1, true>>(d, grid, lds_bytes, stream);
     } else {
-        if (ot == 4) go(kz_conv1x1_split<4, false>);
-        else if (ot == 2) go(kz_conv1x1_split<2, false>);
-        else go(kz_conv1x1_split<1, false>);
+        if (ot == 4) go<kz_conv1x1_split<4, false>>(d, grid, lds_bytes, stream);
+        else if (ot == 2) go<kz_conv1x1_split<2, false>>(d, grid, lds_bytes, stream);
+        else go<kz_conv1x1_split<1, false>>(d, grid, lds_bytes, stream);
     }
 }
 

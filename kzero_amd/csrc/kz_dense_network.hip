@@ -5,6 +5,7 @@
 // inputs across the lanes (f32 FMA, coalesced weight rows).  These are networks of a few ten thousand parameters: the kernel
 // is here so that every network the reference's Python can export runs, not for its rate.
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 namespace {
@@ -88,13 +89,7 @@ size_t dense_network_block_elems(int size) { return (size_t)2 * size * size + 6 
 
 void launch_dense_network(const DenseNetArgs &a, hipStream_t stream) {
     if (a.batch <= 0) return;
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_dense_network, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        done_mask |= 1ull << (dev & 63);
-    }
+    allow_dynamic_lds<kz_dense_network>(160 * 1024);
     kz_dense_network<<<a.batch, DN_THREADS, dn_lds_bytes(a.hw, a.cin_p, a.size, a.policy_len), stream>>>(a);
 }
 

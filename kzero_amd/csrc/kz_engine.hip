@@ -379,6 +379,13 @@ static int check_packed(const kz_engine *e, const char *fn) {
     return 0;
 }
 
+// a submit runs on its slot's stream (when the slot has one) and puts the engine's own back when it returns
+struct StreamSwap {
+    kz_engine *e;
+    hipStream_t saved;
+    ~StreamSwap() { e->stream = saved; }
+};
+
 static int check_batch(const kz_engine *e, int batch, const char *fn) {
     if (!e) return fail(std::string(fn) + ": null engine");
     if (batch < 0 || batch > e->max_batch)  // assert!(batch_size <= max_batch_size), cudnn.rs:58
@@ -407,17 +414,13 @@ KZ_API int kz_engine_submit_packed(kz_engine *e, int slot, const uint8_t *bits, 
         if (m.n_scalar) memcpy(s.h_sin, scalars_in, (size_t)batch * m.n_scalar * 4);
         // on the fused path every slot has its own stream, so two submitted batches run side by side (each resident
         // launch covers half of the CUs at batch 256); otherwise the slots share the activation buffers and one stream
-        struct StreamSwap {
-            kz_engine *e;
-            hipStream_t saved;
-            ~StreamSwap() { e->stream = saved; }
-        } swap{e, e->stream};
+        StreamSwap swap{e, e->stream};
         if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
         if (e->zero_copy) {
             // the one launch reads 136 B per board from pinned host memory and writes its 7.5 KB per board there
             e->arm(s);
             e->nf_flag = reinterpret_cast<int *>(s.h_sout);
-            if (e->forward_packed(s.h_bits, bits_bytes, s.h_sin, batch, s.h_sout + kz_engine::SOUT_HDR, s.h_pol)) return 1;
+            if (e->forward_packed(e->packed_boards(s.h_bits, bits_bytes, s.h_sin), batch, s.h_sout + kz_engine::SOUT_HDR, s.h_pol)) return 1;
             HIP_TRY(hipEventRecord(s.done, e->stream));
             s.batch = batch;
             return 0;
@@ -431,14 +434,14 @@ KZ_API int kz_engine_submit_packed(kz_engine *e, int slot, const uint8_t *bits, 
             e->nf_epoch = s.epoch;
             if (e->replay(slot, batch, s.d_bits, bits_bytes, s.d_sin, s.d_sout, s.d_pol, [&]() -> int {
                     HIP_TRY(hipMemsetAsync(s.d_sout, 0, 4, e->stream));
-                    return e->forward_packed(s.d_bits, bits_bytes, s.d_sin, batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol);
+                    return e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol);
                 }))
                 return 1;
         } else
     #endif
         {
             e->arm(s);
-            if (e->forward_packed(s.d_bits, bits_bytes, s.d_sin, batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+            if (e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
     #ifdef KZ_EXPERIMENTS
             e->graph_warm = true;  // (the first pass runs eagerly: lazy per-kernel set-up must not land in a capture)
     #endif
@@ -539,11 +542,7 @@ KZ_API int kz_engine_submit_packed_decoded(kz_engine *e, int slot, const uint8_t
         memcpy(s.h_moff, move_offsets, (size_t)(batch + 1) * 8);
         if (total) memcpy(s.h_midx, move_indices, total * 4);
         s.h_err[0] = s.h_err[1] = 0;
-        struct StreamSwap {
-            kz_engine *e;
-            hipStream_t saved;
-            ~StreamSwap() { e->stream = saved; }
-        } swap{e, e->stream};
+        StreamSwap swap{e, e->stream};
         if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
         if (e->zero_copy && e->plan.heads) {
             // ONE launch and no copy operation: it reads the packed boards and the move lists from the slot's pinned staging
@@ -553,7 +552,7 @@ KZ_API int kz_engine_submit_packed_decoded(kz_engine *e, int slot, const uint8_t
             e->arm(s);
             e->nf_flag = reinterpret_cast<int *>(s.h_sout);
             const kz::DecodeArgs dec{s.h_moff, s.h_midx, s.h_values, s.h_probs, s.h_err};
-            if (e->forward_packed(s.h_bits, bits_bytes, s.h_sin, batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &dec)) return 1;
+            if (e->forward_packed(e->packed_boards(s.h_bits, bits_bytes, s.h_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &dec)) return 1;
             HIP_TRY(hipEventRecord(s.done, e->stream));
             s.batch = batch;
             s.decoded = s.in_launch = true;
@@ -566,12 +565,12 @@ KZ_API int kz_engine_submit_packed_decoded(kz_engine *e, int slot, const uint8_t
         HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, batch * bits_bytes, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)batch * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
         e->arm(s);
-        if (e->forward_packed(s.d_bits, bits_bytes, s.d_sin, batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
-        e->prof.begin("kz_decode_output", e->stream);
-        kz::launch_decode_output(s.d_sout + kz_engine::SOUT_HDR, s.d_pol, batch, m.policy_len, s.h_moff, s.h_midx, s.h_values,
-                                 s.h_probs, s.h_err, reinterpret_cast<const int *>(s.d_sout), s.epoch, e->stream);
-        e->prof.end(e->stream);
-        HIP_TRY(hipGetLastError());
+        if (e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+        if (e->launch("kz_decode_output", [&] {
+                kz::launch_decode_output(s.d_sout + kz_engine::SOUT_HDR, s.d_pol, batch, m.policy_len, s.h_moff, s.h_midx, s.h_values,
+                                         s.h_probs, s.h_err, reinterpret_cast<const int *>(s.d_sout), s.epoch, e->stream);
+            }))
+            return 1;
         HIP_TRY(hipEventRecord(s.done, e->stream));
         s.batch = batch;
         s.decoded = true;
@@ -668,12 +667,12 @@ KZ_API int kz_engine_enqueue_packed_device(kz_engine *e, const void *d_bits, siz
         if (e->graph_mode()) {
             e->nf_epoch = kz_engine::GRAPH_EPOCH;
             return e->replay(-1, batch, d_bits, bits_stride, d_scalars_in, d_scalars_out, d_policy_out, [&]() -> int {
-                return e->forward_packed(d_bits, bits_stride, d_scalars_in, batch, d_scalars_out, d_policy_out);
+                return e->forward_packed(e->packed_boards(d_bits, bits_stride, d_scalars_in), batch, d_scalars_out, d_policy_out);
             });
         }
         e->graph_warm = true;
     #endif
-        return e->forward_packed(d_bits, bits_stride, d_scalars_in, batch, d_scalars_out, d_policy_out);
+        return e->forward_packed(e->packed_boards(d_bits, bits_stride, d_scalars_in), batch, d_scalars_out, d_policy_out);
     });
 }
 

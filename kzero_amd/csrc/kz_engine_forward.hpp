@@ -12,11 +12,7 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
         b.post_scale = post ? wts->post_scale : nullptr;
         b.post_shift = post ? wts->post_shift : nullptr;
         b.boards = M / (h * wd); b.h = h; b.w = wd; b.cin = w.cin_p; b.cout = w.cout; b.relu = relu;
-        prof.begin("kz_board_conv_split16", stream);
-        kz::launch_board_conv_split(b, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch("kz_board_conv_split16", [&] { kz::launch_board_conv_split(b, stream); });
     }
     if (w.bw) {  // whole boards as LDS-resident spatial tiles
         kz::BoardConvArgs b{};
@@ -25,15 +21,13 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
         b.post_shift = post ? wts->post_shift : nullptr;
         b.boards = M / (h * wd); b.h = h; b.w = wd; b.cin = w.cin_p; b.cout = w.cout; b.relu = relu;
         b.rowmap = wts->bc_rowmap; b.halo = wts->bc_halo; b.n_halo = wts->bc_n_halo;
-        prof.begin("kz_board_conv_f16", stream);
+        return launch("kz_board_conv_f16", [&] {
 #ifdef KZ_EXPERIMENTS
-        if (w.bw2) kz::launch_board_conv2(b, stream);
-        else
+            if (w.bw2) kz::launch_board_conv2(b, stream);
+            else
 #endif
-        kz::launch_board_conv(b, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
-        return 0;
+            kz::launch_board_conv(b, stream);
+        });
     }
     if (w.sw && y && !res && !post && !y32 && ldx >= w.cin_p) {  // 1x1 head convolution: split16 or any f16 path
         kz::Conv1x1SplitArgs c{};
@@ -41,11 +35,7 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
         c.x = x; c.ldx = ldx; c.weights = w.sw; c.bias = w.b; c.y = y; c.ldy = ldy;
         c.M = M; c.cin_p = w.cin_p; c.cout_p = w.cout_p; c.relu = relu;
         c.group = group; c.src_group = src_group; c.src_off = src_off;
-        prof.begin("kz_conv1x1_split", stream);
-        kz::launch_conv1x1_split(c, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch("kz_conv1x1_split", [&] { kz::launch_conv1x1_split(c, stream); });
     }
     kz::ConvArgs a{};
     a.x = x; a.ldx = ldx; a.w = w.w; a.bias = w.b; a.res = res; a.ldres = ldy;
@@ -54,17 +44,13 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
     a.y = y; a.y32 = y32; a.ldy = ldy; a.ldy32 = ldy32;
     a.M = M; a.h = h; a.w_ = wd; a.group = group; a.src_group = src_group; a.src_off = src_off;
     a.cin_p = w.cin_p; a.cout_p = w.cout_p; a.cout = w.cout; a.k = w.k; a.relu = relu;
-    prof.begin(kz::conv_kernel_name(dtype), stream);
-    kz::launch_conv(dtype, a, stream);
-    prof.end(stream);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return launch(kz::conv_kernel_name(dtype), [&] { kz::launch_conv(dtype, a, stream); });
 }
 
 // packed != nullptr (encodes_boards(plan) only): the launch encodes the boards itself.  The "+heads" launches (plan.heads) can
 // end in decode_output (kz_decode_dev.hpp): with `dec` nothing but the decoded values and the available moves' probabilities
 // leave the launch
-inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, const PackedIn *packed,
+inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, const kz::PackedBoards *packed,
               const kz::DecodeArgs *dec) {
     const Model &m = *model;
     const int hw = m.h * m.w, M = batch * hw;
@@ -75,10 +61,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.w_in = wts->dn_w_in; t.b_in = wts->dn_b_in; t.blocks = wts->dn_blocks; t.sf = wts->dn_sf; t.tf = wts->dn_tf;
         t.w_out = wts->dn_w_out; t.b_out = wts->dn_b_out; t.scalars = d_scalars; t.policy = d_policy;
         t.nonfinite_flag = nf_flag; t.epoch = nf_epoch;
-        prof.begin("kz_dense_network", stream);
-        kz::launch_dense_network(t, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
+        if (launch("kz_dense_network", [&] { kz::launch_dense_network(t, stream); })) return 1;
         tower_out = 0;
         return 0;
     }
@@ -88,17 +71,8 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.x0 = x_in; t.cin_p = cin_p; t.w_expand = wts->att16_expand; t.embedding = wts->att_embedding;
         t.w_layers = wts->att16_layers; t.y = act[0]; t.batch = batch; t.depth = m.depth; t.d_model = m.channels;
         t.d_ff = m.att_dff; t.alpha = m.att_alpha; t.eps = m.ln_eps;
-        if (packed) {  // fused board encode
-            t.bits = (const uint8_t *)packed->bits;
-            t.bits_stride = packed->stride;
-            t.scalars_in = (const float *)packed->scalars;
-            t.n_scalar = m.n_scalar;
-            t.n_bool = m.n_bool;
-        }
-        prof.begin(t.f32 ? "kz_att_tower_f32" : "kz_att_tower_f16", stream);
-        kz::launch_att_tower16(t, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
+        if (packed) t.in = *packed;  // fused board encode
+        if (launch(t.f32 ? "kz_att_tower_f32" : "kz_att_tower_f16", [&] { kz::launch_att_tower16(t, stream); })) return 1;
         tower_out = 0;
         return 0;
     }
@@ -109,22 +83,13 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.y = act[0]; t.ldy = cp; t.out_f16 = dtype == KZ_DTYPE_F16;
         t.batch = batch; t.h = m.h; t.w = m.w; t.depth = m.depth; t.d_model = m.channels; t.heads = m.att_heads;
         t.d_k = m.att_dk; t.d_v = m.att_dv; t.d_ff = m.att_dff; t.alpha = m.att_alpha; t.eps = m.ln_eps;
-        prof.begin("kz_att_tower_f32_valu", stream);
-        kz::launch_att_tower(t, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
+        if (launch("kz_att_tower_f32_valu", [&] { kz::launch_att_tower(t, stream); })) return 1;
         tower_out = 0;
         return 0;
     }
     if (plan.tower == Tower::resident_f16) {
         kz::TowerArgs t{};
-        if (packed) {
-            t.bits = (const uint8_t *)packed->bits;
-            t.bits_stride = packed->stride;
-            t.scalars_in = (const float *)packed->scalars;
-            t.n_scalar = m.n_scalar;
-            t.n_bool = m.n_bool;
-        }
+        if (packed) t.in = *packed;  // fused board encode
         t.x0 = x_in; t.cin_p = cin_p; t.w_stem = wts->res_w_stem; t.w_tower = wts->res_w_tower;
         t.bias = wts->res_bias; t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
         t.y = act[0]; t.batch = batch; t.h = m.h; t.w = m.w; t.depth = m.depth;
@@ -134,15 +99,17 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.scalars = d_scalars; t.policy = d_policy;
         t.nonfinite_flag = nf_flag; t.epoch = nf_epoch;
         if (dec && plan.heads) t.decode = *dec;
-        prof.begin("kz_tower_resident_f16", stream);
 #ifdef KZ_EXPERIMENTS
         t.prev = plan.tower_prev;
-        if (plan.nb4) kz::launch_tower_resident4(t, xres, stream);
-        else
 #endif
-        kz::launch_tower_resident(t, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
+        if (launch("kz_tower_resident_f16", [&] {
+#ifdef KZ_EXPERIMENTS
+                if (plan.nb4) kz::launch_tower_resident4(t, xres, stream);
+                else
+#endif
+                kz::launch_tower_resident(t, stream);
+            }))
+            return 1;
         tower_out = 0;
         return 0;
     }
@@ -152,13 +119,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
         t.y = (float *)act[0]; t.ldy = cp; t.batch = batch; t.h = m.h; t.w = m.w; t.channels = m.channels;
         t.depth = m.depth;
-        if (packed) {  // fused board encode
-            t.bits = (const uint8_t *)packed->bits;
-            t.bits_stride = packed->stride;
-            t.scalars_in = (const float *)packed->scalars;
-            t.n_scalar = m.n_scalar;
-            t.n_bool = m.n_bool;
-        }
+        if (packed) t.in = *packed;  // fused board encode
         if (plan.heads && m.policy_kind == kz::POLICY_ATTENTION) {  // (the split launch only)
             kz::Tower32Args::Heads &hd = t.heads;
             hd.on = true;
@@ -189,12 +150,12 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
 #endif
         t.wide = plan.wide;
         const bool f16g = plan.tower == Tower::resident_f16g;
-        prof.begin(split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : "kz_tower_resident_f32", stream);
-        if (split16()) kz::launch_tower_split(t, stream);
-        else if (f16g) kz::launch_tower_pairs(t, false, stream);  // f16 tensors behind the same pointers
-        else kz::launch_tower32(t, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
+        if (launch(split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : "kz_tower_resident_f32", [&] {
+                if (split16()) kz::launch_tower_split(t, stream);
+                else if (f16g) kz::launch_tower_pairs(t, false, stream);  // f16 tensors behind the same pointers
+                else kz::launch_tower32(t, stream);
+            }))
+            return 1;
         tower_out = 0;
         return 0;
     }
@@ -203,15 +164,11 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         // (hi, lo) tensor of the same shape have the same size, so the three activation buffers serve both —, the
         // 2·depth tower convolutions in split arithmetic, the last one writing f32 for the heads
         if (wts->stem_split) {  // encoded f32 planes [M][32] -> (hi, lo) rows -> the board-tile kernel, one chunk
-            prof.begin("kz_split_rows", stream);
-            kz::launch_split_rows((const float *)x_in, act[2], (size_t)M, cin_p, stream);
-            prof.end(stream);
+            if (launch("kz_split_rows", [&] { kz::launch_split_rows((const float *)x_in, act[2], (size_t)M, cin_p, stream); })) return 1;
             if (conv(wts->tower[0], act[2], cin_p, act[0], cp, M, 0, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
         } else {
             if (conv(wts->tower[0], x_in, cin_p, act[2], cp, M, 0, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
-            prof.begin("kz_split_rows", stream);
-            kz::launch_split_rows((const float *)act[2], act[0], (size_t)M, cp, stream);
-            prof.end(stream);
+            if (launch("kz_split_rows", [&] { kz::launch_split_rows((const float *)act[2], act[0], (size_t)M, cp, stream); })) return 1;
         }
         int cur = 0;
         for (int i = 1; i <= m.depth; i++) {
@@ -265,11 +222,7 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
         a.w1 = wts->sh_w1; a.b1 = wts->sh_b1; a.w2 = wts->sh_w2; a.b2 = wts->sh_b2;
         a.flat_to_att = wts->flat_to_att; a.scalars = d_scalars; a.policy = d_policy;
         a.nonfinite_flag = nf_flag; a.epoch = nf_epoch;
-        prof.begin("kz_att_heads_f16", stream);
-        kz::launch_att_heads(a, stream);
-        prof.end(stream);
-        HIP_TRY(hipGetLastError());
-        return 0;
+        return launch("kz_att_heads_f16", [&] { kz::launch_att_heads(a, stream); });
     }
     {
         kz::ScalarHeadArgs a{x, cp, batch, hw, m.channels, m.sh_conv.cout, m.sh_fc0.out,
@@ -281,9 +234,7 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
             a.w0x = wts->sh_w0x; a.pe_bc = wts->pe_bc; a.pe_wl = wts->pe_wl; a.pe_bl = wts->pe_bl;
             a.policy = d_policy; a.policy_len = m.policy_len; a.policy_offset = m.policy_conv_channels * hw;
         }
-        prof.begin("kz_scalar_head", stream);
-        kz::launch_scalar_head(dtype, a, stream);
-        prof.end(stream);
+        if (launch("kz_scalar_head", [&] { kz::launch_scalar_head(dtype, a, stream); })) return 1;
     }
     switch (m.policy_kind) {
         case kz::POLICY_ATAXX_CONV:
@@ -299,23 +250,17 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
                 c.M = M; c.cin_p = c0.cin_p; c.cout_p = c0.cout_p; c.relu = 1;
                 c.group = hw; c.src_group = hw; c.src_off = 0;
                 c.pw1 = wts->p_w1; c.pb1 = wts->p_b1; c.policy = d_policy; c.policy_len = m.policy_len; c.hw = hw;
-                prof.begin("kz_conv1x1_split", stream);
-                kz::launch_conv1x1_split(c, stream);
-                prof.end(stream);
+                if (launch("kz_conv1x1_split", [&] { kz::launch_conv1x1_split(c, stream); })) return 1;
             } else {
                 if (conv(c0, x, cp, head0, c0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
                 kz::PolicyConvArgs a{head0, c0.cout_p, batch, hw, m.channels, pc, wts->p_w1, wts->p_b1,
                                      d_policy, m.policy_len, m.policy_kind == kz::POLICY_ATAXX_CONV ? 1 : 0};
-                prof.begin("kz_policy_conv", stream);
-                kz::launch_policy_conv(dtype, a, stream);
-                prof.end(stream);
+                if (launch("kz_policy_conv", [&] { kz::launch_policy_conv(dtype, a, stream); })) return 1;
             }
             if (m.policy_kind == kz::POLICY_CONV && m.policy_extra_moves && !extra_in_scalar_head()) {
                 kz::PolicyExtraArgs e{x, cp, batch, hw, m.channels, m.policy_extra_moves, wts->pe_wc, wts->pe_bc,
                                       wts->pe_wl, wts->pe_bl, d_policy, m.policy_len, pc * hw};
-                prof.begin("kz_policy_extra", stream);
-                kz::launch_policy_extra(dtype, e, stream);
-                prof.end(stream);
+                if (launch("kz_policy_extra", [&] { kz::launch_policy_extra(dtype, e, stream); })) return 1;
             }
             break;
         }
@@ -325,18 +270,14 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
             if (conv(c0, x, cp, head0, c0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
             kz::PolicyConvArgs a{head0, c0.cout_p, batch, hw, m.channels, 4, wts->p_w1, wts->p_b1,
                                  d_policy + 7, m.policy_len, 0};  // (the four planes start behind the seven scalars)
-            prof.begin("kz_policy_conv", stream);
-            kz::launch_policy_conv(dtype, a, stream);
-            prof.end(stream);
+            if (launch("kz_policy_conv", [&] { kz::launch_policy_conv(dtype, a, stream); })) return 1;
             // the scalar branch has the ScalarHead's shape: the same kernel, seven outputs into the policy rows
             kz::ScalarHeadArgs sa{x, cp, batch, hw, m.channels, m.arimaa_hidden_channels, m.arimaa_hidden_size,
                                   wts->pa_w0, wts->pa_b0, wts->pa_w1, wts->pa_b1, wts->pa_w2, wts->pa_b2, d_policy,
                                   nullptr, 0, wts->pa_w1t};
             sa.n_out = 7;
             sa.out_ld = m.policy_len;
-            prof.begin("kz_scalar_head", stream);
-            kz::launch_scalar_head(dtype, sa, stream);
-            prof.end(stream);
+            if (launch("kz_scalar_head", [&] { kz::launch_scalar_head(dtype, sa, stream); })) return 1;
             break;
         }
         case kz::POLICY_ATTENTION: {
@@ -348,9 +289,7 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
                 return 1;
             kz::AttentionArgs a{head0, head1, wts->p_bulk.cout_p, wts->p_under.cout_p, batch,
                                 m.policy_query_channels, wts->flat_to_att, d_policy, m.policy_len};
-            prof.begin("kz_attention_gather", stream);
-            kz::launch_attention(dtype, a, stream);
-            prof.end(stream);
+            if (launch("kz_attention_gather", [&] { kz::launch_attention(dtype, a, stream); })) return 1;
             break;
         }
         case kz::POLICY_NONE: break;
@@ -378,34 +317,25 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
             break;
         }
     }
-    HIP_TRY(hipGetLastError());
     return 0;
 }
 
 // dec (plan.heads only): the launch ends in decode_output and writes dec->values / dec->probs
-inline int kz_engine::forward_packed(const void *d_bits, size_t stride, const void *d_sin, int batch, void *d_sout, void *d_pol,
-                   const kz::DecodeArgs *dec) {
+inline int kz_engine::forward_packed(const kz::PackedBoards &in, int batch, void *d_sout, void *d_pol, const kz::DecodeArgs *dec) {
     const Model &m = *model;
     if (encodes_boards(plan)) {
-        const PackedIn in{d_bits, stride, d_sin};
         if (run_tower(batch, (float *)d_sout, (float *)d_pol, &in, dec)) return 1;
         return run_heads(batch, (float *)d_sout, (float *)d_pol);
     }
-    prof.begin("kz_encode_packed", stream);
-    kz::launch_encode_packed(dtype, (const uint8_t *)d_bits, stride, (const float *)d_sin, batch, m.n_scalar,
-                             m.n_bool, m.h * m.w, x_in, cin_p, stream);
-    prof.end(stream);
-    HIP_TRY(hipGetLastError());
+    if (launch("kz_encode_packed", [&] { kz::launch_encode_packed(dtype, in, batch, m.h * m.w, x_in, cin_p, stream); })) return 1;
     if (run_tower(batch, (float *)d_sout, (float *)d_pol)) return 1;
     return run_heads(batch, (float *)d_sout, (float *)d_pol);
 }
 
 inline int kz_engine::forward_dense(const void *d_nchw, int batch, void *d_sout, void *d_pol) {
     const Model &m = *model;
-    prof.begin("kz_encode_dense", stream);
-    kz::launch_encode_dense(dtype, (const float *)d_nchw, batch, m.c_in, m.h * m.w, x_in, cin_p, stream);
-    prof.end(stream);
-    HIP_TRY(hipGetLastError());
+    if (launch("kz_encode_dense", [&] { kz::launch_encode_dense(dtype, (const float *)d_nchw, batch, m.c_in, m.h * m.w, x_in, cin_p, stream); }))
+        return 1;
     if (run_tower(batch, (float *)d_sout, (float *)d_pol)) return 1;
     return run_heads(batch, (float *)d_sout, (float *)d_pol);
 }

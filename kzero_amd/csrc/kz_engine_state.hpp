@@ -287,18 +287,26 @@ struct kz_engine {
     }
 
     // ---- the forward pass (kz_engine_forward.hpp) ----
-    struct PackedIn {  // packed boards still to be encoded (the one-launch towers encode inside the launch)
-        const void *bits;
-        size_t stride;
-        const void *scalars;
-    };
+    // the bracket of every launch: `enqueue` starts kernel `name` (the profiler's and kz_engine_kernel_time's name) on `stream`
+    template <class F>
+    int launch(const char *name, F &&enqueue) {
+        prof.begin(name, stream);
+        enqueue();
+        prof.end(stream);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    // the boards of an entry point as the launches take them (kz_kernels.hpp): the model's plane counts go with the pointers
+    kz::PackedBoards packed_boards(const void *bits, size_t stride, const void *scalars) const {
+        return {(const uint8_t *)bits, stride, (const float *)scalars, model->n_scalar, model->n_bool};
+    }
     int conv(const DevConv &w, const void *x, int ldx, void *y, int ldy, int M, int relu, const void *res, bool post,
              int h, int wd, int group, int src_group, int src_off, float *y32 = nullptr, int ldy32 = 0);
-    int run_tower(int batch, float *d_scalars, float *d_policy, const PackedIn *packed = nullptr,
+    // packed: boards still to be encoded (the one-launch towers encode inside the launch)
+    int run_tower(int batch, float *d_scalars, float *d_policy, const kz::PackedBoards *packed = nullptr,
                   const kz::DecodeArgs *dec = nullptr);
     bool extra_in_scalar_head() const;
     int run_heads(int batch, float *d_scalars, float *d_policy);
-    int forward_packed(const void *d_bits, size_t stride, const void *d_sin, int batch, void *d_sout, void *d_pol,
-                       const kz::DecodeArgs *dec = nullptr);
+    int forward_packed(const kz::PackedBoards &in, int batch, void *d_sout, void *d_pol, const kz::DecodeArgs *dec = nullptr);
     int forward_dense(const void *d_nchw, int batch, void *d_sout, void *d_pol);
 };

@@ -12,6 +12,10 @@
 
 namespace kz {
 
+namespace {
+#include "kz_encode_dev.hpp"  // encoded_plane: the board encode's one statement
+}
+
 typedef _Float16 h16;
 typedef h16 h16x8 __attribute__((ext_vector_type(8)));
 typedef h16 h16x4 __attribute__((ext_vector_type(4)));
@@ -30,8 +34,7 @@ struct Elem<h16> {
 
 // ---------------------------------------------------------------------------------------------------------
 // F0: encode.  One thread per (board, square, 8-channel group): 8 contiguous channels of one NHWC row.
-// Channel order = NCHW channel order of encode_input_full: scalar planes first, then bool planes
-// (rust/kz-core/src/mapping/mod.rs:54-59); bool i of a board = bit i%8 of byte i/8 (bit_buffer.rs:73-75).
+// Channel and bit order: kz_encode_dev.hpp.
 // ---------------------------------------------------------------------------------------------------------
 template <typename T>
 __device__ __forceinline__ void store8(T *dst, const float (&v)[8]);
@@ -49,9 +52,7 @@ __device__ __forceinline__ void store8<h16>(h16 *dst, const float (&v)[8]) {
 }
 
 template <typename T>
-__global__ void kz_encode_packed(const uint8_t *__restrict__ bits, size_t bits_stride,
-                                 const float *__restrict__ scalars, int batch, int n_scalar, int n_bool, int hw,
-                                 T *__restrict__ x, int ldx) {
+__global__ void kz_encode_packed(PackedBoards in, int batch, int hw, T *__restrict__ x, int ldx) {
     const int groups = ldx / 8;
     const long total = (long)batch * hw * groups;
     for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
@@ -59,20 +60,9 @@ __global__ void kz_encode_packed(const uint8_t *__restrict__ bits, size_t bits_s
         const long bp = idx / groups;
         const int p = (int)(bp % hw);
         const int b = (int)(bp / hw);
-        const uint8_t *bb = bits + (size_t)b * bits_stride;
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int c = g * 8 + j;
-            float f = 0.0f;
-            if (c < n_scalar) {
-                f = scalars[(size_t)b * n_scalar + c];
-            } else if (c < n_scalar + n_bool) {
-                const unsigned bit = (unsigned)(c - n_scalar) * hw + p;
-                f = (float)((bb[bit >> 3] >> (bit & 7)) & 1);
-            }
-            v[j] = f;
-        }
+        for (int j = 0; j < 8; j++) v[j] = encoded_plane(in, b, g * 8 + j, p, hw);
         store8<T>(x + bp * ldx + g * 8, v);
     }
 }
@@ -102,15 +92,10 @@ static int grid_for(long total, int block) {
     return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
-void launch_encode_packed(int dtype, const uint8_t *bits, size_t bits_stride, const float *scalars, int batch,
-                          int n_scalar, int n_bool, int hw, void *x, int ldx, hipStream_t stream) {
+void launch_encode_packed(int dtype, const PackedBoards &in, int batch, int hw, void *x, int ldx, hipStream_t stream) {
     long total = (long)batch * hw * (ldx / 8);
-    if (dtype == 0)
-        kz_encode_packed<float><<<grid_for(total, 256), 256, 0, stream>>>(bits, bits_stride, scalars, batch, n_scalar,
-                                                                         n_bool, hw, (float *)x, ldx);
-    else
-        kz_encode_packed<h16><<<grid_for(total, 256), 256, 0, stream>>>(bits, bits_stride, scalars, batch, n_scalar,
-                                                                       n_bool, hw, (h16 *)x, ldx);
+    if (dtype == 0) kz_encode_packed<float><<<grid_for(total, 256), 256, 0, stream>>>(in, batch, hw, (float *)x, ldx);
+    else kz_encode_packed<h16><<<grid_for(total, 256), 256, 0, stream>>>(in, batch, hw, (h16 *)x, ldx);
 }
 
 void launch_encode_dense(int dtype, const float *nchw, int batch, int c, int hw, void *x, int ldx,

@@ -11,10 +11,19 @@ namespace kz {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// A batch of boards as the host packs them: bits [batch][stride] u8 (one BitBuffer of n_bool * hw bits per board) and
+// scalars [batch][n_scalar] f32.  What a launch with a fused board encode is told about its input; bits == nullptr: the
+// launch reads its encoded x0 rows instead.  How a kernel turns it into planes: kz_encode_dev.hpp.
+struct PackedBoards {
+    const uint8_t *bits = nullptr;
+    size_t stride = 0;
+    const float *scalars = nullptr;
+    int n_scalar = 0, n_bool = 0;
+};
+
 // F0 — board encode (rust/kz-core/src/mapping/mod.rs:40-63) on the GPU.
-// packed: bits [batch][bits_stride] u8 (BitBuffer layout) + scalars [batch][n_scalar] f32 -> x [batch*hw][ldx]
-void launch_encode_packed(int dtype, const uint8_t *bits, size_t bits_stride, const float *scalars, int batch,
-                          int n_scalar, int n_bool, int hw, void *x, int ldx, hipStream_t stream);
+// packed: in -> x [batch*hw][ldx]
+void launch_encode_packed(int dtype, const PackedBoards &in, int batch, int hw, void *x, int ldx, hipStream_t stream);
 // dense: NCHW f32 [batch][c][hw] -> x [batch*hw][ldx] (channels >= c zero-filled)
 void launch_encode_dense(int dtype, const float *nchw, int batch, int c, int hw, void *x, int ldx,
                          hipStream_t stream);
@@ -198,11 +207,7 @@ struct AttTower16Args {
     const float *embedding;
     const void *w_layers;  // att_tower16_pack_layer, layer after layer
     void *y;               // [batch*64][d_model]
-    // fused board encode (F0): packed boards straight into the launch (bits == nullptr: read x0)
-    const uint8_t *bits = nullptr;
-    size_t bits_stride = 0;
-    const float *scalars_in = nullptr;
-    int n_scalar = 0, n_bool = 0;
+    PackedBoards in;       // fused board encode (F0): packed boards straight into the launch (in.bits == nullptr: read x0)
     int batch, depth, d_model, d_ff;
     float alpha, eps;
 };
@@ -260,11 +265,8 @@ struct Tower32Args {
     float *y;             // tower output [batch*hw][ldy] f32
     int ldy, batch, h, w, channels, depth;
     // launch_tower_split / launch_tower_pairs only: fused board encode (F0) — packed boards straight into the launch
-    // (bits == nullptr: read x0)
-    const uint8_t *bits = nullptr;
-    size_t bits_stride = 0;
-    const float *scalars_in = nullptr;
-    int n_scalar = 0, n_bool = 0;
+    // (in.bits == nullptr: read x0)
+    PackedBoards in;
     bool wide = false;    // launch_tower_pairs: twice the boards per workgroup (tower_split_wide_supported) — the engine's
                           // choice at max_batch; a launch whose own batch is too small for it takes the narrow tiles
     bool dense3 = false;  // launch_tower32, experiment build: three 7x7 boards per workgroup (tower32_dense3_supported)
@@ -372,13 +374,9 @@ void launch_conv1x1_split(const Conv1x1SplitArgs &a, hipStream_t stream);
 // ---- board-resident tower (kz_tower.hip): the whole ResTower in ONE launch, activations never leave LDS ----
 // Requirements: f16, 8x8, channels == 256 (cp), any depth >= 1, at most 224 input planes.
 struct TowerArgs {
-    const void *x0;       // encoded input [batch*hw][cin_p] f16 (used when bits == nullptr)
+    const void *x0;       // encoded input [batch*hw][cin_p] f16 (used when in.bits == nullptr)
     int cin_p;            // input planes padded to a multiple of 32 (<= 224)
-    // fused board encode: packed boards straight into the launch (bits == nullptr: read x0 instead)
-    const uint8_t *bits;
-    size_t bits_stride;
-    const float *scalars_in;
-    int n_scalar, n_bool;
+    PackedBoards in;      // fused board encode: packed boards straight into the launch (in.bits == nullptr: read x0 instead)
     const void *w_stem;   // fragment-packed stem weights
     const void *w_tower;  // fragment-packed weights of the 2*depth 3x3 convs
     const float *bias;    // [1 + 2*depth][256]

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 
@@ -38,6 +39,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 namespace {
 
 #include "kz_decode_dev.hpp"  // DecodeDev, decode_board_wave: decode_output as the last step of the launch
+#include "kz_encode_dev.hpp"  // encoded_plane: the board encode's one statement
 
 constexpr int C = 256;          // tower channels (= attention query channels in the fused-heads variant)
 constexpr int RS = C * 2 + 16;  // LDS bytes per pixel row: 512 B of channels + 16 B pad, so that the 16 rows of a
@@ -54,11 +56,7 @@ struct TowerDev {
     const float *bias, *post_scale, *post_shift;
     h16 *y;
     int cin_p, batch, depth;
-    // fused encode (F0): packed boards; when bits == nullptr the stem input comes from x0
-    const uint8_t *bits;
-    size_t bits_stride;
-    const float *scalars_in;
-    int n_scalar, n_bool;
+    PackedBoards in;  // fused encode (F0); when in.bits == nullptr the stem input comes from x0
     // fused heads
     const float *sh_w0, *sh_b0, *sh_w1, *sh_b1, *sh_w2, *sh_b2;
     const int32_t *att_idx;  // [1880]: (flat_to_att / 88) * 96 + flat_to_att % 88
@@ -182,24 +180,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
         const int board = board0 + (row >> 6);
         uint4 v = make_uint4(0, 0, 0, 0);
         if (board < a.batch) {
-            if (a.bits) {
-                // encode_input_full (rust/kz-core/src/mapping/mod.rs:40-63) for 8 channels of one square: scalar planes
-                // first, then the bool planes; bool i = bit i%8 of byte i/8 (bit_buffer.rs:73-75)
-                const uint8_t *bb = a.bits + (size_t)board * a.bits_stride;
-                const int p = row & 63;
+            if (a.in.bits) {  // 8 channels of one square (kz_encode_dev.hpp)
                 h16x8 e;
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int ch = c * 8 + j;
-                    float f = 0.0f;
-                    if (ch < a.n_scalar) {
-                        f = a.scalars_in[(size_t)board * a.n_scalar + ch];
-                    } else if (ch < a.n_scalar + a.n_bool) {
-                        const unsigned bit = (unsigned)(ch - a.n_scalar) * 64 + p;
-                        f = (float)((bb[bit >> 3] >> (bit & 7)) & 1);
-                    }
-                    e[j] = (h16)f;
-                }
+                for (int j = 0; j < 8; j++) e[j] = (h16)encoded_plane(a.in, board, c * 8 + j, row & 63, 64);
                 v = *reinterpret_cast<const uint4 *>(&e);
             } else {
                 v = *reinterpret_cast<const uint4 *>(a.x0 + ((size_t)board0 * 64 + row) * a.cin_p + c * 8);
@@ -748,6 +732,14 @@ void tower_pack_heads(const float *w_bulk /*[512][256]*/, const float *b_bulk, c
     }
 }
 
+namespace {
+template <auto Kernel>
+void launch_instance(const TowerDev &d, int grid, int bytes, hipStream_t stream) {
+    allow_dynamic_lds<Kernel>(bytes);
+    Kernel<<<grid, 256, bytes, stream>>>(d);
+}
+}  // namespace
+
 void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
     TowerDev d{};
     d.x0 = static_cast<const h16 *>(t.x0);
@@ -760,8 +752,7 @@ void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
     d.cin_p = t.cin_p;
     d.batch = t.batch;
     d.depth = t.depth;
-    d.bits = t.bits; d.bits_stride = t.bits_stride; d.scalars_in = t.scalars_in; d.n_scalar = t.n_scalar;
-    d.n_bool = t.n_bool;
+    d.in = t.in;
     d.sh_w0 = t.sh_w0; d.sh_b0 = t.sh_b0; d.sh_w1 = t.sh_w1; d.sh_b1 = t.sh_b1; d.sh_w2 = t.sh_w2; d.sh_b2 = t.sh_b2;
     d.att_idx = t.att_idx;
     d.scalars = t.scalars;
@@ -771,45 +762,33 @@ void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
     d.dec = DecodeDev{t.fused_heads ? t.decode.move_offsets : nullptr, t.decode.move_indices, t.decode.values, t.decode.probs,
                       t.decode.error_flag, POLICY};
     const bool heads = t.fused_heads;
-    // (the dynamic-LDS attribute is per device: set it on every launch's current device, it is a cheap host call,
-    //  but only once per kernel and device)
-    auto launch = [&](auto kernel, int grid, int bytes) {
-        static thread_local unsigned long long done_mask = 0;  // per instantiation (the lambda is generic)
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (!((done_mask >> (dev & 63)) & 1)) {
-            (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-            done_mask |= 1ull << (dev & 63);
-        }
-        kernel<<<grid, 256, bytes, stream>>>(d);
-    };
 #ifdef KZ_EXPERIMENTS
     if (t.prev) {  // (the round-6 instances: tests/test_tower_overlap.py)
         const int grid = (t.batch + 1) / 2;
         if (t.cin_p > 32) {
-            if (heads) launch(kz_tower_resident<2, true, PF_NB2, true, true>, grid, Layout<2>::BYTES);
-            else launch(kz_tower_resident<2, false, PF_NB2, true, true>, grid, Layout<2>::BYTES);
+            if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, true, true>>(d, grid, Layout<2>::BYTES, stream);
+            else launch_instance<kz_tower_resident<2, false, PF_NB2, true, true>>(d, grid, Layout<2>::BYTES, stream);
         } else if (boards_per_wg() == 1) {
-            if (heads) launch(kz_tower_resident<1, true, PF_NB1, false, true>, t.batch, Layout<1>::BYTES);
-            else launch(kz_tower_resident<1, false, PF_NB1, false, true>, t.batch, Layout<1>::BYTES);
+            if (heads) launch_instance<kz_tower_resident<1, true, PF_NB1, false, true>>(d, t.batch, Layout<1>::BYTES, stream);
+            else launch_instance<kz_tower_resident<1, false, PF_NB1, false, true>>(d, t.batch, Layout<1>::BYTES, stream);
         } else {
-            if (heads) launch(kz_tower_resident<2, true, PF_NB2, false, true>, grid, Layout<2>::BYTES);
-            else launch(kz_tower_resident<2, false, PF_NB2, false, true>, grid, Layout<2>::BYTES);
+            if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, false, true>>(d, grid, Layout<2>::BYTES, stream);
+            else launch_instance<kz_tower_resident<2, false, PF_NB2, false, true>>(d, grid, Layout<2>::BYTES, stream);
         }
         return;
     }
 #endif
     if (t.cin_p > 32) {  // (ChessHistoryMapper: 34 / 47 / 60 planes; always two boards per workgroup)
         const int grid = (t.batch + 1) / 2;
-        if (heads) launch(kz_tower_resident<2, true, PF_NB2, true>, grid, Layout<2>::BYTES);
-        else launch(kz_tower_resident<2, false, PF_NB2, true>, grid, Layout<2>::BYTES);
+        if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, true>>(d, grid, Layout<2>::BYTES, stream);
+        else launch_instance<kz_tower_resident<2, false, PF_NB2, true>>(d, grid, Layout<2>::BYTES, stream);
     } else if (boards_per_wg() == 1) {
-        if (heads) launch(kz_tower_resident<1, true, PF_NB1>, t.batch, Layout<1>::BYTES);
-        else launch(kz_tower_resident<1, false, PF_NB1>, t.batch, Layout<1>::BYTES);
+        if (heads) launch_instance<kz_tower_resident<1, true, PF_NB1>>(d, t.batch, Layout<1>::BYTES, stream);
+        else launch_instance<kz_tower_resident<1, false, PF_NB1>>(d, t.batch, Layout<1>::BYTES, stream);
     } else {
         const int grid = (t.batch + 1) / 2;
-        if (heads) launch(kz_tower_resident<2, true, PF_NB2>, grid, Layout<2>::BYTES);
-        else launch(kz_tower_resident<2, false, PF_NB2>, grid, Layout<2>::BYTES);
+        if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2>>(d, grid, Layout<2>::BYTES, stream);
+        else launch_instance<kz_tower_resident<2, false, PF_NB2>>(d, grid, Layout<2>::BYTES, stream);
     }
 }
 

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 
@@ -55,6 +56,7 @@ namespace {
 #define KZ_HEADS_STAMP(slot) KZ_STAMP(slot)
 #include "kz_decode_dev.hpp"  // DecodeDev, decode_board_wave: decode_output as the last step of the launch
 #include "kz_conv_heads.hpp"  // plane_of, conv_heads_f32 (inside this namespace)
+#include "kz_encode_dev.hpp"  // encoded_plane: the board encode's one statement
 
 struct TowerF32Dev {
     const float *x0;    // encoded input [batch*hw][ldx0]
@@ -64,11 +66,7 @@ struct TowerF32Dev {
     float *y;           // tower output [batch*hw][ldy]
     int ldx0, ldy, batch, h, w_, hw, depth, stem_groups, nb;
     unsigned inv_w, inv_hw;  // ceil(65536 / w), ceil(65536 / hw): exact quotients for values < 512
-    // fused board encode (bits != nullptr: x0 is not read)
-    const uint8_t *bits;
-    size_t bits_stride;
-    const float *scalars_in;
-    int n_scalar, n_bool;
+    PackedBoards in;  // fused board encode (in.bits != nullptr: x0 is not read)
     // fused heads (HEADS launches)
     int hc, hs, pc, policy_len, zero_tail, extra, epoch;
     const float *sh_b0, *sh_w1t, *sh_b1, *sh_w2, *sh_b2, *p_b1, *pe_bc, *pe_wl, *pe_bl;
@@ -113,20 +111,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
             if (DENSE && r >= rows_img) continue;
             f32x4 v = f32x4{0, 0, 0, 0};
             if (r < rows_valid) {
-                if (a.bits) {  // F0 (rust/kz-core/src/mapping/mod.rs:40-63, bit order bit_buffer.rs:73-75): scalar planes, then bit planes
+                if (a.in.bits) {  // F0 (kz_encode_dev.hpp)
                     const int bb = (int)(((unsigned)r * a.inv_hw) >> 16), q = r - bb * a.hw;
-                    const uint8_t *bits = a.bits + (size_t)(board0 + bb) * a.bits_stride;
 #pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        const int c = p * 4 + j;
-                        float f = 0.0f;
-                        if (c < a.n_scalar) f = a.scalars_in[(size_t)(board0 + bb) * a.n_scalar + c];
-                        else if (c < a.n_scalar + a.n_bool) {
-                            const unsigned bit = (unsigned)(c - a.n_scalar) * a.hw + q;
-                            f = (float)((bits[bit >> 3] >> (bit & 7)) & 1);
-                        }
-                        v[j] = f;
-                    }
+                    for (int j = 0; j < 4; j++) v[j] = encoded_plane(a.in, board0 + bb, p * 4 + j, q, a.hw);
                 } else {
                     v = *reinterpret_cast<const f32x4 *>(a.x0 + ((size_t)board0 * a.hw + r) * a.ldx0 + p * 4);
                 }
@@ -359,14 +347,7 @@ int tiles_for(int hw, int channels) {
 template <int C, int NT, bool HEADS, bool DENSE = false>
 void launch1(const TowerF32Dev &d, int grid, hipStream_t stream) {
     const int LDS_BYTES = (16 + 2 * (DENSE ? d.nb * d.hw : NT * 16)) * (C * 4 + 16);
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_tower_resident_f32<C, NT, HEADS, DENSE>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        done_mask |= 1ull << (dev & 63);
-    }
+    allow_dynamic_lds<kz_tower_resident_f32<C, NT, HEADS, DENSE>>(LDS_BYTES);
 #ifdef KZ_T32_STAMPS
     static unsigned long long *stamp_buf = nullptr;
     static int launches = 0;
@@ -537,11 +518,7 @@ void launch_tower32(const Tower32Args &t, hipStream_t stream) {
     d.nb = nt * 16 / d.hw;
     d.inv_w = (65536u + (unsigned)t.w - 1) / (unsigned)t.w;
     d.inv_hw = (65536u + (unsigned)d.hw - 1) / (unsigned)d.hw;
-    d.bits = t.bits;
-    d.bits_stride = t.bits_stride;
-    d.scalars_in = t.scalars_in;
-    d.n_scalar = t.n_scalar;
-    d.n_bool = t.n_bool;
+    d.in = t.in;
     const Tower32Args::Heads &hd = t.heads;
     d.hc = hd.hc; d.hs = hd.hs; d.pc = hd.pc; d.policy_len = hd.policy_len; d.zero_tail = hd.zero_tail; d.epoch = hd.epoch;
     d.sh_b0 = hd.sh_b0; d.sh_w1t = hd.sh_w1t; d.sh_b1 = hd.sh_b1; d.sh_w2 = hd.sh_w2; d.sh_b2 = hd.sh_b2;

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "kz_kernels.hpp"
+#include "kz_launch.hpp"
 
 namespace kz {
 
@@ -42,6 +43,7 @@ namespace {
 
 #include "kz_decode_dev.hpp"  // DecodeDev, decode_board_wave: decode_output as the last step of a launch with the heads inside
 #include "kz_conv_heads.hpp"  // conv_heads_f32: the conv policy heads and the scalar head on f32 row images in LDS
+#include "kz_encode_dev.hpp"  // encoded_plane: the board encode's one statement
 
 constexpr int SG_MFMA = 0x8, SG_VMEM_READ = 0x20, SG_DS_READ = 0x100;
 
@@ -113,11 +115,7 @@ struct SplitDev {
     int ldx0, ldy, batch, depth, h, w_, hw, nb;
     int stem_chunks;    // 32-channel chunks of the (padded) input planes: 9 * stem_chunks stem k-steps
     unsigned inv_w, inv_hw;  // ceil(65536 / w), ceil(65536 / hw): exact quotients for values < 512
-    // fused encode (F0): packed boards; when bits == nullptr the stem input comes from x0
-    const uint8_t *bits;
-    size_t bits_stride;
-    const float *scalars_in;
-    int n_scalar, n_bool;
+    PackedBoards in;  // fused encode (F0); when in.bits == nullptr the stem input comes from x0
     // fused heads (HEADS: chess attention network, 256 channels = query channels): ScalarHead + AttentionPolicyHead on the
     // LDS-resident tower output.  The weight stream carries 5 more passes of 8 k-steps (conv_bulk[0:Q), conv_under as
     // three s-major passes, conv_bulk[Q:2Q)), the bias table 5 more rows in the same order.
@@ -211,23 +209,12 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
     for (int id = tid; id < L::ROWS * spieces; id += 256) {  // (row, 4-channel piece)
         const int row = id / spieces, c4 = id - row * spieces;
         const bool have = row < rows_valid && c4 * 4 < a.ldx0;
-        if (a.bits) {
-            // encode_input_full (rust/kz-core/src/mapping/mod.rs:40-63) for 4 channels of one square: scalar planes first,
-            // then the bool planes; bool i = bit i%8 of byte i/8 (bit_buffer.rs:73-75)
+        if (a.in.bits) {  // 4 channels of one square (kz_encode_dev.hpp)
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
             if (row < rows_valid) {
                 const int b = (int)(((unsigned)row * a.inv_hw) >> 16), q = row - b * a.hw;
-                const uint8_t *bb = a.bits + (size_t)(board0 + b) * a.bits_stride;
 #pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int ch = c4 * 4 + j;
-                    if (ch < a.n_scalar) {
-                        v[j] = a.scalars_in[(size_t)(board0 + b) * a.n_scalar + ch];
-                    } else if (ch < a.n_scalar + a.n_bool) {
-                        const unsigned bit = (unsigned)(ch - a.n_scalar) * a.hw + q;
-                        v[j] = (float)((bb[bit >> 3] >> (bit & 7)) & 1);
-                    }
-                }
+                for (int j = 0; j < 4; j++) v[j] = encoded_plane(a.in, board0 + b, c4 * 4 + j, q, a.hw);
             }
             h16x4 hi, lo;
             split4(v, hi, lo);
@@ -787,20 +774,13 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
 
 template <int C, int NT, bool SPLIT, int HEADS = 0>
 void launch(const SplitDev &d, int grid, hipStream_t stream) {
-    static thread_local unsigned long long done_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
     // (the conv heads' tail: the split launch wants the two images as f32 rows; the plain-f16 launch the tail's scratch,
     // F16_TAIL_SCRATCH_BYTES, behind its own images)
     constexpr int F32_IMAGES = (16 + 2 * NT * 16) * (C * 4 + 16), OWN = Geo<C, NT, SPLIT>::LDS_BYTES;
     static_assert(OWN == pairs_own_lds_bytes(C, NT, SPLIT), "the host's restatement of the LDS geometry");
     constexpr int LDS = HEADS != 2 ? OWN : !SPLIT ? OWN + pairs_f16_tail_scratch_bytes(C, NT) : F32_IMAGES > OWN ? F32_IMAGES : OWN;
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    if (!((done_mask >> (dev & 63)) & 1)) {
-        (void)hipFuncSetAttribute((const void *)kz_tower_resident_split<C, NT, SPLIT, HEADS>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        done_mask |= 1ull << (dev & 63);
-    }
+    allow_dynamic_lds<kz_tower_resident_split<C, NT, SPLIT, HEADS>>(LDS);
     kz_tower_resident_split<C, NT, SPLIT, HEADS><<<grid, 256, LDS, stream>>>(d);
 }
 
@@ -809,11 +789,7 @@ void launch(const SplitDev &d, int grid, hipStream_t stream) {
 // nt: tiles of 16 pixel rows per workgroup of the instance to launch; grid: workgroups.
 inline SplitDev make_split_dev(const Tower32Args &t, bool split, int &nt, int &grid) {
     SplitDev d{};
-    d.bits = t.bits;
-    d.bits_stride = t.bits_stride;
-    d.scalars_in = t.scalars_in;
-    d.n_scalar = t.n_scalar;
-    d.n_bool = t.n_bool;
+    d.in = t.in;
     d.x0 = t.x0;  // (f16 tensors behind the same pointers when !split)
     d.ldx0 = t.ldx0;
     d.w = static_cast<const uint4 *>(t.weights);
