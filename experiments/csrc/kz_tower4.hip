@@ -59,7 +59,13 @@ struct Tower4Dev {
     h16 *y;
     uint4 *xres;  // [grid][XCHUNKS][256] x 16 B
     int cin_p, batch, depth;
-    PackedBoards in;
+    // the packed boards without symmetry ids (this launch takes none: the engine refuses them on it): the five fields the
+    // kernel had before PackedBoards grew, so that its register allocation — which the asm MFMAs depend on — stays what the
+    // audit and the parity test were passed with
+    const uint8_t *bits;
+    size_t stride;
+    const float *scalars;
+    int n_scalar, n_bool;
 };
 
 // The 256 accumulator registers of a wave (64 output channels x 256 pixels) are the WHOLE accumulator file.  Left to the
@@ -113,10 +119,11 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident4(Tower4Dev a) {
         const int board = board0 + b;
         uint4 v = make_uint4(0, 0, 0, 0);
         if (board < a.batch) {
-            if (a.in.bits) {  // 8 channels of one square (kz_encode_dev.hpp)
+            if (a.bits) {  // 8 channels of one square (kz_encode_dev.hpp)
+                const PackedBoards in{a.bits, a.stride, a.scalars, a.n_scalar, a.n_bool};
                 h16x8 e;
 #pragma unroll
-                for (int j = 0; j < 8; j++) e[j] = (h16)encoded_plane(a.in, board, c * 8 + j, p, 64);
+                for (int j = 0; j < 8; j++) e[j] = (h16)encoded_plane(in, board, c * 8 + j, p, 64);
                 v = *reinterpret_cast<const uint4 *>(&e);
             } else {
                 v = *reinterpret_cast<const uint4 *>(a.x0 + ((size_t)board * 64 + p) * a.cin_p + c * 8);
@@ -421,7 +428,7 @@ void launch_tower_resident4(const TowerArgs &t, void *xres, hipStream_t stream) 
     d.y = static_cast<h16 *>(t.y);
     d.xres = static_cast<uint4 *>(xres);
     d.cin_p = t.cin_p; d.batch = t.batch; d.depth = t.depth;
-    d.in = t.in;
+    d.bits = t.in.bits; d.stride = t.in.stride; d.scalars = t.in.scalars; d.n_scalar = t.in.n_scalar; d.n_bool = t.in.n_bool;
     allow_dynamic_lds<kz_tower_resident4<4, 8>>(L4::BYTES);
     kz_tower_resident4<4, 8><<<(t.batch + NB - 1) / NB, 256, L4::BYTES, stream>>>(d);
 }

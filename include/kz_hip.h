@@ -161,6 +161,30 @@ int kz_engine_submit_packed_decoded(kz_engine *engine, int slot, const uint8_t *
                                     const int32_t *move_indices);
 int kz_engine_wait_decoded(kz_engine *engine, int slot, const float **values_out, const float **probs_out);
 
+/* ---- board symmetries inside the launch: `RandomSymmetryNetwork` (rust/kz-core/src/network/symmetry.rs:18-68,126-148;
+ * the `eval_random_symmetries` start-up setting) without host work.  The reference maps the board, evaluates the mapped
+ * board and reads each move's probability at the index of its mapped move; here the launch does both permutations, so the
+ * caller passes the ORIGINAL board's bits and the move_to_index of the ORIGINAL board's moves, plus one symmetry id per board.
+ * The library does not know the game: a symmetry is a row of each of two tables,
+ *   square_src [n_sym][board_h * board_w]: the mapped board's bool planes at square s are the board's own at
+ *                                          square_src[id][s] (a permutation of the squares; scalar planes do not move),
+ *   policy_map [n_sym][policy_len]:        the move with policy index i has index policy_map[id][i] on the mapped board;
+ *                                          -1 = the mapped board has no such move.
+ * kz_engine_set_symmetries checks 1 <= n_sym <= 255, that every square_src row is a permutation and every policy_map entry
+ * is in [-1, policy_len), and copies the tables to the device.  It may be called again (other tables) while no batch is in
+ * flight, on an engine of any path and dtype.  host/symmetry.hpp builds the D4 tables of Ataxx and Go.
+ * The _sym entries are kz_engine_eval_packed_decoded / kz_engine_submit_packed_decoded with `sym` [batch], one id per board;
+ * sym == NULL makes them those entries, ids without tables fail.  The probabilities come back in the caller's move order,
+ * kz_engine_wait_decoded waits for the submit.  An id >= n_sym, or a listed move whose policy_map entry is -1, fails the call
+ * that returns the batch, like a move index outside the policy (no read leaves the tables). */
+int kz_engine_set_symmetries(kz_engine *engine, int n_sym, const int32_t *square_src, const int32_t *policy_map);
+int kz_engine_eval_packed_decoded_sym(kz_engine *engine, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                      int batch, const uint8_t *sym, const int64_t *move_offsets,
+                                      const int32_t *move_indices, float *values_out, float *probs_out);
+int kz_engine_submit_packed_decoded_sym(kz_engine *engine, int slot, const uint8_t *bits, size_t bits_stride,
+                                        const float *scalars_in, int batch, const uint8_t *sym,
+                                        const int64_t *move_offsets, const int32_t *move_indices);
+
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and
  * returns; kz_engine_synchronize waits. */

@@ -63,6 +63,11 @@ SIGNATURES = {
     "kz_engine_submit_packed_decoded": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                                   C.c_void_p, C.c_void_p]),
     "kz_engine_wait_decoded": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "kz_engine_set_symmetries": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "kz_engine_eval_packed_decoded_sym": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kz_engine_submit_packed_decoded_sym": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "kz_engine_enqueue_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                                   C.c_void_p, C.c_void_p]),
     "kz_engine_enqueue_dense_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -231,8 +236,27 @@ class Engine:
                                            scalars.ctypes.data, policy.ctypes.data))
         return scalars, policy
 
-    def eval_packed_decoded(self, bits: np.ndarray, scalars_in: np.ndarray, move_lists):
-        """decode_output on the GPU: returns (values [batch,5], [probs per board])."""
+    def set_symmetries(self, square_src: np.ndarray, policy_map: np.ndarray):
+        """The board symmetries as tables (kz_engine_set_symmetries): square_src [n_sym, h*w], policy_map [n_sym, policy_len]."""
+        square_src = np.ascontiguousarray(square_src, dtype=np.int32)
+        policy_map = np.ascontiguousarray(policy_map, dtype=np.int32)
+        info = self.model.info
+        if square_src.ndim != 2 or policy_map.ndim != 2 or square_src.shape[0] != policy_map.shape[0] or \
+                square_src.shape[1] != info.board_h * info.board_w or policy_map.shape[1] != info.policy_len:
+            raise KzError(f"set_symmetries: tables of shape {square_src.shape} and {policy_map.shape}, expected "
+                          f"[n_sym, {info.board_h * info.board_w}] and [n_sym, {info.policy_len}]")
+        check(load().kz_engine_set_symmetries(self._h, square_src.shape[0], square_src.ctypes.data, policy_map.ctypes.data))
+
+    @staticmethod
+    def _sym_ids(sym, batch: int) -> np.ndarray:
+        sym = np.ascontiguousarray(sym, dtype=np.uint8)
+        if sym.shape != (batch,):
+            raise KzError(f"sym: one id per board expected ({batch}), got shape {sym.shape}")
+        return sym
+
+    def eval_packed_decoded(self, bits: np.ndarray, scalars_in: np.ndarray, move_lists, sym=None):
+        """decode_output on the GPU: returns (values [batch,5], [probs per board]).  sym: one symmetry id per board
+        (set_symmetries): the boards go through the network mapped, the probabilities come back for the listed moves."""
         bits = np.ascontiguousarray(bits, dtype=np.uint8)
         scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
         batch = bits.shape[0]
@@ -242,6 +266,12 @@ class Engine:
                                    dtype=np.int32)
         values = np.empty((batch, 5), np.float32)
         probs = np.empty(max(len(idx), 1), np.float32)
+        if sym is not None:
+            sym = self._sym_ids(sym, batch)
+            check(load().kz_engine_eval_packed_decoded_sym(self._h, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                                           scalars_in.ctypes.data, batch, sym.ctypes.data, offsets.ctypes.data,
+                                                           idx.ctypes.data, values.ctypes.data, probs.ctypes.data))
+            return values, [probs[offsets[i]:offsets[i + 1]].copy() for i in range(batch)]
         check(load().kz_engine_eval_packed_decoded(self._h, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
                                                    scalars_in.ctypes.data, batch, offsets.ctypes.data, idx.ctypes.data,
                                                    values.ctypes.data, probs.ctypes.data))
@@ -260,21 +290,32 @@ class Engine:
         check(load().kz_engine_wait(self._h, slot, scalars.ctypes.data, policy.ctypes.data))
         return scalars, policy
 
-    def submit_packed_decoded(self, slot: int, bits: np.ndarray, scalars_in: np.ndarray, move_lists):
+    def submit_packed_decoded(self, slot: int, bits: np.ndarray, scalars_in: np.ndarray, move_lists, sym=None):
         bits = np.ascontiguousarray(bits, dtype=np.uint8)
         scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
         offsets = np.zeros(len(move_lists) + 1, np.int64)
         offsets[1:] = np.cumsum([len(m) for m in move_lists])
         idx = np.ascontiguousarray(np.concatenate([np.asarray(m, np.int32) for m in move_lists]) if offsets[-1] else
                                    np.zeros(0, np.int32))
+        if sym is not None:
+            sym = self._sym_ids(sym, bits.shape[0])
+            check(load().kz_engine_submit_packed_decoded_sym(self._h, slot, bits.ctypes.data, bits.shape[1],
+                                                             scalars_in.ctypes.data, bits.shape[0], sym.ctypes.data,
+                                                             offsets.ctypes.data, idx.ctypes.data))
+            return offsets
         check(load().kz_engine_submit_packed_decoded(self._h, slot, bits.ctypes.data, bits.shape[1],
                                                      scalars_in.ctypes.data, bits.shape[0], offsets.ctypes.data,
                                                      idx.ctypes.data))
         return offsets
 
-    def submit_packed_decoded_csr(self, slot: int, bits: np.ndarray, scalars_in: np.ndarray, offsets: np.ndarray, idx: np.ndarray):
-        """The same with the CSR move lists already built (contiguous uint8 / float32 / int64 / int32 arrays): what a timed
-        loop calls."""
+    def submit_packed_decoded_csr(self, slot: int, bits: np.ndarray, scalars_in: np.ndarray, offsets: np.ndarray, idx: np.ndarray,
+                                  sym: np.ndarray = None):
+        """The same with the CSR move lists already built (contiguous uint8 / float32 / int64 / int32 arrays; sym: uint8): what
+        a timed loop calls."""
+        if sym is not None:
+            check(load().kz_engine_submit_packed_decoded_sym(self._h, slot, bits.ctypes.data, bits.shape[1], scalars_in.ctypes.data,
+                                                             bits.shape[0], sym.ctypes.data, offsets.ctypes.data, idx.ctypes.data))
+            return
         check(load().kz_engine_submit_packed_decoded(self._h, slot, bits.ctypes.data, bits.shape[1], scalars_in.ctypes.data,
                                                      bits.shape[0], offsets.ctypes.data, idx.ctypes.data))
 

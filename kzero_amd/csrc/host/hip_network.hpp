@@ -9,6 +9,7 @@
 #include <iterator>
 #include <memory>
 #include <mutex>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -19,6 +20,7 @@
 #include "../../../include/kz_hip.h"
 #include "mapping.hpp"
 #include "network.hpp"
+#include "symmetry.hpp"
 
 namespace kz::host {
 
@@ -143,6 +145,24 @@ class HipNetwork : public Network<B> {
     bool device_decode_ = false;
     std::vector<int64_t> move_offsets_[KZ_ENGINE_SLOTS];
     std::vector<int32_t> move_indices_;
+    // random symmetries inside the launch (set_random_symmetries): one id per board, drawn at submit
+    int n_sym_ = 0;
+    std::mt19937_64 sym_rng_;
+    std::vector<uint8_t> sym_ids_;
+
+    // the decoded submit of a prepared batch; with symmetries on, every board gets an id of its own (symmetry.rs:47-52)
+    void submit_decoded(int slot, size_t bits_bytes, size_t n) {
+        if (!n_sym_) {
+            kz_check(kz_engine_submit_packed_decoded(engine_, slot, bits_.data(), bits_bytes, scalars_in_.data(), (int)n,
+                                                     move_offsets_[slot].data(), move_indices_.data()));
+            return;
+        }
+        std::uniform_int_distribution<int> dist(0, n_sym_ - 1);
+        sym_ids_.resize(n);
+        for (size_t i = 0; i < n; i++) sym_ids_[i] = (uint8_t)dist(sym_rng_);
+        kz_check(kz_engine_submit_packed_decoded_sym(engine_, slot, bits_.data(), bits_bytes, scalars_in_.data(), (int)n, sym_ids_.data(),
+                                                     move_offsets_[slot].data(), move_indices_.data()));
+    }
 
     // ---- a batch's host work before the launch: encode_input of every board (cudnn.rs:61-64) and, with the decode on the
     // device, move_to_index of every available move as CSR (common.rs:77-86 up to the gather).  The batch is cut into
@@ -265,8 +285,8 @@ class HipNetwork : public Network<B> {
     HipNetwork(HipNetwork &&o) noexcept
         : mapper_(o.mapper_), model_(std::move(o.model_)), engine_(o.engine_), max_batch_size_(o.max_batch_size_),
           bits_(std::move(o.bits_)), scalars_in_(std::move(o.scalars_in_)), next_slot_(o.next_slot_),
-          oldest_slot_(o.oldest_slot_), in_flight_(o.in_flight_), device_decode_(o.device_decode_), ranges_(std::move(o.ranges_)),
-          helpers_(std::move(o.helpers_)), wait_cpu_ns(o.wait_cpu_ns) {
+          oldest_slot_(o.oldest_slot_), in_flight_(o.in_flight_), device_decode_(o.device_decode_), n_sym_(o.n_sym_),
+          sym_rng_(o.sym_rng_), ranges_(std::move(o.ranges_)), helpers_(std::move(o.helpers_)), wait_cpu_ns(o.wait_cpu_ns) {
         for (int i = 0; i < KZ_ENGINE_SLOTS; i++) {
             pending_boards_[i] = std::move(o.pending_boards_[i]);
             move_offsets_[i] = std::move(o.move_offsets_[i]);
@@ -282,7 +302,23 @@ class HipNetwork : public Network<B> {
     // evaluation cross PCIe and this thread does no softmax.  Same results to f32 rounding (device expf/tanhf).
     void set_device_decode(bool on) {
         if (in_flight_ != 0) throw std::logic_error("set_device_decode while batches are in flight");
+        if (!on && n_sym_) throw std::logic_error("random symmetries need the device decode");
         device_decode_ = on;
+    }
+
+    // `eval_random_symmetries` (symmetry.rs:18-68) inside the launch: every board of every batch is evaluated under a symmetry
+    // drawn from `rng` — the ids RandomSymmetryNetwork<B, HipNetwork> would draw from the same rng — and the engine maps the
+    // planes on the way in and the policy indices on the way out (kz_engine_set_symmetries).  This thread then does what it does
+    // without symmetries: no board is mapped, no move list regenerated or searched.  Turns the device decode on (the mapped
+    // logits never reach the host).  tables: d4_tables(mapper) for Ataxx and Go.
+    void set_random_symmetries(const SymmetryTables &tables, std::mt19937_64 rng) {
+        if (in_flight_ != 0) throw std::logic_error("set_random_symmetries while batches are in flight");
+        if (tables.hw != model_->info.board_h * model_->info.board_w || tables.policy_len != model_->info.policy_len)
+            throw std::invalid_argument("symmetry tables of another board or policy");
+        kz_check(kz_engine_set_symmetries(engine_, tables.n_sym, tables.square_src.data(), tables.policy_map.data()));
+        n_sym_ = tables.n_sym;
+        sym_rng_ = rng;
+        device_decode_ = true;
     }
 
     // Helper threads for a batch's host work (encode_input, move lists): 0 = all of it on the calling executor thread like
@@ -308,8 +344,7 @@ class HipNetwork : public Network<B> {
         const size_t bits_bytes = prepare(boards, n, device_decode_, &move_offsets_[0]);
         if (device_decode_) {
             const float *values = nullptr, *probs = nullptr;
-            kz_check(kz_engine_submit_packed_decoded(engine_, 0, bits_.data(), bits_bytes, scalars_in_.data(), (int)n,
-                                                     move_offsets_[0].data(), move_indices_.data()));
+            submit_decoded(0, bits_bytes, n);
             const uint64_t w0 = thread_cpu_ns();
             kz_check(kz_engine_wait_decoded(engine_, 0, &values, &probs));
             wait_cpu_ns += thread_cpu_ns() - w0;
@@ -337,8 +372,7 @@ class HipNetwork : public Network<B> {
         // the engine copies its inputs to pinned staging before submit returns (include/kz_hip.h)
         if (device_decode_) {
             const uint64_t s0 = thread_cpu_ns();
-            kz_check(kz_engine_submit_packed_decoded(engine_, next_slot_, bits_.data(), bits_bytes, scalars_in_.data(),
-                                                     (int)n, move_offsets_[next_slot_].data(), move_indices_.data()));
+            submit_decoded(next_slot_, bits_bytes, n);
             submit_cpu_ns += thread_cpu_ns() - s0;
             pending_boards_[next_slot_].clear();  // the move lists are all the decode needs
         } else {

@@ -2,6 +2,10 @@
 // Ataxx positions and moves (board-game's D4Symmetry: transpose first, then the flips; pinned against the reference's
 // python/lib/mapping/ataxx_symmetry.json in tests).
 //
+// Two ways to evaluate under a random symmetry: RandomSymmetryNetwork<B, N> below wraps any network and does the mapping on
+// the host (map the board, regenerate its moves, look every move up); SymmetryTables + HipNetwork::set_random_symmetries
+// (hip_network.hpp) hand the symmetries to the engine as two tables and the launch does both permutations.
+//
 // Symmetric-board concept:  static bool symmetry_is_unit();  static int symmetry_count();
 //                           B map(int sym) const;  Move map_move(int sym, const Move&) const;
 #pragma once
@@ -43,6 +47,67 @@ inline uint64_t ataxx_map_tiles(int size, int sym, uint64_t tiles) {
                 out |= 1ull << (ny * size + nx);
             }
     return out;
+}
+
+// The symmetries of a game as the engine takes them (kz_engine_set_symmetries, include/kz_hip.h): per symmetry a square
+// permutation for the bool planes and a map of the policy indices.
+struct SymmetryTables {
+    int n_sym = 0, hw = 0, policy_len = 0;
+    std::vector<int32_t> square_src;  // [n_sym][hw]: the mapped board's planes at square s are the board's own at square_src[sym][s]
+    std::vector<int32_t> policy_map;  // [n_sym][policy_len]: index of the mapped move on the mapped board; -1: no such move
+    SymmetryTables() = default;
+    SymmetryTables(int n_sym, int hw, int policy_len)
+        : n_sym(n_sym), hw(hw), policy_len(policy_len), square_src((size_t)n_sym * hw, 0), policy_map((size_t)n_sym * policy_len, -1) {}
+    int32_t &src(int sym, int square) { return square_src[(size_t)sym * hw + square]; }
+    int32_t src(int sym, int square) const { return square_src[(size_t)sym * hw + square]; }
+    int32_t &map(int sym, size_t index) { return policy_map[(size_t)sym * policy_len + index]; }
+    int32_t map(int sym, size_t index) const { return policy_map[(size_t)sym * policy_len + index]; }
+    // what the launch's encode does to a board's BitBuffer storage of `planes` bool planes (kz_encode_dev.hpp), on the host
+    std::vector<uint8_t> map_bits(int sym, int planes, const std::vector<uint8_t> &bits) const {
+        std::vector<uint8_t> out(bits.size(), 0);
+        for (int p = 0; p < planes; p++)
+            for (int s = 0; s < hw; s++) {
+                const size_t from = (size_t)p * hw + src(sym, s), to = (size_t)p * hw + s;
+                if ((bits[from / 8] >> (from % 8)) & 1) out[to / 8] |= (uint8_t)(1u << (to % 8));
+            }
+        return out;
+    }
+};
+
+// D4 of an Ataxx board: tile (x, y) lands on D4::map_xy(x, y); a move's image is ataxx_map_move's.  A jump index whose source
+// is off the board is no move (index_to_move: nullopt) and maps to -1.
+inline SymmetryTables d4_tables(const AtaxxStdMapper &m) {
+    SymmetryTables t(8, m.size * m.size, (int)m.policy_len());
+    for (int sym = 0; sym < 8; sym++) {
+        const D4 d = D4::from_index(sym);
+        for (int y = 0; y < m.size; y++)
+            for (int x = 0; x < m.size; x++) {
+                int nx = x, ny = y;
+                d.map_xy(m.size, nx, ny);
+                t.src(sym, ny * m.size + nx) = y * m.size + x;
+            }
+        for (size_t i = 0; i < m.policy_len(); i++)
+            if (const auto mv = m.index_to_move(i)) t.map(sym, i) = (int32_t)m.move_to_index(ataxx_map_move(m.size, sym, *mv));
+    }
+    return t;
+}
+
+// D4 of the max_size x max_size Go grid: pass stays pass, placing a stone on a tile maps with the tile
+inline SymmetryTables d4_tables(const GoStdMapper &m) {
+    SymmetryTables t(8, m.max_size * m.max_size, (int)m.policy_len());
+    for (int sym = 0; sym < 8; sym++) {
+        const D4 d = D4::from_index(sym);
+        for (size_t i = 0; i < m.policy_len(); i++) {
+            GoStdMapper::Move mv = m.index_to_move(i);
+            if (!mv.pass) {
+                const int from = mv.y * m.max_size + mv.x;
+                d.map_xy(m.max_size, mv.x, mv.y);
+                t.src(sym, mv.y * m.max_size + mv.x) = from;
+            }
+            t.map(sym, i) = (int32_t)m.move_to_index(mv);
+        }
+    }
+    return t;
 }
 
 // AtaxxPosition with the symmetric-board interface

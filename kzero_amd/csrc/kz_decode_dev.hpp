@@ -10,6 +10,9 @@
 //            a finished board has an empty range and gets nothing               (:77 `map_or(vec![], ..)`)
 //   a softmax sum that is not strictly positive — the reference's assert (:110) — or a move index outside the policy
 //   (the reference would panic on the slice index) raises *error_flag; the host fails the call that returns the batch.
+//   With symmetry ids (d.sym: the board went through the network under the symmetry sym[board], kz_encode_dev.hpp) the
+//   logit of the move with index idx is the mapped board's at policy_map[id][idx] — un-mapping the policy, symmetry.rs:126-148;
+//   the sum keeps the caller's move order.  A mapped index of -1 or an id >= n_sym is a bad index.
 // All five pointers may be pinned host memory (the zero-copy slots): every word of the move list is read once, every
 // output word written once, the flag is a plain store.
 #pragma once
@@ -21,7 +24,15 @@ struct DecodeDev {
     float *probs;                 // parallel to move_indices
     int *error_flag;
     int policy_len;
+    const uint8_t *sym = nullptr;          // [batch] symmetry ids; nullptr: none
+    const int32_t *policy_map = nullptr;   // [n_sym][policy_len]
+    int n_sym = 0;
 };
+
+// what a launch's host side makes of its DecodeArgs (kz_kernels.hpp); on = false: the launch does not decode
+inline DecodeDev decode_dev(const DecodeArgs &a, bool on, int policy_len) {
+    return DecodeDev{on ? a.move_offsets : nullptr, a.move_indices, a.values, a.probs, a.error_flag, policy_len, a.sym, a.policy_map, a.n_sym};
+}
 
 __device__ __forceinline__ float decode_wave_max_nan(float v) {  // max over the wave; a NaN anywhere gives NaN
 #pragma unroll
@@ -59,9 +70,18 @@ __device__ __forceinline__ void decode_board_wave(const DecodeDev &d, int board,
     }
     const int64_t lo = d.move_offsets[board];
     const int n = (int)(d.move_offsets[board + 1] - lo);
+    // the board's row of the policy map; an id beyond the table has none: every move of the board is a bad index, and a
+    // board without moves (whose planes were still read through the clamped row) raises the flag itself
+    const int32_t *pmap = nullptr;
+    if (d.sym) {
+        const int id = d.sym[board];
+        if (id < d.n_sym) pmap = d.policy_map + (size_t)id * d.policy_len;
+        else if (lane == 0) *reinterpret_cast<volatile int *>(d.error_flag) = 1;
+    }
     if (n <= 0) return;
     auto logit_of = [&](int i) {
-        const int idx = d.move_indices[lo + i];
+        int idx = d.move_indices[lo + i];
+        if (d.sym) idx = (pmap && idx >= 0 && idx < d.policy_len) ? pmap[idx] : -1;
         return (idx >= 0 && idx < d.policy_len) ? logit_at(idx) : NAN;  // a bad index poisons the sum -> error flag
     };
     float mx = -INFINITY;

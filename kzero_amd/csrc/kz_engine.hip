@@ -501,81 +501,159 @@ KZ_API int kz_engine_eval_packed(kz_engine *e, const uint8_t *bits, size_t bits_
     });
 }
 
+// kz_engine_submit_packed_decoded and, with sym, kz_engine_submit_packed_decoded_sym
+static int submit_decoded(const char *fn, kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                          int batch, const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices) {
+    if (check_batch(e, batch, fn) || check_packed(e, fn)) return 1;
+    if (sym && !e->n_sym) return fail(std::string(fn) + ": symmetry ids given but no tables set (call kz_engine_set_symmetries first)");
+#ifdef KZ_EXPERIMENTS
+    if (sym && e->plan.nb4) return fail(std::string(fn) + ": the four-board experiment launch takes no symmetry ids");
+#endif
+    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(std::string(fn) + ": bad slot");
+    kz_engine::Slot &s = e->slots[slot];
+    if (s.batch >= 0) return fail(std::string(fn) + ": slot still in flight (call kz_engine_wait_decoded first)");
+    if (batch == 0) {
+        s.batch = 0;
+        s.decoded = true;
+        s.with_sym = false;
+        s.moves = 0;
+        return 0;
+    }
+    if (!bits || !move_offsets) return fail(std::string(fn) + ": null argument");
+    const Model &m = *e->model;
+    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
+    if (bits_stride < bits_bytes) return fail(std::string(fn) + ": bits_stride too small");
+    if (m.n_scalar && !scalars_in) return fail(std::string(fn) + ": null scalars");
+    if (move_offsets[0] != 0) return fail(std::string(fn) + ": move_offsets[0] must be 0");
+    for (int b = 0; b < batch; b++)
+        if (move_offsets[b + 1] < move_offsets[b]) return fail(std::string(fn) + ": move_offsets must be non-decreasing");
+    const size_t total = (size_t)move_offsets[batch];
+    if (total && !move_indices) return fail(std::string(fn) + ": null move list");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!s.h_moff) {  // (pinned only: the decode reads and writes the host staging directly, on every path)
+        if (e->hmalloc((void **)&s.h_moff, (size_t)(e->max_batch + 1) * 8) || e->hmalloc((void **)&s.h_values, (size_t)e->max_batch * 20) ||
+            e->hmalloc((void **)&s.h_err, 16))
+            return 1;
+    }
+    if (total > s.move_cap) {  // the old (smaller) buffers stay on the engine's free list until it is destroyed
+        const size_t cap = std::max(total, std::max(s.move_cap * 2, (size_t)e->max_batch * 64));
+        if (e->hmalloc((void **)&s.h_midx, cap * 4) || e->hmalloc((void **)&s.h_probs, cap * 4)) return 1;
+        s.move_cap = cap;
+    }
+    for (int b = 0; b < batch; b++) memcpy(s.h_bits + b * bits_bytes, bits + b * bits_stride, bits_bytes);
+    if (m.n_scalar) memcpy(s.h_sin, scalars_in, (size_t)batch * m.n_scalar * 4);
+    memcpy(s.h_moff, move_offsets, (size_t)(batch + 1) * 8);
+    if (total) memcpy(s.h_midx, move_indices, total * 4);
+    const uint8_t *ids = nullptr;  // the launches read the ids from the slot's pinned staging, like the move lists
+    if (sym) {
+        memcpy(s.h_sym, sym, (size_t)batch);
+        ids = s.h_sym;
+    }
+    s.with_sym = sym != nullptr;
+    s.h_err[0] = s.h_err[1] = 0;
+    StreamSwap swap{e, e->stream};
+    if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
+    if (e->zero_copy && e->plan.heads) {
+        // ONE launch and no copy operation: it reads the packed boards and the move lists from the slot's pinned staging
+        // and writes the decoded values and the available moves' probabilities there (0.2 KB per chess evaluation cross
+        // PCIe); decode_output (common.rs:16-100) is the launch's last step.  The conv policy heads keep their logits in
+        // device memory (s.d_pol) for the gather; the attention network's never leave LDS.
+        e->arm(s);
+        e->nf_flag = reinterpret_cast<int *>(s.h_sout);
+        kz::DecodeArgs dec{s.h_moff, s.h_midx, s.h_values, s.h_probs, s.h_err};
+        if (ids) {
+            dec.sym = ids;
+            dec.policy_map = e->d_policy_map;
+            dec.n_sym = e->n_sym;
+        }
+        if (e->forward_packed(e->packed_boards(s.h_bits, bits_bytes, s.h_sin, ids), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &dec)) return 1;
+        HIP_TRY(hipEventRecord(s.done, e->stream));
+        s.batch = batch;
+        s.decoded = s.in_launch = true;
+        s.moves = total;
+        return 0;
+    }
+    // heads in launches of their own: the network leaves scalars and logits in device memory, the stand-alone decode kernel
+    // reads the move lists from and writes values / probabilities / flags to the slot's pinned staging directly (every word
+    // once): the two input copies are the only copy operations of the batch
+    HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, batch * bits_bytes, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)batch * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
+    e->arm(s);
+    if (e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin, ids), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+    if (e->launch("kz_decode_output", [&] {
+            kz::launch_decode_output(s.d_sout + kz_engine::SOUT_HDR, s.d_pol, batch, m.policy_len, s.h_moff, s.h_midx, s.h_values,
+                                     s.h_probs, s.h_err, reinterpret_cast<const int *>(s.d_sout), s.epoch, e->stream, ids,
+                                     e->d_policy_map, e->n_sym);
+        }))
+        return 1;
+    HIP_TRY(hipEventRecord(s.done, e->stream));
+    s.batch = batch;
+    s.decoded = true;
+    s.in_launch = false;
+    s.moves = total;
+    return 0;
+}
+
 KZ_API int kz_engine_submit_packed_decoded(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
                                            const float *scalars_in, int batch, const int64_t *move_offsets,
                                            const int32_t *move_indices) {
     return guarded("kz_engine_submit_packed_decoded", [&]() -> int {
-        const char *fn = "kz_engine_submit_packed_decoded";
-        if (check_batch(e, batch, fn) || check_packed(e, fn)) return 1;
-        if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(std::string(fn) + ": bad slot");
-        kz_engine::Slot &s = e->slots[slot];
-        if (s.batch >= 0) return fail(std::string(fn) + ": slot still in flight (call kz_engine_wait_decoded first)");
-        if (batch == 0) {
-            s.batch = 0;
-            s.decoded = true;
-            s.moves = 0;
-            return 0;
-        }
-        if (!bits || !move_offsets) return fail(std::string(fn) + ": null argument");
+        return submit_decoded("kz_engine_submit_packed_decoded", e, slot, bits, bits_stride, scalars_in, batch, nullptr, move_offsets,
+                              move_indices);
+    });
+}
+
+KZ_API int kz_engine_submit_packed_decoded_sym(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
+                                               const float *scalars_in, int batch, const uint8_t *sym,
+                                               const int64_t *move_offsets, const int32_t *move_indices) {
+    return guarded("kz_engine_submit_packed_decoded_sym", [&]() -> int {
+        return submit_decoded("kz_engine_submit_packed_decoded_sym", e, slot, bits, bits_stride, scalars_in, batch, sym, move_offsets,
+                              move_indices);
+    });
+}
+
+// The board symmetries of the game, as the two tables the launches read (include/kz_hip.h).  Validated here, so that no id
+// below n_sym can send a kernel outside a plane or the policy.
+KZ_API int kz_engine_set_symmetries(kz_engine *e, int n_sym, const int32_t *square_src, const int32_t *policy_map) {
+    return guarded("kz_engine_set_symmetries", [&]() -> int {
+        const std::string fn = "kz_engine_set_symmetries";
+        if (!e || !square_src || !policy_map) return fail(fn + ": null argument");
+        if (n_sym < 1 || n_sym > 255) return fail(fn + ": n_sym " + std::to_string(n_sym) + " must be in 1..255");
         const Model &m = *e->model;
-        const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
-        if (bits_stride < bits_bytes) return fail(std::string(fn) + ": bits_stride too small");
-        if (m.n_scalar && !scalars_in) return fail(std::string(fn) + ": null scalars");
-        if (move_offsets[0] != 0) return fail(std::string(fn) + ": move_offsets[0] must be 0");
-        for (int b = 0; b < batch; b++)
-            if (move_offsets[b + 1] < move_offsets[b]) return fail(std::string(fn) + ": move_offsets must be non-decreasing");
-        const size_t total = (size_t)move_offsets[batch];
-        if (total && !move_indices) return fail(std::string(fn) + ": null move list");
+        const int hw = m.h * m.w, plen = m.policy_len;
+        std::vector<char> seen(hw);
+        for (int s = 0; s < n_sym; s++) {
+            std::fill(seen.begin(), seen.end(), 0);
+            for (int q = 0; q < hw; q++) {
+                const int32_t src = square_src[(size_t)s * hw + q];
+                if (src < 0 || src >= hw || seen[src])
+                    return fail(fn + ": square_src row " + std::to_string(s) + " is not a permutation of 0.." + std::to_string(hw - 1));
+                seen[src] = 1;
+            }
+            for (int i = 0; i < plen; i++) {
+                const int32_t to = policy_map[(size_t)s * plen + i];
+                if (to < -1 || to >= plen)
+                    return fail(fn + ": policy_map[" + std::to_string(s) + "][" + std::to_string(i) + "] = " + std::to_string(to) +
+                                " is outside -1.." + std::to_string(plen - 1));
+            }
+        }
+        for (const auto &s : e->slots)
+            if (s.batch >= 0) return fail(fn + ": a batch is in flight (wait for every slot first)");
         HIP_TRY(hipSetDevice(e->device));
-        if (!s.h_moff) {  // (pinned only: the decode reads and writes the host staging directly, on every path)
-            if (e->hmalloc((void **)&s.h_moff, (size_t)(e->max_batch + 1) * 8) || e->hmalloc((void **)&s.h_values, (size_t)e->max_batch * 20) ||
-                e->hmalloc((void **)&s.h_err, 16))
+        if (e->sync_all()) return 1;
+        if (!e->slots[0].h_sym)
+            for (auto &s : e->slots)
+                if (e->hmalloc((void **)&s.h_sym, (size_t)e->max_batch)) return 1;
+        if (n_sym > e->sym_cap) {  // (smaller tables stay on the engine's free list until it is destroyed)
+            e->n_sym = 0;
+            if (e->dmalloc((void **)&e->d_square_src, (size_t)n_sym * hw * 4) || e->dmalloc((void **)&e->d_policy_map, (size_t)n_sym * plen * 4))
                 return 1;
+            e->sym_cap = n_sym;
         }
-        if (total > s.move_cap) {  // the old (smaller) buffers stay on the engine's free list until it is destroyed
-            const size_t cap = std::max(total, std::max(s.move_cap * 2, (size_t)e->max_batch * 64));
-            if (e->hmalloc((void **)&s.h_midx, cap * 4) || e->hmalloc((void **)&s.h_probs, cap * 4)) return 1;
-            s.move_cap = cap;
-        }
-        for (int b = 0; b < batch; b++) memcpy(s.h_bits + b * bits_bytes, bits + b * bits_stride, bits_bytes);
-        if (m.n_scalar) memcpy(s.h_sin, scalars_in, (size_t)batch * m.n_scalar * 4);
-        memcpy(s.h_moff, move_offsets, (size_t)(batch + 1) * 8);
-        if (total) memcpy(s.h_midx, move_indices, total * 4);
-        s.h_err[0] = s.h_err[1] = 0;
-        StreamSwap swap{e, e->stream};
-        if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
-        if (e->zero_copy && e->plan.heads) {
-            // ONE launch and no copy operation: it reads the packed boards and the move lists from the slot's pinned staging
-            // and writes the decoded values and the available moves' probabilities there (0.2 KB per chess evaluation cross
-            // PCIe); decode_output (common.rs:16-100) is the launch's last step.  The conv policy heads keep their logits in
-            // device memory (s.d_pol) for the gather; the attention network's never leave LDS.
-            e->arm(s);
-            e->nf_flag = reinterpret_cast<int *>(s.h_sout);
-            const kz::DecodeArgs dec{s.h_moff, s.h_midx, s.h_values, s.h_probs, s.h_err};
-            if (e->forward_packed(e->packed_boards(s.h_bits, bits_bytes, s.h_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &dec)) return 1;
-            HIP_TRY(hipEventRecord(s.done, e->stream));
-            s.batch = batch;
-            s.decoded = s.in_launch = true;
-            s.moves = total;
-            return 0;
-        }
-        // heads in launches of their own: the network leaves scalars and logits in device memory, the stand-alone decode kernel
-        // reads the move lists from and writes values / probabilities / flags to the slot's pinned staging directly (every word
-        // once): the two input copies are the only copy operations of the batch
-        HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, batch * bits_bytes, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)batch * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
-        e->arm(s);
-        if (e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
-        if (e->launch("kz_decode_output", [&] {
-                kz::launch_decode_output(s.d_sout + kz_engine::SOUT_HDR, s.d_pol, batch, m.policy_len, s.h_moff, s.h_midx, s.h_values,
-                                         s.h_probs, s.h_err, reinterpret_cast<const int *>(s.d_sout), s.epoch, e->stream);
-            }))
-            return 1;
-        HIP_TRY(hipEventRecord(s.done, e->stream));
-        s.batch = batch;
-        s.decoded = true;
-        s.in_launch = false;
-        s.moves = total;
+        e->n_sym = 0;
+        HIP_TRY(hipMemcpy(e->d_square_src, square_src, (size_t)n_sym * hw * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_policy_map, policy_map, (size_t)n_sym * plen * 4, hipMemcpyHostToDevice));
+        e->n_sym = n_sym;
         return 0;
     });
 }
@@ -597,26 +675,45 @@ KZ_API int kz_engine_wait_decoded(kz_engine *e, int slot, const float **values_o
         HIP_TRY(hipEventSynchronize(s.done));
         if (s.in_launch && kz_engine::slot_nonfinite(s)) return fail(kz_engine::nonfinite_message("kz_engine_wait_decoded"));
         if (s.h_err[1]) return fail(kz_engine::nonfinite_message("kz_engine_wait_decoded"));
-        if (s.h_err[0]) return fail("kz_engine_wait_decoded: Softmax input sum must be strictly positive (or a move index is out of range)");
+        if (s.h_err[0])
+            return fail(std::string("kz_engine_wait_decoded: Softmax input sum must be strictly positive (or a move index is out of range") +
+                        (s.with_sym ? ", a symmetry id is not below n_sym, or a listed move has no image under its board's symmetry)" : ")"));
         return 0;
     });
+}
+
+// kz_engine_eval_packed_decoded and, with sym, kz_engine_eval_packed_decoded_sym
+static int eval_decoded(const char *name, kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in, int batch,
+                        const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices, float *values_out, float *probs_out) {
+    const std::string fn = name;
+    if (check_batch(e, batch, name) || check_packed(e, name)) return 1;
+    if (batch == 0) return 0;
+    if (!values_out) return fail(fn + ": null argument");
+    if (move_offsets && batch > 0 && move_offsets[batch] > 0 && !probs_out) return fail(fn + ": null move list");
+    if (submit_decoded(name, e, 0, bits, bits_stride, scalars_in, batch, sym, move_offsets, move_indices)) return 1;
+    const float *values = nullptr, *probs = nullptr;
+    const size_t total = e->slots[0].moves;
+    if (kz_engine_wait_decoded(e, 0, &values, &probs)) return 1;
+    memcpy(values_out, values, (size_t)batch * 20);
+    if (total) memcpy(probs_out, probs, total * 4);
+    return 0;
 }
 
 KZ_API int kz_engine_eval_packed_decoded(kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
                                          int batch, const int64_t *move_offsets, const int32_t *move_indices,
                                          float *values_out, float *probs_out) {
     return guarded("kz_engine_eval_packed_decoded", [&]() -> int {
-        if (check_batch(e, batch, "kz_engine_eval_packed_decoded") || check_packed(e, "kz_engine_eval_packed_decoded")) return 1;
-        if (batch == 0) return 0;
-        if (!values_out) return fail("kz_engine_eval_packed_decoded: null argument");
-        if (move_offsets && batch > 0 && move_offsets[batch] > 0 && !probs_out) return fail("kz_engine_eval_packed_decoded: null move list");
-        if (kz_engine_submit_packed_decoded(e, 0, bits, bits_stride, scalars_in, batch, move_offsets, move_indices)) return 1;
-        const float *values = nullptr, *probs = nullptr;
-        const size_t total = e->slots[0].moves;
-        if (kz_engine_wait_decoded(e, 0, &values, &probs)) return 1;
-        memcpy(values_out, values, (size_t)batch * 20);
-        if (total) memcpy(probs_out, probs, total * 4);
-        return 0;
+        return eval_decoded("kz_engine_eval_packed_decoded", e, bits, bits_stride, scalars_in, batch, nullptr, move_offsets, move_indices,
+                            values_out, probs_out);
+    });
+}
+
+KZ_API int kz_engine_eval_packed_decoded_sym(kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                             int batch, const uint8_t *sym, const int64_t *move_offsets,
+                                             const int32_t *move_indices, float *values_out, float *probs_out) {
+    return guarded("kz_engine_eval_packed_decoded_sym", [&]() -> int {
+        return eval_decoded("kz_engine_eval_packed_decoded_sym", e, bits, bits_stride, scalars_in, batch, sym, move_offsets,
+                            move_indices, values_out, probs_out);
     });
 }
 

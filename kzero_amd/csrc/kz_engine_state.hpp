@@ -142,7 +142,12 @@ struct kz_engine {
         int32_t *h_midx = nullptr;
         float *h_values = nullptr, *h_probs = nullptr;
         int *h_err = nullptr;  // [0] softmax sum / move index, [1] range check (kz_kernels.hpp: launch_decode_output)
+        uint8_t *h_sym = nullptr;  // [max_batch] symmetry ids of the batch (pinned, read by the launches; set_symmetries allocates it)
+        bool with_sym = false;     // what is in flight was submitted with symmetry ids
     } slots[KZ_ENGINE_SLOTS];
+    // board symmetries (kz_engine_set_symmetries): the two tables the encode and the decode read, in device memory
+    int n_sym = 0, sym_cap = 0;
+    int32_t *d_square_src = nullptr, *d_policy_map = nullptr;  // [n_sym][h*w], [n_sym][policy_len]
     float *d_dense = nullptr, *h_dense = nullptr;
     static constexpr int SOUT_HDR = 4;  // floats in front of the scalars
     // range check (see kz::ScalarHeadArgs): every submission gets a new epoch; a kernel that meets a non-finite
@@ -297,8 +302,15 @@ struct kz_engine {
         return 0;
     }
     // the boards of an entry point as the launches take them (kz_kernels.hpp): the model's plane counts go with the pointers
-    kz::PackedBoards packed_boards(const void *bits, size_t stride, const void *scalars) const {
-        return {(const uint8_t *)bits, stride, (const float *)scalars, model->n_scalar, model->n_bool};
+    // sym: the batch's symmetry ids (the engine's tables go with them)
+    kz::PackedBoards packed_boards(const void *bits, size_t stride, const void *scalars, const uint8_t *sym = nullptr) const {
+        kz::PackedBoards in{(const uint8_t *)bits, stride, (const float *)scalars, model->n_scalar, model->n_bool};
+        if (sym) {
+            in.n_sym = n_sym;
+            in.sym = sym;
+            in.square_src = d_square_src;
+        }
+        return in;
     }
     int conv(const DevConv &w, const void *x, int ldx, void *y, int ldy, int M, int relu, const void *res, bool post,
              int h, int wd, int group, int src_group, int src_off, float *y32 = nullptr, int ldy32 = 0);

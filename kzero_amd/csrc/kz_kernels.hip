@@ -802,8 +802,9 @@ __global__ __launch_bounds__(256) void kz_decode_output(const float *__restrict_
 
 void launch_decode_output(const float *scalars, const float *logits, int batch, int policy_len,
                           const int64_t *move_offsets, const int32_t *move_indices, float *values, float *probs,
-                          int *error_flag, const int *nonfinite_flag, int epoch, hipStream_t stream) {
-    const DecodeDev d{move_offsets, move_indices, values, probs, error_flag, policy_len};
+                          int *error_flag, const int *nonfinite_flag, int epoch, hipStream_t stream, const uint8_t *sym,
+                          const int32_t *policy_map, int n_sym) {
+    const DecodeDev d{move_offsets, move_indices, values, probs, error_flag, policy_len, sym, policy_map, n_sym};
     kz_decode_output<<<(batch + 3) / 4, 256, 0, stream>>>(scalars, logits, batch, d, nonfinite_flag, epoch);
 }
 

@@ -14,11 +14,17 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // A batch of boards as the host packs them: bits [batch][stride] u8 (one BitBuffer of n_bool * hw bits per board) and
 // scalars [batch][n_scalar] f32.  What a launch with a fused board encode is told about its input; bits == nullptr: the
 // launch reads its encoded x0 rows instead.  How a kernel turns it into planes: kz_encode_dev.hpp.
+// sym != nullptr: board b is encoded under the symmetry sym[b] — the bool plane value at square s is the board's own at
+// square_src[sym[b]][s] (a square permutation per symmetry; device memory, hw = the launch's squares per board).  An id
+// >= n_sym reads row n_sym - 1; the decode (DecodeArgs) is what reports it.
 struct PackedBoards {
     const uint8_t *bits = nullptr;
     size_t stride = 0;
     const float *scalars = nullptr;
     int n_scalar = 0, n_bool = 0;
+    int n_sym = 0;
+    const uint8_t *sym = nullptr;         // [batch]; nullptr: no symmetry
+    const int32_t *square_src = nullptr;  // [n_sym][hw]
 };
 
 // F0 — board encode (rust/kz-core/src/mapping/mod.rs:40-63) on the GPU.
@@ -125,10 +131,12 @@ void launch_attention(int dtype, const AttentionArgs &a, hipStream_t stream);
 // F7 — decode_output (rust/kz-core/src/network/common.rs:16-100) on the device: values [batch][5] = tanh / wdl softmax /
 // moves_left; probs = per-board softmax over the logits at the available-move indices (CSR lists).
 // error_flag: TWO words — [0] = 1: a softmax sum is not strictly positive (or a move index is out of range); [1] = 1:
-// *nonfinite_flag == epoch (see ScalarHeadArgs).  The move lists, values, probs and error_flag may be pinned host memory
+// *nonfinite_flag == epoch (see ScalarHeadArgs).  The move lists, values, probs and error_flag may be pinned host memory.
+// sym / policy_map / n_sym: the symmetry ids of DecodeArgs (sym == nullptr: none)
 void launch_decode_output(const float *scalars, const float *logits, int batch, int policy_len,
                           const int64_t *move_offsets, const int32_t *move_indices, float *values, float *probs,
-                          int *error_flag, const int *nonfinite_flag, int epoch, hipStream_t stream);
+                          int *error_flag, const int *nonfinite_flag, int epoch, hipStream_t stream,
+                          const uint8_t *sym = nullptr, const int32_t *policy_map = nullptr, int n_sym = 0);
 
 // The same decode as the LAST STEP OF A LAUNCH that has the heads inside (kz_decode_dev.hpp): with move_offsets set, a
 // "...+heads" launch writes values [batch][5] and probs (parallel to move_indices) instead of the raw scalars and logits —
@@ -139,6 +147,12 @@ struct DecodeArgs {
     const int32_t *move_indices = nullptr;
     float *values = nullptr, *probs = nullptr;
     int *error_flag = nullptr;
+    // sym != nullptr: board b was encoded under the symmetry sym[b] (PackedBoards), so the logit of the move with policy
+    // index i is read at policy_map[sym[b]][i] (device memory, [n_sym][policy_len]; -1: the symmetry has no such move).  A
+    // mapped index of -1 and an id >= n_sym raise error_flag like a move index outside the policy
+    const uint8_t *sym = nullptr;  // [batch]
+    const int32_t *policy_map = nullptr;
+    int n_sym = 0;
 };
 
 // ---- per-layer 3x3 convolution with the board as an LDS-resident spatial tile (kz_board_conv.hip): f16, cin and cout

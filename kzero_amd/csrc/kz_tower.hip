@@ -759,8 +759,7 @@ void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
     d.policy = t.policy;
     d.nonfinite_flag = t.nonfinite_flag;
     d.epoch = t.epoch;
-    d.dec = DecodeDev{t.fused_heads ? t.decode.move_offsets : nullptr, t.decode.move_indices, t.decode.values, t.decode.probs,
-                      t.decode.error_flag, POLICY};
+    d.dec = decode_dev(t.decode, t.fused_heads, POLICY);
     const bool heads = t.fused_heads;
 #ifdef KZ_EXPERIMENTS
     if (t.prev) {  // (the round-6 instances: tests/test_tower_overlap.py)

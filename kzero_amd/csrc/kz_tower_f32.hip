@@ -527,8 +527,7 @@ void launch_tower32(const Tower32Args &t, hipStream_t stream) {
     d.small_w = static_cast<const f32x4 *>(static_cast<const void *>(hd.small_w));
     d.stamps = nullptr;
     d.scalars = hd.scalars; d.policy = hd.policy; d.nonfinite_flag = hd.nonfinite_flag;
-    d.dec = DecodeDev{hd.on ? hd.decode.move_offsets : nullptr, hd.decode.move_indices, hd.decode.values, hd.decode.probs,
-                      hd.decode.error_flag, hd.policy_len};
+    d.dec = decode_dev(hd.decode, hd.on, hd.policy_len);
     const int grid = (t.batch + d.nb - 1) / d.nb;
     if (t.channels == 256) launch<256, 4>(d, hd.on, grid, stream);
 #ifdef KZ_EXPERIMENTS

@@ -818,8 +818,7 @@ inline SplitDev make_split_dev(const Tower32Args &t, bool split, int &nt, int &g
         d.att_idx = hd.att_idx;
         d.scalars = hd.scalars; d.policy = hd.policy;
         d.nonfinite_flag = hd.nonfinite_flag; d.epoch = hd.epoch;
-        d.dec = DecodeDev{hd.decode.move_offsets, hd.decode.move_indices, hd.decode.values, hd.decode.probs, hd.decode.error_flag,
-                          hd.small_w ? hd.policy_len : POLICY};
+        d.dec = decode_dev(hd.decode, true, hd.small_w ? hd.policy_len : POLICY);
         if (hd.small_w) {  // conv policy heads (tower_split_conv_heads_supported)
             d.hc = hd.hc; d.hs = hd.hs; d.pc = hd.pc; d.policy_len = hd.policy_len; d.zero_tail = hd.zero_tail; d.extra = hd.extra;
             d.sh_w1t = hd.sh_w1t; d.p_b1 = hd.p_b1; d.pe_bc = hd.pe_bc; d.pe_wl = hd.pe_wl; d.pe_bl = hd.pe_bl;

@@ -104,6 +104,10 @@ extern "C" {
     fn kz_engine_wait_view(engine: *mut c_void, slot: c_int, scalars_out: *mut *const f32, policy_out: *mut *const f32) -> c_int;
     fn kz_engine_submit_packed_decoded(engine: *mut c_void, slot: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, move_offsets: *const i64, move_indices: *const i32) -> c_int;
     fn kz_engine_wait_decoded(engine: *mut c_void, slot: c_int, values_out: *mut *const f32, probs_out: *mut *const f32) -> c_int;
+    // board symmetries inside the launch: two tables once, one id per board with every decoded submit (sym null: no symmetry)
+    fn kz_engine_set_symmetries(engine: *mut c_void, n_sym: c_int, square_src: *const i32, policy_map: *const i32) -> c_int;
+    fn kz_engine_eval_packed_decoded_sym(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, sym: *const u8, move_offsets: *const i64, move_indices: *const i32, values_out: *mut f32, probs_out: *mut f32) -> c_int;
+    fn kz_engine_submit_packed_decoded_sym(engine: *mut c_void, slot: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, sym: *const u8, move_offsets: *const i64, move_indices: *const i32) -> c_int;
     // device-resident entry points and helpers (benchmarks and parity tests; the server does not need them)
     fn kz_engine_enqueue_packed_device(engine: *mut c_void, d_bits: *const c_void, bits_stride: usize, d_scalars_in: *const c_void, batch: c_int, d_scalars_out: *mut c_void, d_policy_out: *mut c_void) -> c_int;
     fn kz_engine_enqueue_dense_device(engine: *mut c_void, d_input_nchw: *const c_void, batch: c_int, d_scalars_out: *mut c_void, d_policy_out: *mut c_void) -> c_int;
@@ -220,6 +224,17 @@ impl Drop for HipModel {
     }
 }
 
+/// The symmetries of a game as the engine takes them (`kz_engine_set_symmetries`): `square_src[sym][s]` is the square of
+/// the board whose planes the mapped board has at `s`, `policy_map[sym][i]` the policy index of the image of the move with
+/// index `i` (-1: the mapped board has no such move).  Built once per game from `B::Symmetry::all()`, `map_coord` /
+/// `map_move` and the mapper's `move_to_index` / `index_to_move`; the C++ mirror's `d4_tables` (host/symmetry.hpp) is the
+/// tested statement for Ataxx and Go.
+pub struct SymmetryTables {
+    pub n_sym: usize,
+    pub square_src: Vec<i32>,
+    pub policy_map: Vec<i32>,
+}
+
 pub struct HipNetwork<B: Board, M: BoardMapper<B>> {
     mapper: M,
     max_batch_size: usize,
@@ -238,6 +253,11 @@ pub struct HipNetwork<B: Board, M: BoardMapper<B>> {
     device_decode: bool,
     move_offsets: Vec<i64>,
     move_indices: Vec<i32>,
+    /// `eval_random_symmetries` inside the launch (`new_with_symmetries`): the number of symmetries (0: off), the source
+    /// of the ids and the ids of the batch being submitted
+    n_sym: usize,
+    sym_rng: Option<Box<dyn rand::RngCore + Send>>,
+    sym_ids: Vec<u8>,
     /// `KZ_HIP_PREP_THREADS` (default 0) + 1 ranges of a batch, each prepared by one thread (`prepare`)
     ranges: Vec<PrepRange>,
     ph: PhantomData<B>,
@@ -327,6 +347,9 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
             },
             move_offsets: vec![],
             move_indices: vec![],
+            n_sym: 0,
+            sym_rng: None,
+            sym_ids: vec![],
             ranges: {
                 // (a malformed value is not worth a panic in a constructor: no helpers, and say so once)
                 let helpers: usize = match std::env::var("KZ_HIP_PREP_THREADS") {
@@ -340,6 +363,37 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
                 (0..helpers + 1).map(|_| PrepRange::default()).collect()
             },
             ph: PhantomData,
+        }
+    }
+
+    /// `RandomSymmetryNetwork::new(HipNetwork::new(..), rng, true)` (symmetry.rs:18-68) without its host work: every board
+    /// of every batch gets a symmetry id drawn from `rng` at submit and the engine maps the planes on the way in and the
+    /// policy indices on the way out, so this thread neither maps a board nor regenerates and searches its move list.
+    /// Needs the decode on the device (the mapped logits never reach the host).
+    pub fn new_with_symmetries(mapper: M, model: Arc<HipModel>, max_batch_size: usize, device: HipDevice, dtype: HipDtype, tables: &SymmetryTables, rng: Box<dyn rand::RngCore + Send>) -> Self {
+        let mut net = Self::new(mapper, model, max_batch_size, device, dtype);
+        assert!(net.device_decode, "random symmetries inside the launch need KZ_HIP_DECODE=device");
+        let info = net._model.info;
+        assert_eq!(tables.square_src.len(), tables.n_sym * (info.board_h * info.board_w) as usize);
+        assert_eq!(tables.policy_map.len(), tables.n_sym * info.policy_len as usize);
+        check(unsafe { kz_engine_set_symmetries(net.engine, tables.n_sym as c_int, tables.square_src.as_ptr(), tables.policy_map.as_ptr()) });
+        net.n_sym = tables.n_sym;
+        net.sym_rng = Some(rng);
+        net
+    }
+
+    /// One id per board of the batch being submitted (symmetry.rs:52); null without symmetries, which makes the `_sym`
+    /// entries the plain ones (include/kz_hip.h).
+    fn draw_symmetries(&mut self, n: usize) -> *const u8 {
+        use rand::Rng;
+        let n_sym = self.n_sym;
+        match self.sym_rng.as_mut() {
+            None => std::ptr::null(),
+            Some(rng) => {
+                self.sym_ids.clear();
+                self.sym_ids.extend((0..n).map(|_| rng.gen_range(0..n_sym) as u8));
+                self.sym_ids.as_ptr()
+            }
         }
     }
 
@@ -410,14 +464,16 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
         let bits_bytes = self.prepare(&boards, self.device_decode);
         let slot = self.next_slot;
         if self.device_decode {
+            let sym = self.draw_symmetries(boards.len());
             check(unsafe {
-                kz_engine_submit_packed_decoded(
+                kz_engine_submit_packed_decoded_sym(
                     self.engine,
                     slot as c_int,
                     self.bits.as_ptr(),
                     bits_bytes,
                     self.scalars_in.as_ptr(),
                     boards.len() as c_int,
+                    sym,
                     self.move_offsets.as_ptr(),
                     self.move_indices.as_ptr(),
                 )
@@ -485,14 +541,16 @@ impl<B: Board, M: BoardMapper<B>> Network<B> for HipNetwork<B, M> {
         let bits_bytes = self.prepare(boards, self.device_decode);
 
         if self.device_decode {
+            let sym = self.draw_symmetries(batch_size);
             check(unsafe {
-                kz_engine_submit_packed_decoded(
+                kz_engine_submit_packed_decoded_sym(
                     self.engine,
                     0,
                     self.bits.as_ptr(),
                     bits_bytes,
                     self.scalars_in.as_ptr(),
                     batch_size as c_int,
+                    sym,
                     self.move_offsets.as_ptr(),
                     self.move_indices.as_ptr(),
                 )

@@ -9,8 +9,8 @@ recent = []   # (line, lo, hi) of the last MFMA destinations
 findings = 0
 last_valu_writes = []  # (line, reg) VGPR writes by VALU in the last few instructions
 for i, l in enumerate(lines):
-    t = l.strip()
-    if not t or t.startswith(';') or t.startswith('.'):
+    t = l.split(';')[0].strip()  # (an instruction may carry a trailing comment: "v_accvgpr_read_b32 v243, a35  ;  Reload Reuse")
+    if not t or t.startswith('.'):
         continue
     if t.startswith('v_mfma'):
         m = re.match(r'v_mfma\S+ a\[(\d+):(\d+)\], (\S+), (\S+), (\S+)', t)
