@@ -350,7 +350,7 @@ KZ_API int kz_engine_launch_geometry(const kz_engine *e, int batch, int *workgro
             case Tower::dense_net:
             case Tower::att_valu: per = 1; break;  // a workgroup is a board
             case Tower::att_mfma: per = kz::att_tower16_boards_per_workgroup(m.channels, m.att_dff, batch, e->dtype == KZ_DTYPE_F32); break;
-            case Tower::resident_f16: per = e->cin_p > 32 ? 2 : kz::tower_resident_boards_per_workgroup(); break;
+            case Tower::resident_f16: per = e->cin_p > 32 ? 2 : p.tower_nb; break;
             case Tower::resident_f32: per = kz::tower32_boards_per_workgroup(m.h, m.w, m.channels); break;
             case Tower::resident_split16:
             case Tower::resident_f16g:  // (per launch: the widest level this batch fills the chip with)

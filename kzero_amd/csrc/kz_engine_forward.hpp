@@ -93,6 +93,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.x0 = x_in; t.cin_p = cin_p; t.w_stem = wts->res_w_stem; t.w_tower = wts->res_w_tower;
         t.bias = wts->res_bias; t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
         t.y = act[0]; t.batch = batch; t.h = m.h; t.w = m.w; t.depth = m.depth;
+        t.boards_per_wg = plan.tower_nb;
         t.fused_heads = plan.heads;
         t.sh_w0 = wts->sh_w0; t.sh_b0 = wts->sh_b0; t.sh_w1 = wts->sh_w1; t.sh_b1 = wts->sh_b1;
         t.sh_w2 = wts->sh_w2; t.sh_b2 = wts->sh_b2; t.att_idx = wts->att_idx;

@@ -397,6 +397,7 @@ struct TowerArgs {
     const float *post_scale, *post_shift;  // final BN [256]
     void *y;              // tower output [batch*hw][256] f16 (unused with fused heads)
     int batch, h, w, depth;
+    int boards_per_wg;    // 1 or 2 (the engine's plan: KZ_TOWER_NB); more than 32 input planes: always two
     // fused chess heads (ScalarHead + AttentionPolicyHead): the launch writes scalars/policy instead of y
     bool fused_heads;
     const float *sh_w0, *sh_b0, *sh_w1, *sh_b1, *sh_w2, *sh_b2;
@@ -408,7 +409,6 @@ struct TowerArgs {
     bool prev;            // experiment build only: the round-6 instance of the kernel (bit-identity reference)
 };
 bool tower_resident_supported(int dtype, int h, int w, int channels, int depth, int c_in);
-int tower_resident_boards_per_workgroup();  // 2 (1 with KZ_TOWER_NB=1)
 bool tower_heads_supported(int policy_kind, int query_channels, int policy_len, int sh_channels, int sh_size);
 size_t tower_packed_weight_elems(int cin_p, int depth);
 size_t tower_heads_weight_elems();

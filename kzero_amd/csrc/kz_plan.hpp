@@ -46,6 +46,7 @@ struct PathPlan {
     bool wide = false;       // resident_f16g with more boards per workgroup (kz::tower_split_wide_supported)
     bool att_heads = false;  // heads in launches of their own: ScalarHead + AttentionPolicyHead as one (kz_att_heads.hip)
     bool keep = false;       // KZ_KEEP_ACTIVATIONS: the per-layer path keeps every layer's output
+    int tower_nb = 2;        // KZ_TOWER_NB: boards per workgroup of the resident_f16 launch at up to 32 input planes (1 or 2)
     int launches = 0;        // kernel launches per batch through the packed-input entry points
 #ifdef KZ_EXPERIMENTS
     // the experiment build's switches (kz_engine.hip: experiment_switches): KZ_TOWER_NB=4, KZ_TOWER_PREV, KZ_T32_BOARDS=3,
@@ -161,6 +162,7 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
                       : Tower::att_valu;
     } else if (!force && kz::tower_resident_supported(dtype, m.h, m.w, m.channels, m.depth, m.c_in)) {  // (f16 only)
         p.tower = Tower::resident_f16;
+        if (const char *nb = getenv("KZ_TOWER_NB"); nb && atoi(nb) == 1) p.tower_nb = 1;
         p.heads = !nofuse && kz::tower_heads_supported((int)m.policy_kind, m.policy_query_channels, m.policy_len, m.sh_conv.cout,
                                                        m.sh_fc0.out);
     } else {

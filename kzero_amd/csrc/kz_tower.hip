@@ -638,15 +638,6 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
 #endif
 constexpr int PF_NB1 = KZ_PF_NB1, PF_NB2 = KZ_PF_NB2;
 
-int boards_per_wg() {
-    static int nb = [] {
-        const char *e = getenv("KZ_TOWER_NB");
-        int v = e ? atoi(e) : 2;
-        return v == 1 ? 1 : 2;
-    }();
-    return nb;
-}
-
 // [256 out][256 in] row-major f32 -> one 8-k-step pass of the weight stream (same layout as a tap of a 3x3 layer)
 void pack_1x1(const float *w, uint16_t *dst) {
     static const int kq_base[4] = {0, 128, 64, 192};
@@ -665,8 +656,6 @@ void pack_1x1(const float *w, uint16_t *dst) {
 }
 
 }  // namespace
-
-int tower_resident_boards_per_workgroup() { return boards_per_wg(); }
 
 // (input planes in chunks of 32; beyond one chunk they are staged in the Y image: 64 B per chunk and row; 7 chunks at
 // most — tower_pack_weights tells a tower layer from a stem by cin_p == 256)
@@ -767,7 +756,7 @@ void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
         if (t.cin_p > 32) {
             if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, true, true>>(d, grid, Layout<2>::BYTES, stream);
             else launch_instance<kz_tower_resident<2, false, PF_NB2, true, true>>(d, grid, Layout<2>::BYTES, stream);
-        } else if (boards_per_wg() == 1) {
+        } else if (t.boards_per_wg == 1) {
             if (heads) launch_instance<kz_tower_resident<1, true, PF_NB1, false, true>>(d, t.batch, Layout<1>::BYTES, stream);
             else launch_instance<kz_tower_resident<1, false, PF_NB1, false, true>>(d, t.batch, Layout<1>::BYTES, stream);
         } else {
@@ -781,7 +770,7 @@ void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
         const int grid = (t.batch + 1) / 2;
         if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, true>>(d, grid, Layout<2>::BYTES, stream);
         else launch_instance<kz_tower_resident<2, false, PF_NB2, true>>(d, grid, Layout<2>::BYTES, stream);
-    } else if (boards_per_wg() == 1) {
+    } else if (t.boards_per_wg == 1) {
         if (heads) launch_instance<kz_tower_resident<1, true, PF_NB1>>(d, t.batch, Layout<1>::BYTES, stream);
         else launch_instance<kz_tower_resident<1, false, PF_NB1>>(d, t.batch, Layout<1>::BYTES, stream);
     } else {

@@ -1,0 +1,374 @@
+"""Exactly representable networks: every weight, bias, input and stored intermediate a short dyadic number, every partial
+sum within 24 bits.  On such a network f32, f16 and split arithmetic (lo halves zero) all return the bits a float64
+evaluation returns, in any summation order: a difference is an indexing, padding, packing or batching error, never
+rounding (DESIGN.md "Exact networks").  Test infrastructure only, no GPU.
+
+`exact_model` draws the network, `exact_boards` the positions, `reference` is PredictionHeads.forward
+(python/lib/model/post_act.py:187-228 with ScalarHead :10-23 and the policy heads :26-173) in plain numpy float64,
+written from that definition and sharing nothing with oracle/kz_oracle.c.  It also measures the two conditions:
+
+  stored:  every tensor a kernel may keep in f16 round-trips through np.float16 and has max |v| / step <= 1024, step the
+           largest power of two dividing all its values (half of what f16 holds: a kernel that stores one more
+           intermediate, or a (hi, lo) pair, stays exact);
+  sums:    every accumulation has sum |a b| / step <= 2^22: exact in f32 whatever the order of the additions and however
+           the matrix unit aligns its 32 products, as long as it keeps 24 bits.
+"""
+import numpy as np
+
+from kzero_amd import synth
+from kzero_amd.model_file import read_model, write_model
+
+STORED_MAX = 1024
+SUM_MAX = 1 << 22
+BN_EPS = 2.0 ** -17          # running_var = 1 - 2^-17 is exact in f32, and var + eps == 1.0: Conv+BN folds without rounding
+DENSE_VALUES = (-2.0, -1.0, 1.0, 2.0)  # magnitudes as well as signs: a permutation inside one sign class shows too
+# one weight in sixteen has magnitude 2: drawn evenly, a dense 256-channel layer in front of the attention head takes
+# sum |q_from q_to| past 2^22 (measured 5.7e6 and 6.3e6 on chess 2x256, 4.6e6 with one in eight; 256 terms of |q|^2, |q| ~ 48 * rms(w) * rms(x))
+DENSE_P = (1 / 32, 15 / 32, 15 / 32, 1 / 32)
+SPARSE_PER_ROW = 2
+LIVE_SHARE = 0.25            # every channel behind a ReLU is positive on at least this share of the (board, square) positions
+HEAD_SCALE = 0.25            # first layer of every head branch: power-of-two scaling costs no bits and keeps the sums small
+
+
+def layer_names(tensors):
+    """Convolution and linear layers in execution order (the state_dict's order): stem, tower convolutions, heads."""
+    return [k[:-len(".weight")] for k, v in tensors.items()
+            if k.endswith(".weight") and v.ndim in (2, 4) and k[:-len(".weight")] + ".running_mean" not in tensors]
+
+
+# the attention head multiplies two of its convolutions' outputs: one entry per row keeps sum |q_from q_to| within 2^22
+_ONE_PER_ROW = {"policy_head.conv_bulk": 1, "policy_head.conv_under": 1}
+_HEAD_FIRST = ("scalar_head.seq.0", "policy_head.seq.0", "policy_head.seq_extra.0", "policy_head.conv_bulk",
+               "policy_head.conv_under", "policy_head.bulk.0", "policy_head.scalar.0")
+
+
+def _draw(game, depth, channels, head, dense_at, seed, density, kw):
+    meta, t0 = read_model(synth.random_model(game, depth, channels, head, seed=seed, **kw))
+    rng = np.random.default_rng([seed, 7919, 0 if dense_at is None else 1 + dense_at])
+    t = {k: v.copy() for k, v in t0.items()}
+    meta["bn_eps"] = BN_EPS
+    names = layer_names(t)
+    if dense_at is not None and not 0 <= dense_at < len(names):
+        raise IndexError(f"dense_at {dense_at}: the network has {len(names)} layers")
+    for k in list(t):
+        if k.endswith(".running_mean"):
+            p = k[:-len(".running_mean")]
+            c = t[k].shape[0]
+            t[p + ".running_mean"] = np.zeros(c, np.float32)
+            t[p + ".running_var"] = np.full(c, 1.0 - BN_EPS, np.float32)
+            if p + ".weight" in t:  # (final_affine=False: no weight / bias)
+                t[p + ".weight"] = np.ones(c, np.float32)
+                t[p + ".bias"] = _bias(rng, c)
+    for i, p in enumerate(names):
+        shape = t[p + ".weight"].shape
+        rows, fan = shape[0], int(np.prod(shape[1:]))
+        if i == dense_at:
+            w = rng.choice(DENSE_VALUES, size=(rows, fan), p=DENSE_P)
+            if density < 1.0:
+                w = w * (rng.uniform(size=(rows, fan)) < density)
+        else:
+            # support uniform over (c_in, tap); the first entry of row r is stratified over the input channels (channel
+            # perm[r mod c_in], any tap), so that every channel is read by some row of a layer with as many rows as inputs
+            w = np.zeros((rows, fan))
+            taps = fan // shape[1]
+            perm = rng.permutation(shape[1])
+            for r in range(rows):
+                idx = [int(perm[r % shape[1]]) * taps + int(rng.integers(taps))]
+                while len(idx) < min(_ONE_PER_ROW.get(p, SPARSE_PER_ROW), fan):
+                    j = int(rng.integers(fan))
+                    if j not in idx:
+                        idx.append(j)
+                w[r, idx] = rng.choice((-1.0, 1.0), size=len(idx))
+        b = _bias(rng, rows).astype(np.float64)
+        if p in _HEAD_FIRST:
+            w, b = w * HEAD_SCALE, b * HEAD_SCALE
+        t[p + ".weight"] = w.reshape(shape).astype(np.float32)
+        t[p + ".bias"] = b.astype(np.float32)
+    return meta, t
+
+
+def _bias(rng, n):
+    b = rng.integers(-1, 2, size=n).astype(np.float32)
+    if not b.any():
+        b[rng.integers(n)] = 1.0
+    return b
+
+
+def draw_exact(game, depth, channels, head, dense_at, seed, density=1.0, boards=None, max_redraws=8, **kw):
+    """(meta, tensors, seed used, (scalars, policy, report) of `reference` on the boards).  Redraws the seed until the
+    reference meets the conditions.  With the weights drawn, one pass of the reference over the boards raises the integer
+    bias in front of every ReLU whose channel would be positive on less than LIVE_SHARE of the (board, square) positions
+    (`revive`): a weight that reads a dead channel could be anything, and one that reads a channel alive on a few squares
+    only shows where the ReLU behind it happens to be open."""
+    bits, scalars = boards if boards is not None else exact_boards(game, 13, seed)
+    for attempt in range(max_redraws):
+        s = seed + 1000 * attempt
+        meta, t = _draw(game, depth, channels, head, dense_at, s, density, kw)
+        out = reference(t, meta, encode(meta, bits, scalars), revive=True)
+        if conditions_hold(out[2]):
+            return meta, t, s, out
+    raise RuntimeError(f"no exact network in {max_redraws} draws: {game} {depth}x{channels} {head} dense_at={dense_at}")
+
+
+def exact_model(game, depth, channels, head, dense_at, seed, **kw):
+    """(blob, tensors).  The layer numbered `dense_at` (layer_names order; None: no such layer) has no zero weight, drawn from
+    DENSE_VALUES — every weight position of it moves an integer output by at least 1 wherever its input is non-zero —,
+    every other layer two +-1 entries per output row.  Keywords: draw_exact's (density, boards, max_redraws) and
+    synth.random_model's."""
+    meta, t, _, _ = draw_exact(game, depth, channels, head, dense_at, seed, **kw)
+    return write_model(meta, t), t
+
+
+def exact_boards(game, batch, seed):
+    """Bool planes as synth.random_boards; scalars small integers (Ataxx, and Go's komi plane: halves) in place of the raw counters."""
+    bits, scalars = synth.random_boards(game, batch, seed=seed)
+    rng = np.random.default_rng([seed, 104729])
+    if game.startswith("ataxx"):
+        scalars = rng.integers(0, 3, size=scalars.shape) / 2.0
+    elif game.startswith("go"):
+        scalars = scalars.copy()
+        scalars[:, 4] = rng.integers(0, 3, size=batch) / 2.0  # komi plane (7.5 / 15 in random_boards)
+    elif scalars.shape[1]:
+        keep = scalars <= 2  # flags and repetition counts stay; the 0..99 / 0..59 counters become 0..2
+        scalars = np.where(keep, scalars, rng.integers(0, 3, size=scalars.shape))
+    return bits, np.ascontiguousarray(scalars, dtype=np.float32)
+
+
+def encode(meta, bits, scalars):
+    """encode_input_full: scalar planes broadcast over the board, then the bool planes (LSB-first bits)."""
+    h, w = meta["board_h"], meta["board_w"]
+    ns, nb = meta["input_scalar_channels"], meta["input_bool_channels"]
+    b = bits.shape[0]
+    planes = np.unpackbits(bits, axis=1, bitorder="little")[:, :nb * h * w].reshape(b, nb, h, w)
+    x = np.empty((b, ns + nb, h, w), np.float64)
+    x[:, :ns] = scalars.astype(np.float64)[:, :, None, None]
+    x[:, ns:] = planes
+    return x
+
+
+# ---- the float64 reference ----
+
+def step_of(v):
+    """Largest power of two dividing every value of v (1.0 for an all-zero tensor)."""
+    v = np.asarray(v, np.float64).ravel()
+    v = v[v != 0]
+    if v.size == 0:
+        return 1.0
+    m, e = np.frexp(np.abs(v))
+    mi = (m * 2.0 ** 53).astype(np.int64)
+    tz = np.log2((mi & -mi).astype(np.float64)).astype(np.int64)
+    return float(2.0 ** int((e - 53 + tz).min()))
+
+
+class _Report:
+    def __init__(self):
+        self.stored = {}  # name -> (max |v| / step, round-trips through f16)
+        self.sums = {}    # name -> max sum |a b| / step
+
+    def store(self, name, v):
+        ok = bool(np.array_equal(v.astype(np.float16).astype(np.float64), v))
+        self.stored[name] = (float(np.abs(v).max() / step_of(v)), ok)
+
+    def acc(self, name, mag, step):
+        self.sums[name] = float(mag.max() / step)
+
+    def worst(self):
+        return max(v for v, _ in self.stored.values()), max(self.sums.values())
+
+
+def conditions_hold(report):
+    return (all(ok and v <= STORED_MAX for v, ok in report.stored.values()) and
+            all(v <= SUM_MAX for v in report.sums.values()))
+
+
+def _conv(rep, name, x, w, b):
+    """Convolution (3x3 same-padded: nine shifted einsums on a zero-padded image; 1x1; any odd k) or, for 2-D w, linear."""
+    w, b = w.astype(np.float64), b.astype(np.float64)
+    step = min(step_of(w) * step_of(x), step_of(b))
+    if w.ndim == 2:
+        y = x @ w.T + b
+        mag = np.abs(x) @ np.abs(w).T + np.abs(b)
+    else:
+        k = w.shape[2]
+        pad = k // 2
+        hh, ww = x.shape[2], x.shape[3]
+        xp = np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
+        y = np.zeros((x.shape[0], w.shape[0], hh, ww))
+        mag = np.zeros_like(y)
+        for dy in range(k):
+            for dx in range(k):
+                win = xp[:, :, dy:dy + hh, dx:dx + ww]
+                y += np.einsum("oc,bchw->bohw", w[:, :, dy, dx], win, optimize=True)
+                mag += np.einsum("oc,bchw->bohw", np.abs(w[:, :, dy, dx]), np.abs(win), optimize=True)
+        y += b[None, :, None, None]
+        mag += np.abs(b)[None, :, None, None]
+    rep.acc(name, mag, step)
+    return y
+
+
+def _bn(t, p, x, eps):
+    y = (x - t[p + ".running_mean"].astype(np.float64)[None, :, None, None]) / np.sqrt(
+        t[p + ".running_var"].astype(np.float64) + eps)[None, :, None, None]
+    if p + ".weight" in t:
+        y = y * t[p + ".weight"].astype(np.float64)[None, :, None, None] + t[p + ".bias"].astype(np.float64)[None, :, None, None]
+    return y
+
+
+def reference(t, meta, x, revive=False):
+    """(scalars [B, 5], policy [B, P], report) in float64; x [B, C_in, H, W].  report.acts holds the tower's and the scalar
+    head's intermediates under the oracle's trace names.  revive (the generator's pass): t is changed in place — the bias
+    in front of a ReLU is raised by whole units wherever the channel would be positive on too few positions."""
+    rep = _Report()
+    acts = rep.acts = {}
+
+    def relu(v, bias_key=None):
+        if revive and bias_key is not None:
+            unit = HEAD_SCALE if bias_key[:-len(".bias")] in _HEAD_FIRST else 1.0
+            top = np.quantile(np.moveaxis(v, 1, 0).reshape(v.shape[1], -1), 1.0 - LIVE_SHARE, axis=1, method="higher")
+            bump = np.where(top <= 0, np.ceil((unit - top) / unit) * unit, 0.0)
+            if bump.any():
+                bias = t[bias_key].astype(np.float64) + bump
+                if not bias.any():  # (a bias of -1 raised by 1: keep the layer's bias non-zero somewhere)
+                    bump = bump + unit * (bump > 0)
+                    bias = t[bias_key].astype(np.float64) + bump
+                t[bias_key] = bias.astype(np.float32)
+                v = v + bump.reshape((1, -1) + (1,) * (v.ndim - 2))
+        return np.maximum(v, 0.0)
+    eps, depth = meta["bn_eps"], meta["tower_depth"]
+    b = x.shape[0]
+
+    def conv(p, v):
+        return _conv(rep, p, v, t[p + ".weight"], t[p + ".bias"])
+
+    x = np.asarray(x, np.float64)
+    rep.store("input", x)
+    cur = conv("common.tower.0", x)  # stem: no BN, no ReLU
+    acts["tower.0"] = cur
+    rep.store("tower.0", cur)
+    for i in range(1, depth + 1):
+        p = f"common.tower.{i}.seq."
+        mid = relu(_bn(t, p + "1", conv(p + "0", cur), eps), p + "1.bias")
+        acts[f"tower.{i}.mid"] = mid
+        rep.store(f"tower.{i}.mid", mid)
+        cur = cur + relu(_bn(t, p + "4", conv(p + "3", mid), eps), p + "4.bias")  # the residual after the ReLU
+        acts[f"tower.{i}"] = cur
+        rep.store(f"tower.{i}", cur)
+    common = _bn(t, f"common.tower.{depth + 1}", cur, eps)
+    acts[f"tower.{depth + 1}"] = common
+    rep.store(f"tower.{depth + 1}", common)
+
+    def hidden(name, v):
+        rep.store(name, v)
+        return v
+
+    def scalar_branch(p, n0, n1, n2):  # conv1x1, ReLU, Flatten (channel-major), Linear, ReLU, Linear
+        a = hidden(p + ".conv_relu", relu(conv(f"{p}.{n0}", common), f"{p}.{n0}.bias"))
+        hid = hidden(p + ".fc0_relu", relu(conv(f"{p}.{n1}", a.reshape(b, -1)), f"{p}.{n1}.bias"))
+        return a, hid, conv(f"{p}.{n2}", hid)
+
+    a, hid, scalars = scalar_branch("scalar_head.seq", 0, 3, 5)
+    acts["scalar_head.conv_relu"], acts["scalar_head.fc0_relu"] = a.reshape(b, -1), hid
+
+    kind = meta["policy_kind"]
+    if kind in ("ataxx_conv", "conv"):
+        hid = hidden("policy_head.hidden", relu(conv("policy_head.seq.0", common), "policy_head.seq.0.bias"))
+        policy = conv("policy_head.seq.2", hid).reshape(b, -1)
+        if kind == "ataxx_conv":
+            policy = np.concatenate([policy, np.zeros((b, 1))], axis=1)
+        elif meta.get("policy_extra_moves", 0):
+            e = hidden("policy_head.extra", conv("policy_head.seq_extra.0", common)).reshape(b, -1)
+            policy = np.concatenate([policy, conv("policy_head.seq_extra.2", e)], axis=1)
+    elif kind == "attention":
+        q = meta["policy_query_channels"]
+        bulk = conv("policy_head.conv_bulk", common)
+        under = conv("policy_head.conv_under", common[:, :, 7:8, :])  # the last rank only
+        q_from = hidden("policy_head.q_from", bulk[:, :q].reshape(b, q, 64))
+        q_to = hidden("policy_head.q_to", np.concatenate([bulk[:, q:].reshape(b, q, 64), under.reshape(b, q, 24)], axis=2))
+        logits = np.einsum("bqi,bqj->bij", q_from, q_to, optimize=True)
+        rep.acc("policy_head.bmm", np.einsum("bqi,bqj->bij", np.abs(q_from), np.abs(q_to), optimize=True), step_of(q_from) * step_of(q_to))
+        policy = (logits / np.sqrt(float(q))).reshape(b, -1)[:, t["policy_head.FLAT_TO_ATT"]]
+    elif kind == "dense":
+        cur, idx = common, 0
+        if meta.get("policy_dense_hidden_channels", 0):
+            cur, idx = hidden("policy_head.hidden_conv", relu(conv("policy_head.seq.0", common), "policy_head.seq.0.bias")), 2
+        cur, idx = cur.reshape(b, -1), idx + 1
+        if meta.get("policy_dense_hidden_size", 0):
+            cur, idx = hidden("policy_head.hidden_fc", relu(conv(f"policy_head.seq.{idx}", cur), f"policy_head.seq.{idx}.bias")), idx + 2
+        policy = conv(f"policy_head.seq.{idx}", cur)
+    elif kind == "arimaa":
+        hid = hidden("policy_head.bulk_hidden", relu(conv("policy_head.bulk.0", common), "policy_head.bulk.0.bias"))
+        bulk = conv("policy_head.bulk.2", hid).reshape(b, -1)
+        _, _, sc = scalar_branch("policy_head.scalar", 0, 3, 5)
+        policy = np.concatenate([sc, bulk], axis=1)
+    else:
+        raise ValueError(f"no exact reference for policy head '{kind}'")
+    # the outputs are f32: they must be exact there
+    for name, v in (("scalars", scalars), ("policy", policy)):
+        assert np.array_equal(v.astype(np.float32).astype(np.float64), v), f"{name}: not exact in f32"
+    return scalars, policy, rep
+
+
+# ---- the committed networks: one per shape a kernel instance addresses on its own (tests/test_gpu_exact.py lists the engines) ----
+# (game, depth, channels, head, synth.random_model keywords, {dense position: density < 1 where full density leaves the headroom})
+# — every position of every network below holds the conditions at full density, so the last field is empty throughout.
+# Attention heads away from 256 channels take 64 query channels: 1 / sqrt(64) is a power of two like 1 / sqrt(256), 1 / sqrt(128) is not.
+_Q64 = dict(query_channels=64)
+NETS = {
+    "chess_2x256_att": ("chess", 2, 256, "attention", {}, {}),
+    "chess_1x256_att": ("chess", 1, 256, "attention", {}, {}),
+    "chesshist1_1x256_att": ("chess-hist-1", 1, 256, "attention", {}, {}),
+    "chesshist3_1x256_att": ("chess-hist-3", 1, 256, "attention", {}, {}),
+    "chess_1x128_att": ("chess", 1, 128, "attention", _Q64, {}),
+    "chess_1x192_att": ("chess", 1, 192, "attention", _Q64, {}),
+    "chess_1x512_att": ("chess", 1, 512, "attention", _Q64, {}),  # (full density holds at 512 channels too)
+    "ataxx7_1x128": ("ataxx-7", 1, 128, "ataxx_conv", {}, {}),
+    "ataxx5_1x128": ("ataxx-5", 1, 128, "ataxx_conv", {}, {}),
+    "ataxx7_1x64": ("ataxx-7", 1, 64, "ataxx_conv", {}, {}),
+    "ataxx7_1x48": ("ataxx-7", 1, 48, "ataxx_conv", {}, {}),
+    "ataxx6_1x128_sh96": ("ataxx-6", 1, 128, "ataxx_conv", dict(scalar_hidden_size=96), {}),
+    "go9_1x128": ("go-9", 1, 128, "conv", {}, {}),
+    "go9_1x256": ("go-9", 1, 256, "conv", {}, {}),
+    "go9_1x96": ("go-9", 1, 96, "conv", {}, {}),
+    "go19_1x64": ("go-19", 1, 64, "conv", {}, {}),
+    "go19_1x128": ("go-19", 1, 128, "conv", {}, {}),
+    "go13_1x128": ("go-13", 1, 128, "conv", {}, {}),
+    "chess_1x128_dense": ("chess", 1, 128, "dense", dict(dense_hidden_channels=8, dense_hidden_size=64), {}),
+    "arimaa_1x96": ("arimaa-split", 1, 96, "arimaa", {}, {}),
+    "ttt_1x32_dense": ("ttt", 1, 32, "dense", {}, {}),
+}
+SEED = 1
+BOARDS = 13  # every engine evaluates slices of these: the conditions are measured on all of them
+
+
+def positions(net):
+    """None and every layer index of the network."""
+    game, depth, channels, head, kw, _ = NETS[net]
+    _, t = read_model(synth.random_model(game, depth, channels, head, seed=SEED, **kw))
+    return [None] + list(range(len(layer_names(t))))
+
+
+class Built:
+    pass
+
+
+_CACHE = {}
+
+
+def build(net, dense_at):
+    """One model per (network, dense position), with its boards and float64 reference; cached (the last few only: the
+    512-channel blobs are tens of MB)."""
+    key = (net, dense_at)
+    if key not in _CACHE:
+        while len(_CACHE) >= 12:
+            _CACHE.pop(next(iter(_CACHE)))
+        game, depth, channels, head, kw, density_at = NETS[net]
+        b = Built()
+        b.bits, b.scalars_in = exact_boards(game, BOARDS, SEED)
+        b.meta, b.tensors, b.seed, (s, p, b.report) = draw_exact(game, depth, channels, head, dense_at, SEED, boards=(b.bits, b.scalars_in),
+                                                                 density=density_at.get(dense_at, 1.0), **kw)
+        b.blob = write_model(b.meta, b.tensors)
+        b.x = encode(b.meta, b.bits, b.scalars_in)
+        b.ref_scalars, b.ref_policy = s.astype(np.float32), p.astype(np.float32)
+        b.layers = layer_names(b.tensors)
+        _CACHE[key] = b
+    return _CACHE[key]

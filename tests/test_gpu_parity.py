@@ -14,6 +14,8 @@ Tolerances:
             a mis-scaled layer or a wrong weight fragment moves the rms by far more than that.
             Two f16 paths of this library against each other (same operands and rounding points, different summation
             order) are bounded relative to the output scale as well: F16_PATHS_REL for 2-block nets, _DEEP for 40+ layers.
+Errors below these bounds (one wrong weight, channel or tap) are tests/test_gpu_exact.py's: networks on which nothing
+rounds, compared bit for bit.
 """
 import os
 
@@ -1257,6 +1259,8 @@ def test_resident_f16_agrees_with_per_layer_paths(dev, nb):
     finally:
         del os.environ["KZ_TOWER_NB"]
     assert eng.tower_path == "tower_resident_f16+heads"
+    # (KZ_TOWER_NB is read per engine: both instances run in one process, whichever ran first)
+    assert eng.launch_geometry(37) == ((37, 1) if nb == "1" else (19, 2))
     os.environ["KZ_FORCE_GENERIC"] = "1"
     os.environ["KZ_NO_BOARD_CONV"] = "1"
     try:
