@@ -317,8 +317,12 @@ struct DeviceWeights {
             const size_t head_elems = p.heads ? kz::tower_heads_weight_elems() : 0;
             std::vector<uint16_t> stem(stem_elems), rest(layer_elems * 2 * m.depth + head_elems + kz::tower_weight_pad_elems());
             kz::tower_pack_weights(m.tower[0].w.data(), C, m.c_in, cin_p, stem.data());
+            bool tap_major = false;  // (the four-board experiment launch reads its layers tap by tap)
+#ifdef KZ_EXPERIMENTS
+            tap_major = p.nb4;
+#endif
             for (int l = 0; l < 2 * m.depth; l++)
-                kz::tower_pack_weights(m.tower[1 + l].w.data(), C, C, 256, rest.data() + layer_elems * l);
+                kz::tower_pack_weights(m.tower[1 + l].w.data(), C, C, 256, rest.data() + layer_elems * l, tap_major);
             std::vector<float> bias((size_t)(1 + 2 * m.depth + (p.heads ? 5 : 0)) * 256);
             for (int l = 0; l < 1 + 2 * m.depth; l++)
                 for (int o = 0; o < 256; o++) bias[(size_t)l * 256 + o] = m.tower[l].b[o];
@@ -450,14 +454,15 @@ struct WeightsKey {
     const Model *model;
     int device, dtype;
     Tower tower;
-    bool heads, att_heads, conv2 = false;
+    bool heads, att_heads, conv2 = false, nb4 = false;
     WeightsKey(const Model *m, int device, int dtype, const PathPlan &p)
         : model(m), device(device), dtype(dtype), tower(p.tower), heads(p.heads && p.tower != Tower::resident_f32), att_heads(p.att_heads) {
 #ifdef KZ_EXPERIMENTS
         conv2 = p.conv2;
+        nb4 = p.nb4;
 #endif
     }
-    auto fields() const { return std::tie(model, device, dtype, tower, heads, att_heads, conv2); }
+    auto fields() const { return std::tie(model, device, dtype, tower, heads, att_heads, conv2, nb4); }
     bool operator<(const WeightsKey &o) const { return fields() < o.fields(); }
 };
 std::mutex g_cache_mutex;

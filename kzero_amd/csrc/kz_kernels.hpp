@@ -416,8 +416,9 @@ size_t tower_weight_pad_elems();  // zero k-steps behind the weight stream (the 
 // heads part of the weight stream (appended after the tower layers) and its 5 x 256 bias rows
 void tower_pack_heads(const float *w_bulk, const float *b_bulk, const float *w_under, const float *b_under,
                       uint16_t *dst, float *bias5);
-// host-side packing: OIHW f32 (BN folded) -> MFMA A-fragment order f16; dst index for conv layer l (0 = stem)
-void tower_pack_weights(const float *oihw, int cout, int cin, int cin_p, uint16_t *dst);
+// host-side packing: OIHW f32 (BN folded) -> MFMA A-fragment order f16; dst index for conv layer l (0 = stem).  A tower
+// layer's k-steps are ordered [dx][chunk][dy] (launch_tower_resident), or tap-major [tap][chunk] (launch_tower_resident4)
+void tower_pack_weights(const float *oihw, int cout, int cin, int cin_p, uint16_t *dst, bool tap_major = false);
 void launch_tower_resident(const TowerArgs &a, hipStream_t stream);
 // the same tower (no fused heads yet) with four boards per workgroup (kz_tower4.hip): single in-place LDS image, the
 // residual stream in a private global scratch slab of tower4_scratch_bytes(max batch)

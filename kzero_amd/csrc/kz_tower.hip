@@ -18,7 +18,9 @@
 //    permuted so that every ds_read_b128 fragment read is bank-conflict-free (see frag_base below).
 //  * Two boards per workgroup: an MFMA pixel tile is line y of board 0 + line y of board 1, so the taps that fall off
 //    the top / bottom edge hit a WHOLE tile (dy = -1: tile 0, dy = +1: tile 7) and those MFMAs are not issued: 8.3 % of
-//    a direct convolution's multiply-adds are multiplications by the zero padding.
+//    a direct convolution's multiply-adds are multiplications by the zero padding.  And tile mt at tap row dy needs
+//    line mt + dy, the fragment tile mt + dy needs at dy = 0: the k-steps run in the order (dx, chunk, dy), the 8 line
+//    fragments of a (dx, chunk) are read from LDS once and serve all three tap rows (conv_3x3_lines).
 //  * Heads (post_act.py:10-23, 115-141) run on the LDS-resident tower output: conv_under and conv_bulk are more passes
 //    of the same weight stream, q_from^T q_to is MFMA on LDS operands, the 1880-entry gather and the scalar head write
 //    the only HBM output of the launch (7.5 KB per board).
@@ -45,7 +47,7 @@ constexpr int C = 256;          // tower channels (= attention query channels in
 constexpr int RS = C * 2 + 16;  // LDS bytes per pixel row: 512 B of channels + 16 B pad, so that the 16 rows of a
                                 // fragment read fall on 16 different 16-byte slots of the 256-byte bank row
 constexpr int URS = 3 * C * 2 + 16;  // row stride of the conv_under image (768 channels)
-constexpr int KSTEPS = 72;      // 9 taps x 8 chunks of 32 channels
+constexpr int KSTEPS = 72;      // 9 taps x 8 chunks of 32 channels, in the order (dx, chunk, dy)
 constexpr int HEAD_KSTEPS = 5 * 8;  // conv_under as 3 passes of 256 channels, conv_bulk as 2: 8 k-steps each
 constexpr int POLICY = 1880, LOGIT_LD = 96;  // 64 x 88 attention logits, rows padded to 96
 constexpr int TOWER_PF_MAX = 8;  // deepest weight ring: the stream is padded by this many k-steps
@@ -65,6 +67,15 @@ struct TowerDev {
     int epoch;
     DecodeDev dec;        // dec.move_offsets set: values / probabilities of the available moves instead of scalars / policy
 };
+
+// f(integral_constant<int, I>) for I in [I, N): a loop whose index is a constant expression in its body
+template <int I, int N, class F>
+__device__ __forceinline__ void static_for(F &&f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<I + 1, N>(f);
+    }
+}
 
 template <int NB>
 struct Layout {
@@ -108,7 +119,8 @@ constexpr int SG_VALU = 0x2, SG_SALU = 0x4, SG_MFMA = 0x8, SG_VMEM_READ = 0x20, 
 // WIDE: more than 32 input planes (the instance for up to 32 keeps its compile-time stem: a same-box A/B of a run-time
 // chunk count in the benchmark's instance cost 0.3 %)
 // PREV: the round-6 address arithmetic (per-lane 64-bit weight addresses with a clamp at the end of the stream, tap rows
-// through short-circuit conditions) — instantiated only in the experiment build, as the bit-identity reference
+// through short-circuit conditions) and one LDS read per (tap, tile) fragment, in the same k-step order — instantiated
+// only in the experiment build, as the bit-identity reference
 template <int NB, bool HEADS, int PF, bool WIDE = false, bool PREV = false>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     using L = Layout<NB>;
@@ -125,7 +137,8 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     const int total_ksteps = layers * KSTEPS + (HEADS ? HEAD_KSTEPS : 0);
     const int bias_rows = layers + (HEADS ? 5 : 0);  // last valid row of the bias table
 
-    // ---- weight stream: per k-step 16 KB = [wave 4][nt 4][lane 64] x 16 B; prime PF stages before anything else.
+    // ---- weight stream: per k-step 16 KB = [wave 4][nt 4][lane 64] x 16 B, the k-steps of a 3x3 layer in the order
+    // [dx][chunk][dy] (tower_pack_weights); prime PF stages before anything else.
     // A refill is global_load_dwordx4 v, v_lane, s[wk:wk+1] offset:1024*nt: the k-step's address is a wave-uniform
     // running pointer (one 64-bit scalar add per k-step) plus the lane's 32-bit offset, and nt is the immediate.  The
     // stream is padded by TOWER_PF_MAX k-steps (tower_weight_pad_elems), so the refills that run past its end read padding
@@ -308,8 +321,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     // (The lane conditions are combined with bitwise operators: as short-circuit conditions the compiler turned every
     // tile's choice into an exec-masked branch, ~100 instructions per tap outside any MFMA's shadow; this way they are
     // eight v_cndmask.)
-    auto tap_rows = [&](int tap, int src_off, int (&T)[MT]) __attribute__((always_inline)) {
-        const int dy = tap / 3 - 1, dx = tap % 3 - 1;
+    auto tap_rows = [&](int dy, int dx, int src_off, int (&T)[MT]) __attribute__((always_inline)) {
         const int shifted = frag_base + src_off + (dy * 8 + dx) * RS;
         // zero row with the slot of the row it stands in for: consecutive line tiles are 8 slots apart, so even and odd
         // tiles differ by 8 rows
@@ -324,113 +336,180 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
             const bool kill_x = ((dx < 0) & x_is0) | ((dx > 0) & x_is7);
 #pragma unroll
             for (int mt = 0; mt < MT; mt++) {
-                bool kill;
-                if constexpr (L::LINE_TILES) kill = kill_x | ((dy < 0) & (mt == 0)) | ((dy > 0) & (mt == MT - 1));
-                else kill = kill_x | (((mt & 3) == 0) & (dy < 0) & yo_is0) | (((mt & 3) == 3) & (dy > 0) & yo_is1);
+                // (line tiles: a tile that dy puts outside the board is never read, so only the x masks are per lane)
+                bool kill = kill_x;
+                if constexpr (!L::LINE_TILES) kill = kill_x | (((mt & 3) == 0) & (dy < 0) & yo_is0) | (((mt & 3) == 3) & (dy > 0) & yo_is1);
                 T[mt] = kill ? ((mt & 1) ? z1 : z0) : shifted + mt * L::TS;
             }
         }
     };
 
-    // One line of taps: acc += sum over taps (DY, dx in [dx_lo, dx_hi)) and all 256 input channels of W * image(src_off),
-    // 8 k-steps per tap.  On entry bf[0] holds the fragments of the first k-step; the last k-step prefetches the first
-    // fragments of tap `tap_after` (what runs next) for ALL tiles.  With line tiles the tiles that DY puts outside the
-    // board are left out: no fragment read, no MFMA.
-    h16x8 bf[2][MT];  // activation fragments, double buffered one k-step ahead
-    auto conv_line = [&](auto dy_tag, int src_off, int dx_lo, int dx_hi, int tap_after) __attribute__((always_inline)) {
-        constexpr int DY = decltype(dy_tag)::value;
-        constexpr int LO = L::LINE_TILES && DY < 0 ? 1 : 0, HI = L::LINE_TILES && DY > 0 ? MT - 1 : MT, NT_ = HI - LO;
-        int T[MT], Tn[MT];
-        tap_rows((DY + 1) * 3 + dx_lo + 1, src_off, T);
+    // k-step order of a pass: (dx, chunk, dy) — all three tap rows of one (dx, chunk) are consecutive k-steps.  The ring
+    // stage of a k-step is its index & (PF - 1): 24 (3x3) or 8 (1x1) k-steps per dx, so it is known at compile time.
+    h16x8 bf[2][MT];  // activation fragments, double buffered
+    // tiles [lo, hi) that a tap row dy touches: with line tiles the tile that dy puts outside the board is left out (no
+    // fragment read, no MFMA)
+    constexpr auto tile_lo = [](int dy) { return L::LINE_TILES && dy < 0 ? 1 : 0; };
+    constexpr auto tile_hi = [](int dy) { return L::LINE_TILES && dy > 0 ? MT - 1 : MT; };
+
+    // Plain reads: one fragment read per (tap, tile), double buffered one k-step ahead.  NDY = 3: the 3x3 layers of the
+    // instances that cannot share fragments between tap rows (NB == 1: a tile is two lines, so a dy shift is not
+    // tile-aligned) or must not (PREV: the reference that reads every fragment from LDS); NDY = 1: the heads' 1x1 passes,
+    // dx in [0, 1).  acc += sum over dx in [dx_lo, dx_hi), the NDY tap rows and all 256 input channels of W * image(src_off).
+    // The first fragments of a pass are read here, after the caller's barrier.
+    auto conv_plain = [&](auto ndy_tag, int src_off, int dx_lo, int dx_hi) __attribute__((always_inline)) {
+        constexpr int NDY = decltype(ndy_tag)::value, DY0 = NDY == 3 ? -1 : 0;
+        int T[NDY][MT], Tn[NDY][MT];
+#pragma unroll
+        for (int i = 0; i < NDY; i++) tap_rows(DY0 + i, dx_lo, src_off, T[i]);
+#pragma unroll
+        for (int mt = tile_lo(DY0); mt < tile_hi(DY0); mt++) bf[0][mt] = *reinterpret_cast<const h16x8 *>(lds + T[0][mt]);
 #pragma nounroll
         for (int dx = dx_lo; dx < dx_hi; dx++) {
-            tap_rows(dx + 1 < dx_hi ? (DY + 1) * 3 + dx + 2 : tap_after, src_off, Tn);
+            // (the last dx has no successor: its prefetch re-reads its own first rows, which nothing uses)
 #pragma unroll
-            for (int ch = 0; ch < 8; ch++) {
-                const int stage = ch & (PF - 1), cur = ch & 1, nxt = cur ^ 1;
+            for (int i = 0; i < NDY; i++) tap_rows(DY0 + i, dx + 1 < dx_hi ? dx + 1 : dx, src_off, Tn[i]);
+            static_for<0, 8 * NDY>([&](auto s_tag) __attribute__((always_inline)) {
+                constexpr int s = decltype(s_tag)::value, ch = s / NDY, i = s % NDY, dy = DY0 + i;
+                constexpr int stage = s & (PF - 1), cur = s & 1, nxt = cur ^ 1;
+                constexpr int lo = tile_lo(dy), hi = tile_hi(dy), nt_ = hi - lo;
                 // next k-step's activation fragments: LDS -> registers
+                constexpr int in_ = (i + 1) % NDY, chn = i + 1 < NDY ? ch : ch + 1;
+                constexpr int lon = tile_lo(DY0 + in_), hin = tile_hi(DY0 + in_), nr = hin - lon;
 #ifndef KZ_TW_NO_DSREAD  // (timing experiments: a build without the fragment reads)
 #pragma unroll
                 for (int mt = 0; mt < MT; mt++) {
-                    if (ch < 7) {
-                        if (mt >= LO && mt < HI) bf[nxt][mt] = *reinterpret_cast<const h16x8 *>(lds + T[mt] + (ch + 1) * 16);
-                    } else {
-                        bf[nxt][mt] = *reinterpret_cast<const h16x8 *>(lds + Tn[mt]);
-                    }
+                    if (mt >= lon && mt < hin)
+                        bf[nxt][mt] = *reinterpret_cast<const h16x8 *>(lds + (chn < 8 ? T[in_][mt] + chn * 16 : Tn[in_][mt]));
                 }
 #endif
                 // this k-step's weight fragments were loaded PF k-steps ago
                 h16x8 af[4];
                 ring_take(stage, af);
-                // 4 x NT_ MFMAs on independent accumulators
+                // 4 x nt_ MFMAs on independent accumulators
                 // (output-channel tile outermost: the weight fragment is held for all pixel tiles and the activation
                 //  fragment changes — same sums, +0.4 % at a full chip against the other order in a same-box A/B)
 #pragma unroll
                 for (int nt = 0; nt < 4; nt++)
 #pragma unroll
-                    for (int mt = LO; mt < HI; mt++)
-                        acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[nt], bf[cur][mt], acc[nt][mt], 0, 0, 0);
+                    for (int mt = 0; mt < MT; mt++)
+                        if (mt >= lo && mt < hi)
+                            acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[nt], bf[cur][mt], acc[nt][mt], 0, 0, 0);
                 // issue order: every memory instruction rides in the shadow of one MFMA — first the 4 ring refills,
                 // then the LDS fragment reads, then the remaining MFMAs back to back.  (Same-box A/B: +0.5 % over a
                 // 2:1 interleave with the LDS reads first, +3 % over the compiler's own order.)
-                constexpr int NR_LAST = MT;
-                const int nr = ch < 7 ? NT_ : NR_LAST;
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
+                for (int j = 0; j < 4; j++) {
                     __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(SG_VMEM_READ, 1, 0);
                 }
 #pragma unroll
-                for (int i = 0; i < MT; i++) {
-                    if (i < nr) {
+                for (int j = 0; j < MT; j++) {
+                    if (j < nr) {
                         __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
                         __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
                     }
                 }
-                // the first k-step of a tap also carries the next tap's row addresses (~35 VALU / SALU): two behind
-                // each of the following MFMAs instead of one block between two of them
-                constexpr int N_FREE = 4 * NT_ - (NT_ + 4), N_ALU = PREV ? 0 : N_FREE < 20 ? N_FREE : 20;
-                if (ch == 0) {
+                // the first k-step of a dx also carries the next dx's row addresses: two VALU / SALU behind each of the
+                // following MFMAs instead of one block between two of them
+                constexpr int n_free = 4 * nt_ - (nr + 4), n_alu = PREV || s != 0 ? 0 : n_free < 20 ? n_free : 20;
 #pragma unroll
-                    for (int i = 0; i < N_ALU; i++) {
+                for (int j = 0; j < 20; j++) {
+                    if (j < n_alu) {
                         __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
                         __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 2, 0);
                     }
-                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 4 * NT_ - (NT_ + 4) - N_ALU, 0);
-                } else if (ch < 7) {
-                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 4 * NT_ - (NT_ + 4), 0);
-                } else {
-                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 4 * NT_ - (NR_LAST + 4), 0);
                 }
+                __builtin_amdgcn_sched_group_barrier(SG_MFMA, n_free - n_alu, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 g++;
-            }
+            });
+#pragma unroll
+            for (int i = 0; i < NDY; i++)
+#pragma unroll
+                for (int mt = 0; mt < MT; mt++) T[i][mt] = Tn[i][mt];
+        }
+    };
+
+    // Line tiles: tile mt at tap row dy reads line mt + dy, which is what tile mt + dy reads at dy = 0 — the same register
+    // content.  So one "super-step" (dx, chunk) reads the 8 line fragments ONCE and three k-steps of weights multiply
+    // them: acc[nt][mt] += W[dy][nt] * frag[mt + dy], tiles 1..7, 0..7, 0..6 (88 MFMAs; 192 fragment reads per wave and
+    // layer where one read per (tap, tile) is 528).  Under the MFMAs ride the 8 reads of the next super-step's
+    // fragments and the 12 ring refills.  Row addresses depend on dx alone: three address blocks per layer, and only
+    // the x masks are per lane.
+    auto conv_3x3_lines = [&](int src_off) __attribute__((always_inline)) {
+        static_assert(!L::LINE_TILES || MT == 8, "one tile per board line");
+        int T[MT], Tn[MT];
+        tap_rows(0, -1, src_off, T);
+#pragma unroll
+        for (int mt = 0; mt < MT; mt++) bf[0][mt] = *reinterpret_cast<const h16x8 *>(lds + T[mt]);
+#pragma nounroll
+        for (int dx = -1; dx < 2; dx++) {
+            // (the last dx has no successor: its prefetch re-reads its own first rows, which nothing uses)
+            tap_rows(0, dx < 1 ? dx + 1 : dx, src_off, Tn);
+            static_for<0, 8>([&](auto ch_tag) __attribute__((always_inline)) {
+                constexpr int ch = decltype(ch_tag)::value, cur = ch & 1, nxt = cur ^ 1;
+                // next super-step's line fragments: LDS -> registers
+#ifndef KZ_TW_NO_DSREAD  // (timing experiments: a build without the fragment reads)
+#pragma unroll
+                for (int mt = 0; mt < MT; mt++)
+                    bf[nxt][mt] = *reinterpret_cast<const h16x8 *>(lds + (ch < 7 ? T[mt] + (ch + 1) * 16 : Tn[mt]));
+#endif
+                static_for<0, 3>([&](auto i_tag) __attribute__((always_inline)) {
+                    constexpr int i = decltype(i_tag)::value, dy = i - 1, stage = (ch * 3 + i) & (PF - 1);
+                    constexpr int lo = tile_lo(dy), hi = tile_hi(dy), nt_ = hi - lo;
+                    // this k-step's weight fragments were loaded PF k-steps ago
+                    h16x8 af[4];
+                    ring_take(stage, af);
+                    // (output-channel tile outermost: the weight fragment is held for all pixel tiles)
+#pragma unroll
+                    for (int nt = 0; nt < 4; nt++)
+#pragma unroll
+                        for (int mt = 0; mt < MT; mt++)
+                            if (mt >= lo && mt < hi)
+                                acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[nt], bf[cur][mt + dy], acc[nt][mt], 0, 0, 0);
+                    // issue order: the 4 ring refills behind the first MFMAs of every k-step; the 8 fragment reads
+                    // behind the next MFMAs of the super-step's first k-step, so they are as far ahead of their use as
+                    // they can be; then, once per dx, the next dx's row addresses two behind each MFMA
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(SG_VMEM_READ, 1, 0);
+                    }
+                    constexpr int nr = i == 0 ? MT : 0;
+#pragma unroll
+                    for (int j = 0; j < MT; j++) {
+                        if (j < nr) {
+                            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                            __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
+                        }
+                    }
+                    constexpr int n_free = 4 * nt_ - (nr + 4), n_alu = ch == 0 && i == 0 ? n_free : 0;
+#pragma unroll
+                    for (int j = 0; j < 4 * MT; j++) {
+                        if (j < n_alu) {
+                            __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                            __builtin_amdgcn_sched_group_barrier(SG_VALU | SG_SALU, 2, 0);
+                        }
+                    }
+                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, n_free - n_alu, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    g++;
+                });
+            });
 #pragma unroll
             for (int mt = 0; mt < MT; mt++) T[mt] = Tn[mt];
         }
     };
-    constexpr std::integral_constant<int, -1> DY_UP{};
-    constexpr std::integral_constant<int, 0> DY_MID{};
-    constexpr std::integral_constant<int, 1> DY_DOWN{};
-    // first fragments of a pass that starts at `tap`
-    auto conv_prime = [&](int src_off, int tap) __attribute__((always_inline)) {
-        int T[MT];
-        tap_rows(tap, src_off, T);
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) bf[0][mt] = *reinterpret_cast<const h16x8 *>(lds + T[mt]);
-    };
+    constexpr std::integral_constant<int, 3> THREE_ROWS{};
+    constexpr std::integral_constant<int, 1> ONE_ROW{};
     // all nine taps
     auto conv_3x3 = [&](int src_off) __attribute__((always_inline)) {
-        conv_prime(src_off, 0);
-        conv_line(DY_UP, src_off, -1, 2, 3);
-        conv_line(DY_MID, src_off, -1, 2, 6);
-        conv_line(DY_DOWN, src_off, -1, 2, 8);
+        if constexpr (L::LINE_TILES && !PREV) conv_3x3_lines(src_off);
+        else conv_plain(THREE_ROWS, src_off, -1, 2);
     };
     // the centre tap only (1x1 convolutions of the heads)
-    auto conv_1x1 = [&](int src_off) __attribute__((always_inline)) {
-        conv_prime(src_off, 4);
-        conv_line(DY_MID, src_off, 0, 1, 4);
-    };
+    auto conv_1x1 = [&](int src_off) __attribute__((always_inline)) { conv_plain(ONE_ROW, src_off, 0, 1); };
 
     // ---- the 2*depth 3x3 convolutions ----
     for (int layer = 1; layer <= layers; layer++) {
@@ -675,15 +754,19 @@ size_t tower_heads_weight_elems() { return (size_t)HEAD_KSTEPS * 16 * 1024 / 2; 
 
 size_t tower_weight_pad_elems() { return (size_t)TOWER_PF_MAX * 16 * 1024 / 2; }
 
-// OIHW f32 -> [tap 9][chunk cin_p/32][wave 4][nt 4][lane 64][8] f16: element j of lane (fr, kq) of (wave, nt) is
-// W[oc = 64*wave + 16*nt + fr][channel][tap] — the A fragment of v_mfma_f32_16x16x32_f16 — where the k-step's channel
-// assignment is the kernel's: cin_p == 256: channel = 8*chunk + {0,128,64,192}[kq] + j (bank-conflict-free LDS reads);
-// stem (cin_p a multiple of 32 below 256: ceil(c_in / 32) chunks): channel = 32*chunk + 8*kq + j.
-void tower_pack_weights(const float *oihw, int cout, int cin, int cin_p, uint16_t *dst) {
+// OIHW f32 -> [k-step][wave 4][nt 4][lane 64][8] f16: element j of lane (fr, kq) of (wave, nt) is
+// W[oc = 64*wave + 16*nt + fr][channel][tap] — the A fragment of v_mfma_f32_16x16x32_f16.
+// Tower layer (cin_p == 256): k-steps in the kernel's order [dx 3][chunk 8][dy 3] (tap = 3*(dy+1) + dx+1), so that the
+// three tap rows that share a line fragment are consecutive; channel = 8*chunk + {0,128,64,192}[kq] + j
+// (bank-conflict-free LDS reads).  tap_major: [tap 9][chunk 8] instead (the four-board experiment launch).
+// Stem (cin_p a multiple of 32 below 256: ceil(c_in / 32) chunks): [tap 9][chunk]; channel = 32*chunk + 8*kq + j.
+void tower_pack_weights(const float *oihw, int cout, int cin, int cin_p, uint16_t *dst, bool tap_major) {
     const int nchunk = cin_p / 32;
+    const bool rows_inner = cin_p == 256 && !tap_major;
     static const int kq_base[4] = {0, 128, 64, 192};
     for (int tap = 0; tap < 9; tap++)
-        for (int chunk = 0; chunk < nchunk; chunk++)
+        for (int chunk = 0; chunk < nchunk; chunk++) {
+            const size_t kstep = rows_inner ? ((size_t)(tap % 3) * 8 + chunk) * 3 + tap / 3 : (size_t)tap * nchunk + chunk;
             for (int wave = 0; wave < 4; wave++)
                 for (int nt = 0; nt < 4; nt++)
                     for (int lane = 0; lane < 64; lane++)
@@ -696,8 +779,9 @@ void tower_pack_weights(const float *oihw, int cout, int cin, int cin_p, uint16_
                             const _Float16 hv = (_Float16)v;
                             uint16_t bits;
                             __builtin_memcpy(&bits, &hv, 2);
-                            dst[(((((size_t)tap * nchunk + chunk) * 4 + wave) * 4 + nt) * 64 + lane) * 8 + j] = bits;
+                            dst[(((kstep * 4 + wave) * 4 + nt) * 64 + lane) * 8 + j] = bits;
                         }
+        }
 }
 
 // Heads part of the weight stream, in execution order: conv_under pass s = 0,1,2 (output channel 3q + s -> row q),
