@@ -12,6 +12,17 @@ written from that definition and sharing nothing with oracle/kz_oracle.c.  It al
            intermediate, or a (hi, lo) pair, stays exact);
   sums:    every accumulation has sum |a b| / step <= 2^22: exact in f32 whatever the order of the additions and however
            the matrix unit aligns its 32 products, as long as it keeps 24 bits.
+
+On those networks a split16 engine's lo halves are all zero.  The wide family (`wide=` of `draw_exact` / `build`, from the
+same draws: `_widen`) has weights, scalar planes and activations that need a (hi, lo) pair, and holds in place of `stored`:
+
+  split-stored:  every such tensor and every layer's weights satisfy v == hi + lo with lo = f16(v - hi), for hi either
+                 f16 neighbour of v, |v| <= 32752, no non-zero lo below 2^-14 (`split_exact`);
+  no lo.lo:      of the two operands of every product a split kernel forms one has no lo half at all, and
+                 hi*hi + hi*lo + lo*hi, computed a second time in float64, equals the plain result;
+
+`sums` as above with the step of the wide values.  The report also says where the lo halves are (`lo_in`, `lo_w`):
+tests/test_exact_nets.py holds that every layer meets them in its input and in every weight fragment.
 """
 import numpy as np
 
@@ -28,6 +39,18 @@ DENSE_P = (1 / 32, 15 / 32, 15 / 32, 1 / 32)
 SPARSE_PER_ROW = 2
 LIVE_SHARE = 0.25            # every channel behind a ReLU is positive on at least this share of the (board, square) positions
 HEAD_SCALE = 0.25            # first layer of every head branch: power-of-two scaling costs no bits and keeps the sums small
+# ---- the wide family (module docstring, "wide") ----
+WIDE = 1.0 + 2.0 ** -11      # +-1 and +-1/4 times this: hi = the weight, lo = 2^-11 of it, both exact in f16 whichever neighbour is hi
+SPLIT_MAX = 32752.0          # half of f16's range
+LO_MIN = 2.0 ** -14          # f16's smallest normal number: no non-zero lo half below it
+FRAGMENT_ENTRIES = 3         # wide weights drawn per weight fragment: one reads one channel on one tap, which a board may leave empty
+LANE = 4                     # attention networks: channel c with c % LANE == LANE - 1 reads such channels only and stays narrow
+NARROW_Q, NARROW_ON = 16, 128
+# ... and the narrow operand of q_from . q_to reads the tower on NARROW_Q query channels, is a constant +-1/4 (its bias alone: one
+# step) on more, NARROW_ON in all, and zero on the rest, each evenly spaced.  A wide value is >= 2^11 steps by definition and
+# the tower's output a few units, so 256 query channels at one step each already come to 2^22 (measured on chess 2x256, all
+# 256 on: 8.0e6 to 1.0e7 with every one reading the tower, 2.6e6 to 4.7e6 with 32 of them; as committed 2.3e6 at the most);
+# Q = 64 keeps every channel on.
 
 
 def layer_names(tensors):
@@ -42,7 +65,7 @@ _HEAD_FIRST = ("scalar_head.seq.0", "policy_head.seq.0", "policy_head.seq_extra.
                "policy_head.conv_under", "policy_head.bulk.0", "policy_head.scalar.0")
 
 
-def _draw(game, depth, channels, head, dense_at, seed, density, kw):
+def _draw(game, depth, channels, head, dense_at, seed, density, kw, wide=None):
     meta, t0 = read_model(synth.random_model(game, depth, channels, head, seed=seed, **kw))
     rng = np.random.default_rng([seed, 7919, 0 if dense_at is None else 1 + dense_at])
     t = {k: v.copy() for k, v in t0.items()}
@@ -84,7 +107,87 @@ def _draw(game, depth, channels, head, dense_at, seed, density, kw):
             w, b = w * HEAD_SCALE, b * HEAD_SCALE
         t[p + ".weight"] = w.reshape(shape).astype(np.float32)
         t[p + ".bias"] = b.astype(np.float32)
+    if wide is not None:
+        _widen(t, meta, names, wide, seed)
     return meta, t
+
+
+def _side_rows(p, q, side):
+    """Output rows of the attention head's convolutions that make up q_from ("from") or q_to ("to")."""
+    if p == "policy_head.conv_bulk":
+        return np.arange(q) if side == "from" else np.arange(q, 2 * q)
+    return np.arange(0) if side == "from" else np.arange(3 * q)  # conv_under: all of q_to
+
+
+def _widen(t, meta, names, wide, seed):
+    """The wide family, from the narrow draw (a pass of its own with a generator of its own: the narrow network of the same
+    seed is the starting point).  wide = (at, side).  at = "input": nothing here (the scalar planes are wide, exact_boards);
+    at = i: layer i gets FRAGMENT_ENTRIES more entries per weight fragment — (16 output rows, tap, 32 input channels) — and all its
+    weights and biases times WIDE; everything in front of layer i is narrow, everything behind it carries lo halves.
+    side (attention heads; None elsewhere) names the operand of q_from . q_to that stays narrow: channels c with
+    c % LANE == LANE - 1 read only such channels from the stem on (the stem's read the bool planes where the scalar planes are
+    wide) and take no wide weight, the rows of that operand read only those channels, and its
+    query channels are thinned out (NARROW_Q, NARROW_ON)."""
+    at, side = wide
+    rng = np.random.default_rng([seed, 15485863])
+    ns, nb = meta["input_scalar_channels"], meta["input_bool_channels"]
+    q = meta.get("policy_query_channels", 0)
+    plain = {}  # layer -> the rows that may go wide
+    for p in names:
+        w = t[p + ".weight"]
+        rows = np.arange(w.shape[0])
+        if side is not None:
+            if p.startswith("common.tower."):
+                narrow = rows[rows % LANE == LANE - 1]
+            elif p in _ONE_PER_ROW:
+                narrow = _side_rows(p, q, side)
+            else:
+                narrow = rows[:0]
+            stem = p == "common.tower.0"
+            for r in narrow:  # move every entry of the row to a narrow input channel, same tap
+                old, w[r] = w[r].copy(), 0.0
+                for c in np.flatnonzero(old.reshape(old.shape[0], -1).any(axis=1)):
+                    to = (ns + c % nb if at == "input" and c < ns else c) if stem else c - c % LANE + LANE - 1
+                    w[r, to] = np.where(old[c] != 0, old[c], w[r, to])
+            const = narrow[:0]
+            if p in _ONE_PER_ROW and len(narrow):
+                qi = (narrow if p == "policy_head.conv_bulk" else narrow // 3) % q
+                const = narrow[qi % max(1, q // NARROW_Q) != 0]
+                off = narrow[qi % max(1, q // NARROW_ON) != 0]
+                w[const] = 0.0
+                bias = t[p + ".bias"]
+                bias[const] = np.where(bias[const] != 0, bias[const], HEAD_SCALE * rng.choice((-1.0, 1.0), size=len(const)))
+                bias[off] = 0.0
+            # a moved entry may have been the only one that read its channel: every input channel is read again, a wide one
+            # (c % LANE != LANE - 1, or a scalar plane where those are wide) by a row that may be wide
+            free = np.setdiff1d(rows, narrow)
+            w3 = w.reshape(w.shape[0], w.shape[1], -1)
+            for c in np.flatnonzero(~w3.any(axis=(0, 2))):
+                lane_in = c >= ns if stem else c % LANE == LANE - 1
+                pick = np.setdiff1d(rows, const) if lane_in or (stem and at != "input") else free
+                if not len(pick):
+                    continue  # (conv_under with q_to narrow: nothing of it may read a wide channel)
+                w3[int(rng.choice(pick)), c, int(rng.integers(w3.shape[2]))] = (HEAD_SCALE if p in _HEAD_FIRST else 1.0) * rng.choice((-1.0, 1.0))
+            rows = np.setdiff1d(rows, narrow)
+        plain[p] = rows
+    if at == "input":
+        return
+    p = names[at]
+    w, rows = t[p + ".weight"], plain[p]
+    w3 = w.reshape(w.shape[0], w.shape[1], -1)  # (a view: 2-D weights have one tap)
+    unit = HEAD_SCALE if p in _HEAD_FIRST else 1.0
+    for r0 in range(0, w.shape[0], 16):
+        tile = rows[(rows >= r0) & (rows < r0 + 16)]
+        if not len(tile):
+            continue
+        for tap in range(w3.shape[2]):
+            for c0 in range(0, w.shape[1], 32):
+                for _ in range(FRAGMENT_ENTRIES):
+                    r, c = int(rng.choice(tile)), c0 + int(rng.integers(min(32, w.shape[1] - c0)))
+                    if w3[r, c, tap] == 0:
+                        w3[r, c, tap] = unit * rng.choice((-1.0, 1.0))
+    w[rows] *= np.float32(WIDE)
+    t[p + ".bias"][rows] *= np.float32(WIDE)  # (f32 in every kernel: the accumulator starts wide, so the output is wide wherever the bias is not zero)
 
 
 def _bias(rng, n):
@@ -94,18 +197,18 @@ def _bias(rng, n):
     return b
 
 
-def draw_exact(game, depth, channels, head, dense_at, seed, density=1.0, boards=None, max_redraws=8, **kw):
+def draw_exact(game, depth, channels, head, dense_at, seed, density=1.0, boards=None, max_redraws=8, wide=None, **kw):
     """(meta, tensors, seed used, (scalars, policy, report) of `reference` on the boards).  Redraws the seed until the
     reference meets the conditions.  With the weights drawn, one pass of the reference over the boards raises the integer
     bias in front of every ReLU whose channel would be positive on less than LIVE_SHARE of the (board, square) positions
     (`revive`): a weight that reads a dead channel could be anything, and one that reads a channel alive on a few squares
-    only shows where the ReLU behind it happens to be open."""
-    bits, scalars = boards if boards is not None else exact_boards(game, 13, seed)
+    only shows where the ReLU behind it happens to be open.  wide = (at, side): a network of the wide family (`_widen`)."""
+    bits, scalars = boards if boards is not None else exact_boards(game, 13, seed, wide=wide is not None and wide[0] == "input")
     for attempt in range(max_redraws):
         s = seed + 1000 * attempt
-        meta, t = _draw(game, depth, channels, head, dense_at, s, density, kw)
+        meta, t = _draw(game, depth, channels, head, dense_at, s, density, kw, wide)
         out = reference(t, meta, encode(meta, bits, scalars), revive=True)
-        if conditions_hold(out[2]):
+        if conditions_hold(out[2], wide is not None):
             return meta, t, s, out
     raise RuntimeError(f"no exact network in {max_redraws} draws: {game} {depth}x{channels} {head} dense_at={dense_at}")
 
@@ -119,8 +222,9 @@ def exact_model(game, depth, channels, head, dense_at, seed, **kw):
     return write_model(meta, t), t
 
 
-def exact_boards(game, batch, seed):
-    """Bool planes as synth.random_boards; scalars small integers (Ataxx, and Go's komi plane: halves) in place of the raw counters."""
+def exact_boards(game, batch, seed, wide=False):
+    """Bool planes as synth.random_boards; scalars small integers (Ataxx, and Go's komi plane: halves) in place of the raw counters.
+    wide: every scalar s becomes (s + 1) * WIDE — no plane is zero, every one has a lo half."""
     bits, scalars = synth.random_boards(game, batch, seed=seed)
     rng = np.random.default_rng([seed, 104729])
     if game.startswith("ataxx"):
@@ -131,6 +235,8 @@ def exact_boards(game, batch, seed):
     elif scalars.shape[1]:
         keep = scalars <= 2  # flags and repetition counts stay; the 0..99 / 0..59 counters become 0..2
         scalars = np.where(keep, scalars, rng.integers(0, 3, size=scalars.shape))
+    if wide:
+        scalars = (scalars + 1.0) * WIDE
     return bits, np.ascontiguousarray(scalars, dtype=np.float32)
 
 
@@ -160,14 +266,54 @@ def step_of(v):
     return float(2.0 ** int((e - 53 + tz).min()))
 
 
+def f16_neighbours(v):
+    """The f16 values just below and just above v (both v itself where f16 holds it)."""
+    v = np.asarray(v, np.float64)
+    with np.errstate(over="ignore"):
+        h = v.astype(np.float16)
+    inf = np.float16(np.inf)
+    return np.where(h > v, np.nextafter(h, -inf), h), np.where(h < v, np.nextafter(h, inf), h)
+
+
+def split16(v):
+    """(hi, lo) in float64 as the kernels form them: hi = f16(v), lo = f16(v - hi), to nearest."""
+    v = np.asarray(v, np.float64)
+    hi = v.astype(np.float16).astype(np.float64)
+    return hi, (v - hi).astype(np.float16).astype(np.float64)
+
+
+def split_exact(v):
+    """(v == hi + lo with lo = f16(v - hi) and no non-zero |lo| below LO_MIN, for hi either f16 neighbour of v — no
+    rounding mode of the conversion is assumed — and max |v| <= SPLIT_MAX; some lo is non-zero)."""
+    v = np.asarray(v, np.float64)
+    if np.abs(v).max(initial=0.0) > SPLIT_MAX:
+        return False, True
+    ok, any_lo = True, False
+    for hi in f16_neighbours(v):
+        lo = (v - hi.astype(np.float64)).astype(np.float16).astype(np.float64)
+        ok = ok and bool(np.array_equal(hi.astype(np.float64) + lo, v)) and not bool(((lo != 0) & (np.abs(lo) < LO_MIN)).any())
+        any_lo = any_lo or bool(lo.any())
+    return ok, any_lo
+
+
 class _Report:
-    def __init__(self):
+    def __init__(self, measure=True):
+        self.measure = measure
         self.stored = {}  # name -> (max |v| / step, round-trips through f16)
         self.sums = {}    # name -> max sum |a b| / step
+        # what the wide family adds (narrow networks hold all of it trivially, every lo being zero)
+        self.split = {}   # name (a stored tensor, or "<layer>.weight") -> (split_exact, step >= LO_MIN or no lo at all)
+        self.lolo = {}    # product -> (one operand has no lo half, hi*hi + hi*lo + lo*hi == the plain result)
+        self.lo_in = {}   # layer -> (share of its input's entries with a lo half, every 32-channel chunk has one)
+        self.lo_w = {}    # layer -> [tile, chunk, tap] bool: that weight fragment (16 rows, tap, 32 input channels) holds a lo half
 
     def store(self, name, v):
+        if not self.measure:
+            return
         ok = bool(np.array_equal(v.astype(np.float16).astype(np.float64), v))
         self.stored[name] = (float(np.abs(v).max() / step_of(v)), ok)
+        ok, any_lo = split_exact(v)
+        self.split[name] = (ok, not any_lo or step_of(v) >= LO_MIN)
 
     def acc(self, name, mag, step):
         self.sums[name] = float(mag.max() / step)
@@ -176,33 +322,74 @@ class _Report:
         return max(v for v, _ in self.stored.values()), max(self.sums.values())
 
 
-def conditions_hold(report):
-    return (all(ok and v <= STORED_MAX for v, ok in report.stored.values()) and
-            all(v <= SUM_MAX for v in report.sums.values()))
+def conditions_hold(report, wide=False):
+    """Narrow family: stored and sums.  Wide family: split-stored, no lo.lo, sums."""
+    sums = all(v <= SUM_MAX for v in report.sums.values())
+    if wide:
+        return sums and all(a and b for a, b in report.split.values()) and all(a and b for a, b in report.lolo.values())
+    return sums and all(ok and v <= STORED_MAX for v, ok in report.stored.values())
 
 
-def _conv(rep, name, x, w, b):
-    """Convolution (3x3 same-padded: nine shifted einsums on a zero-padded image; 1x1; any odd k) or, for 2-D w, linear."""
-    w, b = w.astype(np.float64), b.astype(np.float64)
-    step = min(step_of(w) * step_of(x), step_of(b))
+def _chunks(a, n, axis):
+    """a with `axis` cut into pieces of n (the last one padded with zeros) -> [..., pieces, n, ...]."""
+    pad = -a.shape[axis] % n
+    a = np.pad(a, [(0, pad if i == axis else 0) for i in range(a.ndim)])
+    return a.reshape(a.shape[:axis] + (a.shape[axis] // n, n) + a.shape[axis + 1:])
+
+
+def _edge(hh, ww):
+    m = np.zeros((hh, ww), bool)
+    m[0], m[-1], m[:, 0], m[:, -1] = True, True, True, True
+    return m
+
+
+def _lin(x, w, spoil=None):
+    """w applied to x without the bias (3x3 same-padded: nine shifted einsums on a zero-padded image; 1x1; any odd k; 2-D
+    w: linear), and the same on the magnitudes.  spoil = (dy, dx): what a wrong lo address of the input does — on that tap
+    the board's edge squares read x without its lo halves."""
     if w.ndim == 2:
-        y = x @ w.T + b
-        mag = np.abs(x) @ np.abs(w).T + np.abs(b)
-    else:
-        k = w.shape[2]
-        pad = k // 2
-        hh, ww = x.shape[2], x.shape[3]
-        xp = np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
-        y = np.zeros((x.shape[0], w.shape[0], hh, ww))
-        mag = np.zeros_like(y)
-        for dy in range(k):
-            for dx in range(k):
-                win = xp[:, :, dy:dy + hh, dx:dx + ww]
-                y += np.einsum("oc,bchw->bohw", w[:, :, dy, dx], win, optimize=True)
-                mag += np.einsum("oc,bchw->bohw", np.abs(w[:, :, dy, dx]), np.abs(win), optimize=True)
-        y += b[None, :, None, None]
-        mag += np.abs(b)[None, :, None, None]
-    rep.acc(name, mag, step)
+        return x @ w.T, np.abs(x) @ np.abs(w).T
+    k = w.shape[2]
+    pad = k // 2
+    hh, ww = x.shape[2], x.shape[3]
+    xp = np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
+    y = np.zeros((x.shape[0], w.shape[0], hh, ww))
+    mag = np.zeros_like(y)
+    for dy in range(k):
+        for dx in range(k):
+            win = xp[:, :, dy:dy + hh, dx:dx + ww]
+            if spoil == (dy, dx):
+                win = np.where(_edge(hh, ww), split16(win)[0], win)
+            y += np.einsum("oc,bchw->bohw", w[:, :, dy, dx], win, optimize=True)
+            mag += np.einsum("oc,bchw->bohw", np.abs(w[:, :, dy, dx]), np.abs(win), optimize=True)
+    return y, mag
+
+
+def _conv(rep, name, x, w, b, spoil=None):
+    """Convolution or, for 2-D w, linear layer, with what the report measures of it.  spoil: {"tap": (dy, dx)} (`_lin`), or
+    {"fragment": (tile, (dy, dx), chunk)}: that weight fragment loses its lo halves."""
+    w, b = w.astype(np.float64), b.astype(np.float64)
+    spoil = spoil or {}
+    if "fragment" in spoil:
+        tile, (dy, dx), chunk = spoil["fragment"]
+        w = w.copy()
+        part = w[16 * tile:16 * tile + 16, 32 * chunk:32 * chunk + 32, dy, dx]
+        part[...] = split16(part)[0]
+    y, mag = _lin(x, w, spoil.get("tap"))
+    shape = (1, -1) + (1,) * (y.ndim - 2)
+    y = y + b.reshape(shape)
+    if not rep.measure:
+        return y
+    rep.acc(name, mag + np.abs(b).reshape(shape), min(step_of(w) * step_of(x), step_of(b)))
+    ok, any_lo = split_exact(w)
+    rep.split[name + ".weight"] = (ok, not any_lo or step_of(w) >= LO_MIN)
+    (xh, xl), (wh, wl) = split16(x), split16(w)
+    three = _lin(xh, wh)[0] + (_lin(xl, wh)[0] if xl.any() else 0.0) + (_lin(xh, wl)[0] if wl.any() else 0.0) + b.reshape(shape)
+    rep.lolo[name] = (not (xl.any() and wl.any()), bool(np.array_equal(three, y)))
+    live = _chunks(xl != 0, 32, 1)
+    rep.lo_in[name] = (float(np.mean(xl != 0)), bool(live.any(axis=tuple(i for i in range(live.ndim) if i != 1)).all()))
+    frag = _chunks(_chunks(wl.reshape(wl.shape[0], wl.shape[1], -1) != 0, 16, 0), 32, 2)  # [tile, 16, chunk, 32, tap]
+    rep.lo_w[name] = frag.any(axis=(1, 3))
     return y
 
 
@@ -214,11 +401,13 @@ def _bn(t, p, x, eps):
     return y
 
 
-def reference(t, meta, x, revive=False):
+def reference(t, meta, x, revive=False, spoil=None, exact=True):
     """(scalars [B, 5], policy [B, P], report) in float64; x [B, C_in, H, W].  report.acts holds the tower's and the scalar
     head's intermediates under the oracle's trace names.  revive (the generator's pass): t is changed in place — the bias
-    in front of a ReLU is raised by whole units wherever the channel would be positive on too few positions."""
-    rep = _Report()
+    in front of a ReLU is raised by whole units wherever the channel would be positive on too few positions.
+    spoil = {"layer": name, "tap": (dy, dx)} or {"layer": name, "fragment": (tile, (dy, dx), chunk)}: one wrong lo address
+    (`_conv`).  exact=False: any network (random weights), nothing measured or asserted."""
+    rep = _Report(measure=exact)
     acts = rep.acts = {}
 
     def relu(v, bias_key=None):
@@ -238,7 +427,7 @@ def reference(t, meta, x, revive=False):
     b = x.shape[0]
 
     def conv(p, v):
-        return _conv(rep, p, v, t[p + ".weight"], t[p + ".bias"])
+        return _conv(rep, p, v, t[p + ".weight"], t[p + ".bias"], spoil if spoil and spoil["layer"] == p else None)
 
     x = np.asarray(x, np.float64)
     rep.store("input", x)
@@ -285,7 +474,11 @@ def reference(t, meta, x, revive=False):
         q_from = hidden("policy_head.q_from", bulk[:, :q].reshape(b, q, 64))
         q_to = hidden("policy_head.q_to", np.concatenate([bulk[:, q:].reshape(b, q, 64), under.reshape(b, q, 24)], axis=2))
         logits = np.einsum("bqi,bqj->bij", q_from, q_to, optimize=True)
-        rep.acc("policy_head.bmm", np.einsum("bqi,bqj->bij", np.abs(q_from), np.abs(q_to), optimize=True), step_of(q_from) * step_of(q_to))
+        if exact:
+            rep.acc("policy_head.bmm", np.einsum("bqi,bqj->bij", np.abs(q_from), np.abs(q_to), optimize=True), step_of(q_from) * step_of(q_to))
+            (fh, fl), (th, tl) = split16(q_from), split16(q_to)
+            three = sum(np.einsum("bqi,bqj->bij", u, v, optimize=True) for u, v in ((fh, th), (fh, tl), (fl, th)))
+            rep.lolo["policy_head.bmm"] = (not (fl.any() and tl.any()), bool(np.array_equal(three, logits)))
         policy = (logits / np.sqrt(float(q))).reshape(b, -1)[:, t["policy_head.FLAT_TO_ATT"]]
     elif kind == "dense":
         cur, idx = common, 0
@@ -303,7 +496,7 @@ def reference(t, meta, x, revive=False):
     else:
         raise ValueError(f"no exact reference for policy head '{kind}'")
     # the outputs are f32: they must be exact there
-    for name, v in (("scalars", scalars), ("policy", policy)):
+    for name, v in (("scalars", scalars), ("policy", policy)) if exact else ():
         assert np.array_equal(v.astype(np.float32).astype(np.float64), v), f"{name}: not exact in f32"
     return scalars, policy, rep
 
@@ -347,28 +540,61 @@ def positions(net):
     return [None] + list(range(len(layer_names(t))))
 
 
+# The wide family: the networks a split16 engine runs (tests/test_gpu_exact.py), no dense layer.
+WIDE_NETS = ("chess_2x256_att", "chess_1x128_att", "chess_1x192_att", "ataxx7_1x128", "ataxx5_1x128", "ataxx7_1x64",
+             "go9_1x128", "go19_1x64", "go19_1x128")
+
+
+def wide_positions(net):
+    """(at, side) of every wide variant of a network: the scalar planes wide ("input"), then each layer's weights in turn.
+    Attention heads: each variant twice, q_from or q_to the narrow operand; conv_under makes up q_to only, so it is wide
+    with q_from narrow, and conv_bulk is wide on the other operand's rows: the two variants together cover its fragments."""
+    game, depth, channels, head, kw, _ = NETS[net]
+    _, t = read_model(synth.random_model(game, depth, channels, head, seed=SEED, **kw))
+    names = layer_names(t)
+    sides = ("from", "to") if head == "attention" else (None,)
+    skip = ("policy_head.conv_under", "scalar_head.")  # (the scalar head's variants do not depend on the side: once)
+    return [(at, side) for side in sides for at in ["input"] + list(range(len(names)))
+            if not (side == "to" and at != "input" and names[at].startswith(skip))]
+
+
+def wide_id(wide):
+    return f"wide-{wide[0]}" + (f"-{wide[1]}" if wide[1] else "")
+
+
 class Built:
     pass
 
 
 _CACHE = {}
+_COVER = {}  # (net, wide) -> (report.lo_in, report.lo_w): small, kept for every wide model built
 
 
-def build(net, dense_at):
-    """One model per (network, dense position), with its boards and float64 reference; cached (the last few only: the
-    512-channel blobs are tens of MB)."""
-    key = (net, dense_at)
+def build(net, dense_at, wide=None):
+    """One model per (network, dense position, wide variant), with its boards and float64 reference; cached (the last few
+    only: the 512-channel blobs are tens of MB)."""
+    key = (net, dense_at, wide)
     if key not in _CACHE:
         while len(_CACHE) >= 12:
             _CACHE.pop(next(iter(_CACHE)))
         game, depth, channels, head, kw, density_at = NETS[net]
         b = Built()
-        b.bits, b.scalars_in = exact_boards(game, BOARDS, SEED)
+        b.bits, b.scalars_in = exact_boards(game, BOARDS, SEED, wide=wide is not None and wide[0] == "input")
         b.meta, b.tensors, b.seed, (s, p, b.report) = draw_exact(game, depth, channels, head, dense_at, SEED, boards=(b.bits, b.scalars_in),
-                                                                 density=density_at.get(dense_at, 1.0), **kw)
+                                                                 density=density_at.get(dense_at, 1.0), wide=wide, **kw)
         b.blob = write_model(b.meta, b.tensors)
         b.x = encode(b.meta, b.bits, b.scalars_in)
         b.ref_scalars, b.ref_policy = s.astype(np.float32), p.astype(np.float32)
         b.layers = layer_names(b.tensors)
         _CACHE[key] = b
+        if wide is not None and dense_at is None:
+            _COVER[net, wide] = (b.report.lo_in, b.report.lo_w)
     return _CACHE[key]
+
+
+def coverage(net):
+    """{wide variant: (lo_in, lo_w)} over every wide variant of the network."""
+    for wide in wide_positions(net):
+        if (net, wide) not in _COVER:
+            build(net, None, wide)
+    return {wide: _COVER[net, wide] for wide in wide_positions(net)}

@@ -5,7 +5,8 @@ stored intermediates are short dyadic numbers within half of f16's integer range
 tests/test_exact_nets.py holds both for every case here), so any difference is a wrong address, pad, pack or batch
 offset: exactly the errors that sit below the f16 bounds of tests/test_gpu_parity.py.
 
-Every engine runs with the fully dense layer at each position of its network and with none.  Launches are ragged on
+Every engine runs with the fully dense layer at each position of its network and with none.  The split16 engines, whose lo
+halves are all zero on those networks, run the wide family as well, with the exact-f32 engines of the same networks beside them.  Launches are ragged on
 purpose — boards per workgroup x k + 1 boards, and one board alone; the instances that need a full chip before the
 engine picks them get that many boards, the thirteen distinct ones repeated.
 """
@@ -64,6 +65,7 @@ ENGINES = [
     ("go19x64-board-f16", "go19_1x64", F16, 256, {}, "board_conv_f16", None, 9),
     ("go19x64-board-split16", "go19_1x64", SPLIT, 256, {}, "board_conv_split16", None, 9),
     ("go19x128-board-f16", "go19_1x128", F16, 256, {}, "board_conv_f16", None, 9),               # two output-channel quarters
+    ("go19x128-board-split16", "go19_1x128", SPLIT, 256, {}, "board_conv_split16", None, 9),     # ... in split arithmetic
     ("go13x128-f16g", "go13_1x128", F16, 64, {}, "tower_resident_f16g+heads", 1, 9),          # (where the table sends 13x13)
     ("go13x128-board-f16", "go13_1x128", F16, 256, {"KZ_NO_RESIDENT_F16G": "1"}, "board_conv_f16", None, 9),
     # the generic per-layer path
@@ -86,6 +88,12 @@ ENGINES = [
 # (ordered by network and position: exact_nets.build keeps the last few models, every engine of one model runs in a row)
 CASES = [(e, pos) for net in E.NETS for pos in E.positions(net) for e in ENGINES if e[1] == net]
 IDS = [f"{e[0]}-{'none' if pos is None else pos}" for e, pos in CASES]
+
+
+# The wide family (tests/exact_nets.py: lo halves that are not zero): every split16 engine, and every exact-f32 engine of the same
+# networks — the cross-check that the network is exact, not the kernel lenient.  The f16 engines do not run it.
+WIDE_CASES = [(e, wide) for net in E.WIDE_NETS for wide in E.wide_positions(net) for e in ENGINES if e[1] == net and e[2] in (SPLIT, F32)]
+WIDE_IDS = [f"{e[0]}-{E.wide_id(wide)}" for e, wide in WIDE_CASES]
 
 
 def make_engine(model, dev, max_batch, dtype, switches):
@@ -120,12 +128,23 @@ def dev():
 @pytest.mark.gpu
 @pytest.mark.parametrize("engine,pos", CASES, ids=IDS)
 def test_engine_returns_the_reference_bits(dev, engine, pos):
+    returns_the_reference_bits(dev, engine, E.build(engine[1], pos), f"dense_at={pos}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("engine,wide", WIDE_CASES, ids=WIDE_IDS)
+def test_engine_returns_the_reference_bits_on_a_wide_network(dev, engine, wide):
+    """Activations or weights with lo halves that are not zero: a lo fragment read from the wrong board, tap, chunk, tile
+    or ring stage changes the bits."""
+    returns_the_reference_bits(dev, engine, E.build(engine[1], None, wide), E.wide_id(wide))
+
+
+def returns_the_reference_bits(dev, engine, b, label):
     name, net, dtype, max_batch, switches, path, per, batch = engine
-    b = E.build(net, pos)
     eng = make_engine(capi.Model(blob=b.blob), dev, max_batch, dtype, switches)
     assert eng.tower_path == path
     geometry = eng.launch_geometry(batch)
-    print(f"[exact] {name} dense_at={pos}: {eng.tower_path}, {batch} boards in {geometry[0]} workgroups of {geometry[1]}")
+    print(f"[exact] {name} {label}: {eng.tower_path}, {batch} boards in {geometry[0]} workgroups of {geometry[1]}")
     if per is not None:
         assert geometry == ((batch + per - 1) // per, per)
         assert batch % per == 1 or per == 1, "ragged: the last workgroup holds one board"
@@ -153,12 +172,17 @@ def test_one_process_runs_both_chess_instances_in_either_order(dev):
 @pytest.mark.gpu
 def test_the_split_1x1_kernel_is_among_the_exact_cases(dev):
     """kz_conv1x1_split (the f16 / split engines' 1x1 head convolutions where the plan sends them through it) is reached by
-    the cases above: at least one of them launches it, by its profiled kernel name."""
+    the cases above: at least one of them launches it, by its profiled kernel name — and in split arithmetic on a wide
+    network whose tower output carries lo halves (the stem's weights wide)."""
     reached = []
     for name, net, dtype, max_batch, switches, path, _, _ in ENGINES:
         if dtype == F32 or path.endswith("+heads"):
             continue
-        b = E.build(net, None)
+        wide = next(w for w in E.wide_positions(net) if w[0] == 0) if dtype == SPLIT else None
+        b = E.build(net, None, wide)
+        if wide is not None:
+            heads = [p for p in b.layers if not p.startswith("common.") and b.tensors[p + ".weight"].ndim == 4]
+            assert heads and all(b.report.lo_in[p][0] >= E.LIVE_SHARE and b.report.lo_in[p][1] for p in heads)
         eng = make_engine(capi.Model(blob=b.blob), dev, max_batch, dtype, switches)
         eng.set_profiling(True)
         s, p = eng.eval_packed(b.bits[:3], b.scalars_in[:3])
@@ -166,6 +190,7 @@ def test_the_split_1x1_kernel_is_among_the_exact_cases(dev):
         eng.set_profiling(False)
         assert np.array_equal(s, b.ref_scalars[:3]) and np.array_equal(p, b.ref_policy[:3]), name
         if launches:
-            reached.append(name)
+            reached.append((name, wide))
     print(f"[exact] kz_conv1x1_split runs in: {reached}")
     assert reached
+    assert any(wide is not None for _, wide in reached), "no wide network reaches kz_conv1x1_split"
