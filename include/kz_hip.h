@@ -185,6 +185,33 @@ int kz_engine_submit_packed_decoded_sym(kz_engine *engine, int slot, const uint8
                                         const float *scalars_in, int batch, const uint8_t *sym,
                                         const int64_t *move_offsets, const int32_t *move_indices);
 
+/* ---- every board under every symmetry, averaged: `AverageSymmetryNetwork` (symmetry.rs:70-124,150-184) inside the engine.
+ * The caller passes the ORIGINAL boards and the move_to_index lists of the ORIGINAL boards' moves, ONCE per board; outputs
+ * have the shape of the other decoded entries (values [batch,5], probabilities parallel to move_indices), and
+ * kz_engine_wait_decoded waits for the submit.  The entries use ALL rows of the tables set by kz_engine_set_symmetries, in id
+ * order 0 .. n_sym-1: the ROW ORDER OF THE TABLES IS THE SUMMATION ORDER.  The network runs on batch * n_sym virtual boards —
+ * virtual board b * n_sym + k is board b under symmetry k, the reference's flat_map order (:98-101) — so batch may be at
+ * most max_batch / n_sym.  Per batch three launches on the slot's stream: a fan-out from the pinned staging into device
+ * scratch (boards, scalars and move lists replicated, ids = k), the network with its decode exactly as for the _sym entries,
+ * and the average into the pinned staging; only batch boards go in and batch results come out over PCIe.
+ * Arithmetic, all f32, every division correctly rounded; with v_k, p_k the decoded values and probabilities under symmetry k
+ * as the _sym entry produces them and n = n_sym (symmetry.rs:156-176):
+ *   each of the five values = (((0 + v_0) + v_1) + ... + v_{n-1}) / n
+ *   each probability        = ((0 + p_0 / n) + p_1 / n) + ... + p_{n-1} / n     in the caller's move order
+ * and a finished board (an empty range) gets no probabilities.
+ * Fails before anything is enqueued, with a message of its own each: no tables set; batch > max_batch / n_sym (the message
+ * names that limit); a bad slot; a slot still in flight; null arguments or bad offsets as for the other decoded submits.
+ * batch == 0 is the same no-op.  Errors inside the batch — a listed move without an image under some symmetry, a move index
+ * outside the policy, a softmax sum that is not positive, a non-finite activation, on ANY virtual board — fail the call that
+ * returns the batch with the _sym entries' messages; no read leaves the tables.  kz_engine_set_symmetries refuses while an
+ * averaged batch is in flight. */
+int kz_engine_eval_packed_decoded_avg(kz_engine *engine, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                      int batch, const int64_t *move_offsets, const int32_t *move_indices,
+                                      float *values_out, float *probs_out);
+int kz_engine_submit_packed_decoded_avg(kz_engine *engine, int slot, const uint8_t *bits, size_t bits_stride,
+                                        const float *scalars_in, int batch, const int64_t *move_offsets,
+                                        const int32_t *move_indices);
+
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and
  * returns; kz_engine_synchronize waits. */

@@ -68,6 +68,10 @@ SIGNATURES = {
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kz_engine_submit_packed_decoded_sym": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kz_engine_eval_packed_decoded_avg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kz_engine_submit_packed_decoded_avg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                                      C.c_void_p, C.c_void_p]),
     "kz_engine_enqueue_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                                   C.c_void_p, C.c_void_p]),
     "kz_engine_enqueue_dense_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -307,6 +311,43 @@ class Engine:
                                                      scalars_in.ctypes.data, bits.shape[0], offsets.ctypes.data,
                                                      idx.ctypes.data))
         return offsets
+
+    @staticmethod
+    def _csr(move_lists):
+        offsets = np.zeros(len(move_lists) + 1, np.int64)
+        offsets[1:] = np.cumsum([len(m) for m in move_lists])
+        idx = np.ascontiguousarray(np.concatenate([np.asarray(m, np.int32) for m in move_lists] + [np.zeros(0, np.int32)]),
+                                   dtype=np.int32)
+        return offsets, idx
+
+    def eval_packed_decoded_avg(self, bits: np.ndarray, scalars_in: np.ndarray, move_lists):
+        """Every board under every symmetry of set_symmetries, averaged on the GPU (kz_engine_eval_packed_decoded_avg): the
+        original boards and move lists once per board in, (values [batch,5], [probs per board]) out; at most
+        max_batch // n_sym boards."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        batch = bits.shape[0]
+        offsets, idx = self._csr(move_lists)
+        values = np.empty((batch, 5), np.float32)
+        probs = np.empty(max(len(idx), 1), np.float32)
+        check(load().kz_engine_eval_packed_decoded_avg(self._h, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                                       scalars_in.ctypes.data, batch, offsets.ctypes.data, idx.ctypes.data,
+                                                       values.ctypes.data, probs.ctypes.data))
+        return values, [probs[offsets[i]:offsets[i + 1]].copy() for i in range(batch)]
+
+    def submit_packed_decoded_avg(self, slot: int, bits: np.ndarray, scalars_in: np.ndarray, move_lists):
+        """The asynchronous half (kz_engine_submit_packed_decoded_avg); wait_decoded(slot, the returned offsets) waits."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        offsets, idx = self._csr(move_lists)
+        check(load().kz_engine_submit_packed_decoded_avg(self._h, slot, bits.ctypes.data, bits.shape[1], scalars_in.ctypes.data,
+                                                         bits.shape[0], offsets.ctypes.data, idx.ctypes.data))
+        return offsets
+
+    def submit_packed_decoded_avg_csr(self, slot: int, bits: np.ndarray, scalars_in: np.ndarray, offsets: np.ndarray, idx: np.ndarray):
+        """The same with the CSR move lists already built: what a timed loop calls."""
+        check(load().kz_engine_submit_packed_decoded_avg(self._h, slot, bits.ctypes.data, bits.shape[1], scalars_in.ctypes.data,
+                                                         bits.shape[0], offsets.ctypes.data, idx.ctypes.data))
 
     def submit_packed_decoded_csr(self, slot: int, bits: np.ndarray, scalars_in: np.ndarray, offsets: np.ndarray, idx: np.ndarray,
                                   sym: np.ndarray = None):

@@ -149,9 +149,16 @@ class HipNetwork : public Network<B> {
     int n_sym_ = 0;
     std::mt19937_64 sym_rng_;
     std::vector<uint8_t> sym_ids_;
+    // every board under all n_sym_ symmetries, averaged inside the engine (set_average_symmetries)
+    bool average_ = false;
 
     // the decoded submit of a prepared batch; with symmetries on, every board gets an id of its own (symmetry.rs:47-52)
     void submit_decoded(int slot, size_t bits_bytes, size_t n) {
+        if (average_) {
+            kz_check(kz_engine_submit_packed_decoded_avg(engine_, slot, bits_.data(), bits_bytes, scalars_in_.data(), (int)n,
+                                                         move_offsets_[slot].data(), move_indices_.data()));
+            return;
+        }
         if (!n_sym_) {
             kz_check(kz_engine_submit_packed_decoded(engine_, slot, bits_.data(), bits_bytes, scalars_in_.data(), (int)n,
                                                      move_offsets_[slot].data(), move_indices_.data()));
@@ -286,7 +293,7 @@ class HipNetwork : public Network<B> {
         : mapper_(o.mapper_), model_(std::move(o.model_)), engine_(o.engine_), max_batch_size_(o.max_batch_size_),
           bits_(std::move(o.bits_)), scalars_in_(std::move(o.scalars_in_)), next_slot_(o.next_slot_),
           oldest_slot_(o.oldest_slot_), in_flight_(o.in_flight_), device_decode_(o.device_decode_), n_sym_(o.n_sym_),
-          sym_rng_(o.sym_rng_), ranges_(std::move(o.ranges_)), helpers_(std::move(o.helpers_)), wait_cpu_ns(o.wait_cpu_ns) {
+          sym_rng_(o.sym_rng_), average_(o.average_), ranges_(std::move(o.ranges_)), helpers_(std::move(o.helpers_)), wait_cpu_ns(o.wait_cpu_ns) {
         for (int i = 0; i < KZ_ENGINE_SLOTS; i++) {
             pending_boards_[i] = std::move(o.pending_boards_[i]);
             move_offsets_[i] = std::move(o.move_offsets_[i]);
@@ -302,7 +309,7 @@ class HipNetwork : public Network<B> {
     // evaluation cross PCIe and this thread does no softmax.  Same results to f32 rounding (device expf/tanhf).
     void set_device_decode(bool on) {
         if (in_flight_ != 0) throw std::logic_error("set_device_decode while batches are in flight");
-        if (!on && n_sym_) throw std::logic_error("random symmetries need the device decode");
+        if (!on && n_sym_) throw std::logic_error("symmetries inside the engine need the device decode");
         device_decode_ = on;
     }
 
@@ -313,11 +320,31 @@ class HipNetwork : public Network<B> {
     // logits never reach the host).  tables: d4_tables(mapper) for Ataxx and Go.
     void set_random_symmetries(const SymmetryTables &tables, std::mt19937_64 rng) {
         if (in_flight_ != 0) throw std::logic_error("set_random_symmetries while batches are in flight");
+        if (average_) throw std::logic_error("set_random_symmetries after set_average_symmetries: one or the other");
         if (tables.hw != model_->info.board_h * model_->info.board_w || tables.policy_len != model_->info.policy_len)
             throw std::invalid_argument("symmetry tables of another board or policy");
         kz_check(kz_engine_set_symmetries(engine_, tables.n_sym, tables.square_src.data(), tables.policy_map.data()));
         n_sym_ = tables.n_sym;
         sym_rng_ = rng;
+        device_decode_ = true;
+    }
+
+    // `AverageSymmetryNetwork` (symmetry.rs:70-124,150-184) inside the engine: every board of every batch is evaluated under
+    // ALL symmetries of `tables`, in row order, and values and policy are averaged on the device
+    // (kz_engine_submit_packed_decoded_avg) — this thread encodes each board once and gets one result per board.  The engine
+    // takes max_batch_size() / n_sym boards per call: evaluate_batch chunks by that, the way the wrapper chunks the mapped
+    // boards by the inner network's max_batch_size (:108-113); submit_batch takes at most that many.  max_batch_size() keeps
+    // its meaning (the engine's).  Exclusive with set_random_symmetries; turns the device decode on.
+    void set_average_symmetries(const SymmetryTables &tables) {
+        if (in_flight_ != 0) throw std::logic_error("set_average_symmetries while batches are in flight");
+        if (n_sym_ && !average_) throw std::logic_error("set_average_symmetries after set_random_symmetries: one or the other");
+        if (tables.hw != model_->info.board_h * model_->info.board_w || tables.policy_len != model_->info.policy_len)
+            throw std::invalid_argument("symmetry tables of another board or policy");
+        if (tables.n_sym < 1 || (size_t)tables.n_sym > max_batch_size_)
+            throw std::invalid_argument("max_batch_size must hold one board under every symmetry");
+        kz_check(kz_engine_set_symmetries(engine_, tables.n_sym, tables.square_src.data(), tables.policy_map.data()));
+        n_sym_ = tables.n_sym;
+        average_ = true;
         device_decode_ = true;
     }
 
@@ -341,6 +368,14 @@ class HipNetwork : public Network<B> {
         if (n > max_batch_size_) throw std::invalid_argument("batch_size <= max_batch_size");  // assert!, :58
         if (n == 0) return {};
         if (in_flight_ != 0) throw std::logic_error("evaluate_batch while submitted batches are in flight");
+        if (average_ && n * (size_t)n_sym_ > max_batch_size_) {  // the engine's limit per averaged call: chunk
+            const size_t chunk = max_batch_size_ / (size_t)n_sym_;
+            std::vector<ZeroEvaluation> out;
+            out.reserve(n);
+            for (size_t lo = 0; lo < n; lo += chunk)
+                for (auto &ev : evaluate_batch(boards + lo, std::min(chunk, n - lo))) out.push_back(std::move(ev));
+            return out;
+        }
         const size_t bits_bytes = prepare(boards, n, device_decode_, &move_offsets_[0]);
         if (device_decode_) {
             const float *values = nullptr, *probs = nullptr;
@@ -368,6 +403,7 @@ class HipNetwork : public Network<B> {
     void submit_batch(B *boards, size_t n) {
         if (n == 0 || n > max_batch_size_) throw std::invalid_argument("0 < batch_size <= max_batch_size");
         if (in_flight_ == KZ_ENGINE_SLOTS) throw std::logic_error("every engine slot is in flight");
+        if (average_ && n * (size_t)n_sym_ > max_batch_size_) throw std::invalid_argument("an averaged batch is at most max_batch_size / n_sym boards");
         const size_t bits_bytes = prepare(boards, n, device_decode_, &move_offsets_[next_slot_]);
         // the engine copies its inputs to pinned staging before submit returns (include/kz_hip.h)
         if (device_decode_) {

@@ -501,24 +501,10 @@ KZ_API int kz_engine_eval_packed(kz_engine *e, const uint8_t *bits, size_t bits_
     });
 }
 
-// kz_engine_submit_packed_decoded and, with sym, kz_engine_submit_packed_decoded_sym
-static int submit_decoded(const char *fn, kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
-                          int batch, const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices) {
-    if (check_batch(e, batch, fn) || check_packed(e, fn)) return 1;
-    if (sym && !e->n_sym) return fail(std::string(fn) + ": symmetry ids given but no tables set (call kz_engine_set_symmetries first)");
-#ifdef KZ_EXPERIMENTS
-    if (sym && e->plan.nb4) return fail(std::string(fn) + ": the four-board experiment launch takes no symmetry ids");
-#endif
-    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(std::string(fn) + ": bad slot");
-    kz_engine::Slot &s = e->slots[slot];
-    if (s.batch >= 0) return fail(std::string(fn) + ": slot still in flight (call kz_engine_wait_decoded first)");
-    if (batch == 0) {
-        s.batch = 0;
-        s.decoded = true;
-        s.with_sym = false;
-        s.moves = 0;
-        return 0;
-    }
+// A decoded submit's arguments (batch > 0) checked, then the boards and the CSR move lists copied into the slot's pinned
+// staging (allocated and grown here); the error words cleared.  Shared by every decoded submit.
+static int stage_decoded(const char *fn, kz_engine *e, kz_engine::Slot &s, const uint8_t *bits, size_t bits_stride,
+                         const float *scalars_in, int batch, const int64_t *move_offsets, const int32_t *move_indices, size_t &total_out) {
     if (!bits || !move_offsets) return fail(std::string(fn) + ": null argument");
     const Model &m = *e->model;
     const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
@@ -544,13 +530,39 @@ static int submit_decoded(const char *fn, kz_engine *e, int slot, const uint8_t 
     if (m.n_scalar) memcpy(s.h_sin, scalars_in, (size_t)batch * m.n_scalar * 4);
     memcpy(s.h_moff, move_offsets, (size_t)(batch + 1) * 8);
     if (total) memcpy(s.h_midx, move_indices, total * 4);
+    s.h_err[0] = s.h_err[1] = 0;
+    total_out = total;
+    return 0;
+}
+
+// kz_engine_submit_packed_decoded and, with sym, kz_engine_submit_packed_decoded_sym
+static int submit_decoded(const char *fn, kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                          int batch, const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices) {
+    if (check_batch(e, batch, fn) || check_packed(e, fn)) return 1;
+    if (sym && !e->n_sym) return fail(std::string(fn) + ": symmetry ids given but no tables set (call kz_engine_set_symmetries first)");
+#ifdef KZ_EXPERIMENTS
+    if (sym && e->plan.nb4) return fail(std::string(fn) + ": the four-board experiment launch takes no symmetry ids");
+#endif
+    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(std::string(fn) + ": bad slot");
+    kz_engine::Slot &s = e->slots[slot];
+    if (s.batch >= 0) return fail(std::string(fn) + ": slot still in flight (call kz_engine_wait_decoded first)");
+    if (batch == 0) {
+        s.batch = 0;
+        s.decoded = true;
+        s.with_sym = false;
+        s.moves = 0;
+        return 0;
+    }
+    size_t total = 0;
+    if (stage_decoded(fn, e, s, bits, bits_stride, scalars_in, batch, move_offsets, move_indices, total)) return 1;
+    const Model &m = *e->model;
+    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
     const uint8_t *ids = nullptr;  // the launches read the ids from the slot's pinned staging, like the move lists
     if (sym) {
         memcpy(s.h_sym, sym, (size_t)batch);
         ids = s.h_sym;
     }
     s.with_sym = sym != nullptr;
-    s.h_err[0] = s.h_err[1] = 0;
     StreamSwap swap{e, e->stream};
     if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
     if (e->zero_copy && e->plan.heads) {
@@ -609,6 +621,117 @@ KZ_API int kz_engine_submit_packed_decoded_sym(kz_engine *e, int slot, const uin
     return guarded("kz_engine_submit_packed_decoded_sym", [&]() -> int {
         return submit_decoded("kz_engine_submit_packed_decoded_sym", e, slot, bits, bits_stride, scalars_in, batch, sym, move_offsets,
                               move_indices);
+    });
+}
+
+// The virtual batch's device scratch of a slot (kz_engine::Slot::Virtual): everything sized by max_batch at the first averaged
+// submit, the two move arrays for n_sym * total moves, grown the way move_cap grows.  Every buffer stays below 2 GiB.
+static int virtual_scratch(const char *fn, kz_engine *e, kz_engine::Slot &s, size_t bits_bytes, size_t vmoves) {
+    const Model &m = *e->model;
+    kz_engine::Slot::Virtual &v = s.virt;
+    const size_t limit = ((size_t)1 << 31) - 1, mb = (size_t)e->max_batch;
+    const auto too_large = [&](size_t bytes) {
+        return bytes > limit && fail(std::string(fn) + ": a scratch buffer of the virtual batch would need " + std::to_string(bytes) +
+                                     " bytes (every engine tensor must stay below 2 GiB)");
+    };
+    if (!v.moff) {
+        const size_t ns = m.n_scalar < 0 ? 0 : (size_t)m.n_scalar;
+        if (too_large(mb * bits_bytes) || too_large(mb * ns * 4) || too_large((mb + 1) * 8) || too_large(mb * 20)) return 1;
+        if (e->dmalloc((void **)&v.bits, mb * bits_bytes) || e->dmalloc((void **)&v.sin, mb * ns * 4) || e->dmalloc((void **)&v.sym, mb) ||
+            e->dmalloc((void **)&v.values, mb * 20) || e->dmalloc((void **)&v.err, 16) || e->dmalloc((void **)&v.moff, (mb + 1) * 8))
+            return 1;
+    }
+    if (vmoves > v.move_cap) {  // the old (smaller) buffers stay on the engine's free list until it is destroyed
+        const size_t cap = std::max(vmoves, std::max(v.move_cap * 2, mb * 64));
+        if (too_large(cap * 4)) return 1;
+        if (e->dmalloc((void **)&v.midx, cap * 4) || e->dmalloc((void **)&v.probs, cap * 4)) return 1;
+        v.move_cap = cap;
+    }
+    return 0;
+}
+
+// what both averaged entries check first: tables set, batch * n_sym within max_batch
+static int check_avg(const char *name, const kz_engine *e, int batch) {
+    const std::string fn = name;
+    if (!e) return fail(fn + ": null engine");
+    if (check_packed(e, name)) return 1;
+    if (!e->n_sym) return fail(fn + ": no tables set (call kz_engine_set_symmetries first)");
+#ifdef KZ_EXPERIMENTS
+    if (e->plan.nb4) return fail(fn + ": the four-board experiment launch takes no symmetry ids");
+#endif
+    const int n = e->n_sym, limit = e->max_batch / n;
+    if (batch < 0 || batch > limit)
+        return fail(fn + ": batch " + std::to_string(batch) + " exceeds max_batch / n_sym = " + std::to_string(limit) + " (" +
+                    std::to_string(n) + " symmetries: the network runs on batch * n_sym boards, max_batch " + std::to_string(e->max_batch) + ")");
+    return 0;
+}
+
+// kz_engine_submit_packed_decoded_avg: every board under every symmetry of the tables, averaged (kz_symmetry_avg.hip).  Three
+// launches on the slot's stream: the fan-out from the pinned staging into the virtual batch, the unchanged network pass over
+// it (ids = k; decode inside the launch on the "+heads" paths, kz_decode_output elsewhere) into device scratch, the average
+// into the pinned staging.
+static int submit_decoded_avg(const char *name, kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                              int batch, const int64_t *move_offsets, const int32_t *move_indices) {
+    const std::string fn = name;
+    if (check_avg(name, e, batch)) return 1;
+    const int n = e->n_sym;
+    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(fn + ": bad slot");
+    kz_engine::Slot &s = e->slots[slot];
+    if (s.batch >= 0) return fail(fn + ": slot still in flight (call kz_engine_wait_decoded first)");
+    if (batch == 0) {
+        s.batch = 0;
+        s.decoded = true;
+        s.with_sym = false;
+        s.moves = 0;
+        return 0;
+    }
+    size_t total = 0;
+    if (stage_decoded(name, e, s, bits, bits_stride, scalars_in, batch, move_offsets, move_indices, total)) return 1;
+    const Model &m = *e->model;
+    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
+    if (virtual_scratch(name, e, s, bits_bytes, (size_t)n * total)) return 1;
+    const kz_engine::Slot::Virtual &v = s.virt;
+    const int vbatch = batch * n;
+    s.with_sym = true;  // (the batch's errors are those of the `_sym` entries)
+    StreamSwap swap{e, e->stream};
+    if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
+    const kz::SymFanOutArgs fan{s.h_bits, bits_bytes, s.h_sin, m.n_scalar, batch, n, s.h_moff, s.h_midx,
+                                v.bits, v.sin, v.sym, v.moff, v.midx, v.err};
+    if (e->launch("kz_sym_fan_out", [&] { kz::launch_sym_fan_out(fan, e->stream); })) return 1;
+    const kz::PackedBoards boards = e->packed_boards(v.bits, bits_bytes, v.sin, v.sym);
+    const bool in_launch = e->zero_copy && e->plan.heads;
+    e->arm(s);
+    if (in_launch) {
+        e->nf_flag = reinterpret_cast<int *>(s.h_sout);  // the range check reports into the slot's header, as for every decoded submit
+        kz::DecodeArgs dec{v.moff, v.midx, v.values, v.probs, v.err};
+        dec.sym = v.sym;
+        dec.policy_map = e->d_policy_map;
+        dec.n_sym = n;
+        if (e->forward_packed(boards, vbatch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &dec)) return 1;
+    } else {
+        if (e->forward_packed(boards, vbatch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+        if (e->launch("kz_decode_output", [&] {
+                kz::launch_decode_output(s.d_sout + kz_engine::SOUT_HDR, s.d_pol, vbatch, m.policy_len, v.moff, v.midx, v.values, v.probs,
+                                         v.err, reinterpret_cast<const int *>(s.d_sout), s.epoch, e->stream, v.sym, e->d_policy_map, n);
+            }))
+            return 1;
+    }
+    const kz::SymAverageArgs avg{v.values, v.probs, v.moff, v.err, batch, n, s.h_values, s.h_probs, s.h_err};
+    if (e->launch("kz_sym_average", [&] { kz::launch_sym_average(avg, e->stream); })) return 1;
+    HIP_TRY(hipEventRecord(s.done, e->stream));
+    s.batch = batch;
+    s.decoded = true;
+    s.in_launch = in_launch;
+    s.moves = total;
+    return 0;
+}
+
+KZ_API int kz_engine_submit_packed_decoded_avg(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
+                                               const float *scalars_in, int batch, const int64_t *move_offsets,
+                                               const int32_t *move_indices) {
+    return guarded("kz_engine_submit_packed_decoded_avg", [&]() -> int {
+        return submit_decoded_avg("kz_engine_submit_packed_decoded_avg", e, slot, bits, bits_stride, scalars_in, batch, move_offsets,
+                                  move_indices);
     });
 }
 
@@ -714,6 +837,26 @@ KZ_API int kz_engine_eval_packed_decoded_sym(kz_engine *e, const uint8_t *bits, 
     return guarded("kz_engine_eval_packed_decoded_sym", [&]() -> int {
         return eval_decoded("kz_engine_eval_packed_decoded_sym", e, bits, bits_stride, scalars_in, batch, sym, move_offsets,
                             move_indices, values_out, probs_out);
+    });
+}
+
+KZ_API int kz_engine_eval_packed_decoded_avg(kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                             int batch, const int64_t *move_offsets, const int32_t *move_indices,
+                                             float *values_out, float *probs_out) {
+    return guarded("kz_engine_eval_packed_decoded_avg", [&]() -> int {
+        const char *name = "kz_engine_eval_packed_decoded_avg";
+        const std::string fn = name;
+        if (check_avg(name, e, batch)) return 1;
+        if (batch == 0) return 0;
+        if (!values_out) return fail(fn + ": null argument");
+        if (move_offsets && move_offsets[batch] > 0 && !probs_out) return fail(fn + ": null move list");
+        if (submit_decoded_avg(name, e, 0, bits, bits_stride, scalars_in, batch, move_offsets, move_indices)) return 1;
+        const float *values = nullptr, *probs = nullptr;
+        const size_t total = e->slots[0].moves;
+        if (kz_engine_wait_decoded(e, 0, &values, &probs)) return 1;
+        memcpy(values_out, values, (size_t)batch * 20);
+        if (total) memcpy(probs_out, probs, total * 4);
+        return 0;
     });
 }
 

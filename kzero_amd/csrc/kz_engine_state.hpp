@@ -144,6 +144,18 @@ struct kz_engine {
         int *h_err = nullptr;  // [0] softmax sum / move index, [1] range check (kz_kernels.hpp: launch_decode_output)
         uint8_t *h_sym = nullptr;  // [max_batch] symmetry ids of the batch (pinned, read by the launches; set_symmetries allocates it)
         bool with_sym = false;     // what is in flight was submitted with symmetry ids
+        // every board under every symmetry (the `_avg` entries, kz_symmetry_avg.hip): the VIRTUAL batch in device memory —
+        // what kz_sym_fan_out writes and the network reads, what the decode writes and kz_sym_average reads.  Allocated at
+        // the slot's first averaged submit, for max_batch virtual boards; the two move arrays grow like move_cap
+        struct Virtual {
+            uint8_t *bits = nullptr, *sym = nullptr;  // [max_batch][bits_bytes], [max_batch] ids
+            float *sin = nullptr, *values = nullptr;  // [max_batch][n_scalar], [max_batch][5]
+            int64_t *moff = nullptr;                  // [max_batch + 1]
+            int *err = nullptr;                       // the decode's two flag words
+            int32_t *midx = nullptr;                  // [move_cap]
+            float *probs = nullptr;                   // [move_cap]
+            size_t move_cap = 0;
+        } virt;
     } slots[KZ_ENGINE_SLOTS];
     // board symmetries (kz_engine_set_symmetries): the two tables the encode and the decode read, in device memory
     int n_sym = 0, sym_cap = 0;

@@ -155,6 +155,38 @@ struct DecodeArgs {
     int n_sym = 0;
 };
 
+// ---- every board under every symmetry, averaged (kz_symmetry_avg.hip; `AverageSymmetryNetwork`, symmetry.rs:70-124,150-184):
+// the two kernels around a network pass over the VIRTUAL batch — virtual board b * n_sym + k is board b under symmetry k.
+// The inputs of the fan-out and the outputs of the average may be pinned host memory (every word read or written once);
+// every v_ pointer is device memory. ----
+struct SymFanOutArgs {
+    const uint8_t *bits;          // [batch][bits_bytes]
+    size_t bits_bytes;
+    const float *scalars;         // [batch][n_scalar]
+    int n_scalar, batch, n_sym;
+    const int64_t *move_offsets;  // [batch + 1] CSR
+    const int32_t *move_indices;
+    uint8_t *v_bits;              // [batch * n_sym][bits_bytes]
+    float *v_scalars;             // [batch * n_sym][n_scalar]
+    uint8_t *v_sym;               // [batch * n_sym] = k
+    int64_t *v_move_offsets;      // [batch * n_sym + 1]: voff[b n + k] = n off[b] + k len_b, voff[n batch] = n total
+    int32_t *v_move_indices;      // [n_sym * total]: board b's list n_sym times
+    int *v_error_flag;            // the decode's two words (launch_decode_output), cleared here
+};
+void launch_sym_fan_out(const SymFanOutArgs &a, hipStream_t stream);
+// values[b][j] = (((0 + v_0) + v_1) + ... + v_{n-1}) / n and probs[lo_b + i] = ((0 + p_0 / n) + p_1 / n) + ..., f32 with
+// correctly rounded divisions, k = 0 .. n_sym-1 ascending; error_flag[0..1] = v_error_flag[0..1]
+struct SymAverageArgs {
+    const float *v_values;          // [batch * n_sym][5]
+    const float *v_probs;           // parallel to v_move_indices
+    const int64_t *v_move_offsets;  // as the fan-out wrote them
+    const int *v_error_flag;
+    int batch, n_sym;
+    float *values, *probs;          // [batch][5], parallel to move_indices
+    int *error_flag;
+};
+void launch_sym_average(const SymAverageArgs &a, hipStream_t stream);
+
 // ---- per-layer 3x3 convolution with the board as an LDS-resident spatial tile (kz_board_conv.hip): f16, cin and cout
 // multiples of 64, h*w <= 384.  Same epilogue contract as ConvArgs. ----
 struct BoardConvArgs {

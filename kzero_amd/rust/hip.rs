@@ -108,6 +108,9 @@ extern "C" {
     fn kz_engine_set_symmetries(engine: *mut c_void, n_sym: c_int, square_src: *const i32, policy_map: *const i32) -> c_int;
     fn kz_engine_eval_packed_decoded_sym(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, sym: *const u8, move_offsets: *const i64, move_indices: *const i32, values_out: *mut f32, probs_out: *mut f32) -> c_int;
     fn kz_engine_submit_packed_decoded_sym(engine: *mut c_void, slot: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, sym: *const u8, move_offsets: *const i64, move_indices: *const i32) -> c_int;
+    // every board under every symmetry of the tables, averaged on the device: at most max_batch / n_sym boards per call
+    fn kz_engine_eval_packed_decoded_avg(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, move_offsets: *const i64, move_indices: *const i32, values_out: *mut f32, probs_out: *mut f32) -> c_int;
+    fn kz_engine_submit_packed_decoded_avg(engine: *mut c_void, slot: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, move_offsets: *const i64, move_indices: *const i32) -> c_int;
     // device-resident entry points and helpers (benchmarks and parity tests; the server does not need them)
     fn kz_engine_enqueue_packed_device(engine: *mut c_void, d_bits: *const c_void, bits_stride: usize, d_scalars_in: *const c_void, batch: c_int, d_scalars_out: *mut c_void, d_policy_out: *mut c_void) -> c_int;
     fn kz_engine_enqueue_dense_device(engine: *mut c_void, d_input_nchw: *const c_void, batch: c_int, d_scalars_out: *mut c_void, d_policy_out: *mut c_void) -> c_int;
@@ -258,6 +261,9 @@ pub struct HipNetwork<B: Board, M: BoardMapper<B>> {
     n_sym: usize,
     sym_rng: Option<Box<dyn rand::RngCore + Send>>,
     sym_ids: Vec<u8>,
+    /// `AverageSymmetryNetwork` inside the engine (`new_with_average_symmetries`): every board under all `n_sym`
+    /// symmetries, averaged on the device; a batch is then at most `max_batch_size / n_sym` boards per engine call
+    average_symmetries: bool,
     /// `KZ_HIP_PREP_THREADS` (default 0) + 1 ranges of a batch, each prepared by one thread (`prepare`)
     ranges: Vec<PrepRange>,
     ph: PhantomData<B>,
@@ -350,6 +356,7 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
             n_sym: 0,
             sym_rng: None,
             sym_ids: vec![],
+            average_symmetries: false,
             ranges: {
                 // (a malformed value is not worth a panic in a constructor: no helpers, and say so once)
                 let helpers: usize = match std::env::var("KZ_HIP_PREP_THREADS") {
@@ -380,6 +387,60 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
         net.n_sym = tables.n_sym;
         net.sym_rng = Some(rng);
         net
+    }
+
+    /// `AverageSymmetryNetwork::new(HipNetwork::new(..))` (symmetry.rs:70-124,150-184) without its host work: the engine
+    /// evaluates every board under every row of `tables` and averages values and policy on the device
+    /// (`kz_engine_submit_packed_decoded_avg`: the row order of the tables is the summation order).  This thread encodes
+    /// each board once and receives one result per board.  `evaluate_batch` goes through the engine in chunks of
+    /// `max_batch_size / n_sym` boards (the wrapper's `chunks(inner.max_batch_size())`, :108-113); `submit_batch` takes at
+    /// most that many.  Exclusive with `new_with_symmetries`; needs the decode on the device.
+    pub fn new_with_average_symmetries(mapper: M, model: Arc<HipModel>, max_batch_size: usize, device: HipDevice, dtype: HipDtype, tables: &SymmetryTables) -> Self {
+        let mut net = Self::new(mapper, model, max_batch_size, device, dtype);
+        assert!(net.device_decode, "averaged symmetries inside the engine need KZ_HIP_DECODE=device");
+        let info = net._model.info;
+        assert_eq!(tables.square_src.len(), tables.n_sym * (info.board_h * info.board_w) as usize);
+        assert_eq!(tables.policy_map.len(), tables.n_sym * info.policy_len as usize);
+        assert!(tables.n_sym >= 1 && tables.n_sym <= max_batch_size, "max_batch_size must hold one board under every symmetry");
+        check(unsafe { kz_engine_set_symmetries(net.engine, tables.n_sym as c_int, tables.square_src.as_ptr(), tables.policy_map.as_ptr()) });
+        net.n_sym = tables.n_sym;
+        net.average_symmetries = true;
+        net
+    }
+
+    /// The decoded submit of the batch `prepare` has staged: averaged over all symmetries, or with one drawn id per board
+    /// (null ids without symmetries).
+    fn submit_decoded(&mut self, slot: usize, bits_bytes: usize, n: usize) {
+        if self.average_symmetries {
+            assert!(n * self.n_sym <= self.max_batch_size, "an averaged batch is at most max_batch_size / n_sym boards");
+            check(unsafe {
+                kz_engine_submit_packed_decoded_avg(
+                    self.engine,
+                    slot as c_int,
+                    self.bits.as_ptr(),
+                    bits_bytes,
+                    self.scalars_in.as_ptr(),
+                    n as c_int,
+                    self.move_offsets.as_ptr(),
+                    self.move_indices.as_ptr(),
+                )
+            });
+            return;
+        }
+        let sym = self.draw_symmetries(n);
+        check(unsafe {
+            kz_engine_submit_packed_decoded_sym(
+                self.engine,
+                slot as c_int,
+                self.bits.as_ptr(),
+                bits_bytes,
+                self.scalars_in.as_ptr(),
+                n as c_int,
+                sym,
+                self.move_offsets.as_ptr(),
+                self.move_indices.as_ptr(),
+            )
+        });
     }
 
     /// One id per board of the batch being submitted (symmetry.rs:52); null without symmetries, which makes the `_sym`
@@ -464,20 +525,7 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
         let bits_bytes = self.prepare(&boards, self.device_decode);
         let slot = self.next_slot;
         if self.device_decode {
-            let sym = self.draw_symmetries(boards.len());
-            check(unsafe {
-                kz_engine_submit_packed_decoded_sym(
-                    self.engine,
-                    slot as c_int,
-                    self.bits.as_ptr(),
-                    bits_bytes,
-                    self.scalars_in.as_ptr(),
-                    boards.len() as c_int,
-                    sym,
-                    self.move_offsets.as_ptr(),
-                    self.move_indices.as_ptr(),
-                )
-            });
+            self.submit_decoded(slot, bits_bytes, boards.len());
             // (the engine has copied the lists to its pinned staging: only the offsets are needed to cut up the reply)
             self.pending.push_back((slot, vec![], self.move_offsets.clone()));
         } else {
@@ -538,23 +586,15 @@ impl<B: Board, M: BoardMapper<B>> Network<B> for HipNetwork<B, M> {
         }
 
         assert!(self.pending.is_empty(), "evaluate_batch while submitted batches are in flight");
+        if self.average_symmetries && batch_size * self.n_sym > self.max_batch_size {
+            // the engine takes max_batch_size / n_sym boards per averaged call: chunk like the wrapper (symmetry.rs:108-113)
+            let chunk = self.max_batch_size / self.n_sym;
+            return boards.chunks(chunk).flat_map(|part| self.evaluate_batch(part)).collect();
+        }
         let bits_bytes = self.prepare(boards, self.device_decode);
 
         if self.device_decode {
-            let sym = self.draw_symmetries(batch_size);
-            check(unsafe {
-                kz_engine_submit_packed_decoded_sym(
-                    self.engine,
-                    0,
-                    self.bits.as_ptr(),
-                    bits_bytes,
-                    self.scalars_in.as_ptr(),
-                    batch_size as c_int,
-                    sym,
-                    self.move_offsets.as_ptr(),
-                    self.move_indices.as_ptr(),
-                )
-            });
+            self.submit_decoded(0, bits_bytes, batch_size);
             let (mut values, mut probs) = (std::ptr::null::<f32>(), std::ptr::null::<f32>());
             check(unsafe { kz_engine_wait_decoded(self.engine, 0, &mut values, &mut probs) });
             let total = *self.move_offsets.last().unwrap() as usize;
