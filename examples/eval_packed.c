@@ -52,6 +52,24 @@ int main(int argc, char **argv) {
                scalars_out[b * 5], scalars_out[b * 5 + 1], scalars_out[b * 5 + 2], scalars_out[b * 5 + 3],
                scalars_out[b * 5 + 4], policy[(size_t)b * info.policy_len]);
 
+    /* decoded output with a status per board instead of a failing batch: two moves per board; board 1 lists a move index
+     * outside the policy, so it comes back as KZ_BOARD_BAD_DECODE and the other boards' results stand.  (An f16 / split16
+     * engine after kz_engine_set_range_fallback(engine, KZ_DTYPE_F32) reports a board it re-evaluated in exact f32 as
+     * KZ_BOARD_FELL_BACK.) */
+    int64_t move_offsets[5] = {0, 2, 4, 6, 8};
+    int32_t move_indices[8] = {0, 1, 0, 1, 0, 1, 0, 1};
+    move_indices[3] = info.policy_len;
+    float values[4 * 5], probs[8];
+    uint8_t status[4];
+    CHECK(kz_engine_eval_packed_decoded_status(engine, bits, (size_t)info.bits_bytes, scalars_in, batch, NULL, move_offsets,
+                                               move_indices, values, probs, status));
+    for (int b = 0; b < batch; b++) {
+        if (status[b] == KZ_BOARD_OK || status[b] == KZ_BOARD_FELL_BACK)
+            printf("board %d: status %d  value %+.4f  p(move 0) %.4f  p(move 1) %.4f\n", b, status[b], values[b * 5], probs[2 * b], probs[2 * b + 1]);
+        else
+            printf("board %d: status %d (its results are unspecified)\n", b, status[b]);
+    }
+
     free(bits);
     free(scalars_in);
     kz_engine_destroy(engine);

@@ -28,7 +28,8 @@ extern "C" {
                           residual stream beyond +-65504 overflows; the overflow is DETECTED, not saturated: the call that
                           returns the batch (kz_engine_eval_*, kz_engine_wait*, or kz_engine_synchronize after the
                           device-resident entry points) fails with a "non-finite activation" message and the caller
-                          should evaluate that network with KZ_DTYPE_F32.  The same limit and the same check apply to
+                          should evaluate that network with KZ_DTYPE_F32 — or, board by board and inside the engine, turn on
+                          kz_engine_set_range_fallback (below).  The same limit and the same check apply to
                           KZ_DTYPE_F32_SPLIT16 (its (hi, lo) pairs are f16 too) */
 #define KZ_DTYPE_F32_SPLIT16 2 /* f32 tensors and the same <=1e-4 parity as KZ_DTYPE_F32, but the tower's products run on
                                   the f16 matrix cores: every activation and weight as a (hi, lo) f16 pair, three MFMAs per
@@ -211,6 +212,45 @@ int kz_engine_eval_packed_decoded_avg(kz_engine *engine, const uint8_t *bits, si
 int kz_engine_submit_packed_decoded_avg(kz_engine *engine, int slot, const uint8_t *bits, size_t bits_stride,
                                         const float *scalars_in, int batch, const int64_t *move_offsets,
                                         const int32_t *move_indices);
+
+/* ---- per-board status and the exact-f32 range fallback ----
+ * Every error a launch detects is detected for ONE board (boards are independent columns of every product here), and beside
+ * the per-batch verdict of the entries above the engine keeps a status per board, a set of bits: */
+#define KZ_BOARD_OK 0
+#define KZ_BOARD_BAD_DECODE 1 /* softmax sum not strictly positive, move index outside the policy, id >= n_sym, no image under the symmetry */
+#define KZ_BOARD_NONFINITE 2  /* the range check fired for this board */
+#define KZ_BOARD_FELL_BACK 4  /* re-evaluated by the range fallback; its results are the exact-f32 ones */
+/* A board out of range normally has a NaN softmax sum as well, so it usually carries KZ_BOARD_BAD_DECODE | KZ_BOARD_NONFINITE.
+ * kz_engine_wait_decoded_status is kz_engine_wait_decoded, except that an error inside the batch does not fail the call: it
+ * returns 0 and *status_out points at uint8_t [batch], library-owned, with the lifetime of the two views (typed void for the
+ * bindings' sake).  It serves the plain, _sym and _avg decoded submits; for an averaged batch a board's status is the OR over
+ * its n_sym virtual boards.  Boards with status 0 hold exactly what kz_engine_wait_decoded would have given them; the values and
+ * probabilities of a board with any other status than exactly KZ_BOARD_FELL_BACK are unspecified, but only that board's own
+ * ranges are touched.  Argument, slot and in-flight errors fail as before.
+ * kz_engine_eval_packed_decoded_status is kz_engine_eval_packed_decoded_sym (sym == NULL: no symmetry ids) with a caller-owned
+ * status_out, uint8_t [batch]. */
+int kz_engine_wait_decoded_status(kz_engine *engine, int slot, const float **values_out, const float **probs_out,
+                                  void **status_out);
+int kz_engine_eval_packed_decoded_status(kz_engine *engine, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                         int batch, const uint8_t *sym, const int64_t *move_offsets,
+                                         const int32_t *move_indices, float *values_out, float *probs_out, void *status_out);
+/* The range fallback: dtype = KZ_DTYPE_F32 turns it on, -1 off (the default).  Fails, with a message of its own each, on an
+ * engine whose own dtype is KZ_DTYPE_F32, while a batch is in flight, and for any other dtype value.  Turning it on creates —
+ * here, so that a failure surfaces here — a sibling engine of the same model on the same device in exact f32 with a small
+ * max_batch of its own (at most 64); it shares nothing with this engine's streams and staging (only the cached device weights
+ * of other exact-f32 engines of the model).  kz_engine_set_symmetries on the engine reaches the sibling too.
+ * With the fallback on, every host-boundary call that returns a batch — kz_engine_wait, kz_engine_wait_view,
+ * kz_engine_eval_packed, the decoded waits and evals in their plain, _sym and _avg forms, and the two status entries — looks
+ * at the per-board status once the batch is complete and re-evaluates exactly the boards that carry KZ_BOARD_NONFINITE, from
+ * the slot's input staging, through the sibling's matching entry (the same symmetry id for _sym, the averaged entry for _avg;
+ * averaged batches only while n_sym <= the sibling's max_batch), in chunks, inside the returning call; the sibling's results
+ * replace those boards' rows and ranges.  A board whose exact-f32 evaluation is clean gets status KZ_BOARD_FELL_BACK alone,
+ * and the calls without a status output then succeed; a board still bad in f32 keeps its bits beside KZ_BOARD_FELL_BACK and
+ * those calls fail with the messages they have without the fallback.  KZ_BOARD_BAD_DECODE without KZ_BOARD_NONFINITE is never
+ * re-evaluated: that is the caller's move list.  A fell-back board costs a synchronous exact-f32 launch on the calling thread
+ * (DESIGN.md 6.4.3).  The device-resident entry points below are outside the fallback and keep failing at
+ * kz_engine_synchronize. */
+int kz_engine_set_range_fallback(kz_engine *engine, int dtype);
 
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and

@@ -15,6 +15,11 @@ KZ_DTYPE_F32 = 0
 KZ_DTYPE_F16 = 1
 KZ_DTYPE_F32_SPLIT16 = 2
 KZ_ENGINE_SLOTS = 4
+# per-board status bits (kz_engine_wait_decoded_status / kz_engine_eval_packed_decoded_status)
+KZ_BOARD_OK = 0
+KZ_BOARD_BAD_DECODE = 1
+KZ_BOARD_NONFINITE = 2
+KZ_BOARD_FELL_BACK = 4
 
 POLICY_KINDS = {0: "ataxx_conv", 1: "conv", 2: "attention", 3: "dense"}
 
@@ -72,6 +77,11 @@ SIGNATURES = {
                                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "kz_engine_submit_packed_decoded_avg": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                                       C.c_void_p, C.c_void_p]),
+    "kz_engine_wait_decoded_status": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                                C.POINTER(C.c_void_p)]),
+    "kz_engine_eval_packed_decoded_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kz_engine_set_range_fallback": (C.c_int, [C.c_void_p, C.c_int]),
     "kz_engine_enqueue_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                                   C.c_void_p, C.c_void_p]),
     "kz_engine_enqueue_dense_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -374,6 +384,39 @@ class Engine:
         values = np.ctypeslib.as_array(C.cast(pv, C.POINTER(C.c_float)), shape=(batch, 5)).copy() if batch else np.empty((0, 5), np.float32)
         probs = np.ctypeslib.as_array(C.cast(pp, C.POINTER(C.c_float)), shape=(total,)).copy() if total else np.zeros(0, np.float32)
         return values, [probs[offsets[i]:offsets[i + 1]] for i in range(batch)]
+
+    def wait_decoded_status(self, slot: int, offsets: np.ndarray):
+        """wait_decoded that does not fail for an error inside the batch (kz_engine_wait_decoded_status): values [batch,5],
+        one probability array per board and status uint8 [batch] (KZ_BOARD_* bits), copies of the slot's staging."""
+        pv, pp, ps = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(load().kz_engine_wait_decoded_status(self._h, slot, C.byref(pv), C.byref(pp), C.byref(ps)))
+        batch, total = len(offsets) - 1, int(offsets[-1])
+        values = np.ctypeslib.as_array(C.cast(pv, C.POINTER(C.c_float)), shape=(batch, 5)).copy() if batch else np.empty((0, 5), np.float32)
+        probs = np.ctypeslib.as_array(C.cast(pp, C.POINTER(C.c_float)), shape=(total,)).copy() if total else np.zeros(0, np.float32)
+        status = np.ctypeslib.as_array(C.cast(ps, C.POINTER(C.c_uint8)), shape=(batch,)).copy() if batch else np.zeros(0, np.uint8)
+        return values, [probs[offsets[i]:offsets[i + 1]] for i in range(batch)], status
+
+    def eval_packed_decoded_status(self, bits: np.ndarray, scalars_in: np.ndarray, move_lists, sym=None):
+        """eval_packed_decoded with the per-board status instead of a failing call (kz_engine_eval_packed_decoded_status):
+        returns (values [batch,5], [probs per board], status uint8 [batch])."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        batch = bits.shape[0]
+        offsets, idx = self._csr(move_lists)
+        values = np.empty((batch, 5), np.float32)
+        probs = np.empty(max(len(idx), 1), np.float32)
+        status = np.zeros(max(batch, 1), np.uint8)
+        sym = self._sym_ids(sym, batch) if sym is not None else None
+        check(load().kz_engine_eval_packed_decoded_status(self._h, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                                          scalars_in.ctypes.data, batch, sym.ctypes.data if sym is not None else None,
+                                                          offsets.ctypes.data, idx.ctypes.data, values.ctypes.data, probs.ctypes.data,
+                                                          status.ctypes.data))
+        return values, [probs[offsets[i]:offsets[i + 1]].copy() for i in range(batch)], status[:batch]
+
+    def set_range_fallback(self, dtype: int):
+        """KZ_DTYPE_F32: the calls that return a batch re-evaluate its out-of-range boards in exact f32 inside the engine
+        (kz_engine_set_range_fallback); -1: off (the default)."""
+        check(load().kz_engine_set_range_fallback(self._h, dtype))
 
     def wait_view(self, slot: int, batch: int):
         """Zero-copy wait: arrays over the slot's pinned staging, valid until the next submit on that slot."""

@@ -257,6 +257,32 @@ class HipNetwork : public Network<B> {
         return (input_bool_len(mapper_) + 7) / 8;
     }
 
+    // kz_engine_wait_decoded through the status entry (kz_engine_wait_decoded_status): boards the range fallback re-evaluated
+    // (status exactly KZ_BOARD_FELL_BACK: their results are the exact-f32 ones) are counted; any other non-zero status throws —
+    // the reference panics on every executor error — naming the boards
+    void wait_decoded_checked(int slot, size_t n, const float **values, const float **probs) {
+        void *status_view = nullptr;
+        kz_check(kz_engine_wait_decoded_status(engine_, slot, values, probs, &status_view));
+        const uint8_t *status = static_cast<const uint8_t *>(status_view);
+        std::string bad;
+        bool nonfinite = false;
+        for (size_t b = 0; b < n; b++) {
+            if (status[b] == KZ_BOARD_OK) continue;
+            if (status[b] == KZ_BOARD_FELL_BACK) {
+                fell_back_boards++;
+                continue;
+            }
+            nonfinite = nonfinite || (status[b] & KZ_BOARD_NONFINITE);
+            bad += (bad.empty() ? "" : ", ") + std::to_string(b);
+        }
+        if (bad.empty()) return;
+        throw std::runtime_error(std::string("kzhip: ") +
+                                 (nonfinite ? "non-finite activation (beyond +-65504 the f16 and split-f16 paths overflow: set_range_fallback(true) "
+                                              "re-evaluates such boards in exact f32)"
+                                            : "Softmax input sum must be strictly positive (or a move index or symmetry id is out of range)") +
+                                 " on boards " + bad + " of the batch");
+    }
+
     // values [n,5] (already tanh / softmax) + probabilities parallel to the move lists -> evaluations
     static std::vector<ZeroEvaluation> assemble_decoded(size_t n, const std::vector<int64_t> &offsets, const float *values,
                                                         const float *probs) {
@@ -276,6 +302,8 @@ class HipNetwork : public Network<B> {
     // ... and where the rest goes (measurement, tests/cpp/bench_executor.cpp): this thread's share of a batch's preparation, the
     // merge of the ranges, the engine's submit call (copies into pinned staging + the launch), building the evaluations
     uint64_t prep_own_cpu_ns = 0, merge_cpu_ns = 0, submit_cpu_ns = 0, assemble_cpu_ns = 0;
+    // boards the range fallback has re-evaluated in exact f32 so far (set_range_fallback; the device decode's calls count them)
+    uint64_t fell_back_boards = 0;
     // cudnn.rs:29-43 (check_graph_shapes: common.rs:165-198)
     HipNetwork(M mapper, std::shared_ptr<const HipModel> model, size_t max_batch_size, int device, int dtype)
         : mapper_(mapper), model_(std::move(model)), max_batch_size_(max_batch_size) {
@@ -293,7 +321,8 @@ class HipNetwork : public Network<B> {
         : mapper_(o.mapper_), model_(std::move(o.model_)), engine_(o.engine_), max_batch_size_(o.max_batch_size_),
           bits_(std::move(o.bits_)), scalars_in_(std::move(o.scalars_in_)), next_slot_(o.next_slot_),
           oldest_slot_(o.oldest_slot_), in_flight_(o.in_flight_), device_decode_(o.device_decode_), n_sym_(o.n_sym_),
-          sym_rng_(o.sym_rng_), average_(o.average_), ranges_(std::move(o.ranges_)), helpers_(std::move(o.helpers_)), wait_cpu_ns(o.wait_cpu_ns) {
+          sym_rng_(o.sym_rng_), average_(o.average_), ranges_(std::move(o.ranges_)), helpers_(std::move(o.helpers_)), wait_cpu_ns(o.wait_cpu_ns),
+          fell_back_boards(o.fell_back_boards) {
         for (int i = 0; i < KZ_ENGINE_SLOTS; i++) {
             pending_boards_[i] = std::move(o.pending_boards_[i]);
             move_offsets_[i] = std::move(o.move_offsets_[i]);
@@ -311,6 +340,14 @@ class HipNetwork : public Network<B> {
         if (in_flight_ != 0) throw std::logic_error("set_device_decode while batches are in flight");
         if (!on && n_sym_) throw std::logic_error("symmetries inside the engine need the device decode");
         device_decode_ = on;
+    }
+
+    // true: a board of an f16 / split16 batch whose activations leave the f16 range is re-evaluated in exact f32 inside the
+    // engine (kz_engine_set_range_fallback: a sibling engine, created here) instead of failing the batch; fell_back_boards
+    // counts them.  Off by default, like hip.rs's KZ_HIP_RANGE_FALLBACK.  An exact-f32 engine refuses it (the call throws).
+    void set_range_fallback(bool on) {
+        if (in_flight_ != 0) throw std::logic_error("set_range_fallback while batches are in flight");
+        kz_check(kz_engine_set_range_fallback(engine_, on ? KZ_DTYPE_F32 : -1));
     }
 
     // `eval_random_symmetries` (symmetry.rs:18-68) inside the launch: every board of every batch is evaluated under a symmetry
@@ -381,7 +418,7 @@ class HipNetwork : public Network<B> {
             const float *values = nullptr, *probs = nullptr;
             submit_decoded(0, bits_bytes, n);
             const uint64_t w0 = thread_cpu_ns();
-            kz_check(kz_engine_wait_decoded(engine_, 0, &values, &probs));
+            wait_decoded_checked(0, n, &values, &probs);
             wait_cpu_ns += thread_cpu_ns() - w0;
             return assemble_decoded(n, move_offsets_[0], values, probs);
         }
@@ -428,7 +465,7 @@ class HipNetwork : public Network<B> {
         if (device_decode_) {
             const float *values = nullptr, *probs = nullptr;
             const uint64_t w0 = thread_cpu_ns();
-            kz_check(kz_engine_wait_decoded(engine_, slot, &values, &probs));
+            wait_decoded_checked(slot, move_offsets_[slot].size() - 1, &values, &probs);
             const uint64_t w1 = thread_cpu_ns();
             wait_cpu_ns += w1 - w0;
             auto out = assemble_decoded(move_offsets_[slot].size() - 1, move_offsets_[slot], values, probs);

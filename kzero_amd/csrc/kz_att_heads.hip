@@ -168,7 +168,10 @@ __global__ __launch_bounds__(AH_THREADS) void kz_att_heads_f16(AttHeadsDev a) {
             t += AH_WAVES;
         }
     }
-    if (bad && a.nonfinite_flag) *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: the flag may live in pinned host memory)
+    if (bad && a.nonfinite_flag) {
+        *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: the flag may live in pinned host memory)
+        raise_nonfinite_board(a.nonfinite_flag, a.epoch, board);
+    }
     __syncthreads();
 
     // ---- logits^T [to][from] = k_to q_from^T / sqrt(Q): 6 x 4 tile pairs ----

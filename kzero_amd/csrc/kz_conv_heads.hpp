@@ -72,19 +72,23 @@ __device__ __forceinline__ void conv_heads_tail(const Dev &a, unsigned char *lds
     for (int i = tid; i < 5 * a.hs; i += 256) sw2[i] = a.sh_w2[i];
     KZ_HEADS_STAMP(56);
     // scalar head Conv1x1 C->hc + ReLU and the extra moves' Conv1x1 C->1 (post_act.py:8-31, :86-96): one small conv over x
-    bool bad = false;  // a non-finite sum = a non-finite value somewhere in this board's tower output
+    unsigned bad = 0;  // bit bb: a non-finite sum = a non-finite value somewhere in the tower output of board board0 + bb
     small_conv(0, [&](int mt, int q, int row, float v) {
         const int oc = mt * 16 + kq * 4 + q;
         const int bb = (int)(((unsigned)row * a.inv_hw) >> 16), p = row - bb * a.hw;
         if (oc < a.hc) {
-            bad |= !(fabsf(v) <= 3.0e38f);
+            bad |= (unsigned)!(fabsf(v) <= 3.0e38f) << bb;
             sact[bb * n_in + oc * a.hw + p] = fmaxf(v + sb[mt][q], 0.0f);
         } else if (oc == a.hc && a.extra) {
             sext[row] = v + sb[mt][q];
         }
     });
     KZ_HEADS_STAMP(57);
-    if (bad && a.nonfinite_flag) *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: the flag may live in pinned host memory)
+    if (bad && a.nonfinite_flag) {
+        *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: the flag may live in pinned host memory)
+        for (int bb = 0; bb < boards; bb++)
+            if (bad >> bb & 1) raise_nonfinite_board(a.nonfinite_flag, a.epoch, board0 + bb);
+    }
     // policy (post_act.py:75-110): Conv1x1 C->pc on the hidden layer, channel-major flatten
     small_conv(1, [&](int mt, int q, int row, float v) {
         const int oc = mt * 16 + kq * 4 + q;

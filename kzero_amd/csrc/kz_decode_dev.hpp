@@ -9,7 +9,8 @@
 //   probs  = softmax over the logits at the board's available-move indices, in the order given (common.rs:77-86);
 //            a finished board has an empty range and gets nothing               (:77 `map_or(vec![], ..)`)
 //   a softmax sum that is not strictly positive — the reference's assert (:110) — or a move index outside the policy
-//   (the reference would panic on the slice index) raises *error_flag; the host fails the call that returns the batch.
+//   (the reference would panic on the slice index) raises *error_flag and the board's own word behind it (error_flag[ERR_HDR +
+//   2 board], kz_kernels.hpp); the host fails the call that returns the batch, or hands the per-board status out.
 //   With symmetry ids (d.sym: the board went through the network under the symmetry sym[board], kz_encode_dev.hpp) the
 //   logit of the move with index idx is the mapped board's at policy_map[id][idx] — un-mapping the policy, symmetry.rs:126-148;
 //   the sum keeps the caller's move order.  A mapped index of -1 or an id >= n_sym is a bad index.
@@ -43,6 +44,12 @@ __device__ __forceinline__ float decode_wave_max_nan(float v) {  // max over the
     return v;
 }
 
+// the per-batch word and the board's own (kz_kernels.hpp: per-board status words), both plain stores of 1 by the board's wave
+__device__ __forceinline__ void decode_raise(const DecodeDev &d, int board) {
+    *reinterpret_cast<volatile int *>(d.error_flag) = 1;
+    raise_decode_board(d.error_flag, board);
+}
+
 __device__ __forceinline__ float decode_wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -66,7 +73,7 @@ __device__ __forceinline__ void decode_board_wave(const DecodeDev &d, int board,
         v[2] = e1 / sum;
         v[3] = e2 / sum;
         v[4] = s4;
-        if (!(sum > 0.0f)) *reinterpret_cast<volatile int *>(d.error_flag) = 1;
+        if (!(sum > 0.0f)) decode_raise(d, board);
     }
     const int64_t lo = d.move_offsets[board];
     const int n = (int)(d.move_offsets[board + 1] - lo);
@@ -76,7 +83,7 @@ __device__ __forceinline__ void decode_board_wave(const DecodeDev &d, int board,
     if (d.sym) {
         const int id = d.sym[board];
         if (id < d.n_sym) pmap = d.policy_map + (size_t)id * d.policy_len;
-        else if (lane == 0) *reinterpret_cast<volatile int *>(d.error_flag) = 1;
+        else if (lane == 0) decode_raise(d, board);
     }
     if (n <= 0) return;
     auto logit_of = [&](int i) {
@@ -98,6 +105,6 @@ __device__ __forceinline__ void decode_board_wave(const DecodeDev &d, int board,
         sum += e;
     }
     sum = decode_wave_sum(sum);
-    if (lane == 0 && !(sum > 0.0f)) *reinterpret_cast<volatile int *>(d.error_flag) = 1;
+    if (lane == 0 && !(sum > 0.0f)) decode_raise(d, board);
     for (int i = lane; i < n; i += 64) d.probs[lo + i] = (i < cap ? stage[i] : expf(logit_of(i) - mx)) / sum;
 }

@@ -45,6 +45,11 @@ __global__ __launch_bounds__(DN_THREADS) void kz_dense_network(DenseNetArgs a) {
     __syncthreads();
     dn_linear(a.w_in, a.b_in, IN, n_in, cur, size);
     __syncthreads();
+    // range check, first half: an f16 engine's input rows hold inf for a plane value beyond +-65504, and the input projection
+    // turns it into inf / NaN — which every later fmaxf(.., 0) would silently replace by 0 (fmaxf returns its other operand for
+    // a NaN), so the outputs alone cannot tell.  The arithmetic from here on is f32
+    bool bad = false;
+    for (int i = tid; i < size; i += DN_THREADS) bad |= !(fabsf(cur[i]) <= 3.0e38f);
     const float *blk = a.blocks;
     for (int l = 0; l < a.depth; l++) {
         const float *sa = blk, *ta = sa + size, *wa = ta + size, *ba = wa + (size_t)size * size, *sb = ba + size, *tb = sb + size,
@@ -65,14 +70,16 @@ __global__ __launch_bounds__(DN_THREADS) void kz_dense_network(DenseNetArgs a) {
     __syncthreads();
     dn_linear(a.w_out, a.b_out, act, size, out, 5 + a.policy_len);
     __syncthreads();
-    bool bad = false;
     for (int i = tid; i < 5 + a.policy_len; i += DN_THREADS) {
         const float v = out[i];
         bad |= !(fabsf(v) <= 3.0e38f);
         if (i < 5) a.scalars[(size_t)board * 5 + i] = v;
         else a.policy[(size_t)board * a.policy_len + (i - 5)] = v;
     }
-    if (bad && a.nonfinite_flag) *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: may be pinned host memory)
+    if (bad && a.nonfinite_flag) {
+        *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: may be pinned host memory)
+        raise_nonfinite_board(a.nonfinite_flag, a.epoch, board);
+    }
 }
 
 size_t dn_lds_bytes(int hw, int cin_p, int size, int policy_len) { return ((size_t)hw * cin_p + 3 * (size_t)size + 5 + policy_len) * 4; }

@@ -171,6 +171,7 @@ KZ_API int kz_model_get_info(const kz_model *model, kz_model_info *out) {
 
 KZ_API void kz_engine_destroy(kz_engine *e) {
     if (!e) return;
+    kz_engine_destroy(e->fallback);  // (the range fallback's sibling engine)
     (void)hipSetDevice(e->device);
     for (auto st : e->slot_stream)
         if (st) (void)hipStreamSynchronize(st);
@@ -218,6 +219,7 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
 
         std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(new kz_engine(), kz_engine_destroy);
         e->model = effective_model(model, split16 ? KZ_DTYPE_F32_SPLIT16 : dtype, max_batch);
+        e->source_model = model->m;
         e->out_channels = model->m->channels;
         const Model &m = *e->model;
         e->device = device;
@@ -286,23 +288,31 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
 
         const int nb_planes = m.n_bool < 0 ? 0 : m.n_bool, ns_planes = m.n_scalar < 0 ? 0 : m.n_scalar;
         const size_t bits_bytes = (size_t)(nb_planes * hw + 7) / 8;
+        // every flag word a launch is handed has the range check's per-board words in front of it (kz_engine_state.hpp: Slot)
+        const size_t front = (size_t)e->front_words();
         for (auto &s : e->slots) {
+            float *d_base = nullptr, *h_base = nullptr;
             if (e->dmalloc((void **)&s.d_bits, max_batch * bits_bytes) ||
                 e->dmalloc((void **)&s.d_sin, (size_t)max_batch * ns_planes * 4) ||
-                e->dmalloc((void **)&s.d_sout, ((size_t)max_batch * 5 + kz_engine::SOUT_HDR) * 4) ||
+                e->dmalloc((void **)&d_base, (front + (size_t)max_batch * 5 + kz_engine::SOUT_HDR) * 4) ||
                 e->dmalloc((void **)&s.d_pol, (size_t)max_batch * m.policy_len * 4))
                 return 1;
             if (e->hmalloc((void **)&s.h_bits, max_batch * bits_bytes) ||
                 e->hmalloc((void **)&s.h_sin, (size_t)max_batch * ns_planes * 4) ||
-                e->hmalloc((void **)&s.h_sout, ((size_t)max_batch * 5 + kz_engine::SOUT_HDR) * 4) ||
+                e->hmalloc((void **)&h_base, (front + (size_t)max_batch * 5 + kz_engine::SOUT_HDR) * 4) ||
                 e->hmalloc((void **)&s.h_pol, (size_t)max_batch * m.policy_len * 4))
                 return 1;
             HIP_TRY(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-            HIP_TRY(hipMemset(s.d_sout, 0, kz_engine::SOUT_HDR * 4));
-            memset(s.h_sout, 0, kz_engine::SOUT_HDR * 4);
+            HIP_TRY(hipMemset(d_base, 0, (front + kz_engine::SOUT_HDR) * 4));
+            memset(h_base, 0, (front + kz_engine::SOUT_HDR) * 4);
+            s.d_sout = d_base + front;
+            s.h_sout = h_base + front;
+            s.status.assign((size_t)max_batch, 0);
         }
-        if (e->dmalloc((void **)&e->d_devflag, 16)) return 1;
-        HIP_TRY(hipMemset(e->d_devflag, 0, 16));
+        int *devflag_base = nullptr;
+        if (e->dmalloc((void **)&devflag_base, (front + 4) * 4)) return 1;
+        HIP_TRY(hipMemset(devflag_base, 0, (front + 4) * 4));
+        e->d_devflag = devflag_base + front;
         *out = e.release();
         return 0;
     });
@@ -433,7 +443,7 @@ KZ_API int kz_engine_submit_packed(kz_engine *e, int slot, const uint8_t *bits, 
             e->nf_flag = reinterpret_cast<int *>(s.d_sout);
             e->nf_epoch = s.epoch;
             if (e->replay(slot, batch, s.d_bits, bits_bytes, s.d_sin, s.d_sout, s.d_pol, [&]() -> int {
-                    HIP_TRY(hipMemsetAsync(s.d_sout, 0, 4, e->stream));
+                    HIP_TRY(hipMemsetAsync(s.d_sout - e->front_words(), 0, ((size_t)e->front_words() + 1) * 4, e->stream));
                     return e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol);
                 }))
                 return 1;
@@ -446,13 +456,130 @@ KZ_API int kz_engine_submit_packed(kz_engine *e, int slot, const uint8_t *bits, 
             e->graph_warm = true;  // (the first pass runs eagerly: lazy per-kernel set-up must not land in a capture)
     #endif
         }
-        HIP_TRY(hipMemcpyAsync(s.h_sout, s.d_sout, ((size_t)batch * 5 + kz_engine::SOUT_HDR) * 4, hipMemcpyDeviceToHost,
+        // (one copy: the batch's per-board range words, the header, the scalars)
+        HIP_TRY(hipMemcpyAsync(s.h_sout - batch, s.d_sout - batch, ((size_t)batch * 6 + kz_engine::SOUT_HDR) * 4, hipMemcpyDeviceToHost,
                                e->stream));
         HIP_TRY(hipMemcpyAsync(s.h_pol, s.d_pol, (size_t)batch * m.policy_len * 4, hipMemcpyDeviceToHost, e->stream));
         HIP_TRY(hipEventRecord(s.done, e->stream));
         s.batch = batch;  // in flight only once the event is recorded: a failed submit leaves the slot free
         return 0;
     });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-board status (KZ_BOARD_*) and the range fallback: what the calls that return a batch do once its event has been waited for
+// ------------------------------------------------------------------------------------------------
+// The status of the first `batch` boards of a finished slot, from the per-board words the launches wrote (kz_kernels.hpp),
+// into s.status.  Where this batch's range words are: in front of the slot's pinned header when its results came through that
+// header — raw rows, or a decode inside the launch (an averaged launch's words count VIRTUAL boards: kz_sym_average has folded
+// them) —, and beside the decode's words otherwise (kz_decode_output / kz_sym_average copied them there).
+static void board_status(kz_engine::Slot &s, int batch, bool decoded) {
+    const int *nf = reinterpret_cast<const int *>(s.h_sout);
+    const bool nf_front = !decoded || (s.in_launch && !s.avg);
+    for (int b = 0; b < batch; b++) {
+        uint8_t st = KZ_BOARD_OK;
+        if (decoded) {
+            if (s.h_err[kz::ERR_HDR + 2 * b]) st |= KZ_BOARD_BAD_DECODE;
+            if (s.h_err[kz::ERR_HDR + 2 * b + 1]) st |= KZ_BOARD_NONFINITE;
+        }
+        if (nf_front && nf[-1 - b] == s.epoch) st |= KZ_BOARD_NONFINITE;
+        s.status[b] = st;
+    }
+}
+
+// The boards of a finished slot that carry KZ_BOARD_NONFINITE, re-evaluated through the sibling engine's matching entry (raw
+// rows, decoded with the same symmetry ids, or averaged) from the slot's pinned input staging, in chunks of the sibling's
+// max_batch; its results go over those boards' rows and ranges of the slot's output staging and their status becomes
+// KZ_BOARD_FELL_BACK (a board still bad in exact f32 keeps its bits beside it).  Host-driven, inside the returning call.
+static int range_fallback(kz_engine *e, kz_engine::Slot &s, int batch, bool decoded) {
+    kz_engine *f = e->fallback;
+    std::vector<int> bad;
+    for (int b = 0; b < batch; b++)
+        if (s.status[b] & KZ_BOARD_NONFINITE) bad.push_back(b);
+    if (bad.empty()) return 0;
+    const Model &m = *e->model;
+    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8, ns = (size_t)std::max(m.n_scalar, 0), plen = (size_t)m.policy_len;
+    const bool avg = decoded && s.avg;
+    const size_t per = avg ? (size_t)(f->max_batch / std::max(e->n_sym, 1)) : (size_t)f->max_batch;
+    if (per < 1) return 0;  // (more symmetries than the sibling holds boards: such an averaged batch keeps its verdict)
+    kz_engine::Slot &fs = f->slots[0];
+    std::vector<uint8_t> bits, sym;
+    std::vector<float> sin;
+    std::vector<int64_t> moff;
+    std::vector<int32_t> midx;
+    for (size_t lo = 0; lo < bad.size(); lo += per) {
+        const int n = (int)std::min(per, bad.size() - lo);
+        bits.resize((size_t)n * bits_bytes);
+        sin.resize((size_t)n * ns);
+        sym.resize((size_t)n);
+        moff.assign(1, 0);
+        midx.clear();
+        for (int i = 0; i < n; i++) {
+            const int b = bad[lo + i];
+            memcpy(bits.data() + (size_t)i * bits_bytes, s.h_bits + (size_t)b * bits_bytes, bits_bytes);
+            if (ns) memcpy(sin.data() + (size_t)i * ns, s.h_sin + (size_t)b * ns, ns * 4);
+            if (!decoded) continue;
+            if (s.with_sym && !avg) sym[i] = s.h_sym[b];
+            if (s.h_moff[b + 1] > s.h_moff[b]) midx.insert(midx.end(), s.h_midx + s.h_moff[b], s.h_midx + s.h_moff[b + 1]);
+            moff.push_back((int64_t)midx.size());
+        }
+        midx.push_back(0);  // (never read: a non-null pointer for an empty list)
+        int rc;
+        if (!decoded) rc = kz_engine_submit_packed(f, 0, bits.data(), bits_bytes, sin.data(), n);
+        else if (avg) rc = kz_engine_submit_packed_decoded_avg(f, 0, bits.data(), bits_bytes, sin.data(), n, moff.data(), midx.data());
+        else rc = kz_engine_submit_packed_decoded_sym(f, 0, bits.data(), bits_bytes, sin.data(), n, s.with_sym ? sym.data() : nullptr,
+                                                      moff.data(), midx.data());
+        if (rc) return 1;
+        // the sibling's slot is waited for here, not through its entries: its per-board verdict is what is wanted
+        fs.batch = -1;
+        fs.decoded = false;
+        HIP_TRY(hipEventSynchronize(fs.done));
+        board_status(fs, n, decoded);
+        for (int i = 0; i < n; i++) {
+            const int b = bad[lo + i];
+            if (!decoded) {
+                memcpy(s.h_sout + kz_engine::SOUT_HDR + (size_t)b * 5, fs.h_sout + kz_engine::SOUT_HDR + (size_t)i * 5, 20);
+                memcpy(s.h_pol + (size_t)b * plen, fs.h_pol + (size_t)i * plen, plen * 4);
+            } else {
+                memcpy(s.h_values + (size_t)b * 5, fs.h_values + (size_t)i * 5, 20);
+                const size_t len = (size_t)(moff[i + 1] - moff[i]);
+                if (len) memcpy(s.h_probs + s.h_moff[b], fs.h_probs + moff[i], len * 4);
+            }
+            s.status[b] = fs.status[i] ? (uint8_t)(s.status[b] | KZ_BOARD_FELL_BACK) : (uint8_t)KZ_BOARD_FELL_BACK;
+        }
+    }
+    return 0;
+}
+
+// What every call that returns a batch does after the slot's event: the per-board status, the fallback where it is on, and —
+// judge = true, the entries without a status output — the verdict those entries have always given, with their messages.
+// Without a fell-back board the verdict is read from the per-batch words exactly as before; with one, from the boards' status
+// (the per-batch words still hold what the replaced results raised).
+static int finish_batch(const char *name, kz_engine *e, kz_engine::Slot &s, int batch, bool decoded, bool judge) {
+    const std::string fn = name;
+    board_status(s, batch, decoded);
+    if (e->fallback && range_fallback(e, s, batch, decoded)) return 1;
+    if (!judge) return 0;
+    const auto softmax_message = [&] {
+        return fn + ": Softmax input sum must be strictly positive (or a move index is out of range" +
+               (s.with_sym ? ", a symmetry id is not below n_sym, or a listed move has no image under its board's symmetry)" : ")");
+    };
+    bool fell_back = false, nonfinite = false, bad_decode = false;
+    for (int b = 0; b < batch; b++) {
+        fell_back |= (s.status[b] & KZ_BOARD_FELL_BACK) != 0;
+        nonfinite |= (s.status[b] & KZ_BOARD_NONFINITE) != 0;
+        bad_decode |= (s.status[b] & KZ_BOARD_BAD_DECODE) != 0;
+    }
+    if (fell_back) {
+        if (nonfinite) return fail(kz_engine::nonfinite_message(name));
+        if (bad_decode) return fail(softmax_message());
+        return 0;
+    }
+    if (!decoded) return kz_engine::slot_nonfinite(s) ? fail(kz_engine::nonfinite_message(name)) : 0;
+    if (s.in_launch && kz_engine::slot_nonfinite(s)) return fail(kz_engine::nonfinite_message(name));
+    if (s.h_err[1]) return fail(kz_engine::nonfinite_message(name));
+    if (s.h_err[0]) return fail(softmax_message());
+    return 0;
 }
 
 KZ_API int kz_engine_wait(kz_engine *e, int slot, float *scalars_out, float *policy_out) {
@@ -467,10 +594,10 @@ KZ_API int kz_engine_wait(kz_engine *e, int slot, float *scalars_out, float *pol
         if (!scalars_out || !policy_out) return fail("kz_engine_wait: null output");
         HIP_TRY(hipSetDevice(e->device));
         HIP_TRY(hipEventSynchronize(s.done));
+        const int rc = finish_batch("kz_engine_wait", e, s, batch, false, true);
         memcpy(scalars_out, s.h_sout + kz_engine::SOUT_HDR, (size_t)batch * 5 * 4);
         memcpy(policy_out, s.h_pol, (size_t)batch * e->model->policy_len * 4);
-        if (kz_engine::slot_nonfinite(s)) return fail(kz_engine::nonfinite_message("kz_engine_wait"));
-        return 0;
+        return rc;
     });
 }
 
@@ -488,8 +615,7 @@ KZ_API int kz_engine_wait_view(kz_engine *e, int slot, const float **scalars_out
         if (batch == 0) return 0;
         HIP_TRY(hipSetDevice(e->device));
         HIP_TRY(hipEventSynchronize(s.done));
-        if (kz_engine::slot_nonfinite(s)) return fail(kz_engine::nonfinite_message("kz_engine_wait_view"));
-        return 0;
+        return finish_batch("kz_engine_wait_view", e, s, batch, false, true);
     });
 }
 
@@ -518,7 +644,7 @@ static int stage_decoded(const char *fn, kz_engine *e, kz_engine::Slot &s, const
     HIP_TRY(hipSetDevice(e->device));
     if (!s.h_moff) {  // (pinned only: the decode reads and writes the host staging directly, on every path)
         if (e->hmalloc((void **)&s.h_moff, (size_t)(e->max_batch + 1) * 8) || e->hmalloc((void **)&s.h_values, (size_t)e->max_batch * 20) ||
-            e->hmalloc((void **)&s.h_err, 16))
+            e->hmalloc((void **)&s.h_err, kz::error_flag_words(e->max_batch) * 4))
             return 1;
     }
     if (total > s.move_cap) {  // the old (smaller) buffers stay on the engine's free list until it is destroyed
@@ -530,7 +656,7 @@ static int stage_decoded(const char *fn, kz_engine *e, kz_engine::Slot &s, const
     if (m.n_scalar) memcpy(s.h_sin, scalars_in, (size_t)batch * m.n_scalar * 4);
     memcpy(s.h_moff, move_offsets, (size_t)(batch + 1) * 8);
     if (total) memcpy(s.h_midx, move_indices, total * 4);
-    s.h_err[0] = s.h_err[1] = 0;
+    memset(s.h_err, 0, kz::error_flag_words(batch) * 4);  // the per-batch words and this batch's per-board ones: cleared per submit
     total_out = total;
     return 0;
 }
@@ -563,6 +689,7 @@ static int submit_decoded(const char *fn, kz_engine *e, int slot, const uint8_t 
         ids = s.h_sym;
     }
     s.with_sym = sym != nullptr;
+    s.avg = false;
     StreamSwap swap{e, e->stream};
     if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
     if (e->zero_copy && e->plan.heads) {
@@ -638,7 +765,7 @@ static int virtual_scratch(const char *fn, kz_engine *e, kz_engine::Slot &s, siz
         const size_t ns = m.n_scalar < 0 ? 0 : (size_t)m.n_scalar;
         if (too_large(mb * bits_bytes) || too_large(mb * ns * 4) || too_large((mb + 1) * 8) || too_large(mb * 20)) return 1;
         if (e->dmalloc((void **)&v.bits, mb * bits_bytes) || e->dmalloc((void **)&v.sin, mb * ns * 4) || e->dmalloc((void **)&v.sym, mb) ||
-            e->dmalloc((void **)&v.values, mb * 20) || e->dmalloc((void **)&v.err, 16) || e->dmalloc((void **)&v.moff, (mb + 1) * 8))
+            e->dmalloc((void **)&v.values, mb * 20) || e->dmalloc((void **)&v.err, kz::error_flag_words(e->max_batch) * 4) || e->dmalloc((void **)&v.moff, (mb + 1) * 8))
             return 1;
     }
     if (vmoves > v.move_cap) {  // the old (smaller) buffers stay on the engine's free list until it is destroyed
@@ -693,6 +820,7 @@ static int submit_decoded_avg(const char *name, kz_engine *e, int slot, const ui
     const kz_engine::Slot::Virtual &v = s.virt;
     const int vbatch = batch * n;
     s.with_sym = true;  // (the batch's errors are those of the `_sym` entries)
+    s.avg = true;
     StreamSwap swap{e, e->stream};
     if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
     const kz::SymFanOutArgs fan{s.h_bits, bits_bytes, s.h_sin, m.n_scalar, batch, n, s.h_moff, s.h_midx,
@@ -716,7 +844,10 @@ static int submit_decoded_avg(const char *name, kz_engine *e, int slot, const ui
             }))
             return 1;
     }
-    const kz::SymAverageArgs avg{v.values, v.probs, v.moff, v.err, batch, n, s.h_values, s.h_probs, s.h_err};
+    // (the "+heads" launch stamped its virtual boards' range words in front of the slot's pinned header; the stand-alone
+    // decode has already copied them into v.err)
+    const kz::SymAverageArgs avg{v.values, v.probs, v.moff, v.err, batch, n, s.h_values, s.h_probs, s.h_err,
+                                 in_launch ? reinterpret_cast<const int *>(s.h_sout) : nullptr, s.epoch};
     if (e->launch("kz_sym_average", [&] { kz::launch_sym_average(avg, e->stream); })) return 1;
     HIP_TRY(hipEventRecord(s.done, e->stream));
     s.batch = batch;
@@ -777,49 +908,99 @@ KZ_API int kz_engine_set_symmetries(kz_engine *e, int n_sym, const int32_t *squa
         HIP_TRY(hipMemcpy(e->d_square_src, square_src, (size_t)n_sym * hw * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(e->d_policy_map, policy_map, (size_t)n_sym * plen * 4, hipMemcpyHostToDevice));
         e->n_sym = n_sym;
+        e->h_square_src.assign(square_src, square_src + (size_t)n_sym * hw);
+        e->h_policy_map.assign(policy_map, policy_map + (size_t)n_sym * plen);
+        if (e->fallback) return kz_engine_set_symmetries(e->fallback, n_sym, square_src, policy_map);  // (the range fallback's sibling)
         return 0;
     });
 }
 
+// kz_engine_wait_decoded (status_out == nullptr: an error inside the batch fails the call) and kz_engine_wait_decoded_status
+static int wait_decoded(const char *name, kz_engine *e, int slot, const float **values_out, const float **probs_out, void **status_out) {
+    const std::string fn = name;
+    if (!e) return fail(fn + ": null engine");
+    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(fn + ": bad slot");
+    if (!values_out || !probs_out) return fail(fn + ": null output");
+    kz_engine::Slot &s = e->slots[slot];
+    if (s.batch < 0 || !s.decoded) return fail(fn + ": nothing submitted with a move list on this slot");
+    const int batch = s.batch;
+    s.batch = -1;
+    s.decoded = false;
+    *values_out = s.h_values;
+    *probs_out = s.h_probs;
+    if (status_out) *status_out = s.status.data();
+    if (batch == 0) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipEventSynchronize(s.done));
+    return finish_batch(name, e, s, batch, true, status_out == nullptr);
+}
+
 KZ_API int kz_engine_wait_decoded(kz_engine *e, int slot, const float **values_out, const float **probs_out) {
-    return guarded("kz_engine_wait_decoded", [&]() -> int {
-        if (!e) return fail("kz_engine_wait_decoded: null engine");
-        if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail("kz_engine_wait_decoded: bad slot");
-        if (!values_out || !probs_out) return fail("kz_engine_wait_decoded: null output");
-        kz_engine::Slot &s = e->slots[slot];
-        if (s.batch < 0 || !s.decoded) return fail("kz_engine_wait_decoded: nothing submitted with a move list on this slot");
-        const int batch = s.batch;
-        s.batch = -1;
-        s.decoded = false;
-        *values_out = s.h_values;
-        *probs_out = s.h_probs;
-        if (batch == 0) return 0;
-        HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipEventSynchronize(s.done));
-        if (s.in_launch && kz_engine::slot_nonfinite(s)) return fail(kz_engine::nonfinite_message("kz_engine_wait_decoded"));
-        if (s.h_err[1]) return fail(kz_engine::nonfinite_message("kz_engine_wait_decoded"));
-        if (s.h_err[0])
-            return fail(std::string("kz_engine_wait_decoded: Softmax input sum must be strictly positive (or a move index is out of range") +
-                        (s.with_sym ? ", a symmetry id is not below n_sym, or a listed move has no image under its board's symmetry)" : ")"));
+    return guarded("kz_engine_wait_decoded", [&]() -> int { return wait_decoded("kz_engine_wait_decoded", e, slot, values_out, probs_out, nullptr); });
+}
+
+KZ_API int kz_engine_wait_decoded_status(kz_engine *e, int slot, const float **values_out, const float **probs_out, void **status_out) {
+    return guarded("kz_engine_wait_decoded_status", [&]() -> int {
+        if (!status_out) return fail("kz_engine_wait_decoded_status: null output");
+        return wait_decoded("kz_engine_wait_decoded_status", e, slot, values_out, probs_out, status_out);
+    });
+}
+
+KZ_API int kz_engine_set_range_fallback(kz_engine *e, int dtype) {
+    return guarded("kz_engine_set_range_fallback", [&]() -> int {
+        const std::string fn = "kz_engine_set_range_fallback";
+        if (!e) return fail(fn + ": null engine");
+        if (dtype != KZ_DTYPE_F32 && dtype != -1) return fail(fn + ": dtype must be KZ_DTYPE_F32 (on) or -1 (off), got " + std::to_string(dtype));
+        if (e->dtype == KZ_DTYPE_F32 && !e->split16())
+            return fail(fn + ": this engine evaluates in KZ_DTYPE_F32 already (exact f32 has no f16 range to fall back from)");
+        for (const auto &s : e->slots)
+            if (s.batch >= 0) return fail(fn + ": a batch is in flight (wait for every slot first)");
+        if (dtype == -1) {
+            kz_engine_destroy(e->fallback);
+            e->fallback = nullptr;
+            return 0;
+        }
+        if (e->fallback) return 0;
+        // the sibling: same model and device, exact f32, a small max_batch of its own (flagged boards go through it in chunks)
+        const kz_model source(e->source_model);
+        kz_engine *f = nullptr;
+        if (kz_engine_create(&source, e->device, std::min(e->max_batch, 64), KZ_DTYPE_F32, &f)) return 1;
+        if (e->n_sym && kz_engine_set_symmetries(f, e->n_sym, e->h_square_src.data(), e->h_policy_map.data())) {
+            kz_engine_destroy(f);
+            return 1;
+        }
+        e->fallback = f;
         return 0;
     });
 }
 
 // kz_engine_eval_packed_decoded and, with sym, kz_engine_eval_packed_decoded_sym
 static int eval_decoded(const char *name, kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in, int batch,
-                        const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices, float *values_out, float *probs_out) {
+                        const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices, float *values_out, float *probs_out,
+                        void *status_out = nullptr, bool with_status = false) {
     const std::string fn = name;
     if (check_batch(e, batch, name) || check_packed(e, name)) return 1;
     if (batch == 0) return 0;
-    if (!values_out) return fail(fn + ": null argument");
+    if (!values_out || (with_status && !status_out)) return fail(fn + ": null argument");
     if (move_offsets && batch > 0 && move_offsets[batch] > 0 && !probs_out) return fail(fn + ": null move list");
     if (submit_decoded(name, e, 0, bits, bits_stride, scalars_in, batch, sym, move_offsets, move_indices)) return 1;
     const float *values = nullptr, *probs = nullptr;
     const size_t total = e->slots[0].moves;
-    if (kz_engine_wait_decoded(e, 0, &values, &probs)) return 1;
+    void *status = nullptr;
+    if (wait_decoded(with_status ? name : "kz_engine_wait_decoded", e, 0, &values, &probs, with_status ? &status : nullptr)) return 1;
     memcpy(values_out, values, (size_t)batch * 20);
     if (total) memcpy(probs_out, probs, total * 4);
+    if (with_status) memcpy(status_out, status, (size_t)batch);
     return 0;
+}
+
+KZ_API int kz_engine_eval_packed_decoded_status(kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                                int batch, const uint8_t *sym, const int64_t *move_offsets,
+                                                const int32_t *move_indices, float *values_out, float *probs_out, void *status_out) {
+    return guarded("kz_engine_eval_packed_decoded_status", [&]() -> int {
+        return eval_decoded("kz_engine_eval_packed_decoded_status", e, bits, bits_stride, scalars_in, batch, sym, move_offsets,
+                            move_indices, values_out, probs_out, status_out, true);
+    });
 }
 
 KZ_API int kz_engine_eval_packed_decoded(kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in,

@@ -128,7 +128,9 @@ struct kz_engine {
         uint8_t *d_bits = nullptr, *h_bits = nullptr;
         float *d_sin = nullptr, *h_sin = nullptr;
         // d_sout / h_sout start with a 16-byte header: [0] = the range-check flag (kz::ScalarHeadArgs::nonfinite_flag),
-        // so that it crosses PCIe in the same copy as the scalars
+        // so that it crosses PCIe in the same copy as the scalars.  IN FRONT of the header lie the range check's per-board
+        // words (kz_kernels.hpp "per-board status words": board b's at [-1 - b], front_words() of them in both buffers,
+        // epoch-stamped like the flag), so the copy that fetches a batch starts `batch` words earlier
         float *d_sout = nullptr, *h_sout = nullptr;
         float *d_pol = nullptr, *h_pol = nullptr;
         hipEvent_t done = nullptr;
@@ -141,7 +143,10 @@ struct kz_engine {
         int64_t *h_moff = nullptr;
         int32_t *h_midx = nullptr;
         float *h_values = nullptr, *h_probs = nullptr;
-        int *h_err = nullptr;  // [0] softmax sum / move index, [1] range check (kz_kernels.hpp: launch_decode_output)
+        int *h_err = nullptr;  // [0] softmax sum / move index, [1] range check, then two words per board (kz_kernels.hpp:
+                               // launch_decode_output, error_flag_words(max_batch)); cleared per submit by stage_decoded
+        bool avg = false;      // what is in flight is an averaged submit (the launches' range words count virtual boards)
+        std::vector<uint8_t> status;  // [max_batch] KZ_BOARD_* of the batch last waited for (kz_engine_wait_decoded_status's view)
         uint8_t *h_sym = nullptr;  // [max_batch] symmetry ids of the batch (pinned, read by the launches; set_symmetries allocates it)
         bool with_sym = false;     // what is in flight was submitted with symmetry ids
         // every board under every symmetry (the `_avg` entries, kz_symmetry_avg.hip): the VIRTUAL batch in device memory —
@@ -151,7 +156,7 @@ struct kz_engine {
             uint8_t *bits = nullptr, *sym = nullptr;  // [max_batch][bits_bytes], [max_batch] ids
             float *sin = nullptr, *values = nullptr;  // [max_batch][n_scalar], [max_batch][5]
             int64_t *moff = nullptr;                  // [max_batch + 1]
-            int *err = nullptr;                       // the decode's two flag words
+            int *err = nullptr;                       // the decode's flag words (error_flag_words(max_batch))
             int32_t *midx = nullptr;                  // [move_cap]
             float *probs = nullptr;                   // [move_cap]
             size_t move_cap = 0;
@@ -160,6 +165,14 @@ struct kz_engine {
     // board symmetries (kz_engine_set_symmetries): the two tables the encode and the decode read, in device memory
     int n_sym = 0, sym_cap = 0;
     int32_t *d_square_src = nullptr, *d_policy_map = nullptr;  // [n_sym][h*w], [n_sym][policy_len]
+    std::vector<int32_t> h_square_src, h_policy_map;          // the same tables as the caller gave them (for a sibling created later)
+    // the range fallback (kz_engine_set_range_fallback): a sibling engine of the same model and device in exact f32 with a
+    // small max_batch of its own; the call that returns a batch re-evaluates the boards whose range word fired through it
+    // (kz_engine.hip: range_fallback).  It has its own streams, slots and staging; only DeviceWeights' cache is shared.
+    std::shared_ptr<Model> source_model;  // the model as loaded (`model` may be the widened one)
+    kz_engine *fallback = nullptr;
+    // words in front of every range-check flag word the engine hands to a launch (a multiple of 4: the scalars stay 16-byte aligned)
+    int front_words() const { return (max_batch + 3) / 4 * 4; }
     float *d_dense = nullptr, *h_dense = nullptr;
     static constexpr int SOUT_HDR = 4;  // floats in front of the scalars
     // range check (see kz::ScalarHeadArgs): every submission gets a new epoch; a kernel that meets a non-finite
@@ -176,13 +189,14 @@ struct kz_engine {
         if (epoch >= GRAPH_EPOCH - 1) {  // start over: settle the device-resident flag first (slot flags compare for equality)
             (void)sync_all();
             check_devflag_pending();
-            if (d_devflag) (void)hipMemset(d_devflag, 0, 4);
+            if (d_devflag) (void)hipMemset(d_devflag - front_words(), 0, ((size_t)front_words() + 1) * 4);
             // the slots' own flag words too: a slot that once recorded a non-finite batch at epoch X keeps X in its header,
             // and X is about to be issued again (everything is idle here: sync_all above)
             for (auto &s : slots) {
                 if (s.batch >= 0) continue;  // (a finished batch nobody has waited for yet keeps its verdict)
-                if (s.d_sout) (void)hipMemset(s.d_sout, 0, 4);
-                if (s.h_sout) *reinterpret_cast<int *>(s.h_sout) = 0;
+                // (with their per-board words in front: epoch-stamped like the flag itself)
+                if (s.d_sout) (void)hipMemset(s.d_sout - front_words(), 0, ((size_t)front_words() + 1) * 4);
+                if (s.h_sout) memset(s.h_sout - front_words(), 0, ((size_t)front_words() + 1) * 4);
                 s.epoch = 0;
             }
             epoch = dev_epoch_enqueued = dev_epoch_checked = 0;
@@ -271,7 +285,8 @@ struct kz_engine {
     }
     static std::string nonfinite_message(const char *fn) {
         return std::string(fn) + ": non-finite activation in the network output of this batch (beyond +-65504 the f16 "
-               "and split-f16 paths overflow: evaluate this network with KZ_DTYPE_F32)";
+               "and split-f16 paths overflow: evaluate this network with KZ_DTYPE_F32).  kz_engine_set_range_fallback(engine, "
+               "KZ_DTYPE_F32) makes the engine re-evaluate just the out-of-range boards in exact f32 instead of failing the batch";
     }
 
     // debugging (PathPlan::keep)

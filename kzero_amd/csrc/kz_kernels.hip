@@ -522,7 +522,10 @@ __global__ __launch_bounds__(256) void kz_scalar_head(ScalarHeadDev a) {
             act[o] = fmaxf(v, 0.0f);
         }
     }
-    if (bad && a.nonfinite_flag) *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: the flag may live in pinned host memory)
+    if (bad && a.nonfinite_flag) {
+        *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: the flag may live in pinned host memory)
+        raise_nonfinite_board(a.nonfinite_flag, a.epoch, b);
+    }
     __syncthreads();
     const int n_in = a.hc * a.hw;
     if (a.w1t && a.hs == 32) {
@@ -780,7 +783,8 @@ __global__ __launch_bounds__(256) void kz_attention_mfma(AttentionDev a) {
 //   values = [tanh(s0), softmax(s1..s3), s4]  (:60-74)
 //   probs  = softmax over the logits gathered at the board's available-move indices, in the given order (:77-86)
 // error_flag[0] = 1: a softmax sum is not strictly positive (where the reference asserts, :110) or a move index is outside
-// the policy; error_flag[1] = 1: *nonfinite_flag == epoch (the range check of ScalarHeadArgs).  Move lists, values,
+// the policy; error_flag[1] = 1: *nonfinite_flag == epoch (the range check of ScalarHeadArgs); behind them the two words per
+// board of kz_kernels.hpp ("per-board status words"): the decode's and, copied from nonfinite_flag[-1 - b], the range check's.  Move lists, values,
 // probabilities and the flag words may be pinned host memory: every word is read or written once, flags by plain stores.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
@@ -796,6 +800,9 @@ __global__ __launch_bounds__(256) void kz_decode_output(const float *__restrict_
     if (blockIdx.x == 0 && threadIdx.x == 0 && nonfinite_flag && *nonfinite_flag == epoch)
         *reinterpret_cast<volatile int *>(d.error_flag + 1) = 1;
     if (b >= batch) return;
+    // the board's own range word, for the host: this launch runs after the network's, so the epoch-stamped word is final
+    if (lane == 0 && nonfinite_flag && nonfinite_flag[-1 - b] == epoch)
+        *reinterpret_cast<volatile int *>(d.error_flag + ERR_HDR + 2 * b + 1) = 1;
     const float *lg = logits + (size_t)b * d.policy_len;
     decode_board_wave(d, b, lane, scalars + (size_t)b * 5, stage[wave], DECODE_STAGE, [&](int idx) { return lg[idx]; });
 }

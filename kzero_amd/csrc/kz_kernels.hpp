@@ -11,6 +11,27 @@ namespace kz {
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// ---- per-board status words (include/kz_hip.h: KZ_BOARD_*), beside the two per-batch flag words.  No launch has an argument
+// for them: they lie around the word its flag pointer already names, in buffers the engine owns and sizes for max_batch
+// boards (kz_engine_state.hpp: Slot, d_devflag).  A flag pointer of any other origin must be laid out the same way.
+//   range check (ScalarHeadArgs::nonfinite_flag): board b's word is nonfinite_flag[-1 - b], IN FRONT of the per-batch word,
+//     and is EPOCH-STAMPED like it — it counts only while it equals the submission's epoch, so nothing clears it between
+//     batches (the engine clears the words when the epochs start over).
+//   decode (DecodeArgs::error_flag): ERR_HDR words — [0], [1] the per-batch ones, as before — then two words per board:
+//     error_flag[ERR_HDR + 2 b] = 1: board b's decode failed; error_flag[ERR_HDR + 2 b + 1] = 1: the range check fired for
+//     board b, written only by the kernels that run AFTER the network (kz_decode_output, kz_sym_average), which read the
+//     epoch-stamped words above.  These are CLEARED PER SUBMIT, with the per-batch words (the host for the pinned staging,
+//     kz_sym_fan_out for the virtual batch).
+// All of them are plain stores of one value per word, in the cold branches that raise the per-batch words.
+constexpr int ERR_HDR = 4;
+inline size_t error_flag_words(int max_batch) { return ERR_HDR + 2 * (size_t)max_batch; }
+__device__ __forceinline__ void raise_nonfinite_board(int *nonfinite_flag, int epoch, int board) {
+    *reinterpret_cast<volatile int *>(nonfinite_flag - 1 - board) = epoch;
+}
+__device__ __forceinline__ void raise_decode_board(int *error_flag, int board) {
+    *reinterpret_cast<volatile int *>(error_flag + ERR_HDR + 2 * board) = 1;
+}
+
 // A batch of boards as the host packs them: bits [batch][stride] u8 (one BitBuffer of n_bool * hw bits per board) and
 // scalars [batch][n_scalar] f32.  What a launch with a fused board encode is told about its input; bits == nullptr: the
 // launch reads its encoded x0 rows instead.  How a kernel turns it into planes: kz_encode_dev.hpp.
@@ -131,7 +152,9 @@ void launch_attention(int dtype, const AttentionArgs &a, hipStream_t stream);
 // F7 — decode_output (rust/kz-core/src/network/common.rs:16-100) on the device: values [batch][5] = tanh / wdl softmax /
 // moves_left; probs = per-board softmax over the logits at the available-move indices (CSR lists).
 // error_flag: TWO words — [0] = 1: a softmax sum is not strictly positive (or a move index is out of range); [1] = 1:
-// *nonfinite_flag == epoch (see ScalarHeadArgs).  The move lists, values, probs and error_flag may be pinned host memory.
+// *nonfinite_flag == epoch (see ScalarHeadArgs); then two words per board ("per-board status words" above: error_flag has
+// error_flag_words(batch) words, nonfinite_flag batch words in front of it).  The move lists, values, probs and error_flag may
+// be pinned host memory.
 // sym / policy_map / n_sym: the symmetry ids of DecodeArgs (sym == nullptr: none)
 void launch_decode_output(const float *scalars, const float *logits, int batch, int policy_len,
                           const int64_t *move_offsets, const int32_t *move_indices, float *values, float *probs,
@@ -171,11 +194,13 @@ struct SymFanOutArgs {
     uint8_t *v_sym;               // [batch * n_sym] = k
     int64_t *v_move_offsets;      // [batch * n_sym + 1]: voff[b n + k] = n off[b] + k len_b, voff[n batch] = n total
     int32_t *v_move_indices;      // [n_sym * total]: board b's list n_sym times
-    int *v_error_flag;            // the decode's two words (launch_decode_output), cleared here
+    int *v_error_flag;            // the decode's words (launch_decode_output: two, then two per virtual board), cleared here
 };
 void launch_sym_fan_out(const SymFanOutArgs &a, hipStream_t stream);
 // values[b][j] = (((0 + v_0) + v_1) + ... + v_{n-1}) / n and probs[lo_b + i] = ((0 + p_0 / n) + p_1 / n) + ..., f32 with
-// correctly rounded divisions, k = 0 .. n_sym-1 ascending; error_flag[0..1] = v_error_flag[0..1]
+// correctly rounded divisions, k = 0 .. n_sym-1 ascending; error_flag[0..1] = v_error_flag[0..1], and each of a board's two
+// status words = the OR over its n_sym virtual boards' (the range check's also from nonfinite_flag[-1 - v] == epoch, the
+// words a "+heads" launch over the virtual batch stamps; nullptr: none)
 struct SymAverageArgs {
     const float *v_values;          // [batch * n_sym][5]
     const float *v_probs;           // parallel to v_move_indices
@@ -184,6 +209,8 @@ struct SymAverageArgs {
     int batch, n_sym;
     float *values, *probs;          // [batch][5], parallel to move_indices
     int *error_flag;
+    const int *nonfinite_flag = nullptr;
+    int epoch = 0;
 };
 void launch_sym_average(const SymAverageArgs &a, hipStream_t stream);
 

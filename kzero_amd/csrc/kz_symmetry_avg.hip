@@ -46,6 +46,7 @@ __global__ __launch_bounds__(FAN_THREADS) void kz_sym_fan_out(SymFanOutArgs a) {
     }
     if (b == a.batch - 1 && t == 0) a.v_move_offsets[(size_t)n * a.batch] = (int64_t)n * hi;
     if (b == 0 && t == 0) a.v_error_flag[0] = a.v_error_flag[1] = 0;  // the decode of this batch raises them
+    for (int i = t; i < 2 * n; i += FAN_THREADS) a.v_error_flag[ERR_HDR + 2 * v0 + i] = 0;  // ... and its virtual boards' own words (two each): cleared per submit
 }
 
 // One WAVE per source board.  Lanes 0..4 reduce the five values; then the lanes stride over the board's moves and each sums
@@ -61,6 +62,18 @@ __global__ __launch_bounds__(AVG_WAVES * 64) void kz_sym_average(SymAverageArgs 
     if (b >= a.batch) return;
     const float nf = (float)n;
     const size_t v0 = (size_t)b * n;
+    // the source board's status = the OR over its n virtual boards: the decode's word, and the range check's from either
+    // place a virtual board's can be (the stand-alone decode's copy, or the launch's epoch-stamped word)
+    if (lane == 0) {
+        int dec = 0, range = 0;
+        for (int k = 0; k < n; k++) {
+            dec |= a.v_error_flag[ERR_HDR + 2 * (v0 + k)];
+            range |= a.v_error_flag[ERR_HDR + 2 * (v0 + k) + 1];
+            if (a.nonfinite_flag) range |= a.nonfinite_flag[-1 - (int)(v0 + k)] == a.epoch;
+        }
+        if (dec) a.error_flag[ERR_HDR + 2 * b] = 1;
+        if (range) a.error_flag[ERR_HDR + 2 * b + 1] = 1;
+    }
     if (lane < 5) {
         float acc = 0.0f;
         for (int k = 0; k < n; k++) acc = acc + a.v_values[(v0 + k) * 5 + lane];

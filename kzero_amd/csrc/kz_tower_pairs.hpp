@@ -633,8 +633,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
                 for (int j = 0; j < 4; j++)
                     sum += ((float)xh[j] + (float)xl[j]) * w0[j] + ((float)xh[4 + j] + (float)xl[4 + j]) * w1[j];
             }
-            if (!(fabsf(sum) <= 3.0e38f) && a.nonfinite_flag)
+            if (!(fabsf(sum) <= 3.0e38f) && a.nonfinite_flag) {
                 *reinterpret_cast<volatile int *>(a.nonfinite_flag) = a.epoch;  // (plain store: the flag may be in pinned host memory)
+                raise_nonfinite_board(a.nonfinite_flag, a.epoch, board0);  // (this launch form holds one board per workgroup)
+            }
             act[tid] = fmaxf(sum, 0.0f);
         }
 

@@ -75,6 +75,11 @@ pub const KZ_DTYPE_F16: c_int = 1;
 /// f32 tensors and the same <= 1e-4 parity as KZ_DTYPE_F32, the tower's products as three f16 MFMAs on (hi, lo) pairs
 pub const KZ_DTYPE_F32_SPLIT16: c_int = 2;
 pub const KZ_ENGINE_SLOTS: usize = 4;
+/// Per-board status bits of `kz_engine_wait_decoded_status` / `kz_engine_eval_packed_decoded_status` (include/kz_hip.h)
+pub const KZ_BOARD_OK: u8 = 0;
+pub const KZ_BOARD_BAD_DECODE: u8 = 1;
+pub const KZ_BOARD_NONFINITE: u8 = 2;
+pub const KZ_BOARD_FELL_BACK: u8 = 4;
 
 // The C ABI of include/kz_hip.h, declaration for declaration (tests/test_rust_shim_text.py compares the two files:
 // every function of the header is bound here with the same name, arity and pointer-ness).  `kz_model` / `kz_engine`
@@ -111,6 +116,10 @@ extern "C" {
     // every board under every symmetry of the tables, averaged on the device: at most max_batch / n_sym boards per call
     fn kz_engine_eval_packed_decoded_avg(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, move_offsets: *const i64, move_indices: *const i32, values_out: *mut f32, probs_out: *mut f32) -> c_int;
     fn kz_engine_submit_packed_decoded_avg(engine: *mut c_void, slot: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, move_offsets: *const i64, move_indices: *const i32) -> c_int;
+    // per-board status instead of a failing batch (status: u8 [batch], typed void in the header), and the exact-f32 range fallback
+    fn kz_engine_wait_decoded_status(engine: *mut c_void, slot: c_int, values_out: *mut *const f32, probs_out: *mut *const f32, status_out: *mut *mut c_void) -> c_int;
+    fn kz_engine_eval_packed_decoded_status(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, sym: *const u8, move_offsets: *const i64, move_indices: *const i32, values_out: *mut f32, probs_out: *mut f32, status_out: *mut c_void) -> c_int;
+    fn kz_engine_set_range_fallback(engine: *mut c_void, dtype: c_int) -> c_int;
     // device-resident entry points and helpers (benchmarks and parity tests; the server does not need them)
     fn kz_engine_enqueue_packed_device(engine: *mut c_void, d_bits: *const c_void, bits_stride: usize, d_scalars_in: *const c_void, batch: c_int, d_scalars_out: *mut c_void, d_policy_out: *mut c_void) -> c_int;
     fn kz_engine_enqueue_dense_device(engine: *mut c_void, d_input_nchw: *const c_void, batch: c_int, d_scalars_out: *mut c_void, d_policy_out: *mut c_void) -> c_int;
@@ -264,6 +273,10 @@ pub struct HipNetwork<B: Board, M: BoardMapper<B>> {
     /// `AverageSymmetryNetwork` inside the engine (`new_with_average_symmetries`): every board under all `n_sym`
     /// symmetries, averaged on the device; a batch is then at most `max_batch_size / n_sym` boards per engine call
     average_symmetries: bool,
+    /// `KZ_HIP_RANGE_FALLBACK=1` (default off; read here, never by the library): boards of an f16 / split16 batch whose
+    /// activations leave the f16 range are re-evaluated in exact f32 inside the engine (`kz_engine_set_range_fallback`)
+    /// instead of panicking the executor; how many boards that has happened to so far
+    pub fell_back_boards: u64,
     /// `KZ_HIP_PREP_THREADS` (default 0) + 1 ranges of a batch, each prepared by one thread (`prepare`)
     ranges: Vec<PrepRange>,
     ph: PhantomData<B>,
@@ -334,6 +347,12 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
         let mut engine = std::ptr::null_mut();
         let dtype = dtype.resolve(&model);
         check(unsafe { kz_engine_create(model.ptr, device.0 as c_int, max_batch_size as c_int, dtype, &mut engine) });
+        match std::env::var("KZ_HIP_RANGE_FALLBACK").as_deref() {
+            Err(_) | Ok("0") => {}
+            // (an exact-f32 engine has no f16 range to fall back from: the library refuses it, so it is not asked)
+            Ok("1") => if dtype != KZ_DTYPE_F32 { check(unsafe { kz_engine_set_range_fallback(engine, KZ_DTYPE_F32) }) },
+            Ok(other) => panic!("KZ_HIP_RANGE_FALLBACK must be 0 or 1, got '{}'", other),
+        }
 
         HipNetwork {
             mapper,
@@ -357,6 +376,7 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
             sym_rng: None,
             sym_ids: vec![],
             average_symmetries: false,
+            fell_back_boards: 0,
             ranges: {
                 // (a malformed value is not worth a panic in a constructor: no helpers, and say so once)
                 let helpers: usize = match std::env::var("KZ_HIP_PREP_THREADS") {
@@ -501,6 +521,27 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
         bits_bytes
     }
 
+    /// `kz_engine_wait_decoded` through the status entry: the two views of the slot's pinned staging.  Boards the range
+    /// fallback re-evaluated (status exactly `KZ_BOARD_FELL_BACK`: their results are the exact-f32 ones) are counted;
+    /// any other non-zero status panics like the reference does on every executor error, naming the boards.
+    fn wait_decoded_checked(&mut self, slot: usize, n: usize) -> (*const f32, *const f32) {
+        let (mut values, mut probs) = (std::ptr::null::<f32>(), std::ptr::null::<f32>());
+        let mut status = std::ptr::null_mut::<c_void>();
+        check(unsafe { kz_engine_wait_decoded_status(self.engine, slot as c_int, &mut values, &mut probs, &mut status) });
+        let status = unsafe { std::slice::from_raw_parts(status as *const u8, n) };
+        self.fell_back_boards += status.iter().filter(|&&s| s == KZ_BOARD_FELL_BACK).count() as u64;
+        let bad: Vec<usize> = (0..n).filter(|&b| status[b] != KZ_BOARD_OK && status[b] != KZ_BOARD_FELL_BACK).collect();
+        if let Some(&first) = bad.first() {
+            let what = if status[first] & KZ_BOARD_NONFINITE != 0 {
+                "non-finite activation (beyond +-65504 the f16 and split-f16 paths overflow: set KZ_HIP_RANGE_FALLBACK=1 or KZ_HIP_DTYPE=f32)"
+            } else {
+                "Softmax input sum must be strictly positive (or a move index or symmetry id is out of range)"
+            };
+            panic!("kzhip: {} on boards {:?} of the batch", what, bad);
+        }
+        (values, probs)
+    }
+
     /// values [n, 5] (tanh / softmax already applied on the device) + probabilities parallel to the move lists
     fn assemble(offsets: &[i64], values: &[f32], probs: &[f32]) -> Vec<ZeroEvaluation<'static>> {
         (0..offsets.len() - 1)
@@ -548,9 +589,8 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
     pub fn wait_batch(&mut self) -> Vec<ZeroEvaluation<'static>> {
         let (slot, boards, offsets) = self.pending.pop_front().expect("wait_batch with nothing in flight");
         if self.device_decode {
-            let (mut values, mut probs) = (std::ptr::null::<f32>(), std::ptr::null::<f32>());
-            check(unsafe { kz_engine_wait_decoded(self.engine, slot as c_int, &mut values, &mut probs) });
             let (n, total) = (offsets.len() - 1, *offsets.last().unwrap() as usize);
+            let (values, probs) = self.wait_decoded_checked(slot, n);
             // views into the engine's pinned staging, valid until the next submit on this slot (include/kz_hip.h)
             let values = unsafe { std::slice::from_raw_parts(values, n * 5) };
             let probs = if total == 0 { &[][..] } else { unsafe { std::slice::from_raw_parts(probs, total) } };
@@ -595,8 +635,7 @@ impl<B: Board, M: BoardMapper<B>> Network<B> for HipNetwork<B, M> {
 
         if self.device_decode {
             self.submit_decoded(0, bits_bytes, batch_size);
-            let (mut values, mut probs) = (std::ptr::null::<f32>(), std::ptr::null::<f32>());
-            check(unsafe { kz_engine_wait_decoded(self.engine, 0, &mut values, &mut probs) });
+            let (values, probs) = self.wait_decoded_checked(0, batch_size);
             let total = *self.move_offsets.last().unwrap() as usize;
             let values = unsafe { std::slice::from_raw_parts(values, batch_size * 5) };
             let probs = if total == 0 { &[][..] } else { unsafe { std::slice::from_raw_parts(probs, total) } };
