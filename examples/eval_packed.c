@@ -56,6 +56,11 @@ int main(int argc, char **argv) {
      * outside the policy, so it comes back as KZ_BOARD_BAD_DECODE and the other boards' results stand.  (An f16 / split16
      * engine after kz_engine_set_range_fallback(engine, KZ_DTYPE_F32) reports a board it re-evaluated in exact f32 as
      * KZ_BOARD_FELL_BACK.) */
+    /* ... and, beside it, the shadow audit: the batch's boards also run on a sibling engine in another <= 1e-4 arithmetic and
+     * the engine accumulates how far the two are apart (this engine is exact f32, so the sibling is the split-f16 one; an f16
+     * engine would be audited against KZ_DTYPE_F32_SPLIT16 or KZ_DTYPE_F32 the same way).  Nothing of the batch changes. */
+    const int audited = kz_model_supports_dtype(model, KZ_DTYPE_F32_SPLIT16) == 1;
+    if (audited) CHECK(kz_engine_set_audit(engine, KZ_DTYPE_F32_SPLIT16, 1, batch));
     int64_t move_offsets[5] = {0, 2, 4, 6, 8};
     int32_t move_indices[8] = {0, 1, 0, 1, 0, 1, 0, 1};
     move_indices[3] = info.policy_len;
@@ -68,6 +73,13 @@ int main(int argc, char **argv) {
             printf("board %d: status %d  value %+.4f  p(move 0) %.4f  p(move 1) %.4f\n", b, status[b], values[b * 5], probs[2 * b], probs[2 * b + 1]);
         else
             printf("board %d: status %d (its results are unspecified)\n", b, status[b]);
+    }
+
+    if (audited) {
+        kz_audit_stats audit;
+        CHECK(kz_engine_audit_stats(engine, &audit, 0));
+        printf("audit against split16: %lld boards compared, %lld skipped, max |dp| %.3g\n", (long long)audit.boards,
+               (long long)audit.skipped, audit.max_abs_prob);
     }
 
     free(bits);

@@ -252,6 +252,45 @@ int kz_engine_eval_packed_decoded_status(kz_engine *engine, const uint8_t *bits,
  * kz_engine_synchronize. */
 int kz_engine_set_range_fallback(kz_engine *engine, int dtype);
 
+/* ---- shadow audit: a sample of the decoded batches, evaluated a second time in a <= 1e-4 arithmetic ----
+ * Answers "is this network, on the positions it is actually asked about, inside the f16 contract?" without a second engine in
+ * the caller.  kz_engine_set_audit(engine, dtype, period, boards): dtype = KZ_DTYPE_F32 or KZ_DTYPE_F32_SPLIT16 turns the audit
+ * on, -1 off (the default; period and boards are then ignored).  Turning it on creates - here, so that a failure surfaces here -
+ * a sibling engine of the same model on the same device in `dtype` with max_batch = min(64, the engine's), hands it the
+ * symmetry tables already set (kz_engine_set_symmetries reaches it afterwards) and zeroes the statistics; calling it again
+ * while on replaces the settings and zeroes them again.  It is not the range fallback's sibling: both may be on at once.
+ * Fails, with a message of its own each: dtype equal to the engine's own; KZ_DTYPE_F16 or any other value; KZ_DTYPE_F32_SPLIT16
+ * on a model for which kz_model_supports_dtype is 0; period < 1; boards < 1 or larger than the sibling's max_batch; a batch in
+ * flight on any slot.
+ * The engine counts the decoded submits with batch > 0 - plain, _sym and _avg, and the kz_engine_eval_* forms that go through
+ * them - from this call on; submits number 1, 1 + period, 1 + 2 * period ... are audited.  Of an audited batch the FIRST k
+ * boards are: k = min(boards, batch), for an averaged batch min(boards, batch, sibling max_batch / n_sym) (0: the batch is not
+ * audited and counts nowhere).  Right after the batch's own launch is enqueued those k boards go, from the slot's pinned input
+ * staging, to the sibling's slot of the same index through the matching entry (the same symmetry ids, or the averaged entry),
+ * and run there on the sibling's own stream beside the batch; a failing sibling submit fails the submit with its message (the
+ * slot is then free).  The call that returns the batch - after the per-board status and after the range fallback - waits for
+ * the sibling and compares on the host.  No result, status or verdict of any batch changes.  kz_engine_submit_packed,
+ * kz_engine_eval_dense and the device-resident entry points are outside the audit.
+ * A sampled board is compared only when its status is exactly KZ_BOARD_OK on both sides (after the fallback); every other one,
+ * a fell-back board included, adds 1 to `skipped`.  Per compared board, in batch order, for each of its five values and then
+ * for each of its probabilities in the caller's move order: d = fabsf(engine - sibling) in f32, max = fmaxf(max, d),
+ * sum_sq += (double)d * (double)d, accumulated sequentially; batches accumulate in the order they are returned.
+ * kz_engine_audit_stats copies the totals and, with reset != 0, zeroes them afterwards; it fails while the audit is off and
+ * while an audited batch is still in flight; `out` is a kz_audit_stats * (typed void for the bindings' sake, like the status
+ * outputs above).  With the audit off a decoded submit and a returning call pay one pointer test. */
+typedef struct kz_audit_stats {
+    int64_t batches;          /* audited batches that were returned */
+    int64_t boards;           /* boards compared */
+    int64_t moves;            /* probabilities compared */
+    int64_t skipped;          /* sampled boards left out: status != KZ_BOARD_OK on either side */
+    float   max_abs_value[5]; /* per decoded column: value, win, draw, loss, moves_left */
+    float   max_abs_prob;
+    double  sum_sq_value[5];
+    double  sum_sq_prob;
+} kz_audit_stats;
+int kz_engine_set_audit(kz_engine *engine, int dtype, int period, int boards);
+int kz_engine_audit_stats(kz_engine *engine, void *out, int reset);
+
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and
  * returns; kz_engine_synchronize waits. */

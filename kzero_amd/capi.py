@@ -41,6 +41,40 @@ class ModelInfo(C.Structure):
     ]
 
 
+class AuditStats(C.Structure):
+    """kz_audit_stats: what the shadow audit has accumulated (kz_engine_audit_stats)."""
+    _fields_ = [
+        ("batches", C.c_int64), ("boards", C.c_int64), ("moves", C.c_int64), ("skipped", C.c_int64),
+        ("max_abs_value", C.c_float * 5), ("max_abs_prob", C.c_float),
+        ("sum_sq_value", C.c_double * 5), ("sum_sq_prob", C.c_double),
+    ]
+
+
+class AuditResult:
+    """The eight fields of kz_audit_stats as Python numbers (the per-column ones as float32 / float64 arrays of 5: value, win,
+    draw, loss, moves_left), and the root mean squares derived from them."""
+
+    def __init__(self, raw: AuditStats):
+        self.batches, self.boards, self.moves, self.skipped = int(raw.batches), int(raw.boards), int(raw.moves), int(raw.skipped)
+        self.max_abs_value = np.array(raw.max_abs_value[:], np.float32)
+        self.max_abs_prob = np.float32(raw.max_abs_prob)
+        self.sum_sq_value = np.array(raw.sum_sq_value[:], np.float64)
+        self.sum_sq_prob = float(raw.sum_sq_prob)
+
+    @property
+    def rms_prob(self) -> float:
+        return float(np.sqrt(self.sum_sq_prob / self.moves)) if self.moves else 0.0
+
+    @property
+    def rms_value(self) -> np.ndarray:
+        return np.sqrt(self.sum_sq_value / self.boards) if self.boards else np.zeros(5)
+
+    def __repr__(self):
+        return (f"AuditResult(batches={self.batches}, boards={self.boards}, moves={self.moves}, skipped={self.skipped}, "
+                f"max_abs_value={self.max_abs_value.tolist()}, max_abs_prob={float(self.max_abs_prob)}, "
+                f"rms_value={self.rms_value.tolist()}, rms_prob={self.rms_prob})")
+
+
 # name -> (restype, argtypes); every symbol include/kz_hip.h declares
 SIGNATURES = {
     "kz_last_error": (C.c_char_p, []),
@@ -82,6 +116,8 @@ SIGNATURES = {
     "kz_engine_eval_packed_decoded_status": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kz_engine_set_range_fallback": (C.c_int, [C.c_void_p, C.c_int]),
+    "kz_engine_set_audit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "kz_engine_audit_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "kz_engine_enqueue_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                                   C.c_void_p, C.c_void_p]),
     "kz_engine_enqueue_dense_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -417,6 +453,17 @@ class Engine:
         """KZ_DTYPE_F32: the calls that return a batch re-evaluate its out-of-range boards in exact f32 inside the engine
         (kz_engine_set_range_fallback); -1: off (the default)."""
         check(load().kz_engine_set_range_fallback(self._h, dtype))
+
+    def set_audit(self, dtype: int, period: int = 1, boards: int = 16):
+        """KZ_DTYPE_F32 / KZ_DTYPE_F32_SPLIT16: the first `boards` boards of every `period`-th decoded submit also run on a
+        sibling engine of that dtype and the deviation is accumulated (kz_engine_set_audit); -1: off (the default)."""
+        check(load().kz_engine_set_audit(self._h, dtype, period, boards))
+
+    def audit_stats(self, reset: bool = False) -> AuditResult:
+        """What the audit has accumulated (kz_engine_audit_stats); reset: zero it afterwards."""
+        raw = AuditStats()
+        check(load().kz_engine_audit_stats(self._h, C.byref(raw), int(reset)))
+        return AuditResult(raw)
 
     def wait_view(self, slot: int, batch: int):
         """Zero-copy wait: arrays over the slot's pinned staging, valid until the next submit on that slot."""

@@ -350,6 +350,21 @@ class HipNetwork : public Network<B> {
         kz_check(kz_engine_set_range_fallback(engine_, on ? KZ_DTYPE_F32 : -1));
     }
 
+    // The shadow audit (kz_engine_set_audit: a second sibling engine, created here): the first `boards` boards of every
+    // `period`-th batch of the device decode also run in `dtype` — KZ_DTYPE_F32_SPLIT16 or KZ_DTYPE_F32 — beside the batch and
+    // the engine accumulates the deviation; no evaluation changes.  dtype -1 turns it off.  Off by default, like the Rust
+    // shim's switch for it.  The engine's own dtype, KZ_DTYPE_F16 and a sample larger than min(64, max_batch_size) are refused (throws).
+    void set_audit(int dtype, int period = 1, int boards = 16) {
+        if (in_flight_ != 0) throw std::logic_error("set_audit while batches are in flight");
+        kz_check(kz_engine_set_audit(engine_, dtype, period, boards));
+    }
+    // what the audit has accumulated so far (kz_engine_audit_stats); reset: zero it afterwards
+    kz_audit_stats audit_stats(bool reset = false) {
+        kz_audit_stats out;
+        kz_check(kz_engine_audit_stats(engine_, &out, reset ? 1 : 0));
+        return out;
+    }
+
     // `eval_random_symmetries` (symmetry.rs:18-68) inside the launch: every board of every batch is evaluated under a symmetry
     // drawn from `rng` — the ids RandomSymmetryNetwork<B, HipNetwork> would draw from the same rng — and the engine maps the
     // planes on the way in and the policy indices on the way out (kz_engine_set_symmetries).  This thread then does what it does

@@ -172,6 +172,10 @@ KZ_API int kz_model_get_info(const kz_model *model, kz_model_info *out) {
 KZ_API void kz_engine_destroy(kz_engine *e) {
     if (!e) return;
     kz_engine_destroy(e->fallback);  // (the range fallback's sibling engine)
+    if (e->audit) {  // (the audit's)
+        kz_engine_destroy(e->audit->sibling);
+        delete e->audit;
+    }
     (void)hipSetDevice(e->device);
     for (auto st : e->slot_stream)
         if (st) (void)hipStreamSynchronize(st);
@@ -487,6 +491,39 @@ static void board_status(kz_engine::Slot &s, int batch, bool decoded) {
     }
 }
 
+// `n` boards of a slot's pinned input staging, picked by index into one contiguous batch for a sibling's submit: bits, scalars
+// and — decoded — the CSR move lists, with the symmetry ids when `ids`.  The one gather of the range fallback and the audit.
+static void gather_boards(const kz_engine *e, const kz_engine::Slot &s, const int *boards, int n, bool decoded, bool ids, BoardGather &g) {
+    const Model &m = *e->model;
+    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8, ns = (size_t)std::max(m.n_scalar, 0);
+    g.bits.resize((size_t)n * bits_bytes);
+    g.sin.resize((size_t)n * ns);
+    g.sym.resize((size_t)n);
+    g.moff.assign(1, 0);
+    g.midx.clear();
+    for (int i = 0; i < n; i++) {
+        const int b = boards[i];
+        memcpy(g.bits.data() + (size_t)i * bits_bytes, s.h_bits + (size_t)b * bits_bytes, bits_bytes);
+        if (ns) memcpy(g.sin.data() + (size_t)i * ns, s.h_sin + (size_t)b * ns, ns * 4);
+        if (!decoded) continue;
+        if (ids) g.sym[i] = s.h_sym[b];
+        if (s.h_moff[b + 1] > s.h_moff[b]) g.midx.insert(g.midx.end(), s.h_midx + s.h_moff[b], s.h_midx + s.h_moff[b + 1]);
+        g.moff.push_back((int64_t)g.midx.size());
+    }
+    g.midx.push_back(0);  // (never read: a non-null pointer for an empty list)
+}
+
+// A gathered batch submitted to slot `slot` of sibling `f` through the entry that matches the slot's own submit: raw rows,
+// decoded with the same symmetry ids (or none), or averaged.
+static int submit_gathered(kz_engine *e, const kz_engine::Slot &s, kz_engine *f, int slot, int n, bool decoded, const BoardGather &g) {
+    const Model &m = *e->model;
+    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
+    if (!decoded) return kz_engine_submit_packed(f, slot, g.bits.data(), bits_bytes, g.sin.data(), n);
+    if (s.avg) return kz_engine_submit_packed_decoded_avg(f, slot, g.bits.data(), bits_bytes, g.sin.data(), n, g.moff.data(), g.midx.data());
+    return kz_engine_submit_packed_decoded_sym(f, slot, g.bits.data(), bits_bytes, g.sin.data(), n, s.with_sym ? g.sym.data() : nullptr,
+                                               g.moff.data(), g.midx.data());
+}
+
 // The boards of a finished slot that carry KZ_BOARD_NONFINITE, re-evaluated through the sibling engine's matching entry (raw
 // rows, decoded with the same symmetry ids, or averaged) from the slot's pinned input staging, in chunks of the sibling's
 // max_batch; its results go over those boards' rows and ranges of the slot's output staging and their status becomes
@@ -497,39 +534,17 @@ static int range_fallback(kz_engine *e, kz_engine::Slot &s, int batch, bool deco
     for (int b = 0; b < batch; b++)
         if (s.status[b] & KZ_BOARD_NONFINITE) bad.push_back(b);
     if (bad.empty()) return 0;
-    const Model &m = *e->model;
-    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8, ns = (size_t)std::max(m.n_scalar, 0), plen = (size_t)m.policy_len;
+    const size_t plen = (size_t)e->model->policy_len;
     const bool avg = decoded && s.avg;
     const size_t per = avg ? (size_t)(f->max_batch / std::max(e->n_sym, 1)) : (size_t)f->max_batch;
     if (per < 1) return 0;  // (more symmetries than the sibling holds boards: such an averaged batch keeps its verdict)
     kz_engine::Slot &fs = f->slots[0];
-    std::vector<uint8_t> bits, sym;
-    std::vector<float> sin;
-    std::vector<int64_t> moff;
-    std::vector<int32_t> midx;
+    BoardGather g;
     for (size_t lo = 0; lo < bad.size(); lo += per) {
         const int n = (int)std::min(per, bad.size() - lo);
-        bits.resize((size_t)n * bits_bytes);
-        sin.resize((size_t)n * ns);
-        sym.resize((size_t)n);
-        moff.assign(1, 0);
-        midx.clear();
-        for (int i = 0; i < n; i++) {
-            const int b = bad[lo + i];
-            memcpy(bits.data() + (size_t)i * bits_bytes, s.h_bits + (size_t)b * bits_bytes, bits_bytes);
-            if (ns) memcpy(sin.data() + (size_t)i * ns, s.h_sin + (size_t)b * ns, ns * 4);
-            if (!decoded) continue;
-            if (s.with_sym && !avg) sym[i] = s.h_sym[b];
-            if (s.h_moff[b + 1] > s.h_moff[b]) midx.insert(midx.end(), s.h_midx + s.h_moff[b], s.h_midx + s.h_moff[b + 1]);
-            moff.push_back((int64_t)midx.size());
-        }
-        midx.push_back(0);  // (never read: a non-null pointer for an empty list)
-        int rc;
-        if (!decoded) rc = kz_engine_submit_packed(f, 0, bits.data(), bits_bytes, sin.data(), n);
-        else if (avg) rc = kz_engine_submit_packed_decoded_avg(f, 0, bits.data(), bits_bytes, sin.data(), n, moff.data(), midx.data());
-        else rc = kz_engine_submit_packed_decoded_sym(f, 0, bits.data(), bits_bytes, sin.data(), n, s.with_sym ? sym.data() : nullptr,
-                                                      moff.data(), midx.data());
-        if (rc) return 1;
+        gather_boards(e, s, bad.data() + lo, n, decoded, s.with_sym && !avg, g);
+        if (submit_gathered(e, s, f, 0, n, decoded, g)) return 1;
+        const std::vector<int64_t> &moff = g.moff;
         // the sibling's slot is waited for here, not through its entries: its per-board verdict is what is wanted
         fs.batch = -1;
         fs.decoded = false;
@@ -551,6 +566,76 @@ static int range_fallback(kz_engine *e, kz_engine::Slot &s, int batch, bool deco
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The shadow audit (kz_engine_set_audit): a sample of the decoded batches, evaluated a second time by a sibling engine in a
+// <= 1e-4 arithmetic and compared on the host.  Nothing of the batch itself is touched.
+// ------------------------------------------------------------------------------------------------
+// The tail of every decoded submit while the audit is on, once the batch's own launches are enqueued and the slot is in
+// flight: counts the submit and, every period-th time, hands the first k boards of the slot's input staging to the sibling's
+// slot of the same index, where they run on the sibling's own stream beside the batch.  A failing sibling submit fails this
+// submit with the sibling's message, and the slot is free again.
+static int audit_submit(kz_engine *e, int slot) {
+    kz_engine::Audit &a = *e->audit;
+    kz_engine::Slot &s = e->slots[slot];
+    s.audit_k = 0;
+    if (a.submits++ % a.period) return 0;
+    int k = std::min(a.boards, s.batch);
+    if (s.avg) k = std::min(k, a.sibling->max_batch / std::max(e->n_sym, 1));
+    if (k < 1) return 0;
+    kz_engine::Slot &fs = a.sibling->slots[slot];
+    if (fs.batch >= 0) {  // (left behind by a returning call that failed before its comparison)
+        (void)hipEventSynchronize(fs.done);
+        fs.batch = -1;
+        fs.decoded = false;
+    }
+    std::vector<int> &first = a.first;
+    if ((int)first.size() < k)
+        for (int b = (int)first.size(); b < k; b++) first.push_back(b);
+    gather_boards(e, s, first.data(), k, true, s.with_sym && !s.avg, a.gather);
+    if (submit_gathered(e, s, a.sibling, slot, k, true, a.gather)) {
+        (void)hipEventSynchronize(s.done);
+        s.batch = -1;
+        s.decoded = false;
+        return 1;
+    }
+    s.audit_k = k;
+    return 0;
+}
+
+static void audit_accumulate(float engine, float sibling, float &max_abs, double &sum_sq) {
+    const float d = fabsf(engine - sibling);
+    max_abs = fmaxf(max_abs, d);
+    sum_sq += (double)d * (double)d;
+}
+
+// The returning call's half, after the status and the fallback: waits for the sibling's slot (its event, not its entries: the
+// per-board verdict is wanted), then compares the boards whose status is 0 on both sides, in batch order — the five values,
+// then the probabilities in the caller's move order.
+static int audit_compare(kz_engine *e, kz_engine::Slot &s) {
+    kz_engine::Audit &a = *e->audit;
+    const int k = s.audit_k;
+    s.audit_k = 0;
+    kz_engine::Slot &fs = a.sibling->slots[&s - e->slots];
+    fs.batch = -1;
+    fs.decoded = false;
+    HIP_TRY(hipEventSynchronize(fs.done));
+    board_status(fs, k, true);
+    kz_audit_stats &st = a.stats;
+    st.batches++;
+    for (int b = 0; b < k; b++) {
+        if (s.status[b] != KZ_BOARD_OK || fs.status[b] != KZ_BOARD_OK) {
+            st.skipped++;
+            continue;
+        }
+        st.boards++;
+        for (int c = 0; c < 5; c++) audit_accumulate(s.h_values[(size_t)b * 5 + c], fs.h_values[(size_t)b * 5 + c], st.max_abs_value[c], st.sum_sq_value[c]);
+        // (the first k boards: the sibling's ranges start where the batch's do)
+        for (int64_t i = s.h_moff[b]; i < s.h_moff[b + 1]; i++) audit_accumulate(s.h_probs[i], fs.h_probs[i], st.max_abs_prob, st.sum_sq_prob);
+        st.moves += s.h_moff[b + 1] - s.h_moff[b];
+    }
+    return 0;
+}
+
 // What every call that returns a batch does after the slot's event: the per-board status, the fallback where it is on, and —
 // judge = true, the entries without a status output — the verdict those entries have always given, with their messages.
 // Without a fell-back board the verdict is read from the per-batch words exactly as before; with one, from the boards' status
@@ -559,6 +644,7 @@ static int finish_batch(const char *name, kz_engine *e, kz_engine::Slot &s, int 
     const std::string fn = name;
     board_status(s, batch, decoded);
     if (e->fallback && range_fallback(e, s, batch, decoded)) return 1;
+    if (e->audit && decoded && s.audit_k && audit_compare(e, s)) return 1;
     if (!judge) return 0;
     const auto softmax_message = [&] {
         return fn + ": Softmax input sum must be strictly positive (or a move index is out of range" +
@@ -710,7 +796,7 @@ static int submit_decoded(const char *fn, kz_engine *e, int slot, const uint8_t 
         s.batch = batch;
         s.decoded = s.in_launch = true;
         s.moves = total;
-        return 0;
+        return e->audit ? audit_submit(e, slot) : 0;
     }
     // heads in launches of their own: the network leaves scalars and logits in device memory, the stand-alone decode kernel
     // reads the move lists from and writes values / probabilities / flags to the slot's pinned staging directly (every word
@@ -730,7 +816,7 @@ static int submit_decoded(const char *fn, kz_engine *e, int slot, const uint8_t 
     s.decoded = true;
     s.in_launch = false;
     s.moves = total;
-    return 0;
+    return e->audit ? audit_submit(e, slot) : 0;
 }
 
 KZ_API int kz_engine_submit_packed_decoded(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
@@ -854,7 +940,7 @@ static int submit_decoded_avg(const char *name, kz_engine *e, int slot, const ui
     s.decoded = true;
     s.in_launch = in_launch;
     s.moves = total;
-    return 0;
+    return e->audit ? audit_submit(e, slot) : 0;
 }
 
 KZ_API int kz_engine_submit_packed_decoded_avg(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
@@ -910,7 +996,8 @@ KZ_API int kz_engine_set_symmetries(kz_engine *e, int n_sym, const int32_t *squa
         e->n_sym = n_sym;
         e->h_square_src.assign(square_src, square_src + (size_t)n_sym * hw);
         e->h_policy_map.assign(policy_map, policy_map + (size_t)n_sym * plen);
-        if (e->fallback) return kz_engine_set_symmetries(e->fallback, n_sym, square_src, policy_map);  // (the range fallback's sibling)
+        if (e->fallback && kz_engine_set_symmetries(e->fallback, n_sym, square_src, policy_map)) return 1;  // (the range fallback's sibling)
+        if (e->audit && kz_engine_set_symmetries(e->audit->sibling, n_sym, square_src, policy_map)) return 1;  // (the audit's)
         return 0;
     });
 }
@@ -970,6 +1057,70 @@ KZ_API int kz_engine_set_range_fallback(kz_engine *e, int dtype) {
             return 1;
         }
         e->fallback = f;
+        return 0;
+    });
+}
+
+static_assert(sizeof(kz_audit_stats) == 104, "kz_audit_stats is part of the C ABI (capi.py and hip.rs mirror its layout)");
+
+KZ_API int kz_engine_set_audit(kz_engine *e, int dtype, int period, int boards) {
+    return guarded("kz_engine_set_audit", [&]() -> int {
+        const std::string fn = "kz_engine_set_audit";
+        if (!e) return fail(fn + ": null engine");
+        if (dtype != KZ_DTYPE_F32 && dtype != KZ_DTYPE_F32_SPLIT16 && dtype != -1)
+            return fail(fn + ": dtype must be KZ_DTYPE_F32 or KZ_DTYPE_F32_SPLIT16 (on: an arithmetic within 1e-4) or -1 (off), got " +
+                        std::to_string(dtype));
+        if (dtype == (e->split16() ? KZ_DTYPE_F32_SPLIT16 : e->dtype))
+            return fail(fn + ": this engine evaluates in that dtype already (an audit against its own arithmetic compares nothing)");
+        for (const auto &s : e->slots)
+            if (s.batch >= 0) return fail(fn + ": a batch is in flight (wait for every slot first)");
+        if (dtype == -1) {
+            if (e->audit) kz_engine_destroy(e->audit->sibling);
+            delete e->audit;
+            e->audit = nullptr;
+            return 0;
+        }
+        if (period < 1) return fail(fn + ": period " + std::to_string(period) + " must be at least 1");
+        const int sibling_batch = std::min(e->max_batch, 64);
+        if (boards < 1 || boards > sibling_batch)
+            return fail(fn + ": boards " + std::to_string(boards) + " must be in 1.." + std::to_string(sibling_batch) +
+                        " (the sibling engine's max_batch)");
+        const kz_model source(e->source_model);
+        if (dtype == KZ_DTYPE_F32_SPLIT16 && kz_model_supports_dtype(&source, dtype) != 1)
+            return fail(fn + ": this model has no KZ_DTYPE_F32_SPLIT16 kernels (kz_model_supports_dtype is 0): audit it against KZ_DTYPE_F32");
+        if (!e->audit || e->audit->dtype != dtype) {
+            // the sibling: same model and device, `dtype`, a small max_batch of its own; created before the old one goes
+            kz_engine *f = nullptr;
+            if (kz_engine_create(&source, e->device, sibling_batch, dtype, &f)) return 1;
+            if (e->n_sym && kz_engine_set_symmetries(f, e->n_sym, e->h_square_src.data(), e->h_policy_map.data())) {
+                kz_engine_destroy(f);
+                return 1;
+            }
+            if (!e->audit) e->audit = new kz_engine::Audit();
+            kz_engine_destroy(e->audit->sibling);
+            e->audit->sibling = f;
+            e->audit->dtype = dtype;
+        }
+        kz_engine::Audit &a = *e->audit;
+        a.period = period;
+        a.boards = boards;
+        a.submits = 0;
+        a.stats = kz_audit_stats{};
+        for (auto &s : e->slots) s.audit_k = 0;
+        return 0;
+    });
+}
+
+KZ_API int kz_engine_audit_stats(kz_engine *e, void *out, int reset) {
+    return guarded("kz_engine_audit_stats", [&]() -> int {
+        const std::string fn = "kz_engine_audit_stats";
+        if (!e) return fail(fn + ": null engine");
+        if (!out) return fail(fn + ": null output");
+        if (!e->audit) return fail(fn + ": the audit is off (call kz_engine_set_audit first)");
+        for (const auto &s : e->slots)
+            if (s.batch >= 0 && s.decoded && s.audit_k) return fail(fn + ": an audited batch is in flight (wait for it first)");
+        memcpy(out, &e->audit->stats, sizeof(kz_audit_stats));
+        if (reset) e->audit->stats = kz_audit_stats{};
         return 0;
     });
 }

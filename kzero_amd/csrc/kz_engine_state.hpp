@@ -92,6 +92,15 @@ std::shared_ptr<Model> effective_model(const kz_model *model, int dtype_in, int 
 }
 }  // namespace
 
+// Boards of a slot's pinned input staging picked out as one contiguous batch for a sibling engine's submit: bits, scalars,
+// symmetry ids and (decoded) the CSR move lists.  The range fallback gathers the flagged boards, the audit the sampled ones.
+struct BoardGather {
+    std::vector<uint8_t> bits, sym;
+    std::vector<float> sin;
+    std::vector<int64_t> moff;
+    std::vector<int32_t> midx;
+};
+
 struct kz_engine {
     std::shared_ptr<Model> model;
     std::shared_ptr<DeviceWeights> wts;
@@ -149,6 +158,7 @@ struct kz_engine {
         std::vector<uint8_t> status;  // [max_batch] KZ_BOARD_* of the batch last waited for (kz_engine_wait_decoded_status's view)
         uint8_t *h_sym = nullptr;  // [max_batch] symmetry ids of the batch (pinned, read by the launches; set_symmetries allocates it)
         bool with_sym = false;     // what is in flight was submitted with symmetry ids
+        int audit_k = 0;           // the first audit_k boards of what is in flight also run on the audit's sibling (same slot index)
         // every board under every symmetry (the `_avg` entries, kz_symmetry_avg.hip): the VIRTUAL batch in device memory —
         // what kz_sym_fan_out writes and the network reads, what the decode writes and kz_sym_average reads.  Allocated at
         // the slot's first averaged submit, for max_batch virtual boards; the two move arrays grow like move_cap
@@ -171,6 +181,19 @@ struct kz_engine {
     // (kz_engine.hip: range_fallback).  It has its own streams, slots and staging; only DeviceWeights' cache is shared.
     std::shared_ptr<Model> source_model;  // the model as loaded (`model` may be the widened one)
     kz_engine *fallback = nullptr;
+    // the shadow audit (kz_engine_set_audit): a SECOND sibling, in a <= 1e-4 arithmetic, that evaluates the first boards of every
+    // period-th decoded submit on its own stream beside the batch; the call that returns the batch compares the two on the host
+    // and accumulates the deviation (kz_engine.hip: audit_submit, audit_compare).  Null while the audit is off: the one test the
+    // decoded submits and finish_batch pay for it.
+    struct Audit {
+        kz_engine *sibling = nullptr;
+        int dtype = -1, period = 1, boards = 1;
+        int64_t submits = 0;  // decoded submits with batch > 0 since kz_engine_set_audit
+        kz_audit_stats stats{};
+        BoardGather gather;      // (kept between submits: no allocation per audited batch)
+        std::vector<int> first;  // 0, 1, 2 ...: the sampled boards' indices, as the gather takes them
+    };
+    Audit *audit = nullptr;
     // words in front of every range-check flag word the engine hands to a launch (a multiple of 4: the scalars stay 16-byte aligned)
     int front_words() const { return (max_batch + 3) / 4 * 4; }
     float *d_dense = nullptr, *h_dense = nullptr;

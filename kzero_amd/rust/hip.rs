@@ -70,6 +70,20 @@ pub struct KzPathPlan {
     pub reserved: [i32; 3],
 }
 
+/// What the shadow audit has accumulated (`kz_audit_stats`, include/kz_hip.h; 104 bytes)
+#[repr(C)]
+#[derive(Debug, Default, Copy, Clone)]
+pub struct KzAuditStats {
+    pub batches: i64,
+    pub boards: i64,
+    pub moves: i64,
+    pub skipped: i64,
+    pub max_abs_value: [f32; 5],
+    pub max_abs_prob: f32,
+    pub sum_sq_value: [f64; 5],
+    pub sum_sq_prob: f64,
+}
+
 pub const KZ_DTYPE_F32: c_int = 0;
 pub const KZ_DTYPE_F16: c_int = 1;
 /// f32 tensors and the same <= 1e-4 parity as KZ_DTYPE_F32, the tower's products as three f16 MFMAs on (hi, lo) pairs
@@ -120,6 +134,9 @@ extern "C" {
     fn kz_engine_wait_decoded_status(engine: *mut c_void, slot: c_int, values_out: *mut *const f32, probs_out: *mut *const f32, status_out: *mut *mut c_void) -> c_int;
     fn kz_engine_eval_packed_decoded_status(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, sym: *const u8, move_offsets: *const i64, move_indices: *const i32, values_out: *mut f32, probs_out: *mut f32, status_out: *mut c_void) -> c_int;
     fn kz_engine_set_range_fallback(engine: *mut c_void, dtype: c_int) -> c_int;
+    // the shadow audit: a sample of the decoded batches on a sibling engine of a <= 1e-4 dtype (out: a KzAuditStats, typed void in the header)
+    fn kz_engine_set_audit(engine: *mut c_void, dtype: c_int, period: c_int, boards: c_int) -> c_int;
+    fn kz_engine_audit_stats(engine: *mut c_void, out: *mut c_void, reset: c_int) -> c_int;
     // device-resident entry points and helpers (benchmarks and parity tests; the server does not need them)
     fn kz_engine_enqueue_packed_device(engine: *mut c_void, d_bits: *const c_void, bits_stride: usize, d_scalars_in: *const c_void, batch: c_int, d_scalars_out: *mut c_void, d_policy_out: *mut c_void) -> c_int;
     fn kz_engine_enqueue_dense_device(engine: *mut c_void, d_input_nchw: *const c_void, batch: c_int, d_scalars_out: *mut c_void, d_policy_out: *mut c_void) -> c_int;
@@ -277,6 +294,11 @@ pub struct HipNetwork<B: Board, M: BoardMapper<B>> {
     /// activations leave the f16 range are re-evaluated in exact f32 inside the engine (`kz_engine_set_range_fallback`)
     /// instead of panicking the executor; how many boards that has happened to so far
     pub fell_back_boards: u64,
+    /// `KZ_HIP_AUDIT=<period>[:<boards>[:f32|split16]]` (default off; read here, never by the library): the first `boards`
+    /// (default 16) boards of every `period`-th decoded batch also run on a sibling engine in a <= 1e-4 arithmetic (default
+    /// split16 where the model has it and the engine is not split16 itself, else f32) and the deviation is accumulated
+    /// (`kz_engine_set_audit`); `drop` prints the totals to stderr in one line, i.e. once per network generation
+    audit: bool,
     /// `KZ_HIP_PREP_THREADS` (default 0) + 1 ranges of a batch, each prepared by one thread (`prepare`)
     ranges: Vec<PrepRange>,
     ph: PhantomData<B>,
@@ -353,6 +375,31 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
             Ok("1") => if dtype != KZ_DTYPE_F32 { check(unsafe { kz_engine_set_range_fallback(engine, KZ_DTYPE_F32) }) },
             Ok(other) => panic!("KZ_HIP_RANGE_FALLBACK must be 0 or 1, got '{}'", other),
         }
+        let audit = match std::env::var("KZ_HIP_AUDIT") {
+            Err(_) => false,
+            Ok(v) => {
+                fn usage(v: &str) -> ! {
+                    panic!("KZ_HIP_AUDIT must be <period>[:<boards>[:f32|split16]], got '{}'", v)
+                }
+                let mut parts = v.split(':');
+                let period: c_int = parts.next().and_then(|p| p.trim().parse().ok()).unwrap_or_else(|| usage(&v));
+                let boards: c_int = parts.next().map_or(16, |b| b.trim().parse().unwrap_or_else(|_| usage(&v)));
+                let split16_fits = dtype != KZ_DTYPE_F32_SPLIT16 && unsafe { kz_model_supports_dtype(model.ptr, KZ_DTYPE_F32_SPLIT16) } == 1;
+                let against = match parts.next() {
+                    None => if split16_fits { KZ_DTYPE_F32_SPLIT16 } else { KZ_DTYPE_F32 },
+                    Some("f32") => KZ_DTYPE_F32,
+                    Some("split16") => KZ_DTYPE_F32_SPLIT16,
+                    Some(_) => usage(&v),
+                };
+                if parts.next().is_some() {
+                    usage(&v);
+                }
+                // (a sample larger than the sibling engine holds is the sibling's whole batch)
+                let boards = boards.min(max_batch_size.min(64) as c_int);
+                check(unsafe { kz_engine_set_audit(engine, against, period, boards) });
+                true
+            }
+        };
 
         HipNetwork {
             mapper,
@@ -377,6 +424,7 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
             sym_ids: vec![],
             average_symmetries: false,
             fell_back_boards: 0,
+            audit,
             ranges: {
                 // (a malformed value is not worth a panic in a constructor: no helpers, and say so once)
                 let helpers: usize = match std::env::var("KZ_HIP_PREP_THREADS") {
@@ -609,6 +657,18 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
 
 impl<B: Board, M: BoardMapper<B>> Drop for HipNetwork<B, M> {
     fn drop(&mut self) {
+        if self.audit {
+            // one line per network generation: what the sampled boards deviated by from the <= 1e-4 arithmetic
+            let mut st = KzAuditStats::default();
+            if unsafe { kz_engine_audit_stats(self.engine, &mut st as *mut KzAuditStats as *mut c_void, 0) } == 0 {
+                let rms = |sum_sq: f64, n: i64| if n > 0 { (sum_sq / n as f64).sqrt() } else { 0.0 };
+                eprintln!(
+                    "kz_hip audit: batches {} boards {} moves {} skipped {} | max|dp| {:.3e} rms dp {:.3e} | max|d| value {:.3e} wdl {:.3e} moves_left {:.3e}",
+                    st.batches, st.boards, st.moves, st.skipped, st.max_abs_prob, rms(st.sum_sq_prob, st.moves), st.max_abs_value[0],
+                    st.max_abs_value[1].max(st.max_abs_value[2]).max(st.max_abs_value[3]), st.max_abs_value[4]
+                );
+            }
+        }
         unsafe { kz_engine_destroy(self.engine) }
     }
 }
