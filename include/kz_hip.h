@@ -41,6 +41,22 @@ extern "C" {
                                   all-zero filters (same outputs).  kz_engine_create fails for the rest — a tower without
                                   blocks, more than 512 channels in no multiple of 64 — and kz_model_supports_dtype
                                   tells.  Everything outside the tower is the KZ_DTYPE_F32 path */
+#define KZ_DTYPE_BF16 3 /* f32 tensors at every boundary, like KZ_DTYPE_F32_SPLIT16 — the f32 engine with the tower's launch
+                           exchanged —, the tower in bf16: products bf16 x bf16 with f32 accumulation
+                           (v_mfma_f32_16x16x32_bf16, the rate of the f16 instruction), the residual stream and the mid
+                           activation stored as bf16 (round to nearest even), bias, ReLU, residual add and the final BN in
+                           f32.  RANGE: bf16 has f32's exponent, so a residual stream beyond +-65504 — every ResBlock adds a
+                           non-negative term that nothing re-normalises before the final BN — does NOT overflow here: no
+                           status to watch, no sibling engine; the non-finite check stays and can only fire on an f32
+                           overflow.  PRECISION: 8 significant bits where f16 has 11 (the contract: README, "which number is
+                           which arithmetic"; kz_engine_set_audit measures it on a network's own positions).  One launch
+                           per batch ("tower_resident_bf16g", "+heads" with the conv policy heads at 128 / 256 channels,
+                           their tail in exact f32) for the shapes of the plain-f16 one-launch tower: 64 .. 512 tower
+                           channels in a multiple of 64 (others widened, as above) on the small boards — 256 / 320
+                           channels on <= 96 squares, 384 / 512 on <= 64, 192 on <= 176, 128 on <= 208, 64 on <= 96.
+                           kz_engine_create fails, and kz_model_supports_dtype says 0, for Go 19x19 and any other shape
+                           that runs per layer, AttentionTower networks, DenseNetworks and a tower without blocks.
+                           Everything outside the tower is the KZ_DTYPE_F32 path */
 
 #define KZ_POLICY_ATAXX_CONV 0 /* AtaxxConvPolicyHead, python/lib/model/post_act.py:91-112 */
 #define KZ_POLICY_CONV 1       /* ConvPolicyHead,      post_act.py:54-88 */
@@ -259,6 +275,7 @@ int kz_engine_set_range_fallback(kz_engine *engine, int dtype);
  * a sibling engine of the same model on the same device in `dtype` with max_batch = min(64, the engine's), hands it the
  * symmetry tables already set (kz_engine_set_symmetries reaches it afterwards) and zeroes the statistics; calling it again
  * while on replaces the settings and zeroes them again.  It is not the range fallback's sibling: both may be on at once.
+ * (A KZ_DTYPE_BF16 engine takes either sibling.)
  * Fails, with a message of its own each: dtype equal to the engine's own; KZ_DTYPE_F16 or any other value; KZ_DTYPE_F32_SPLIT16
  * on a model for which kz_model_supports_dtype is 0; period < 1; boards < 1 or larger than the sibling's max_batch; a batch in
  * flight on any slot.
@@ -338,13 +355,14 @@ int kz_engine_kernel_time(kz_engine *engine, const char *prefix, double *total_m
  * (exact f32, other heads), "tower_resident_split16+heads" (KZ_DTYPE_F32_SPLIT16: the chess attention network at 256
  * channels and the conv-policy networks at 128 / 256 channels: encode, tower, scalar head and policy head in one launch),
  * "tower_resident_split16" (the other shapes of
- * KZ_DTYPE_F32_SPLIT16: tower launch + f32 head kernels).  One launch per layer:
+ * KZ_DTYPE_F32_SPLIT16: tower launch + f32 head kernels), "tower_resident_bf16g+heads" / "tower_resident_bf16g"
+ * (KZ_DTYPE_BF16: conv policy heads at 128 / 256 channels inside; else tower launch + f32 head kernels).  One launch per layer:
  * "board_conv_f16" (whole boards as LDS tiles, Go-size boards), "board_conv_split16" (the same per-layer kernel in split
  * arithmetic: KZ_DTYPE_F32_SPLIT16 on boards the one-launch split tower cannot hold), "conv_igemm_f16", "conv_igemm_f32".
  * Networks whose tower is the reference's AttentionTower (python/lib/model/attention.py:8-45) instead of the ResTower — one
  * launch for the tower: "attention_tower_f16" / "attention_tower_f32" (8x8 boards, 8 heads of d_k = d_v = 16, d_model 128 / 256:
  * f16 and exact f32 on the matrix cores), "attention_tower_f32_valu" (every other shape: exact f32 on the vector ALUs; an f16
- * engine reads and writes f16 rows around it).  KZ_DTYPE_F32_SPLIT16 has no AttentionTower kernel: kz_model_supports_dtype = 0.
+ * engine reads and writes f16 rows around it).  KZ_DTYPE_F32_SPLIT16 and KZ_DTYPE_BF16 have no AttentionTower kernel: kz_model_supports_dtype = 0.
  * "dense_network_f32": a DenseNetwork (python/lib/model/simple.py), the whole network in one launch, f32 arithmetic. */
 const char *kz_engine_tower_path(const kz_engine *engine);
 /* How the dominant launch of that path covers the chip for a batch of `batch` boards: workgroups per launch and boards

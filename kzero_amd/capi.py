@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("KZ_LIB_PATH") or os.path.join(_HERE, "libkzhip.so")
 KZ_DTYPE_F32 = 0
 KZ_DTYPE_F16 = 1
 KZ_DTYPE_F32_SPLIT16 = 2
+KZ_DTYPE_BF16 = 3  # f32 tensors, the tower in bf16 (f32 range at the f16 rate, 8 significant bits)
 KZ_ENGINE_SLOTS = 4
 # per-board status bits (kz_engine_wait_decoded_status / kz_engine_eval_packed_decoded_status)
 KZ_BOARD_OK = 0

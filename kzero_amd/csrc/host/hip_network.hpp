@@ -305,6 +305,8 @@ class HipNetwork : public Network<B> {
     // boards the range fallback has re-evaluated in exact f32 so far (set_range_fallback; the device decode's calls count them)
     uint64_t fell_back_boards = 0;
     // cudnn.rs:29-43 (check_graph_shapes: common.rs:165-198)
+    // dtype: KZ_DTYPE_F32 / KZ_DTYPE_F16 / KZ_DTYPE_F32_SPLIT16 / KZ_DTYPE_BF16 (f32 tensors like split16, the one-launch ResTower
+    // in bf16: f32's range, nothing for set_range_fallback to catch; kz_model_supports_dtype tells whether the model has it)
     HipNetwork(M mapper, std::shared_ptr<const HipModel> model, size_t max_batch_size, int device, int dtype)
         : mapper_(mapper), model_(std::move(model)), max_batch_size_(max_batch_size) {
         const kz_model_info &info = model_->info;
@@ -353,7 +355,7 @@ class HipNetwork : public Network<B> {
     // The shadow audit (kz_engine_set_audit: a second sibling engine, created here): the first `boards` boards of every
     // `period`-th batch of the device decode also run in `dtype` — KZ_DTYPE_F32_SPLIT16 or KZ_DTYPE_F32 — beside the batch and
     // the engine accumulates the deviation; no evaluation changes.  dtype -1 turns it off.  Off by default, like the Rust
-    // shim's switch for it.  The engine's own dtype, KZ_DTYPE_F16 and a sample larger than min(64, max_batch_size) are refused (throws).
+    // shim's switch for it.  (A KZ_DTYPE_BF16 network takes either.)  The engine's own dtype, KZ_DTYPE_F16 and a sample larger than min(64, max_batch_size) are refused (throws).
     void set_audit(int dtype, int period = 1, int boards = 16) {
         if (in_flight_ != 0) throw std::logic_error("set_audit while batches are in flight");
         kz_check(kz_engine_set_audit(engine_, dtype, period, boards));

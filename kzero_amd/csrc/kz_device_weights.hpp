@@ -242,7 +242,9 @@ struct DeviceWeights {
                 all.insert(all.end(), l.ff1.begin(), l.ff1.end());
             }
             if (upload_f32(m.att_expand, &att_expand) || upload_f32(m.att_embedding, &att_embedding) || upload_f32(all, &att_layers)) return 1;
-        } else if (p.tower == Tower::resident_split16 || p.tower == Tower::resident_f16g) {
+        } else if (p.tower == Tower::resident_split16 || p.tower == Tower::resident_f16g || p.tower == Tower::resident_bf16g) {
+            // (resident_bf16g: the plain stream with bf16 elements; its conv heads' small convolutions as for the f32 launch)
+            const bool bf16 = p.tower == Tower::resident_bf16g;
             // f16 fragments — (hi, lo) pairs for split16 — in fragment order: 9 * ceil(c_in / 32) stem k-steps, then 9*C/32 per convolution
             // (+ the attention heads' five passes and bias rows when the split launch carries the heads)
             const bool conv_heads = p.heads && m.policy_kind != kz::POLICY_ATTENTION;  // (Ataxx, Go 9x9)
@@ -252,17 +254,17 @@ struct DeviceWeights {
                                          (conv_heads ? kz::tower_split_conv_heads_weight_elems(C, split16) : 0));
             const size_t step_elems = (size_t)(split16 ? 2 : 1) * C * 32, stem_elems = kz::tower_split_stem_elems(C, m.c_in, split16),
                          layer_elems = (size_t)9 * (C / 32) * step_elems;
-            kz::tower_split_pack_weights(m.tower[0].w.data(), C, m.c_in, hw, true, split16, packed.data());
+            kz::tower_split_pack_weights(m.tower[0].w.data(), C, m.c_in, hw, true, split16, packed.data(), bf16);
             for (int l = 0; l < 2 * m.depth; l++)
                 kz::tower_split_pack_weights(m.tower[1 + l].w.data(), C, C, hw, false, split16,
-                                             packed.data() + stem_elems + layer_elems * l);
+                                             packed.data() + stem_elems + layer_elems * l, bf16);
             std::vector<float> bias((size_t)(1 + 2 * m.depth + (heads ? 5 : conv_heads ? 1 : 0)) * C);
             for (int l = 0; l < 1 + 2 * m.depth; l++)
                 for (int o = 0; o < C; o++) bias[(size_t)l * C + o] = m.tower[l].b[o];
             if (conv_heads) {  // the policy head's hidden layer as one more pass; the small convolutions as for the f32 launch
-                kz::tower_split_pack_conv_heads(m.p_conv0.w.data(), C, split16, packed.data() + tower_elems);
+                kz::tower_split_pack_conv_heads(m.p_conv0.w.data(), C, split16, packed.data() + tower_elems, bf16);
                 for (int o = 0; o < C; o++) bias[(size_t)(1 + 2 * m.depth) * C + o] = m.p_conv0.b[o];
-                if (!split16) {  // the plain-f16 launch runs the two small convolutions as f16 MFMAs
+                if (!split16 && !bf16) {  // the plain-f16 launch runs the two small convolutions as f16 MFMAs
                     std::vector<uint16_t> small(kz::tower_split_small_weight16_elems(C));
                     kz::tower_split_pack_small_weights16(m.sh_conv.w.data(), m.sh_conv.cout,
                                                          m.policy_extra_moves ? m.p_extra_conv.w.data() : nullptr,
@@ -448,7 +450,8 @@ struct DeviceWeights {
     }
 };
 
-// what build reads: engines with equal keys share one DeviceWeights.  (The exact-f32 stream carries the conv heads wherever
+// what build reads: engines with equal keys share one DeviceWeights.  (`tower` tells the bf16 stream from the f32 engine's
+// other streams of the same dtype field.)  (The exact-f32 stream carries the conv heads wherever
 // the kernel can run them, whether the launch does or not.)
 struct WeightsKey {
     const Model *model;

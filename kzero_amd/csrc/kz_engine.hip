@@ -193,6 +193,10 @@ KZ_API void kz_engine_destroy(kz_engine *e) {
     delete e;
 }
 
+static bool known_dtype(int dtype) {
+    return dtype == KZ_DTYPE_F32 || dtype == KZ_DTYPE_F16 || dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16;
+}
+
 KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, int dtype, kz_engine **out) {
     return guarded("kz_engine_create", [&]() -> int {
         if (!model || !out) return fail("kz_engine_create: null argument");
@@ -209,11 +213,10 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
         if (too_large((size_t)4 * std::max<size_t>((size_t)mm.h * mm.w * round_up(std::max(mm.channels, mm.c_in), 64),
                                                    (size_t)std::max(mm.policy_len, 1))))
             return 1;
-        if (dtype != KZ_DTYPE_F32 && dtype != KZ_DTYPE_F16 && dtype != KZ_DTYPE_F32_SPLIT16)
-            return fail("kz_engine_create: unknown dtype");
-        // KZ_DTYPE_F32_SPLIT16 is the f32 engine with one kernel exchanged: everything below sees KZ_DTYPE_F32
-        const bool split16 = dtype == KZ_DTYPE_F32_SPLIT16;
-        if (split16) dtype = KZ_DTYPE_F32;
+        if (!known_dtype(dtype)) return fail("kz_engine_create: unknown dtype");
+        // KZ_DTYPE_F32_SPLIT16 and bf16 are the f32 engine with one kernel exchanged: everything below sees KZ_DTYPE_F32
+        const int dtype_in = dtype;
+        if (dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16) dtype = KZ_DTYPE_F32;
         int ndev = 0;
         HIP_TRY(hipGetDeviceCount(&ndev));
         if (device < 0 || device >= ndev)
@@ -222,7 +225,7 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
         HIP_TRY(hipSetDevice(device));
 
         std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(new kz_engine(), kz_engine_destroy);
-        e->model = effective_model(model, split16 ? KZ_DTYPE_F32_SPLIT16 : dtype, max_batch);
+        e->model = effective_model(model, dtype_in, max_batch);
         e->source_model = model->m;
         e->out_channels = model->m->channels;
         const Model &m = *e->model;
@@ -234,7 +237,7 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
         e->cp = round_up(m.channels, 32);
         // which kernels run this network: plan_path (kz_plan.hpp) — the table of DESIGN.md §5 is printed from it
         std::string why;
-        if (!plan_path(m, max_batch, split16 ? KZ_DTYPE_F32_SPLIT16 : dtype, e->plan, why)) return fail("kz_engine_create: " + why);
+        if (!plan_path(m, max_batch, dtype_in, e->plan, why)) return fail("kz_engine_create: " + why);
         experiment_switches(m, dtype, e->cin_p, e->plan);
         const PathPlan &plan = e->plan;
         {
@@ -325,7 +328,7 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
 KZ_API int kz_model_supports_dtype(const kz_model *model, int dtype) {
     return guarded("kz_model_supports_dtype", [&]() -> int {
         if (!model) return -1;
-        if (dtype != KZ_DTYPE_F32 && dtype != KZ_DTYPE_F16 && dtype != KZ_DTYPE_F32_SPLIT16) return -1;
+        if (!known_dtype(dtype)) return -1;
         // (larger boards in split arithmetic run per layer: the engine additionally needs max_batch * h * w * channels * 4 bytes
         // < 2 GiB, asked here for one board)
         PathPlan plan;
@@ -338,7 +341,7 @@ KZ_API int kz_model_plan(const kz_model *model, int max_batch, int dtype, kz_pat
     return guarded("kz_model_plan", [&]() -> int {
         if (!model || !out) return fail("kz_model_plan: null argument");
         if (max_batch <= 0) return fail("kz_model_plan: max_batch must be positive");
-        if (dtype != KZ_DTYPE_F32 && dtype != KZ_DTYPE_F16 && dtype != KZ_DTYPE_F32_SPLIT16) return fail("kz_model_plan: unknown dtype");
+        if (!known_dtype(dtype)) return fail("kz_model_plan: unknown dtype");
         PathPlan plan;
         std::string why;
         if (!plan_path(*effective_model(model, dtype, max_batch), max_batch, dtype, plan, why)) return fail("kz_model_plan: " + why);
@@ -368,6 +371,7 @@ KZ_API int kz_engine_launch_geometry(const kz_engine *e, int batch, int *workgro
             case Tower::resident_f32: per = kz::tower32_boards_per_workgroup(m.h, m.w, m.channels); break;
             case Tower::resident_split16:
             case Tower::resident_f16g:  // (per launch: the widest level this batch fills the chip with)
+            case Tower::resident_bf16g:
                 per = kz::tower_split_boards_per_workgroup(m.h, m.w, m.channels, e->split16(), p.wide ? batch : 0);
                 break;
             case Tower::board_conv_f16:
@@ -1038,7 +1042,7 @@ KZ_API int kz_engine_set_range_fallback(kz_engine *e, int dtype) {
         const std::string fn = "kz_engine_set_range_fallback";
         if (!e) return fail(fn + ": null engine");
         if (dtype != KZ_DTYPE_F32 && dtype != -1) return fail(fn + ": dtype must be KZ_DTYPE_F32 (on) or -1 (off), got " + std::to_string(dtype));
-        if (e->dtype == KZ_DTYPE_F32 && !e->split16())
+        if (e->dtype == KZ_DTYPE_F32 && !e->split16() && !e->bf16())
             return fail(fn + ": this engine evaluates in KZ_DTYPE_F32 already (exact f32 has no f16 range to fall back from)");
         for (const auto &s : e->slots)
             if (s.batch >= 0) return fail(fn + ": a batch is in flight (wait for every slot first)");
@@ -1070,7 +1074,7 @@ KZ_API int kz_engine_set_audit(kz_engine *e, int dtype, int period, int boards) 
         if (dtype != KZ_DTYPE_F32 && dtype != KZ_DTYPE_F32_SPLIT16 && dtype != -1)
             return fail(fn + ": dtype must be KZ_DTYPE_F32 or KZ_DTYPE_F32_SPLIT16 (on: an arithmetic within 1e-4) or -1 (off), got " +
                         std::to_string(dtype));
-        if (dtype == (e->split16() ? KZ_DTYPE_F32_SPLIT16 : e->dtype))
+        if (dtype == e->public_dtype())
             return fail(fn + ": this engine evaluates in that dtype already (an audit against its own arithmetic compares nothing)");
         for (const auto &s : e->slots)
             if (s.batch >= 0) return fail(fn + ": a batch is in flight (wait for every slot first)");

@@ -114,7 +114,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         tower_out = 0;
         return 0;
     }
-    if (!per_layer(plan)) {  // resident_f32, resident_split16, resident_f16g
+    if (!per_layer(plan)) {  // resident_f32, resident_split16, resident_f16g, resident_bf16g
         kz::Tower32Args t{};
         t.x0 = (const float *)x_in; t.ldx0 = cin_p; t.c_in = m.c_in; t.weights = wts->res32_w; t.bias = wts->res_bias;
         t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
@@ -151,8 +151,9 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
 #endif
         t.wide = plan.wide;
         const bool f16g = plan.tower == Tower::resident_f16g;
-        if (launch(split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : "kz_tower_resident_f32", [&] {
+        if (launch(split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : "kz_tower_resident_f32", [&] {
                 if (split16()) kz::launch_tower_split(t, stream);
+                else if (bf16()) kz::launch_tower_bf16(t, stream);  // f32 tensors, like the split launch
                 else if (f16g) kz::launch_tower_pairs(t, false, stream);  // f16 tensors behind the same pointers
                 else kz::launch_tower32(t, stream);
             }))

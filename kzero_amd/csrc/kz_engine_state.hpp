@@ -123,6 +123,9 @@ struct kz_engine {
     std::vector<void *> allocs, pinned;
     PathPlan plan;  // which kernels run the network (plan_path, then the experiment build's switches)
     bool split16() const { return split_arithmetic(plan); }
+    bool bf16() const { return plan.tower == Tower::resident_bf16g; }
+    // the dtype kz_engine_create was given (`dtype` is KZ_DTYPE_F32 for the two f32 engines with an exchanged tower)
+    int public_dtype() const { return bf16() ? KZ_DTYPE_BF16 : split16() ? KZ_DTYPE_F32_SPLIT16 : dtype; }
     void *xres = nullptr;  // (experiment build, PathPlan::nb4: the four-board launch's residual scratch)
 
     // activations

@@ -397,7 +397,7 @@ int tower_split_boards_per_workgroup(int h, int w, int channels, bool split, int
 bool tower_split_wide_supported(int h, int w, int channels, int max_batch);
 size_t tower_split_stem_elems(int channels, int c_in, bool split);              // f16 elements of the 9 * ceil(c_in / 32) stem k-steps
 size_t tower_split_weight_elems(int channels, int depth, int c_in, bool split);  // f16 elements: stem + 2 * depth layers
-void tower_split_pack_weights(const float *oihw, int cout, int cin, int hw, bool stem, bool split, uint16_t *dst);
+void tower_split_pack_weights(const float *oihw, int cout, int cin, int hw, bool stem, bool split, uint16_t *dst, bool bf16 = false);
 void launch_tower_split(const Tower32Args &a, hipStream_t stream);
 // the chess attention network's heads inside that launch (a.heads.on; scalars and policy are then its only output)
 bool tower_split_heads_supported(int policy_kind, int query_channels, int policy_len, int h, int w, int channels, int sh_channels,
@@ -417,10 +417,15 @@ size_t tower_split_small_weight16_elems(int channels);  // f16 elements
 void tower_split_pack_small_weights16(const float *sh_w0, int hc, const float *pe_wc /* or null */, const float *p_w1, int pc,
                                       int channels, uint16_t *dst);
 size_t tower_split_conv_heads_weight_elems(int channels, bool split);
-void tower_split_pack_conv_heads(const float *w /* [C][C] */, int channels, bool split, uint16_t *dst);
+void tower_split_pack_conv_heads(const float *w /* [C][C] */, int channels, bool split, uint16_t *dst, bool bf16 = false);
 // the same launch without the lo halves (split = false): plain f16 arithmetic, x0 and y are f16 tensors behind the
 // float pointers of Tower32Args — the board-resident f16 tower for the shapes kz_tower.hip does not take
 void launch_tower_pairs(const Tower32Args &a, bool split, hipStream_t stream);
+// the plain launch on bf16 elements (kz_tower_bf16g.hip: bf16 x bf16 products, f32 accumulation; f32's exponent, 8 significant
+// bits): the shapes, tiles and wide tiles of launch_tower_pairs(t, false) (tower_split_supported / tower_split_wide_supported /
+// tower_split_conv_heads_supported with split = false) with the split launch's tensors — f32 x0 and y (or packed boards in) —,
+// `weights` = the split = false stream packed with bf16 = true, Heads::small_w = tower32_pack_small_weights (the tail is exact f32)
+void launch_tower_bf16(const Tower32Args &a, hipStream_t stream);
 
 // ---- 1x1 convolution in the same split arithmetic (the head convolutions behind the split tower), f32 in and out:
 // y[r][0..cout_p) = [relu](bias + W x[row(r)]), row(r) = (r / group) * src_group + src_off + r % group ----

@@ -18,12 +18,14 @@
 //   dtype f32split16:  a shape of kz_tower_split.hip (split)      -> tower_resident_split16 [+heads]
 //                      else channels % 64 == 0                    -> board_conv_split16      (one launch per layer)
 //                      else                                       -> refused (kz_model_supports_dtype says 0)
+//   dtype bf16 (3):    a shape of kz_tower_f16g.hip               -> tower_resident_bf16g [+heads: conv heads at 128 / 256]
+//                      else                                       -> refused
 // ------------------------------------------------------------------------------------------------
 //   AttentionTower (attention.py) instead of the ResTower:
 //     8x8, 8 heads of d_k = d_v = 16, d_model 128 / 256: dtype f16 -> attention_tower_f16, f32 -> attention_tower_f32 (the same
 //                                                       launch on v_mfma_f32_16x16x4_f32; d_ff <= 256)
 //     any other shape (f32, or f16 rows around f32 arithmetic)   -> attention_tower_f32_valu (one launch, vector ALUs)
-//     f32split16                                                 -> refused
+//     f32split16, bf16                                           -> refused
 //   DenseNetwork (simple.py: no tower, no heads), f32 / f16         -> dense_network_f32 (one launch, f32 arithmetic)
 
 // the kernel family that runs the tower (path_name: the name kz_model_plan / kz_engine_tower_path report)
@@ -35,6 +37,7 @@ enum class Tower {
     resident_f32,        // kz_tower_f32.hip: exact f32, one launch
     resident_split16,    // kz_tower_split.hip: split arithmetic, one launch
     resident_f16g,       // kz_tower_f16g.hip: the split kernel without its lo halves — plain f16, generic shapes
+    resident_bf16g,      // kz_tower_bf16g.hip: that plain kernel on bf16 elements, f32 tensors around it
     board_conv_f16,      // kz_board_conv.hip: one launch per layer, whole boards as LDS tiles
     board_conv_split16,  // the same per layer in split arithmetic (boards the one-launch split tower cannot hold)
     conv_igemm,          // kz_kernels.hip: one implicit GEMM per layer
@@ -66,7 +69,7 @@ bool per_layer(const PathPlan &p) {
 // the tower launch reads the packed boards itself (no encode launch in front of it)
 bool encodes_boards(const PathPlan &p) { return !per_layer(p) && p.tower != Tower::dense_net && p.tower != Tower::att_valu; }
 
-// dtype: KZ_DTYPE_F32 / KZ_DTYPE_F16 (/ KZ_DTYPE_F32_SPLIT16, whose towers are all split)
+// dtype: KZ_DTYPE_F32 / KZ_DTYPE_F16 (/ KZ_DTYPE_F32_SPLIT16, whose towers are all split; / bf16, whose tower is resident_bf16g)
 const char *path_name(const PathPlan &p, int dtype) {
     const bool f16 = dtype == KZ_DTYPE_F16;
     switch (p.tower) {
@@ -77,6 +80,7 @@ const char *path_name(const PathPlan &p, int dtype) {
         case Tower::resident_f32: return p.heads ? "tower_resident_f32+heads" : "tower_resident_f32";
         case Tower::resident_split16: return p.heads ? "tower_resident_split16+heads" : "tower_resident_split16";
         case Tower::resident_f16g: return p.heads ? "tower_resident_f16g+heads" : "tower_resident_f16g";
+        case Tower::resident_bf16g: return p.heads ? "tower_resident_bf16g+heads" : "tower_resident_bf16g";
         case Tower::board_conv_f16: return "board_conv_f16";
         case Tower::board_conv_split16: return "board_conv_split16";
         case Tower::conv_igemm: return f16 ? "conv_igemm_f16" : "conv_igemm_f32";
@@ -125,14 +129,19 @@ int head_launches(const Model &m, int dtype, const PathPlan &p, int cp) {
     return n;
 }
 
-// dtype_in: KZ_DTYPE_F32 / KZ_DTYPE_F16 / KZ_DTYPE_F32_SPLIT16.  false + why: kz_engine_create refuses.
+// dtype_in: KZ_DTYPE_F32 / KZ_DTYPE_F16 / KZ_DTYPE_F32_SPLIT16 / KZ_DTYPE_BF16.  false + why: kz_engine_create refuses.
+// (The messages say "bf16" or "dtype 3": the library's strings name no KZ_ identifier but the documented ones.)
 bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::string &why) {
-    const bool split16 = dtype_in == KZ_DTYPE_F32_SPLIT16;
-    const int dtype = split16 ? KZ_DTYPE_F32 : dtype_in;  // KZ_DTYPE_F32_SPLIT16 is the f32 engine with one kernel exchanged
+    const bool split16 = dtype_in == KZ_DTYPE_F32_SPLIT16, bf16 = dtype_in == KZ_DTYPE_BF16;
+    const int dtype = split16 || bf16 ? KZ_DTYPE_F32 : dtype_in;  // both are the f32 engine with the tower's launch exchanged
     const int cp = round_up(m.channels, 32);
     const bool force = env_on("KZ_FORCE_GENERIC"), nofuse = env_on("KZ_NO_FUSED_HEADS");
     p = PathPlan();
     if (m.tower_kind == kz::TOWER_DENSE_NET) {  // DenseNetwork (simple.py): the whole network is one launch behind the encode
+        if (bf16) {
+            why = "the bf16 arithmetic (dtype 3) has no DenseNetwork kernel: a network without a tower runs in f32 arithmetic (dtype f32, or f16 rows around it)";
+            return false;
+        }
         if (split16) {
             why = "KZ_DTYPE_F32_SPLIT16 has no DenseNetwork kernel: such a network runs in f32 arithmetic (KZ_DTYPE_F32, or KZ_DTYPE_F16 rows around it)";
             return false;
@@ -146,6 +155,10 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
         return true;
     }
     if (m.tower_kind == kz::TOWER_ATTENTION) {
+        if (bf16) {
+            why = "the bf16 arithmetic (dtype 3) has no attention-tower kernel: an AttentionTower network runs in exact f32 or in f16";
+            return false;
+        }
         if (split16) {
             why = "KZ_DTYPE_F32_SPLIT16 has no attention-tower kernel: an AttentionTower network runs as KZ_DTYPE_F32 (exact) or KZ_DTYPE_F16";
             return false;
@@ -169,7 +182,34 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
         // the per-layer activation taps of KZ_KEEP_ACTIVATIONS need a per-layer path (the one-launch split tower ignores
         // them, and KZ_FORCE_GENERIC too: DESIGN.md §5)
         p.keep = env_on("KZ_KEEP_ACTIVATIONS");
-        if (split16) {
+        if (bf16) {
+            // the one-launch tower of the plain-f16 family or nothing (like the one-launch split tower it ignores
+            // KZ_FORCE_GENERIC and KZ_KEEP_ACTIVATIONS); the heads, where not inside, are the f32 engine's
+            p.keep = false;
+            if (m.depth < 1) {
+                why = "the bf16 arithmetic (dtype 3) needs a tower with at least one residual block: without blocks there is no "
+                      "residual stream to keep in range, and the stem alone runs as exact f32";
+                return false;
+            }
+            if (!kz::tower_split_supported(m.h, m.w, m.channels, m.depth, m.c_in, false)) {
+                why = "the bf16 arithmetic (dtype 3) has the one-launch tower only: 64 to 512 tower channels in a multiple of 64 on a "
+                      "board that fits a workgroup's LDS (256 / 320 channels on at most 96 squares, 384 / 512 on at most 64, 192 on "
+                      "at most 176, 128 on at most 208, 64 on at most 96) with no more input planes than tower channels; a "
+                      "larger board (Go 19x19) runs per layer, which has no bf16 kernel";
+                return false;
+            }
+            p.tower = Tower::resident_bf16g;
+            const auto conv_heads = [&](int wide_batch) {
+                return !nofuse && kz::tower_split_conv_heads_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels, m.h,
+                                                                       m.w, m.channels, m.sh_conv.cout, m.sh_fc0.out, false, wide_batch);
+            };
+            p.wide = kz::tower_split_wide_supported(m.h, m.w, m.channels, max_batch);
+            p.heads = conv_heads(p.wide ? max_batch : 0);
+            if (p.wide && !p.heads && conv_heads(0)) {  // (as for resident_f16g below: one launch per batch before wide tiles)
+                p.wide = false;
+                p.heads = true;
+            }
+        } else if (split16) {
             if (kz::tower_split_supported(m.h, m.w, m.channels, m.depth, m.c_in, true)) {
                 p.tower = Tower::resident_split16;  // same tensors in and out as the exact-f32 resident launch
                 p.heads = !nofuse && (kz::tower_split_heads_supported((int)m.policy_kind, m.policy_query_channels, m.policy_len, m.h, m.w,

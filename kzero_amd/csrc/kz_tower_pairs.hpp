@@ -1,8 +1,9 @@
-// kz_tower_pairs.hpp — the device code of the one-launch tower on (hi, lo) f16 pairs and of its plain-f16 sibling: ONE template,
-// `kz_tower_resident_split<C, NT, SPLIT, HEADS>`, instantiated by two translation units so that each kernel family has a source
+// kz_tower_pairs.hpp — the device code of the one-launch tower on (hi, lo) f16 pairs and of its plain-f16 and bf16 siblings: ONE
+// template, `kz_tower_resident_split<C, NT, SPLIT, HEADS, BF>`, instantiated by three translation units so that each kernel family has a source
 // file of its own (bench.py hashes a kernel's sources to tell whether its committed HBM-traffic record still belongs to it):
 //   kz_tower_split.hip  SPLIT = true   "tower_resident_split16[+heads]"  (KZ_DTYPE_F32_SPLIT16)
 //   kz_tower_f16g.hip   SPLIT = false  "tower_resident_f16g[+heads]"      (KZ_DTYPE_F16 on the shapes kz_tower.hip does not take)
+//   kz_tower_bf16g.hip  BF = true      "tower_resident_bf16g[+heads]"     (KZ_DTYPE_BF16: the plain arithmetic on bf16 elements)
 // Host-side weight packing and the support predicates: kz_tower_pairs_pack.hip; instance selection: kz_tower_pairs_shapes.hpp.
 //
 // every weight is carried as a pair of f16 values (hi = f16(v), lo = f16(v - hi): 22 significant bits) and every product
@@ -22,9 +23,17 @@
 // tensors — i.e. the one-launch f16 tower for the shapes kz_tower.hip (chess: 8x8, 256 channels, fused heads) does not
 // cover: "tower_resident_f16g".
 //
+// BF = true is that plain launch with the element type exchanged — bf16 images, bf16 weight fragments,
+// v_mfma_f32_16x16x32_bf16 at the f16 instruction's rate, every f32 -> bf16 conversion rounding to nearest even
+// (v_cvt_pk_bf16_f32) — and the split launch's boundary: packed boards or f32 planes in, f32 rows out, the conv heads' tail
+// in exact f32.  bf16 has f32's exponent: a residual stream that leaves the f16 range (every block adds a non-negative term
+// that nothing re-normalises before the final BN) stays finite here, at 8 significant bits instead of 11.  Geo, the ring
+// depths, the two-plane images and the wide tiles are the plain-f16 instance's (an element is 2 bytes either way).
+//
 // Arithmetic follows python/lib/model/post_act.py:201-239 with Conv+BN folded on the host (kz_model.cpp).
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 #include "kz_kernels.hpp"
@@ -133,19 +142,36 @@ struct SplitDev {
     DecodeDev dec;  // dec.move_offsets set (fused heads only): decode_output inside the launch
 };
 
-__device__ __forceinline__ void split4(f32x4 v, h16x4 &hi, h16x4 &lo) {
+template <typename E, typename V4>
+__device__ __forceinline__ void split4(f32x4 v, V4 &hi, V4 &lo) {
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        hi[j] = (h16)v[j];
-        lo[j] = (h16)(v[j] - (float)hi[j]);
+        hi[j] = (E)v[j];
+        lo[j] = (E)(v[j] - (float)hi[j]);
     }
 }
 
+__device__ __forceinline__ void split4(f32x4 v, h16x4 &hi, h16x4 &lo) { split4<h16>(v, hi, lo); }  // (the f16-only callers)
+
+// one product of the tower: f16 or bf16 fragments (8 values of k per lane), f32 accumulators
+template <bool BF, typename V8>
+__device__ __forceinline__ f32x4 mfma_16x16x32(V8 a, V8 b, f32x4 c) {
+    if constexpr (BF) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+
 // HEADS: 0 = the tower alone; 1 = + the chess attention network's heads; 2 = + conv policy heads and the scalar head
-template <int C, int NT, bool SPLIT, int HEADS = 0>
+// BF: the plain arithmetic (SPLIT = false) on bf16 elements — the images, the weight fragments and the MFMA — with the split
+// launch's f32 tensors in and out
+template <int C, int NT, bool SPLIT, int HEADS = 0, bool BF = false>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
     static_assert(HEADS != 1 || (C == 256 && NT == 4 && SPLIT), "attention heads: the chess network in split arithmetic");
     static_assert(HEADS != 2 || C == 256 || C == 128, "conv heads: a channel count of kz_tower_f32.hip");
+    static_assert(!(BF && SPLIT), "bf16 is a plain arithmetic: one image per activation");
+    using E = std::conditional_t<BF, __bf16, h16>;  // the element of an image and of a weight fragment
+    using e16x8 = E __attribute__((ext_vector_type(8)));
+    using e16x4 = E __attribute__((ext_vector_type(4)));
+    constexpr bool F32_IO = SPLIT || BF;  // f32 tensors at the launch's boundary (else f16)
     using L = Geo<C, NT, SPLIT>;
     constexpr int PARTS = L::PARTS, PF = L::PF;
     constexpr int RS = L::RS, OT = L::OT, G = L::G, DELTA = L::DELTA, XH = L::XH, YH = L::YH, ZH = L::ZH;
@@ -177,11 +203,11 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
 #pragma unroll
             for (int ot = 0; ot < OT; ot++) wreg[s][part][ot] = wload(s < total_ksteps ? s : total_ksteps - 1, part, ot);
     int g = 0;
-    auto ring_take = [&](int stage, h16x8 (&ah)[OT], h16x8 (&al)[OT]) __attribute__((always_inline)) {
+    auto ring_take = [&](int stage, e16x8 (&ah)[OT], e16x8 (&al)[OT]) __attribute__((always_inline)) {
 #pragma unroll
         for (int ot = 0; ot < OT; ot++) {
-            ah[ot] = *reinterpret_cast<const h16x8 *>(&wreg[stage][0][ot]);
-            if constexpr (SPLIT) al[ot] = *reinterpret_cast<const h16x8 *>(&wreg[stage][PARTS - 1][ot]);
+            ah[ot] = *reinterpret_cast<const e16x8 *>(&wreg[stage][0][ot]);
+            if constexpr (SPLIT) al[ot] = *reinterpret_cast<const e16x8 *>(&wreg[stage][PARTS - 1][ot]);
         }
         const int gn = g + PF < total_ksteps ? g + PF : total_ksteps - 1;
 #pragma unroll
@@ -216,21 +242,21 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
 #pragma unroll
                 for (int j = 0; j < 4; j++) v[j] = encoded_plane(a.in, board0 + b, c4 * 4 + j, q, a.hw);
             }
-            h16x4 hi, lo;
-            split4(v, hi, lo);
-            *reinterpret_cast<h16x4 *>(lds + stem_h + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = hi;
-            if constexpr (SPLIT) *reinterpret_cast<h16x4 *>(lds + stem_l + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = lo;
-        } else if constexpr (SPLIT) {
+            e16x4 hi, lo;
+            split4<E>(v, hi, lo);
+            *reinterpret_cast<e16x4 *>(lds + stem_h + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = hi;
+            if constexpr (SPLIT) *reinterpret_cast<e16x4 *>(lds + stem_l + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = lo;
+        } else if constexpr (F32_IO) {
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
             if (have) v = *reinterpret_cast<const f32x4 *>(static_cast<const float *>(a.x0) + ((size_t)board0 * a.hw + row) * a.ldx0 + c4 * 4);
-            h16x4 hi, lo;
-            split4(v, hi, lo);
-            *reinterpret_cast<h16x4 *>(lds + stem_h + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = hi;
-            *reinterpret_cast<h16x4 *>(lds + stem_l + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = lo;
+            e16x4 hi, lo;
+            split4<E>(v, hi, lo);
+            *reinterpret_cast<e16x4 *>(lds + stem_h + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = hi;
+            if constexpr (SPLIT) *reinterpret_cast<e16x4 *>(lds + stem_l + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = lo;
         } else {
-            h16x4 v = h16x4{};
-            if (have) v = *reinterpret_cast<const h16x4 *>(static_cast<const h16 *>(a.x0) + ((size_t)board0 * a.hw + row) * a.ldx0 + c4 * 4);
-            *reinterpret_cast<h16x4 *>(lds + stem_h + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = v;
+            e16x4 v = e16x4{};
+            if (have) v = *reinterpret_cast<const e16x4 *>(static_cast<const h16 *>(a.x0) + ((size_t)board0 * a.hw + row) * a.ldx0 + c4 * 4);
+            *reinterpret_cast<e16x4 *>(lds + stem_h + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = v;
         }
     }
 
@@ -266,7 +292,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
     };
 
     // three MFMAs per (output tile, pixel tile): hi*hi + hi*lo + lo*hi
-    auto mfma3 = [&](const h16x8 (&ah)[OT], const h16x8 (&al)[OT], const h16x8 (&bh)[NT], const h16x8 (&bl)[NT])
+    auto mfma3 = [&](const e16x8 (&ah)[OT], const e16x8 (&al)[OT], const e16x8 (&bh)[NT], const e16x8 (&bl)[NT])
                      __attribute__((always_inline)) {
 #pragma unroll
         for (int nt = 0; nt < NT; nt++)
@@ -276,7 +302,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
                     acc[ot][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[ot], bh[nt], acc[ot][nt], 0, 0, 0);
                     acc[ot][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ot], bl[nt], acc[ot][nt], 0, 0, 0);
                 }
-                acc[ot][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ot], bh[nt], acc[ot][nt], 0, 0, 0);
+                acc[ot][nt] = mfma_16x16x32<BF>(ah[ot], bh[nt], acc[ot][nt]);
             }
     };
     auto ok_of = [&](int tap) __attribute__((always_inline)) {
@@ -293,22 +319,22 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
         const int tap = sc == 1 ? ks : ks / sc, chunk = ks - tap * sc;
         const int shift = (tap / 3 - 1) * a.w_ + (tap % 3 - 1);
         const unsigned ok = ok_of(tap);
-        h16x8 ah[OT], al[OT], bh[NT], bl[NT];
+        e16x8 ah[OT], al[OT], bh[NT], bl[NT];
 #pragma unroll
         for (int ot = 0; ot < OT; ot++) {
             const uint4 th = wp_stem[(size_t)ks * L::STEP + ot * 64];
-            ah[ot] = *reinterpret_cast<const h16x8 *>(&th);
+            ah[ot] = *reinterpret_cast<const e16x8 *>(&th);
             if constexpr (SPLIT) {
                 const uint4 tl = wp_stem[(size_t)ks * L::STEP + 4 * OT * 64 + ot * 64];
-                al[ot] = *reinterpret_cast<const h16x8 *>(&tl);
+                al[ot] = *reinterpret_cast<const e16x8 *>(&tl);
             }
         }
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) {
             const int off = stem_at(nt * 16 + fr + shift, chunk) + kq * 16;  // stem: natural k (channel = 32 chunk + 8 kq + j)
             const bool valid = (ok >> nt) & 1;
-            bh[nt] = valid ? *reinterpret_cast<const h16x8 *>(lds + stem_h + off) : h16x8{};
-            if constexpr (SPLIT) bl[nt] = valid ? *reinterpret_cast<const h16x8 *>(lds + stem_l + off) : h16x8{};
+            bh[nt] = valid ? *reinterpret_cast<const e16x8 *>(lds + stem_h + off) : e16x8{};
+            if constexpr (SPLIT) bl[nt] = valid ? *reinterpret_cast<const e16x8 *>(lds + stem_l + off) : e16x8{};
         }
         mfma3(ah, al, bh, bl);
     }
@@ -333,22 +359,22 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
                     for (int j = 0; j < 4; j++) v[j] = v[j] > 0.0f ? v[j] : 0.0f;
                 }
                 if (residual) {  // added in f32, AFTER the ReLU (post_act.py:227-228)
-                    const h16x4 rh = *reinterpret_cast<const h16x4 *>(lds + XH + off);
+                    const e16x4 rh = *reinterpret_cast<const e16x4 *>(lds + XH + off);
 #pragma unroll
                     for (int j = 0; j < 4; j++) v[j] += (float)rh[j];
                     if constexpr (SPLIT) {
-                        const h16x4 rl = *reinterpret_cast<const h16x4 *>(lds + XH + DELTA + off);
+                        const e16x4 rl = *reinterpret_cast<const e16x4 *>(lds + XH + DELTA + off);
 #pragma unroll
                         for (int j = 0; j < 4; j++) v[j] += (float)rl[j];
                     }
                 }
                 if constexpr (SPLIT) {
-                    h16x4 hi, lo;
-                    split4(v, hi, lo);
-                    *reinterpret_cast<h16x4 *>(lds + dst_h + off) = hi;
-                    *reinterpret_cast<h16x4 *>(lds + dst_h + DELTA + off) = lo;
+                    e16x4 hi, lo;
+                    split4<E>(v, hi, lo);
+                    *reinterpret_cast<e16x4 *>(lds + dst_h + off) = hi;
+                    *reinterpret_cast<e16x4 *>(lds + dst_h + DELTA + off) = lo;
                 } else {
-                    *reinterpret_cast<h16x4 *>(lds + dst_h + off) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                    *reinterpret_cast<e16x4 *>(lds + dst_h + off) = e16x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]};
                 }
             }
     };
@@ -371,9 +397,9 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
     };
     auto conv_3x3 = [&](int src_h) __attribute__((always_inline)) {
         int T[NT], Tn[NT];
-        h16x8 bh[2][NT], bl[2][NT];
+        e16x8 bh[2][NT], bl[2][NT];
         tap_rows(0, src_h, T);
-        auto rd = [&](int t, int extra) __attribute__((always_inline)) { return *reinterpret_cast<const h16x8 *>(lds + t + extra); };
+        auto rd = [&](int t, int extra) __attribute__((always_inline)) { return *reinterpret_cast<const e16x8 *>(lds + t + extra); };
 #pragma unroll
         for (int nt = 0; nt < NT; nt++) {
             bh[0][nt] = rd(T[nt], 0);
@@ -393,7 +419,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
                     bh[nxt][nt] = ch < G - 1 ? rd(T[nt], (ch + 1) * 16) : rd(Tn[nt], 0);
                     if constexpr (SPLIT) bl[nxt][nt] = ch < G - 1 ? rd(T[nt], DELTA + (ch + 1) * 16) : rd(Tn[nt], DELTA);
                 }
-                h16x8 ah[OT], al[OT];
+                e16x8 ah[OT], al[OT];
                 ring_take(stage, ah, al);
                 mfma3(ah, al, bh[cur], bl[cur]);
                 // every memory instruction in the shadow of an MFMA: the ring refills, the fragment reads, then the
@@ -442,31 +468,31 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
                     f32x4 v = acc[ot][nt];
 #pragma unroll
                     for (int j = 0; j < 4; j++) v[j] = v[j] > 0.0f ? v[j] : 0.0f;
-                    const h16x4 rh = *reinterpret_cast<const h16x4 *>(lds + XH + off);
+                    const e16x4 rh = *reinterpret_cast<const e16x4 *>(lds + XH + off);
 #pragma unroll
                     for (int j = 0; j < 4; j++) v[j] += (float)rh[j];
                     if constexpr (SPLIT) {
-                        const h16x4 rl = *reinterpret_cast<const h16x4 *>(lds + XH + DELTA + off);
+                        const e16x4 rl = *reinterpret_cast<const e16x4 *>(lds + XH + DELTA + off);
 #pragma unroll
                         for (int j = 0; j < 4; j++) v[j] += (float)rl[j];
                     }
                     v = v * ps + pt;
                     if constexpr (HEADS != 0) {  // the heads read the tower output from X (in place: this lane owns the slot)
                         if constexpr (SPLIT) {
-                            h16x4 hi, lo;
-                            split4(v, hi, lo);
-                            *reinterpret_cast<h16x4 *>(lds + XH + off) = hi;
-                            *reinterpret_cast<h16x4 *>(lds + XH + DELTA + off) = lo;
+                            e16x4 hi, lo;
+                            split4<E>(v, hi, lo);
+                            *reinterpret_cast<e16x4 *>(lds + XH + off) = hi;
+                            *reinterpret_cast<e16x4 *>(lds + XH + DELTA + off) = lo;
                         } else {
-                            *reinterpret_cast<h16x4 *>(lds + XH + off) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                            *reinterpret_cast<e16x4 *>(lds + XH + off) = e16x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]};
                         }
                         continue;
                     }
                     const int r = nt * 16 + fr;
                     const size_t o = ((size_t)board0 * a.hw + r) * a.ldy + oc;
                     if (r < rows_valid) {
-                        if constexpr (SPLIT) *reinterpret_cast<f32x4 *>(static_cast<float *>(a.y) + o) = v;
-                        else *reinterpret_cast<h16x4 *>(static_cast<h16 *>(a.y) + o) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                        if constexpr (F32_IO) *reinterpret_cast<f32x4 *>(static_cast<float *>(a.y) + o) = v;
+                        else *reinterpret_cast<e16x4 *>(static_cast<h16 *>(a.y) + o) = e16x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]};
                     }
                 }
             }
@@ -481,12 +507,12 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
         init_acc();
 #pragma unroll
         for (int ch = 0; ch < G; ch++) {
-            h16x8 ah[OT], al[OT], bh[NT], bl[NT];
+            e16x8 ah[OT], al[OT], bh[NT], bl[NT];
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) {
                 const int t = XH + frag_base + nt * 16 * RS + ch * 16;
-                bh[nt] = *reinterpret_cast<const h16x8 *>(lds + t);
-                if constexpr (SPLIT) bl[nt] = *reinterpret_cast<const h16x8 *>(lds + t + DELTA);
+                bh[nt] = *reinterpret_cast<const e16x8 *>(lds + t);
+                if constexpr (SPLIT) bl[nt] = *reinterpret_cast<const e16x8 *>(lds + t + DELTA);
             }
             ring_take(ch % PF, ah, al);
             mfma3(ah, al, bh, bl);
@@ -494,7 +520,59 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
         }
         epilogue(YH, true, false);
         __syncthreads();
-        if constexpr (!SPLIT) {
+        if constexpr (BF) {
+            // bf16: the tail is the exact-f32 one — kz_conv_heads.hpp's small convolutions on v_mfma_f32_16x16x4_f32 with the
+            // f32 fragments of tower32_pack_small_weights, in conv_heads_f32's order of accumulation — but the f32 copy of an
+            // image element is made in a register as it is read (a bf16 value is the upper half of its f32), not as a second
+            // pair of images: the launch keeps the plain-f16 instance's LDS footprint, so every tile count of that family
+            // (the wide tiles, one Go 13x13 board in eleven tiles) has its heads inside, with the tail's scratch behind the
+            // launch's own images like there.  Lane group kq of step gs takes channels 4 gs + {0, C/2, C/4, 3C/4}[kq] + q
+            // (C = 256: 4 gs + 64 kq + q), which is plane_of<C>(kq) / 4 of the f32 rows.
+            constexpr int TW = (NT + 3) / 4, G4 = C / 16;
+            const int kch = C == 256 ? 64 * kq : 64 * (kq & 1) + 32 * (kq >> 1);
+            const int koff4 = L::chan_off(kch * 2);  // (the four-channel pieces of a lane group stay inside one plane)
+            auto small_conv = [&](int which, auto emit) {
+                const int img = which ? YH : XH;
+                const f32x4 *wfrag = a.small_w + which * (G4 * 2 * 64);  // [G4][2][64]
+                f32x4 sa[2][TW];
+                int base[TW];
+#pragma unroll
+                for (int t = 0; t < TW; t++) {
+                    sa[0][t] = sa[1][t] = f32x4{0, 0, 0, 0};
+                    const int row = (wave + 4 * t) * 16 + fr;
+                    base[t] = img + (row < L::ROWS ? row : L::ROWS - 1) * RS + koff4;
+                }
+#pragma unroll
+                for (int gs = 0; gs < G4; gs++) {
+                    const f32x4 w0 = wfrag[(gs * 2 + 0) * 64 + lane], w1 = wfrag[(gs * 2 + 1) * 64 + lane];
+                    f32x4 bt[TW];
+#pragma unroll
+                    for (int t = 0; t < TW; t++) {
+                        const e16x4 b = *reinterpret_cast<const e16x4 *>(lds + base[t] + gs * 8);
+#pragma unroll
+                        for (int q = 0; q < 4; q++) bt[t][q] = (float)b[q];
+                    }
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+#pragma unroll
+                        for (int t = 0; t < TW; t++) {
+                            sa[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w0[q], bt[t][q], sa[0][t], 0, 0, 0);
+                            sa[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w1[q], bt[t][q], sa[1][t], 0, 0, 0);
+                        }
+                }
+#pragma unroll
+                for (int t = 0; t < TW; t++) {
+                    const int row = (wave + 4 * t) * 16 + fr;
+                    if (wave + 4 * t < NT && row < rows_valid) {
+#pragma unroll
+                        for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+                            for (int q = 0; q < 4; q++) emit(mt, q, row, sa[mt][t][q]);
+                    }
+                }
+            };
+            conv_heads_tail<C, NT>(a, lds, L::LDS_BYTES, board0, boards, rows_valid, small_conv, XH, L::IMG);
+        } else if constexpr (!SPLIT) {
             // Plain f16: the two small convolutions run as f16 MFMAs straight on the two f16 images (the tower's own fragment
             // reads: lane group kq's 16-byte piece of k-step g at kq_off + 16 g of the row; the weights packed to match),
             // row tiles split over the waves like in the f32 provider; the tail's scratch is F16_TAIL_SCRATCH_BYTES BEHIND the
@@ -514,10 +592,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
 #pragma unroll
                 for (int gs = 0; gs < G; gs++) {
                     const uint4 w0 = wfrag[(gs * 2 + 0) * 64 + lane], w1 = wfrag[(gs * 2 + 1) * 64 + lane];
-                    const h16x8 a0 = *reinterpret_cast<const h16x8 *>(&w0), a1 = *reinterpret_cast<const h16x8 *>(&w1);
+                    const e16x8 a0 = *reinterpret_cast<const e16x8 *>(&w0), a1 = *reinterpret_cast<const e16x8 *>(&w1);
 #pragma unroll
                     for (int t = 0; t < TW; t++) {
-                        const h16x8 b = *reinterpret_cast<const h16x8 *>(lds + base[t] + gs * 16);
+                        const e16x8 b = *reinterpret_cast<const e16x8 *>(lds + base[t] + gs * 16);
                         sa[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b, sa[0][t], 0, 0, 0);
                         sa[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b, sa[1][t], 0, 0, 0);
                     }
@@ -546,14 +624,14 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
                 const int id = tid + k * 256;
                 if (id < PIECES) {
                     const int r = id / (C / 4), p4 = id - r * (C / 4), off = r * RS + L::chan_off(p4 * 8);
-                    const h16x4 xh = *reinterpret_cast<const h16x4 *>(lds + XH + off), yh = *reinterpret_cast<const h16x4 *>(lds + YH + off);
+                    const e16x4 xh = *reinterpret_cast<const e16x4 *>(lds + XH + off), yh = *reinterpret_cast<const e16x4 *>(lds + YH + off);
 #pragma unroll
                     for (int j = 0; j < 4; j++) {
                         vx[k][j] = (float)xh[j];
                         vy[k][j] = (float)yh[j];
                     }
                     if constexpr (SPLIT) {
-                        const h16x4 xl = *reinterpret_cast<const h16x4 *>(lds + XH + DELTA + off), yl = *reinterpret_cast<const h16x4 *>(lds + YH + DELTA + off);
+                        const e16x4 xl = *reinterpret_cast<const e16x4 *>(lds + XH + DELTA + off), yl = *reinterpret_cast<const e16x4 *>(lds + YH + DELTA + off);
 #pragma unroll
                         for (int j = 0; j < 4; j++) {
                             vx[k][j] += (float)xl[j];
@@ -595,12 +673,12 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
             // centre tap only; `tiles` = 4: all 64 rows, 1: the tile of rows 48..63 (the far rank is rows 56..63)
 #pragma unroll
             for (int ch = 0; ch < G; ch++) {
-                h16x8 ah[OT], al[OT], bh[NT], bl[NT];
+                e16x8 ah[OT], al[OT], bh[NT], bl[NT];
 #pragma unroll
                 for (int nt = 0; nt < NT; nt++) {
                     const int t = src_h + frag_base + (tiles == 1 ? 3 : nt) * 16 * RS + ch * 16;
-                    bh[nt] = *reinterpret_cast<const h16x8 *>(lds + t);
-                    bl[nt] = *reinterpret_cast<const h16x8 *>(lds + t + DELTA);
+                    bh[nt] = *reinterpret_cast<const e16x8 *>(lds + t);
+                    bl[nt] = *reinterpret_cast<const e16x8 *>(lds + t + DELTA);
                 }
                 ring_take(ch % PF, ah, al);
                 if (tiles == 1) {
@@ -627,7 +705,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
             float sum = a.sh_b0[c4];
 #pragma unroll 4
             for (int i = 0; i < C; i += 8) {
-                const h16x8 xh = *reinterpret_cast<const h16x8 *>(row + i * 2), xl = *reinterpret_cast<const h16x8 *>(row + DELTA + i * 2);
+                const e16x8 xh = *reinterpret_cast<const e16x8 *>(row + i * 2), xl = *reinterpret_cast<const e16x8 *>(row + DELTA + i * 2);
                 const f32x4 w0 = *reinterpret_cast<const f32x4 *>(w + i), w1 = *reinterpret_cast<const f32x4 *>(w + i + 4);
 #pragma unroll
                 for (int j = 0; j < 4; j++)
@@ -663,11 +741,11 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
             if (fr >= 8) {
 #pragma unroll
                 for (int ot = 0; ot < OT; ot++) {
-                    h16x4 hi, lo;
-                    split4(acc[ot][0], hi, lo);
+                    e16x4 hi, lo;
+                    split4<E>(acc[ot][0], hi, lo);
                     const int off = UA + (fr - 8) * RS + ((wave * OT + ot) * 16 + kq * 4) * 2;
-                    *reinterpret_cast<h16x4 *>(lds + off) = hi;
-                    *reinterpret_cast<h16x4 *>(lds + off + UDELTA) = lo;
+                    *reinterpret_cast<e16x4 *>(lds + off) = hi;
+                    *reinterpret_cast<e16x4 *>(lds + off + UDELTA) = lo;
                 }
             }
             __syncthreads();
@@ -675,8 +753,8 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
             const int ua = UA + (fr & 7) * RS + kq_off, qf = YH + (wave * 16 + fr) * RS + kq_off;
 #pragma unroll
             for (int ch = 0; ch < G; ch++) {
-                const h16x8 uh = *reinterpret_cast<const h16x8 *>(lds + ua + ch * 16), ul = *reinterpret_cast<const h16x8 *>(lds + ua + UDELTA + ch * 16);
-                const h16x8 qh = *reinterpret_cast<const h16x8 *>(lds + qf + ch * 16), ql = *reinterpret_cast<const h16x8 *>(lds + qf + DELTA + ch * 16);
+                const e16x8 uh = *reinterpret_cast<const e16x8 *>(lds + ua + ch * 16), ul = *reinterpret_cast<const e16x8 *>(lds + ua + UDELTA + ch * 16);
+                const e16x8 qh = *reinterpret_cast<const e16x8 *>(lds + qf + ch * 16), ql = *reinterpret_cast<const e16x8 *>(lds + qf + DELTA + ch * 16);
                 l = __builtin_amdgcn_mfma_f32_16x16x32_f16(ul, qh, l, 0, 0, 0);
                 l = __builtin_amdgcn_mfma_f32_16x16x32_f16(uh, ql, l, 0, 0, 0);
                 l = __builtin_amdgcn_mfma_f32_16x16x32_f16(uh, qh, l, 0, 0, 0);
@@ -720,11 +798,11 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
             for (int jt = 0; jt < 4; jt++) la[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ch = 0; ch < G; ch++) {
-                const h16x8 qh = *reinterpret_cast<const h16x8 *>(lds + qf + ch * 16), ql = *reinterpret_cast<const h16x8 *>(lds + qf + DELTA + ch * 16);
+                const e16x8 qh = *reinterpret_cast<const e16x8 *>(lds + qf + ch * 16), ql = *reinterpret_cast<const e16x8 *>(lds + qf + DELTA + ch * 16);
 #pragma unroll
                 for (int jt = 0; jt < 4; jt++) {
                     const int tj = XH + (jt * 16 + fr) * RS + kq_off + ch * 16;
-                    const h16x8 th = *reinterpret_cast<const h16x8 *>(lds + tj), tl = *reinterpret_cast<const h16x8 *>(lds + tj + DELTA);
+                    const e16x8 th = *reinterpret_cast<const e16x8 *>(lds + tj), tl = *reinterpret_cast<const e16x8 *>(lds + tj + DELTA);
                     la[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(tl, qh, la[jt], 0, 0, 0);
                     la[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(th, ql, la[jt], 0, 0, 0);
                     la[jt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(th, qh, la[jt], 0, 0, 0);
@@ -774,7 +852,8 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
 #include "kz_tower_pairs_exp32.hpp"
 #endif
 
-template <int C, int NT, bool SPLIT, int HEADS = 0>
+// BF (with SPLIT = false): the bf16 instances — the plain-f16 instance's LDS, conv heads' tail scratch included
+template <int C, int NT, bool SPLIT, int HEADS = 0, bool BF = false>
 void launch(const SplitDev &d, int grid, hipStream_t stream) {
     // (the conv heads' tail: the split launch wants the two images as f32 rows; the plain-f16 launch the tail's scratch,
     // F16_TAIL_SCRATCH_BYTES, behind its own images)
@@ -782,13 +861,14 @@ void launch(const SplitDev &d, int grid, hipStream_t stream) {
     static_assert(OWN == pairs_own_lds_bytes(C, NT, SPLIT), "the host's restatement of the LDS geometry");
     constexpr int LDS = HEADS != 2 ? OWN : !SPLIT ? OWN + pairs_f16_tail_scratch_bytes(C, NT) : F32_IMAGES > OWN ? F32_IMAGES : OWN;
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    allow_dynamic_lds<kz_tower_resident_split<C, NT, SPLIT, HEADS>>(LDS);
-    kz_tower_resident_split<C, NT, SPLIT, HEADS><<<grid, 256, LDS, stream>>>(d);
+    allow_dynamic_lds<kz_tower_resident_split<C, NT, SPLIT, HEADS, BF>>(LDS);
+    kz_tower_resident_split<C, NT, SPLIT, HEADS, BF><<<grid, 256, LDS, stream>>>(d);
 }
 
 
 // The launch arguments of a Tower32Args: what both translation units fill in before they pick an instance.
-// nt: tiles of 16 pixel rows per workgroup of the instance to launch; grid: workgroups.
+// nt: tiles of 16 pixel rows per workgroup of the instance to launch; grid: workgroups.  (split = false: the plain
+// geometry — the plain-f16 launch and the bf16 one)
 inline SplitDev make_split_dev(const Tower32Args &t, bool split, int &nt, int &grid) {
     SplitDev d{};
     d.in = t.in;
@@ -825,7 +905,7 @@ inline SplitDev make_split_dev(const Tower32Args &t, bool split, int &nt, int &g
             d.hc = hd.hc; d.hs = hd.hs; d.pc = hd.pc; d.policy_len = hd.policy_len; d.zero_tail = hd.zero_tail; d.extra = hd.extra;
             d.sh_w1t = hd.sh_w1t; d.p_b1 = hd.p_b1; d.pe_bc = hd.pe_bc; d.pe_wl = hd.pe_wl; d.pe_bl = hd.pe_bl;
             d.small_w = reinterpret_cast<const f32x4 *>(hd.small_w);
-            d.small_w16 = reinterpret_cast<const uint4 *>(hd.small_w);  // (one pointer: f32 fragments for the split launch, f16 for the plain one)
+            d.small_w16 = reinterpret_cast<const uint4 *>(hd.small_w);  // (one pointer: f32 fragments for the split and bf16 launches, f16 for the plain one)
         }
     }
     return d;

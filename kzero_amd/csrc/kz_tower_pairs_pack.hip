@@ -1,4 +1,4 @@
-// kz_tower_pairs_pack.hip — host side of the one-launch (hi, lo) / plain-f16 towers (kz_tower_pairs.hpp): which shapes they
+// kz_tower_pairs_pack.hip — host side of the one-launch (hi, lo) / plain-f16 / bf16 towers (kz_tower_pairs.hpp): which shapes they
 // take, the weight streams in MFMA fragment order, the heads' weights.  No kernel in this file.
 #include <cstdlib>
 #include <vector>
@@ -9,6 +9,20 @@ namespace kz {
 
 namespace {
 #include "kz_tower_pairs_shapes.hpp"
+
+// One weight as the 16 bits of a fragment element: f16, or bf16 (round to nearest even, like the launch's own conversions;
+// model loading has refused NaN and inf, and a finite f32 beyond bf16's largest value rounds to inf as it does on the device)
+uint16_t element_bits(float v, bool bf16) {
+    if (bf16) {
+        uint32_t u;
+        __builtin_memcpy(&u, &v, 4);
+        return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+    }
+    const _Float16 h = (_Float16)v;
+    uint16_t b;
+    __builtin_memcpy(&b, &h, 2);
+    return b;
+}
 }  // namespace
 
 
@@ -46,13 +60,14 @@ size_t tower_split_weight_elems(int channels, int depth, int c_in, bool split) {
 // is W[oc = 16*(wave*C/64 + ot) + fr][channel][tap], channel = 8*chunk + {0, C/2, C/4, 3C/4}[kq] + j for a tower layer (one
 // k-step per tap and chunk of 32 channels) and 32*chunk + 8*kq + j for the stem (one k-step per tap and chunk of 32 padded
 // input channels).
-void tower_split_pack_weights(const float *oihw, int cout, int cin, int hw, bool stem, bool split, uint16_t *dst) {
+// bf16 (with split = false): the same stream with bf16 elements, for kz_tower_bf16g.hip
+void tower_split_pack_weights(const float *oihw, int cout, int cin, int hw, bool stem, bool split, uint16_t *dst, bool bf16) {
     const int kq_base[4] = {0, cout / 2, cout / 4, 3 * cout / 4};  // tower layers: cin == cout
     const int nchunk = stem ? (cin + 31) / 32 : cin / 32, ot_n = cout / 64;
     const size_t part = (size_t)cout * 32;  // f16 elements of the hi (or lo) half of a k-step
     (void)hw;
 #ifdef KZ_EXPERIMENTS
-    if (split_uses_32x32(cout, split_tiles_for(hw, cout, split), split)) {
+    if (!bf16 && split_uses_32x32(cout, split_tiles_for(hw, cout, split), split)) {  // (no bf16 instance of that variant)
         // kz_tower_resident_split32: [hi | lo][wave 4][f 4][lane 64][8]; fragment f = 2 o + half, lane (n, kg): output
         // channel 64 wave + 32 o + n, piece q = 2 half + kg of the k-step: channel 8 chunk + kq_base[q] + j (stem: 8 q + j)
         for (int tap = 0; tap < 9; tap++)
@@ -91,11 +106,15 @@ void tower_split_pack_weights(const float *oihw, int cout, int cin, int hw, bool
                             const int ch = stem ? 32 * chunk + 8 * kq + j : 8 * chunk + kq_base[kq] + j;
                             float v = 0.0f;
                             if (oc < cout && ch < cin) v = oihw[((size_t)oc * cin + ch) * 9 + tap];
+                            const size_t e = (((size_t)wave * ot_n + ot) * 64 + lane) * 8 + j;
+                            if (bf16) {
+                                step[e] = element_bits(v, true);
+                                continue;
+                            }
                             const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
                             uint16_t hb, lb;
                             __builtin_memcpy(&hb, &hi, 2);
                             __builtin_memcpy(&lb, &lo, 2);
-                            const size_t e = (((size_t)wave * ot_n + ot) * 64 + lane) * 8 + j;
                             step[e] = hb;
                             if (split) step[part + e] = lb;
                         }
@@ -176,7 +195,7 @@ size_t tower_split_conv_heads_weight_elems(int channels, bool split) { return (s
 
 // The policy head's first 1x1 convolution [C out][C in] as one pass of C/32 k-steps in the tower layers' (hi, lo) fragment
 // order (lane group kq takes channels 8 chunk + {0, C/2, C/4, 3C/4}[kq] + j)
-void tower_split_pack_conv_heads(const float *w, int channels, bool split, uint16_t *dst) {
+void tower_split_pack_conv_heads(const float *w, int channels, bool split, uint16_t *dst, bool bf16) {
     const int C = channels, ot_n = C / 64;
     const size_t part = (size_t)C * 32;
     for (int chunk = 0; chunk < C / 32; chunk++) {
@@ -189,11 +208,15 @@ void tower_split_pack_conv_heads(const float *w, int channels, bool split, uint1
                         const int oc = 16 * (wave * ot_n + ot) + (lane & 15);
                         const int ch = 8 * chunk + (C / 2) * (kq & 1) + (C / 4) * (kq >> 1) + j;
                         const float v = w[(size_t)oc * C + ch];
+                        const size_t e = (((size_t)wave * ot_n + ot) * 64 + lane) * 8 + j;
+                        if (bf16) {
+                            step[e] = element_bits(v, true);
+                            continue;
+                        }
                         const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
                         uint16_t hb, lb;
                         __builtin_memcpy(&hb, &hi, 2);
                         __builtin_memcpy(&lb, &lo, 2);
-                        const size_t e = (((size_t)wave * ot_n + ot) * 64 + lane) * 8 + j;
                         step[e] = hb;
                         if (split) step[part + e] = lb;
                     }

@@ -1,5 +1,6 @@
-// kz_tower_pairs_shapes.hpp — which instance of the one-launch (hi, lo) / plain-f16 tower (kz_tower_pairs.hpp) a shape
-// takes: host logic only, shared by the two kernel translation units (kz_tower_split.hip, kz_tower_f16g.hip) and the host-side
+// kz_tower_pairs_shapes.hpp — which instance of the one-launch (hi, lo) / plain-f16 / bf16 tower (kz_tower_pairs.hpp) a shape
+// takes: host logic only, shared by the three kernel translation units (kz_tower_split.hip, kz_tower_f16g.hip and
+// kz_tower_bf16g.hip, which takes the plain-f16 family's answers: split = false) and the host-side
 // packing and support predicates (kz_tower_pairs_pack.hip).  Included INSIDE `namespace kz { namespace {`.
 #pragma once
 

@@ -88,6 +88,7 @@ pub const KZ_DTYPE_F32: c_int = 0;
 pub const KZ_DTYPE_F16: c_int = 1;
 /// f32 tensors and the same <= 1e-4 parity as KZ_DTYPE_F32, the tower's products as three f16 MFMAs on (hi, lo) pairs
 pub const KZ_DTYPE_F32_SPLIT16: c_int = 2;
+pub const KZ_DTYPE_BF16: i32 = 3;
 pub const KZ_ENGINE_SLOTS: usize = 4;
 /// Per-board status bits of `kz_engine_wait_decoded_status` / `kz_engine_eval_packed_decoded_status` (include/kz_hip.h)
 pub const KZ_BOARD_OK: u8 = 0;
@@ -192,12 +193,14 @@ impl HipDevice {
 /// `HipSpecialization`).  The reference's executor is f32 only (`DTensor::F32`, cudnn.rs:73) and the stated parity is
 /// 1e-4, so the DEFAULT is the fastest path that keeps it: `KZ_DTYPE_F32_SPLIT16` where the network's shape allows,
 /// else `KZ_DTYPE_F32`.  `f16` (3 x faster again, tolerance 5e-3 of the output scale, range +-65504 with overflow
-/// reported as an error) is opt-in.
+/// reported as an error) is opt-in, and so is `bf16` (`KZ_DTYPE_BF16`: the f16 rate with f32's range — no overflow to
+/// report — at 8 significant bits; the one-launch ResTower shapes only, anything else fails at engine creation).
 #[derive(Debug, Copy, Clone, Eq, PartialEq)]
 pub enum HipDtype {
     Parity,
     F32,
     F16,
+    Bf16,
 }
 
 impl HipDtype {
@@ -206,13 +209,15 @@ impl HipDtype {
             Err(_) | Ok("parity") | Ok("f32split16") => HipDtype::Parity,
             Ok("f32") => HipDtype::F32,
             Ok("f16") => HipDtype::F16,
-            Ok(other) => panic!("KZ_HIP_DTYPE must be parity, f32 or f16, got '{}'", other),
+            Ok("bf16") => HipDtype::Bf16,
+            Ok(other) => panic!("KZ_HIP_DTYPE must be parity, f32, f16 or bf16, got '{}'", other),
         }
     }
     fn resolve(self, model: &HipModel) -> c_int {
         match self {
             HipDtype::F32 => KZ_DTYPE_F32,
             HipDtype::F16 => KZ_DTYPE_F16,
+            HipDtype::Bf16 => KZ_DTYPE_BF16,
             HipDtype::Parity => {
                 if unsafe { kz_model_supports_dtype(model.ptr, KZ_DTYPE_F32_SPLIT16) } == 1 {
                     KZ_DTYPE_F32_SPLIT16

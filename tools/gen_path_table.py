@@ -12,10 +12,15 @@ build container.  It writes tests/golden/path_table.json:
              entries once ("values"), and per case one character per entry, an index into them, in the order
              dtype, max_batch, switch set (the innermost)
 
+tests/golden/path_table_bf16.json (--bf16) is the same column for the bf16 arithmetic (KZ_DTYPE_BF16), in a file of its own so
+that the table above keeps its shape: {"max_batch": [...], "cases": {sweep case id: ["path launches" | "refused", ...]}},
+no switch sets (KZ_NO_FUSED_HEADS is the only switch that arithmetic reads); tests/test_bf16_plan.py recomputes it.
+
 tests/test_path_table.py recomputes both from the built library and fails on any difference: a change of a support
 predicate has to come with a regenerated table (python tools/gen_path_table.py) and shows up in the diff.
 
     python tools/gen_path_table.py            # rewrite the JSON
+    python tools/gen_path_table.py --bf16     # rewrite tests/golden/path_table_bf16.json
     python tools/gen_path_table.py --md       # print the DESIGN table (with measured rates from a sweep record, if given:
                                               #   --rates profiles/r4/shape_sweep.json)
 """
@@ -31,6 +36,7 @@ from kzero_amd import capi, synth  # noqa: E402
 from tests import sweep_cases  # noqa: E402
 
 OUT = os.path.join(REPO, "tests", "golden", "path_table.json")
+OUT_BF16 = os.path.join(REPO, "tests", "golden", "path_table_bf16.json")
 MAX_BATCH = 256
 DTYPES = {"f32": capi.KZ_DTYPE_F32, "f16": capi.KZ_DTYPE_F16, "f32split16": capi.KZ_DTYPE_F32_SPLIT16}
 SWITCH_BATCHES = (1, 8, 256, 2048)
@@ -100,6 +106,22 @@ def switches():
             "values": values, "cases": cases}
 
 
+def build_bf16():
+    """The bf16 column: every sweep case x max_batch (SWITCH_BATCHES) -> "path launches", or "refused"."""
+    cases = {}
+    for case in sweep_cases.CASES:
+        model = capi.Model(blob=synth.random_model(case.game, case.depth, case.channels, case.head, seed=11, **case.kw))
+        row = []
+        for mb in SWITCH_BATCHES:
+            try:
+                row.append("%s %d" % model.plan(mb, capi.KZ_DTYPE_BF16))
+            except capi.KzError:
+                row.append("refused")
+        assert (row[0] != "refused") == model.supports_dtype(capi.KZ_DTYPE_BF16), case.id
+        cases[case.id] = row
+    return {"max_batch": list(SWITCH_BATCHES), "cases": cases}
+
+
 def markdown(table, rates, games=None):
     by = {}
     for r in rates:
@@ -125,8 +147,12 @@ if __name__ == "__main__":
     ap.add_argument("--md", action="store_true")
     ap.add_argument("--rates", default=None)
     ap.add_argument("--games", default=None, help="comma-separated subset of the lattice's games for --md")
+    ap.add_argument("--bf16", action="store_true", help="write the bf16 column (tests/golden/path_table_bf16.json)")
     args = ap.parse_args()
-    if args.md:
+    if args.bf16:
+        json.dump(build_bf16(), open(OUT_BF16, "w"), indent=1, sort_keys=True)
+        print("wrote", OUT_BF16)
+    elif args.md:
         rates = json.load(open(args.rates))["rows"] if args.rates else []
         markdown(json.load(open(OUT)), rates, args.games.split(",") if args.games else None)
     else:
