@@ -23,6 +23,18 @@ same draws: `_widen`) has weights, scalar planes and activations that need a (hi
 
 `sums` as above with the step of the wide values.  The report also says where the lo halves are (`lo_in`, `lo_w`):
 tests/test_exact_nets.py holds that every layer meets them in its input and in every weight fragment.
+
+The rounding family (`draw_rounding` / `build_round`, `rounding=` of `reference`) is for a launch that rounds on purpose: the
+bf16 tower keeps its images and weights in 8 significant bits.  Its values do NOT fit the stored format, and the reference
+rounds where the launch rounds (`bf16_sites`, read off kz_tower_pairs.hpp), by `bf16_rne`.  What a site rounds is one f32
+value, the same in any summation order, so the result is still a matter of bits.  In place of `stored`:
+
+  rounded:  every value in front of a rounding and every stored tensor is finite and exact in f32 (the launch forms it in
+            f32: accumulator, ReLU, residual add, final BN), and the outputs are exact in f32;
+
+`sums` as above, with the steps of the rounded operands.  The report counts, per site, the ties that go down, the ties that
+go up and the values that are no tie: tests/test_round_nets.py holds floors on them and shows that references which round
+otherwise, elsewhere, once more or once less return other outputs.
 """
 import numpy as np
 
@@ -297,8 +309,9 @@ def split_exact(v):
 
 
 class _Report:
-    def __init__(self, measure=True):
+    def __init__(self, measure=True, light=False):
         self.measure = measure
+        self.light = light  # the rounding family: sums, f32 exactness and the rounding counts; nothing of the f16 / split16 conditions
         self.stored = {}  # name -> (max |v| / step, round-trips through f16)
         self.sums = {}    # name -> max sum |a b| / step
         # what the wide family adds (narrow networks hold all of it trivially, every lo being zero)
@@ -306,9 +319,23 @@ class _Report:
         self.lolo = {}    # product -> (one operand has no lo half, hi*hi + hi*lo + lo*hi == the plain result)
         self.lo_in = {}   # layer -> (share of its input's entries with a lo half, every 32-channel chunk has one)
         self.lo_w = {}    # layer -> [tile, chunk, tap] bool: that weight fragment (16 rows, tap, 32 input channels) holds a lo half
+        # what the rounding family adds (`rounding=` of `reference`)
+        self.ties = {}    # rounding site (a stored tensor, or a layer: its weights) -> (ties rounded down, ties rounded up, non-ties) by bf16_rne
+        self.f32 = {}     # stored tensor, and "<site>.before" for what a site rounds -> finite and exact in f32
+        self.values = {}  # every tensor a site could round (a stored tensor, a layer's weights) -> what was carried on
+
+    def count(self, name, v):
+        """A rounding site's input by what round-to-nearest-even to bf16 does to it (magnitudes: down is towards zero)."""
+        self.f32[name + ".before"] = f32_exact(v)
+        lo, frac, _ = _bf16_parts(v)
+        tie = frac == 0.5
+        self.ties[name] = (int((tie & (lo % 2 == 0)).sum()), int((tie & (lo % 2 == 1)).sum()), int(((frac != 0) & ~tie).sum()))
 
     def store(self, name, v):
         if not self.measure:
+            return
+        self.f32[name] = f32_exact(v)
+        if self.light:
             return
         ok = bool(np.array_equal(v.astype(np.float16).astype(np.float64), v))
         self.stored[name] = (float(np.abs(v).max() / step_of(v)), ok)
@@ -343,25 +370,26 @@ def _edge(hh, ww):
     return m
 
 
-def _lin(x, w, spoil=None):
+def _lin(x, w, spoil=None, mags=True):
     """w applied to x without the bias (3x3 same-padded: nine shifted einsums on a zero-padded image; 1x1; any odd k; 2-D
     w: linear), and the same on the magnitudes.  spoil = (dy, dx): what a wrong lo address of the input does — on that tap
-    the board's edge squares read x without its lo halves."""
+    the board's edge squares read x without its lo halves.  mags=False: the magnitudes are not wanted (None)."""
     if w.ndim == 2:
-        return x @ w.T, np.abs(x) @ np.abs(w).T
+        return x @ w.T, np.abs(x) @ np.abs(w).T if mags else None
     k = w.shape[2]
     pad = k // 2
     hh, ww = x.shape[2], x.shape[3]
     xp = np.pad(x, ((0, 0), (0, 0), (pad, pad), (pad, pad)))
     y = np.zeros((x.shape[0], w.shape[0], hh, ww))
-    mag = np.zeros_like(y)
+    mag = np.zeros_like(y) if mags else None
     for dy in range(k):
         for dx in range(k):
             win = xp[:, :, dy:dy + hh, dx:dx + ww]
             if spoil == (dy, dx):
                 win = np.where(_edge(hh, ww), split16(win)[0], win)
             y += np.einsum("oc,bchw->bohw", w[:, :, dy, dx], win, optimize=True)
-            mag += np.einsum("oc,bchw->bohw", np.abs(w[:, :, dy, dx]), np.abs(win), optimize=True)
+            if mags:
+                mag += np.einsum("oc,bchw->bohw", np.abs(w[:, :, dy, dx]), np.abs(win), optimize=True)
     return y, mag
 
 
@@ -375,12 +403,14 @@ def _conv(rep, name, x, w, b, spoil=None):
         w = w.copy()
         part = w[16 * tile:16 * tile + 16, 32 * chunk:32 * chunk + 32, dy, dx]
         part[...] = split16(part)[0]
-    y, mag = _lin(x, w, spoil.get("tap"))
+    y, mag = _lin(x, w, spoil.get("tap"), mags=rep.measure)
     shape = (1, -1) + (1,) * (y.ndim - 2)
     y = y + b.reshape(shape)
     if not rep.measure:
         return y
     rep.acc(name, mag + np.abs(b).reshape(shape), min(step_of(w) * step_of(x), step_of(b)))
+    if rep.light:
+        return y
     ok, any_lo = split_exact(w)
     rep.split[name + ".weight"] = (ok, not any_lo or step_of(w) >= LO_MIN)
     (xh, xl), (wh, wl) = split16(x), split16(w)
@@ -401,14 +431,33 @@ def _bn(t, p, x, eps):
     return y
 
 
-def reference(t, meta, x, revive=False, spoil=None, exact=True):
+def reference(t, meta, x, revive=False, spoil=None, exact=True, rounding=None):
     """(scalars [B, 5], policy [B, P], report) in float64; x [B, C_in, H, W].  report.acts holds the tower's and the scalar
     head's intermediates under the oracle's trace names.  revive (the generator's pass): t is changed in place — the bias
     in front of a ReLU is raised by whole units wherever the channel would be positive on too few positions.
     spoil = {"layer": name, "tap": (dy, dx)} or {"layer": name, "fragment": (tile, (dy, dx), chunk)}: one wrong lo address
-    (`_conv`).  exact=False: any network (random weights), nothing measured or asserted."""
-    rep = _Report(measure=exact)
+    (`_conv`).  exact=False: any network (random weights), nothing measured or asserted.
+    rounding = (sites, fn): what a launch that rounds does (module docstring, "rounding").  At every `store` site named in
+    sites the value is replaced by fn(value) and carried on, and so are the weights of every layer named there; fn is one
+    function, or {site: function} with None as the key of the rest.  Two more sites exist for the mutants only: "tower.i.branch",
+    block i's branch before the residual add, and "tower.<depth>", the last block's output.  The report counts per site
+    what round-to-nearest-even would do (`ties`), keeps what each site carried on (`values`) and says whether every value in
+    front of a rounding, and every stored one, is exact in f32 (`f32`); the f16 and split16 conditions are not measured."""
+    rep = _Report(measure=exact, light=rounding is not None)
     acts = rep.acts = {}
+    sites, fns = rounding if rounding is not None else (frozenset(), None)
+
+    def rnd(name, v):
+        fn = (fns.get(name, fns.get(None)) if isinstance(fns, dict) else fns) if name in sites else None
+        if fn is None:
+            if rounding is not None:
+                rep.values[name] = v
+            return v
+        v = np.asarray(v, np.float64)
+        if rep.measure:
+            rep.count(name, v)
+        rep.values[name] = fn(v)
+        return rep.values[name]
 
     def relu(v, bias_key=None):
         if revive and bias_key is not None:
@@ -427,26 +476,27 @@ def reference(t, meta, x, revive=False, spoil=None, exact=True):
     b = x.shape[0]
 
     def conv(p, v):
-        return _conv(rep, p, v, t[p + ".weight"], t[p + ".bias"], spoil if spoil and spoil["layer"] == p else None)
+        return _conv(rep, p, v, rnd(p, t[p + ".weight"]), t[p + ".bias"], spoil if spoil and spoil["layer"] == p else None)
 
-    x = np.asarray(x, np.float64)
+    x = rnd("input", np.asarray(x, np.float64))
     rep.store("input", x)
-    cur = conv("common.tower.0", x)  # stem: no BN, no ReLU
+    cur = rnd("tower.0", conv("common.tower.0", x))  # stem: no BN, no ReLU
     acts["tower.0"] = cur
     rep.store("tower.0", cur)
     for i in range(1, depth + 1):
         p = f"common.tower.{i}.seq."
-        mid = relu(_bn(t, p + "1", conv(p + "0", cur), eps), p + "1.bias")
+        mid = rnd(f"tower.{i}.mid", relu(_bn(t, p + "1", conv(p + "0", cur), eps), p + "1.bias"))
         acts[f"tower.{i}.mid"] = mid
         rep.store(f"tower.{i}.mid", mid)
-        cur = cur + relu(_bn(t, p + "4", conv(p + "3", mid), eps), p + "4.bias")  # the residual after the ReLU
+        cur = rnd(f"tower.{i}", cur + rnd(f"tower.{i}.branch", relu(_bn(t, p + "4", conv(p + "3", mid), eps), p + "4.bias")))  # the residual after the ReLU
         acts[f"tower.{i}"] = cur
         rep.store(f"tower.{i}", cur)
-    common = _bn(t, f"common.tower.{depth + 1}", cur, eps)
+    common = rnd(f"tower.{depth + 1}", _bn(t, f"common.tower.{depth + 1}", cur, eps))
     acts[f"tower.{depth + 1}"] = common
     rep.store(f"tower.{depth + 1}", common)
 
     def hidden(name, v):
+        v = rnd(name, v)
         rep.store(name, v)
         return v
 
@@ -598,3 +648,233 @@ def coverage(net):
         if (net, wide) not in _COVER:
             build(net, None, wide)
     return {wide: _COVER[net, wide] for wide in wide_positions(net)}
+
+
+# ---- the rounding family: a launch that rounds to bf16 (module docstring, "rounding") ----
+
+def f32_exact(v):
+    v = np.asarray(v, np.float64)
+    with np.errstate(over="ignore"):
+        return bool(np.isfinite(v).all() and np.array_equal(v.astype(np.float32).astype(np.float64), v))
+
+
+def _bf16_parts(v):
+    """|v| = (lo + frac) * 2^(e - 8): lo the integer that holds the 8 significant bits a bf16 value has (128 .. 255; 0 for
+    v = 0), frac in [0, 1) what is beyond them.  Exact in float64 for a v that is exact in f32."""
+    m, e = np.frexp(np.abs(np.asarray(v, np.float64)))  # m in [0.5, 1)
+    lo = np.floor(m * 256.0)
+    return lo, m * 256.0 - lo, e
+
+
+def _bf16(v, up_if):
+    v = np.asarray(v, np.float64)
+    assert f32_exact(v) and np.abs(v).max(initial=0.0) < 2.0 ** 127 and (np.abs(v[v != 0]) > 2.0 ** -120).all(), "bf16: f32 values in the normal range"
+    lo, frac, e = _bf16_parts(v)
+    return np.copysign(np.ldexp(lo + up_if(lo, frac), e - 8), v)
+
+
+def bf16_rne(v):
+    """The nearest value with 8 significant bits, a tie to the one whose last bit is zero — from the definition."""
+    return _bf16(v, lambda lo, frac: (frac > 0.5) | ((frac == 0.5) & (lo % 2 == 1)))
+
+
+def bf16_trunc(v):
+    """(mutant) the upper half of the f32: towards zero."""
+    return _bf16(v, lambda lo, frac: np.zeros(lo.shape, bool))
+
+
+def bf16_half_away(v):
+    """(mutant) to nearest, a tie away from zero."""
+    return _bf16(v, lambda lo, frac: frac >= 0.5)
+
+
+def bf16_sites(meta, heads_inside):
+    """(stored tensors the bf16 launch rounds, layers whose weights it holds in bf16), from kz_tower_pairs.hpp with BF = true:
+    the staged input planes (split4<E>), the stem's epilogue into X, conv A's epilogue into Y (`tower.i.mid`), conv B's epilogue
+    into X for every block but the last — ReLU and residual add in f32 in front of the one conversion —; the last layer's
+    epilogue rounds only with the heads inside, and then behind the final BN (`tower.<depth + 1>`; the last block's own output
+    exists in f32 registers only), and so does the policy head's hidden layer, one more pass of the weight stream into Y.  The
+    weight stream — stem, blocks, and that pass — is packed to bf16 on the host (element_bits); the heads' tail reads the two
+    images and f32 weights."""
+    depth = meta["tower_depth"]
+    sites = ["input", "tower.0"] + [f"tower.{i}.mid" for i in range(1, depth + 1)] + [f"tower.{i}" for i in range(1, depth)]
+    weights = ["common.tower.0"] + [f"common.tower.{i}.seq.{j}" for i in range(1, depth + 1) for j in (0, 3)]
+    if heads_inside:
+        sites += [f"tower.{depth + 1}", "policy_head.hidden"]
+        weights += ["policy_head.seq.0"]
+    return sites, weights
+
+
+# scalar planes and weights times one of these: two ties (to the even neighbour below, to the even neighbour above), two values
+# that are no tie (just above the first tie, just below the upper neighbour), one that bf16 holds
+ROUND_FACTORS = (1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, 1 + 2.0 ** -8 + 2.0 ** -12, 1 + 2.0 ** -7 - 2.0 ** -12, 1 + 2.0 ** -7)
+ROUND_THIN = {256: 8, 64: 4}  # attention heads: one query channel in this many is on (every sum <= SUM_MAX; more where a case needs it)
+
+
+def round_boards(game, batch, seed):
+    """exact_boards with every scalar s replaced by (s + 1) f, f drawn per entry from ROUND_FACTORS."""
+    bits, scalars = exact_boards(game, batch, seed)
+    f = np.random.default_rng([seed, 1299709]).choice(ROUND_FACTORS, size=scalars.shape)
+    return bits, np.ascontiguousarray((scalars.astype(np.float64) + 1.0) * f, dtype=np.float32)
+
+
+def _thin_queries(t, q, every):
+    """Both operands of q_from . q_to are zero, bias included, on all but one query channel in `every`."""
+    for p in _ONE_PER_ROW:
+        rows = np.arange(t[p + ".weight"].shape[0])
+        off = rows[((rows if p == "policy_head.conv_bulk" else rows // 3) % q) % every != 0]
+        t[p + ".weight"][off] = 0.0
+        t[p + ".bias"][off] = 0.0
+
+
+def _read_every_channel(t, p, rng):
+    """The narrow draw gives a layer with few output rows (the policy head's last one: 17 moves, or one) two entries per row,
+    so most channels of the rounded hidden layer in front of it would be read by nothing: one +-1 entry more per such channel."""
+    w = t[p + ".weight"]
+    w3 = w.reshape(w.shape[0], w.shape[1], -1)  # (a view)
+    for c in np.flatnonzero(~w3.any(axis=(0, 2))):
+        w3[int(rng.integers(w.shape[0])), c, int(rng.integers(w3.shape[2]))] = rng.choice((-1.0, 1.0))
+
+
+def round_conditions_hold(report):
+    return all(v <= SUM_MAX for v in report.sums.values()) and all(report.f32.values())
+
+
+def draw_rounding(game, depth, channels, head, variant, seed, heads_inside, max_redraws=4, **kw):
+    """A network of the rounding family, from the narrow draw: a Built with the boards, the rounding reference (`ref_*`, `report`,
+    `rounding`), the seed and the thinning used, and for the input variant the unrounded reference (`plain_*`) an exact-f32
+    engine must return.  Variants:
+      ("dense", at, gain)  layer `at` (layer_names order) dense, its weights times the odd gain: what it sums has more than 8 bits;
+      ("input",)           the scalar planes need rounding (round_boards): every site at once, the stem's output included;
+      ("weights", at)      layer `at` dense and half of its weights times a factor of ROUND_FACTORS: the host's packing rounds
+                           (and so does everything behind that layer).
+    Attention heads multiply two activations: one query channel in ROUND_THIN is on, fewer where the sums ask for it; the input
+    variant, whose unrounded twin carries 13 more bits through the whole tower, keeps q_from narrow the way the wide family
+    does (`_widen`, at = "input").  Accepted if `rounded` and `sums` hold (and for the unrounded twin `sums`, f32 exactness of
+    every stored tensor and of the outputs); else thinned further, then redrawn."""
+    kind = variant[0]
+    att = head == "attention"
+    bits, scalars = round_boards(game, BOARDS, seed) if kind == "input" else exact_boards(game, BOARDS, seed)
+    for attempt in range(max_redraws):
+        s = seed + 1000 * attempt
+        q = thin = None
+        while True:
+            meta, t = _draw(game, depth, channels, head, None if kind == "input" else variant[1], s, 1.0, kw,
+                            ("input", "from") if att and kind == "input" else None)
+            names = layer_names(t)
+            if att:
+                q = meta["policy_query_channels"]
+                thin = ROUND_THIN[q] if thin is None else 2 * thin
+                if thin > q:
+                    break
+                _thin_queries(t, q, thin)
+            if heads_inside:
+                _read_every_channel(t, "policy_head.seq.2", np.random.default_rng([s, 49979687]))
+            if kind == "dense":
+                assert variant[2] % 2 == 1 and variant[2] <= 7
+                t[names[variant[1]] + ".weight"] *= np.float32(variant[2])
+            elif kind == "weights":
+                assert heads_inside, "the attention head outside the launch multiplies two long operands in f32"
+                rng = np.random.default_rng([s, 32452843, variant[1]])
+                w = t[names[variant[1]] + ".weight"]
+                f = rng.choice(ROUND_FACTORS, size=w.shape).astype(np.float32)
+                w *= np.where(rng.uniform(size=w.shape) < 0.5, f, np.float32(1.0))
+            sites, weights = bf16_sites(meta, heads_inside)
+            rounding = (frozenset(sites + weights), bf16_rne)
+            x = encode(meta, bits, scalars)
+            try:
+                out = reference(t, meta, x, revive=True, rounding=rounding)
+                ok = round_conditions_hold(out[2])
+                plain = reference(t, meta, x, rounding=(frozenset(), None)) if ok and kind == "input" else None
+                ok = ok and (plain is None or round_conditions_hold(plain[2]))
+            except AssertionError:  # (outputs not exact in f32, or a value in front of a rounding that is not)
+                ok = False
+            if ok:
+                b = Built()
+                b.bits, b.scalars_in, b.x, b.meta, b.tensors, b.seed, b.thin = bits, scalars, x, meta, t, s, thin
+                b.variant, b.heads_inside, b.rounding, b.sites, b.weights = variant, heads_inside, rounding, sites, weights
+                b.ref64, b.report = out[:2], out[2]
+                b.ref_scalars, b.ref_policy = out[0].astype(np.float32), out[1].astype(np.float32)
+                if plain is not None:
+                    b.plain_report = plain[2]
+                    b.plain_scalars, b.plain_policy = plain[0].astype(np.float32), plain[1].astype(np.float32)
+                b.blob = write_model(meta, t)
+                b.layers = names
+                return b
+            if not att:
+                break
+    raise RuntimeError(f"no rounding network in {max_redraws} draws: {game} {depth}x{channels} {head} {variant}")
+
+
+# The smallest networks that take each branch of the bf16 template: (game, depth, channels, head, keywords, heads inside the launch)
+ROUND_NETS = {
+    "ataxx7_2x128": ("ataxx-7", 2, 128, "ataxx_conv", {}, True),        # heads inside, two-plane images
+    "go9_3x128": ("go-9", 3, 128, "conv", {}, True),                    # heads inside, the pass move, depth 3: two block boundaries
+    "chess_2x256_att": ("chess", 2, 256, "attention", {}, False),       # one-plane image, heads outside
+    "chess_1x192_att": ("chess", 1, 192, "attention", _Q64, False),     # depth 1: the last-layer epilogue alone; the other channel mapping
+}
+# by depth: what the dense layer needs for values that are no tie behind it (gain 1: below 512, ties only).  A case that misses the
+# coverage floors of tests/test_round_nets.py takes a larger odd gain in its variant, not a lower floor; none does.
+ROUND_GAIN = {1: 5, 2: 3, 3: 3}
+
+
+def round_variants(net):
+    """Dense at every tower convolution whose output the launch stores in bf16 (heads outside: not the last one), and at the
+    policy head's hidden layer with the heads inside; the input; the weights of every layer of the bf16 stream (heads inside)."""
+    game, depth, channels, head, kw, inside = ROUND_NETS[net]
+    _, t = read_model(synth.random_model(game, depth, channels, head, seed=SEED, **kw))
+    names = layer_names(t)
+    at = list(range(2 * depth + (1 if inside else 0))) + ([names.index("policy_head.seq.0")] if inside else [])
+    out = [("dense", i, ROUND_GAIN[depth]) for i in at] + [("input",)]
+    return out + ([("weights", i) for i in at] if inside else [])
+
+
+def round_id(variant):
+    return "-".join(str(v) for v in variant[:2])
+
+
+_RCACHE = {}
+
+
+def build_round(net, variant):
+    """One network per (network, variant); cached (the last few only)."""
+    if (net, variant) not in _RCACHE:
+        while len(_RCACHE) >= 6:
+            _RCACHE.pop(next(iter(_RCACHE)))
+        game, depth, channels, head, kw, inside = ROUND_NETS[net]
+        _RCACHE[net, variant] = draw_rounding(game, depth, channels, head, variant, SEED, inside, **kw)
+    return _RCACHE[net, variant]
+
+
+def round_mutants(b):
+    """{name: rounding} of every reference that rounds otherwise than the launch is said to: another direction at every site
+    (activations and weights), truncated weights alone, one site less — each in turn, the post-BN tower output with the heads
+    inside among them —, the branch rounded in front of the residual add (two roundings), the last block's output rounded
+    with the heads outside (the f32 rows that leave the launch)."""
+    sites, weights = b.sites, b.weights
+    both = frozenset(sites + weights)
+    depth = b.meta["tower_depth"]
+    m = {"truncate": (both, bf16_trunc), "half-away": (both, bf16_half_away),
+         "truncated-weights": (both, {**{w: bf16_trunc for w in weights}, None: bf16_rne})}
+    if not any(sum(b.report.ties[w]) for w in weights):
+        del m["truncated-weights"]  # (every weight is a bf16 value: the same reference)
+    for site in sites:
+        if sum(b.report.ties[site]):  # (else nothing rounds there in this case: the same reference)
+            m["without-" + site] = (both - {site}, bf16_rne)
+    m["branch-rounded"] = (both | {f"tower.{i}.branch" for i in range(1, depth + 1)}, bf16_rne)
+    if not b.heads_inside:
+        m["last-block-rounded"] = (both | {f"tower.{depth}"}, bf16_rne)
+    return m
+
+
+def kept(report):
+    """Every tensor the launch keeps, as the reference carried it on: the stream, the sites' values, the rounded weights."""
+    return {k: v for k, v in report.values.items() if not k.endswith(".branch")}
+
+
+def run_mutant(b, rounding):
+    """(scalars, policy, some kept tensor differs from the rounding reference's) of a mutant reference, as f32."""
+    s, p, rep = reference(b.tensors, b.meta, b.x, exact=False, rounding=rounding)
+    base, mine = kept(b.report), kept(rep)
+    applies = any(not np.array_equal(mine[k], base[k]) for k in mine if k in base)
+    return s.astype(np.float32), p.astype(np.float32), applies
