@@ -82,6 +82,29 @@ int main(int argc, char **argv) {
                (long long)audit.skipped, audit.max_abs_prob);
     }
 
+    /* how much f16 headroom this network has on these boards, and the same function with a smaller residual stream: the
+     * range profile measures max |x| per stored tower tensor in exact f32; k = max(0, ceil(log2(m / 65504)) + 2 bits of
+     * headroom), m the maximum over the sites a shift moves (all but the last); the shifted model is an ordinary kz_model.
+     * (ResTower networks with at least one block; the three calls fail with a message for the others.) */
+    int n_sites = 0;
+    if (kz_model_range_sites(model, &n_sites) == 0 && n_sites <= 64) {
+        float site_max[64], board_max[4], m = 0.0f;
+        CHECK(kz_model_range_profile(model, 0, bits, (size_t)info.bits_bytes, scalars_in, batch, site_max, board_max));
+        for (int s = 0; s < n_sites; s++) {
+            char name[32];
+            CHECK(kz_model_range_site_name(model, s, name, sizeof name));
+            printf("site %-12s max |x| %.6g (%.3g of 65504)\n", name, site_max[s], site_max[s] / 65504.0);
+            if (s < n_sites - 1 && site_max[s] > m) m = site_max[s];
+        }
+        int k = 2; /* the headroom; then ceil(log2(m / 65504)) without libm */
+        for (float top = 65504.0f; top < m; top *= 2.0f) k++;
+        for (float top = 32752.0f; top >= m && k > 0; top /= 2.0f) k--;
+        kz_model *shifted = NULL;
+        CHECK(kz_model_stream_shift(model, k, &shifted));
+        printf("stream max %.6g: k = %d (with 2 bits of headroom); the shifted model is evaluated like any other\n", m, k);
+        kz_model_free(shifted);
+    }
+
     free(bits);
     free(scalars_in);
     kz_engine_destroy(engine);

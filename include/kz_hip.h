@@ -308,6 +308,47 @@ typedef struct kz_audit_stats {
 int kz_engine_set_audit(kz_engine *engine, int dtype, int period, int boards);
 int kz_engine_audit_stats(kz_engine *engine, void *out, int reset);
 
+/* ---- stream shift and range profile: f16 for a network whose residual stream leaves +-65504 ----
+ * A ResTower is positively homogeneous in its residual stream: with s = 2^-k, the stem's weights and bias and every block
+ * convolution's folded bias times s, and the final BatchNorm's scale divided by s, give the SAME function with a stream s times
+ * as large — exactly, s being a power of two.  f16 holds 30 binades: a stream that reaches 1e6 fits after a shift.
+ * kz_model_stream_shift(model, k, &out) returns a new immutable model — an ordinary kz_model, to be freed with kz_model_free,
+ * independent of `model` — whose folded tensors are the source's except: the stem convolution's weights and bias times 2^-k,
+ * the folded bias of each of the 2 * depth block convolutions times 2^-k, the final BatchNorm's scale times 2^k.  Block weights,
+ * the final BatchNorm's shift, the heads and the descriptor (kz_model_get_info, kz_model_plan for every dtype and max_batch)
+ * are bit-identical.  k in [-24, 24]; a negative k ENLARGES the stream; k = 0 copies.  Fails, with a message of its own each:
+ * an AttentionTower network (LayerNorm re-normalises: there is nothing to shift), a DenseNetwork, a tower without blocks, k out
+ * of range, and a non-zero value that would leave f32's normal range (nothing is rounded silently).
+ * Every entry point works on the result unchanged; engines of it have device weights of their own.  What the shift moves
+ * is every tensor in front of the final BatchNorm: kz_engine_read_activation on a shifted model returns the SHIFTED stream
+ * ("tower.0" .. "tower.<d>" and the ".mid" ones times 2^-k; "tower.<d+1>" / "tower.out" as before).
+ * What it costs below: a stored value under 2^-14 becomes an f16 subnormal, absolute error at most 2^-25 in the shifted
+ * stream = 2^(k-25) in the unshifted stream's units (in-range values keep their 11 bits: the relative error does not change).
+ * What it cannot reach: the output of the final BatchNorm and the heads' hidden layers — they are the same tensors as before.
+ *
+ * The range profile measures what k has to be: max |x| of every tensor an f16 or split16 kernel of the tower stores, on the
+ * caller's positions, on the GPU in exact f32.  The sites, 2 * tower_depth + 1 of them, in this order and with the names
+ * of kz_engine_read_activation: "tower.0" (the stem's output), then per block i = 1 .. d "tower.<i>.mid" and "tower.<i>" —
+ * except that the last block's output exists only behind the final BatchNorm: the last site is "tower.<d+1>", and it is the
+ * ONLY site a shift does not move.  kz_model_range_sites / kz_model_range_site_name (buf of at least 24 bytes) tell; both,
+ * and the profile, fail for a network without a ResTower or without blocks.
+ * kz_model_range_profile is synchronous: it creates an internal exact-f32 engine of the model on `device` on the per-layer
+ * path ("conv_igemm_f32", whatever kz_model_plan says; no environment switch is read) with max_batch = min(batch, 64),
+ * evaluates the tower on the boards (packed as for kz_engine_eval_packed) in chunks, and destroys the engine.
+ * site_max_out [n_sites]: max |x| over all boards; board_max_out [batch] (may be NULL): per board, the max over the sites a shift
+ * moves (all but the last).  A non-finite value (inf or NaN) reports +inf, never NaN, and a board reports +inf from its first
+ * non-finite site on (behind one the values are not the network's: ReLU turns a NaN into 0); other boards are not affected.
+ * The values are maxima of exact-f32 tensors: the same for any batch split and any scheduling.
+ * Choosing k: with m the maximum over the shifted sites (all but the last; = max of board_max_out),
+ *     k = max(0, ceil(log2(m / 65504)) + headroom_bits)
+ * The library reports and applies, the caller decides; the bindings implement the rule (capi.shift_for, HipNetwork::shift_for,
+ * hip.rs shift_for) and the tools default to 2 bits of headroom: positions not yet seen can be larger than the profiled ones. */
+int kz_model_stream_shift(const kz_model *model, int k, kz_model **out);
+int kz_model_range_sites(const kz_model *model, int *n_sites);
+int kz_model_range_site_name(const kz_model *model, int site, char *buf, size_t len);
+int kz_model_range_profile(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                           int batch, float *site_max_out, float *board_max_out);
+
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and
  * returns; kz_engine_synchronize waits. */
@@ -374,7 +415,9 @@ int kz_engine_launch_geometry(const kz_engine *engine, int batch, int *workgroup
  * d+1 = final BN): only available when the engine was created with the generic per-layer path (set KZ_FORCE_GENERIC=1
  * and KZ_KEEP_ACTIVATIONS=1 in the environment before kz_engine_create); or "tower.out", the tower's output (after the
  * final BN), on every path that writes it to memory (all but the "...+heads" paths; KZ_NO_FUSED_HEADS=1 in the
- * environment before kz_engine_create gives the separate head launches back). */
+ * environment before kz_engine_create gives the separate head launches back).
+ * On a model made by kz_model_stream_shift the activations in front of the final BN are the SHIFTED stream's (2^-k times the
+ * source model's); "tower.<d+1>" and "tower.out" are the source's. */
 int kz_engine_read_activation(kz_engine *engine, const char *name, int batch, float *out_nchw);
 
 #ifdef __cplusplus

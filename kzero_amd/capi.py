@@ -91,6 +91,11 @@ SIGNATURES = {
     "kz_engine_destroy": (None, [C.c_void_p]),
     "kz_model_supports_dtype": (C.c_int, [C.c_void_p, C.c_int]),
     "kz_model_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "kz_model_stream_shift": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "kz_model_range_sites": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "kz_model_range_site_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),
+    "kz_model_range_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                         C.c_void_p]),
     "kz_engine_max_batch": (C.c_int, [C.c_void_p]),
     "kz_engine_eval_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "kz_engine_eval_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
@@ -173,6 +178,22 @@ def device_pci_bus_id(device: int) -> str:
     return buf.value.decode()
 
 
+F16_MAX = 65504.0
+
+
+def shift_for(max_abs: float, headroom_bits: int = 2) -> int:
+    """The k of kz_model_stream_shift for a stream whose shifted sites reach max_abs (include/kz_hip.h):
+    k = max(0, ceil(log2(max_abs / 65504)) + headroom_bits).  Exact: frexp, no floating-point logarithm."""
+    max_abs = float(max_abs)
+    if not np.isfinite(max_abs) or max_abs < 0:
+        raise KzError(f"shift_for: max_abs must be finite and non-negative, got {max_abs}")
+    if max_abs == 0.0:  # (log2(0) = -inf)
+        return 0
+    mant, exp = np.frexp(max_abs / F16_MAX)  # max_abs / 65504 = mant * 2^exp, mant in [0.5, 1)
+    ceil_log2 = int(exp) - 1 if mant == 0.5 else int(exp)
+    return max(0, ceil_log2 + int(headroom_bits))
+
+
 class Model:
     """`Arc<Graph>`: immutable, shareable across engines, threads and devices."""
 
@@ -201,6 +222,45 @@ class Model:
 
     def supports_dtype(self, dtype: int) -> bool:
         return load().kz_model_supports_dtype(self._h, dtype) == 1
+
+    @classmethod
+    def _adopt(cls, handle):
+        self = cls.__new__(cls)
+        self._h = handle
+        self.info = ModelInfo()
+        check(load().kz_model_get_info(self._h, C.byref(self.info)))
+        return self
+
+    def stream_shift(self, k: int) -> "Model":
+        """The same function with a residual stream 2^-k times as large (kz_model_stream_shift): a new Model."""
+        out = C.c_void_p()
+        check(load().kz_model_stream_shift(self._h, int(k), C.byref(out)))
+        return Model._adopt(out)
+
+    def range_sites(self):
+        """The names of the range profile's sites, in order (kz_model_range_sites / kz_model_range_site_name)."""
+        n = C.c_int()
+        check(load().kz_model_range_sites(self._h, C.byref(n)))
+        names = []
+        for site in range(n.value):
+            buf = C.create_string_buffer(32)
+            check(load().kz_model_range_site_name(self._h, site, buf, len(buf)))
+            names.append(buf.value.decode())
+        return names
+
+    def range_profile(self, device: int, bits: np.ndarray, scalars_in: np.ndarray):
+        """max |x| of every stored tower tensor on these boards, in exact f32 on the GPU (kz_model_range_profile):
+        (site_max float32 [n_sites], board_max float32 [batch] over the sites a shift moves)."""
+        n = C.c_int()
+        check(load().kz_model_range_sites(self._h, C.byref(n)))
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        batch = bits.shape[0]
+        site_max = np.zeros(n.value, np.float32)
+        board_max = np.zeros(max(batch, 1), np.float32)
+        check(load().kz_model_range_profile(self._h, device, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                            scalars_in.ctypes.data, batch, site_max.ctypes.data, board_max.ctypes.data))
+        return site_max, board_max[:batch]
 
     def close(self):
         if self._h:

@@ -2,7 +2,9 @@
 // kzero_amd/rust/hip.rs.  Same shape as `CudaNetwork` (rust/kz-core/src/network/cudnn.rs:18-88): encode every board
 // with the mapper, run the engine, decode the outputs.  Talks to the product only through the C ABI.
 #pragma once
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <exception>
 #include <functional>
@@ -14,6 +16,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <vector>
 
 #include <time.h>
 
@@ -109,9 +112,23 @@ class PrepHelper {
     }
 };
 
+// The k of HipModel::stream_shift for a stream whose shifted sites reach max_abs (include/kz_hip.h):
+// k = max(0, ceil(log2(max_abs / 65504)) + headroom_bits), from frexp: no floating-point logarithm.  The library reports
+// (range_profile) and applies (stream_shift); the caller decides.
+inline int shift_for(float max_abs, int headroom_bits = 2) {
+    if (!std::isfinite(max_abs) || max_abs < 0) throw std::invalid_argument("shift_for: max_abs must be finite and non-negative");
+    if (max_abs == 0) return 0;
+    int e = 0;
+    const double mant = std::frexp((double)max_abs / 65504.0, &e);  // max_abs / 65504 = mant * 2^e, mant in [0.5, 1)
+    const int ceil_log2 = mant == 0.5 ? e - 1 : e;
+    return std::max(0, ceil_log2 + headroom_bits);
+}
+
 // the `Arc<Graph>` of the reference: immutable, shared by every executor
 class HipModel {
     kz_model *ptr_ = nullptr;
+
+    explicit HipModel(kz_model *adopted) : ptr_(adopted) { kz_check(kz_model_get_info(ptr_, &info)); }
 
   public:
     kz_model_info info{};
@@ -127,6 +144,37 @@ class HipModel {
     HipModel &operator=(const HipModel &) = delete;
     ~HipModel() { kz_model_free(ptr_); }
     const kz_model *get() const { return ptr_; }
+
+    // The same function with a residual stream 2^-k times as large (kz_model_stream_shift): a new model, k in [-24, 24].
+    std::shared_ptr<const HipModel> stream_shift(int k) const {
+        kz_model *out = nullptr;
+        kz_check(kz_model_stream_shift(ptr_, k, &out));
+        return std::shared_ptr<const HipModel>(new HipModel(out));
+    }
+    // the names of the range profile's sites, in order
+    std::vector<std::string> range_sites() const {
+        int n = 0;
+        kz_check(kz_model_range_sites(ptr_, &n));
+        std::vector<std::string> names;
+        for (int site = 0; site < n; site++) {
+            char buf[32];
+            kz_check(kz_model_range_site_name(ptr_, site, buf, sizeof buf));
+            names.emplace_back(buf);
+        }
+        return names;
+    }
+    // max |x| of every stored tower tensor on `batch` packed boards, exact f32 on `device` (kz_model_range_profile):
+    // site_max [n_sites] over all boards, board_max [batch] over the sites a shift moves
+    struct RangeProfile {
+        std::vector<float> site_max, board_max;
+    };
+    RangeProfile range_profile(int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in, int batch) const {
+        int n = 0;
+        kz_check(kz_model_range_sites(ptr_, &n));
+        RangeProfile r{std::vector<float>((size_t)n), std::vector<float>((size_t)std::max(batch, 0))};
+        kz_check(kz_model_range_profile(ptr_, device, bits, bits_stride, scalars_in, batch, r.site_max.data(), r.board_max.data()));
+        return r;
+    }
 };
 
 template <class B, class M>

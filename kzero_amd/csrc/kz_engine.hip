@@ -197,8 +197,10 @@ static bool known_dtype(int dtype) {
     return dtype == KZ_DTYPE_F32 || dtype == KZ_DTYPE_F16 || dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16;
 }
 
-KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, int dtype, kz_engine **out) {
-    return guarded("kz_engine_create", [&]() -> int {
+// kz_engine_create; profile: the range profile's internal engine (kz_model_range_profile) — exact f32 on the per-layer
+// implicit GEMM whatever plan_path would choose, no environment switch read, every stash site a range measurement
+static int create_engine(const kz_model *model, int device, int max_batch, int dtype, bool profile, kz_engine **out) {
+    {
         if (!model || !out) return fail("kz_engine_create: null argument");
         if (max_batch <= 0) return fail("kz_engine_create: max_batch must be positive");
         // every tensor of an engine is addressed with 32-bit byte offsets (buffer descriptors, int row indices): max_batch times
@@ -225,7 +227,7 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
         HIP_TRY(hipSetDevice(device));
 
         std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(new kz_engine(), kz_engine_destroy);
-        e->model = effective_model(model, dtype_in, max_batch);
+        e->model = profile ? model->m : effective_model(model, dtype_in, max_batch);
         e->source_model = model->m;
         e->out_channels = model->m->channels;
         const Model &m = *e->model;
@@ -237,8 +239,14 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
         e->cp = round_up(m.channels, 32);
         // which kernels run this network: plan_path (kz_plan.hpp) — the table of DESIGN.md §5 is printed from it
         std::string why;
-        if (!plan_path(m, max_batch, dtype_in, e->plan, why)) return fail("kz_engine_create: " + why);
-        experiment_switches(m, dtype, e->cin_p, e->plan);
+        if (profile) {
+            e->plan = PathPlan();  // (Tower::conv_igemm)
+            e->plan.keep = true;
+            e->plan.launches = 2 + 2 * m.depth;
+        } else {
+            if (!plan_path(m, max_batch, dtype_in, e->plan, why)) return fail("kz_engine_create: " + why);
+            experiment_switches(m, dtype, e->cin_p, e->plan);
+        }
         const PathPlan &plan = e->plan;
         {
             std::lock_guard<std::mutex> lock(g_cache_mutex);
@@ -320,9 +328,14 @@ KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, in
         if (e->dmalloc((void **)&devflag_base, (front + 4) * 4)) return 1;
         HIP_TRY(hipMemset(devflag_base, 0, (front + 4) * 4));
         e->d_devflag = devflag_base + front;
+        if (profile && e->dmalloc((void **)&e->range_out, (size_t)(2 * m.depth + 1) * max_batch * 4)) return 1;
         *out = e.release();
         return 0;
-    });
+    }
+}
+
+KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, int dtype, kz_engine **out) {
+    return guarded("kz_engine_create", [&]() -> int { return create_engine(model, device, max_batch, dtype, false, out); });
 }
 
 KZ_API int kz_model_supports_dtype(const kz_model *model, int dtype) {
@@ -348,6 +361,111 @@ KZ_API int kz_model_plan(const kz_model *model, int max_batch, int dtype, kz_pat
         memset(out, 0, sizeof *out);
         snprintf(out->tower_path, sizeof out->tower_path, "%s", path_name(plan, dtype));
         out->launches_per_batch = plan.launches;
+        return 0;
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Stream shift and range profile: the same function with a residual stream 2^-k times as large (kz::stream_shift), and how
+// large the stored tower tensors of a network are on the caller's positions, measured in exact f32
+// ------------------------------------------------------------------------------------------------
+KZ_API int kz_model_stream_shift(const kz_model *model, int k, kz_model **out) {
+    return guarded("kz_model_stream_shift", [&]() -> int {
+        if (!model || !out) return fail("kz_model_stream_shift: null argument");
+        std::string err;
+        Model *m = kz::stream_shift(*model->m, k, err);
+        if (!m) return fail("kz_model_stream_shift: " + err);
+        *out = new kz_model(std::shared_ptr<Model>(m));
+        return 0;
+    });
+}
+
+// the sites exist for a ResTower with at least one block: 2 * depth + 1 of them, in run_tower's stash order
+static int range_site_count(const char *fn, const kz_model *model, int &n) {
+    if (!model) return fail(std::string(fn) + ": null argument");
+    const Model &m = *model->m;
+    if (m.tower_kind != kz::TOWER_RES) return fail(std::string(fn) + ": the range sites are a ResTower's (this network has none)");
+    if (m.depth < 1) return fail(std::string(fn) + ": a tower without blocks has no residual stream to profile");
+    n = 2 * m.depth + 1;
+    return 0;
+}
+
+KZ_API int kz_model_range_sites(const kz_model *model, int *n_sites) {
+    return guarded("kz_model_range_sites", [&]() -> int {
+        int n = 0;
+        if (range_site_count("kz_model_range_sites", model, n)) return 1;
+        if (!n_sites) return fail("kz_model_range_sites: null argument");
+        *n_sites = n;
+        return 0;
+    });
+}
+
+KZ_API int kz_model_range_site_name(const kz_model *model, int site, char *buf, size_t len) {
+    return guarded("kz_model_range_site_name", [&]() -> int {
+        int n = 0;
+        if (range_site_count("kz_model_range_site_name", model, n)) return 1;
+        if (site < 0 || site >= n) return fail("kz_model_range_site_name: site " + std::to_string(site) + " out of range (" + std::to_string(n) + " sites)");
+        // site 0: the stem; 2i - 1: block i's mid activation; 2i: block i's output, the last one behind the final BN
+        const std::string name = site == 0       ? "tower.0"
+                                 : site % 2      ? "tower." + std::to_string((site + 1) / 2) + ".mid"
+                                 : site == n - 1 ? "tower." + std::to_string(site / 2 + 1)
+                                                 : "tower." + std::to_string(site / 2);
+        if (!buf || len < name.size() + 1) return fail("kz_model_range_site_name: buffer of at least " + std::to_string(name.size() + 1) + " bytes needed");
+        memcpy(buf, name.c_str(), name.size() + 1);
+        return 0;
+    });
+}
+
+KZ_API int kz_model_range_profile(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                  int batch, float *site_max_out, float *board_max_out) {
+    return guarded("kz_model_range_profile", [&]() -> int {
+        const std::string fn = "kz_model_range_profile";
+        int n = 0;
+        if (range_site_count("kz_model_range_profile", model, n)) return 1;
+        const Model &m = *model->m;
+        if (m.n_scalar < 0)
+            return fail(fn + ": the model was loaded from ONNX without the scalar/bool plane split; load it with "
+                             "kz_model_load_onnx(path, input_scalar_channels) to use packed inputs");
+        if (batch < 1) return fail(fn + ": batch must be positive");
+        if (!bits || (m.n_scalar && !scalars_in) || !site_max_out) return fail(fn + ": null argument");
+        const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
+        if (bits_stride < bits_bytes) return fail(fn + ": bits_stride too small");
+        const int chunk = std::min(batch, 64);
+        kz_engine *raw = nullptr;
+        if (create_engine(model, device, chunk, KZ_DTYPE_F32, true, &raw)) return 1;
+        std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(raw, kz_engine_destroy);
+        kz_engine::Slot &s = e->slots[0];
+        std::vector<float> host((size_t)n * chunk);
+        for (int i = 0; i < n; i++) site_max_out[i] = 0.0f;
+        // (the kernel's values are never NaN: a non-finite board reports +inf)
+        for (int lo = 0; lo < batch; lo += chunk) {
+            const int nb = std::min(chunk, batch - lo);
+            for (int b = 0; b < nb; b++) memcpy(s.h_bits + b * bits_bytes, bits + (size_t)(lo + b) * bits_stride, bits_bytes);
+            if (m.n_scalar) memcpy(s.h_sin, scalars_in + (size_t)lo * m.n_scalar, (size_t)nb * m.n_scalar * 4);
+            HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, nb * bits_bytes, hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)nb * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
+            // the tower only: the heads read nothing the profile reports
+            e->arm(s);
+            if (e->launch("kz_encode_packed", [&] {
+                    kz::launch_encode_packed(e->dtype, e->packed_boards(s.d_bits, bits_bytes, s.d_sin), nb, m.h * m.w, e->x_in, e->cin_p, e->stream);
+                }))
+                return 1;
+            if (e->run_tower(nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+            if (e->range_site != n) return fail(fn + ": internal error: " + std::to_string(e->range_site) + " sites measured, " + std::to_string(n) + " expected");
+            HIP_TRY(hipMemcpyAsync(host.data(), e->range_out, host.size() * 4, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            for (int b = 0; b < nb; b++) {
+                // behind a non-finite tensor the values are not the network's (ReLU turns a NaN into 0): the board reports +inf
+                // from its first non-finite site on
+                bool nonfinite = false;
+                for (int i = 0; i < n; i++) {
+                    nonfinite = nonfinite || host[(size_t)i * chunk + b] == INFINITY;
+                    const float v = nonfinite ? INFINITY : host[(size_t)i * chunk + b];
+                    site_max_out[i] = std::max(site_max_out[i], v);
+                    if (board_max_out && i < n - 1) board_max_out[lo + b] = i == 0 ? v : std::max(board_max_out[lo + b], v);
+                }
+            }
+        }
         return 0;
     });
 }

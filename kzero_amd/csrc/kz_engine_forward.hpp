@@ -186,6 +186,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         return 0;
     }
     // stem: conv + bias, no activation (post_act.py:205)
+    range_site = 0;
     if (conv(wts->tower[0], x_in, cin_p, act[0], cp, M, 0, nullptr, m.depth == 0, m.h, m.w, hw, hw, 0)) return 1;
     if (stash(m.depth == 0 ? "tower.1" : "tower.0", act[0], batch)) return 1;
     int cur = 0;

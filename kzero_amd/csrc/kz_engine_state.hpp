@@ -331,8 +331,20 @@ struct kz_engine {
         return 0;
     }
 
+    // the range profile (kz_model_range_profile): a profiling engine — exact f32 on the per-layer path, plan.keep set — takes
+    // max |x| per board at every site where run_tower stashes, instead of the copy: range_out [n_sites][max_batch] in device
+    // memory, range_site counts the sites of the running pass in stash order (kz_model_range_site_name's order)
+    float *range_out = nullptr;
+    int range_site = 0;
+
     int stash(const std::string &name, const void *src, int batch) {
         if (!plan.keep) return 0;
+        if (range_out) {
+            float *out = range_out + (size_t)range_site++ * max_batch;
+            return launch("kz_range_absmax", [&] {
+                kz::launch_range_absmax((const float *)src, batch, model->h * model->w, model->channels, cp, out, stream);
+            });
+        }
         const size_t bytes = (size_t)batch * model->h * model->w * cp * esz;
         auto it = kept.find(name);
         if (it == kept.end()) {

@@ -55,6 +55,10 @@ void launch_encode_packed(int dtype, const PackedBoards &in, int batch, int hw, 
 void launch_encode_dense(int dtype, const float *nchw, int batch, int c, int hw, void *x, int ldx,
                          hipStream_t stream);
 
+// The range profile (kz_range_profile.hip): out[b] = max |x| over board b's hw rows of `channels` real f32 values, row stride
+// cp floats (a multiple of 32: rows are 128-byte aligned); +inf for a board with any non-finite value.  One workgroup per board.
+void launch_range_absmax(const float *x, int boards, int hw, int channels, int cp, float *out, hipStream_t stream);
+
 // Implicit-GEMM convolution, kernel k in {1,3}, pad k/2, fused epilogue:
 //   v = acc + bias[oc];  if (relu) v = max(v, 0);  if (res) v += res[row][oc];
 //   if (post_scale) v = v * post_scale[oc] + post_shift[oc];  y[row][oc] = v

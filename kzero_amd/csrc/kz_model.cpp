@@ -614,4 +614,48 @@ Model *pad_channels(const Model &m, int cpad) {
     return o.release();
 }
 
+// ---- the same function with the residual stream 2^-k times as large ----
+namespace {
+// v * 2^e, exact: false when a non-zero v would become inf, subnormal or zero
+bool scale_pow2(std::vector<float> &v, int e) {
+    for (float &x : v) {
+        if (x == 0.0f) continue;
+        const float y = std::ldexp(x, e);
+        if (!std::isnormal(y)) return false;
+        x = y;
+    }
+    return true;
+}
+}  // namespace
+
+Model *stream_shift(const Model &m, int k, std::string &err) {
+    if (m.tower_kind == TOWER_ATTENTION) {
+        err = "an AttentionTower network has no stream to shift: every LayerNorm re-normalises it";
+        return nullptr;
+    }
+    if (m.tower_kind == TOWER_DENSE_NET) {
+        err = "a DenseNetwork has no residual tower to shift";
+        return nullptr;
+    }
+    if (m.depth < 1 || m.tower.size() != (size_t)(2 * m.depth + 1)) {
+        err = "a tower without blocks has no residual stream to shift";
+        return nullptr;
+    }
+    if (k < -STREAM_SHIFT_MAX || k > STREAM_SHIFT_MAX) {
+        err = "k = " + std::to_string(k) + " out of range: the shift is 2^-k with k in [-" + std::to_string(STREAM_SHIFT_MAX) + ", " +
+              std::to_string(STREAM_SHIFT_MAX) + "]";
+        return nullptr;
+    }
+    std::unique_ptr<Model> o(new Model(m));
+    bool ok = scale_pow2(o->tower[0].w, -k);
+    for (Conv &c : o->tower) ok = ok && scale_pow2(c.b, -k);
+    ok = ok && scale_pow2(o->final_scale, k);
+    if (!ok) {
+        err = "shifting by k = " + std::to_string(k) + " would take a non-zero weight, bias or final-BN scale out of f32's normal "
+              "range (no value is rounded silently: choose a smaller |k|)";
+        return nullptr;
+    }
+    return o.release();
+}
+
 }  // namespace kz

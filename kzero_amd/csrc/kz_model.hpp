@@ -103,6 +103,15 @@ Model *parse_model(const void *blob, size_t len, std::string &err);
 // and board-tile kernels instead of the generic implicit GEMM.  nullptr when cpad <= channels.
 Model *pad_channels(const Model &m, int cpad);
 
+// The same function with a residual stream 2^-k times as large (the ResTower is positively homogeneous in its stream): the
+// stem's weights and bias and every block convolution's folded bias times 2^-k, final_scale times 2^k; everything else is
+// the source's, bit for bit.  Powers of two: exact, and a non-zero value that would leave f32's normal range is refused
+// instead of rounded.  k in [-STREAM_SHIFT_MAX, STREAM_SHIFT_MAX]; negative k enlarges the stream, k = 0 copies.
+// Returns nullptr and sets `err` for an AttentionTower network, a DenseNetwork, a tower without blocks, k out of range and
+// a value out of range.
+constexpr int STREAM_SHIFT_MAX = 24;
+Model *stream_shift(const Model &m, int k, std::string &err);
+
 // ONNX as exported by the trainer (python/lib/save_onnx.py:60-122), kz_onnx.cpp.  n_scalar = how many of the input
 // planes are broadcast scalars (InputMapper::input_scalar_count, rust/kz-core/src/mapping/mod.rs:21) — the graph does
 // not carry that split; pass -1 when unknown (then only the dense-input entry points work).

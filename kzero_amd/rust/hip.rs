@@ -114,6 +114,11 @@ extern "C" {
     fn kz_engine_destroy(engine: *mut c_void);
     fn kz_model_supports_dtype(model: *const c_void, dtype: c_int) -> c_int;
     fn kz_model_plan(model: *const c_void, max_batch: c_int, dtype: c_int, out: *mut KzPathPlan) -> c_int;
+    // stream shift (a new model: the same function, the residual stream 2^-k times as large) and the exact-f32 range profile
+    fn kz_model_stream_shift(model: *const c_void, k: c_int, out: *mut *mut c_void) -> c_int;
+    fn kz_model_range_sites(model: *const c_void, n_sites: *mut c_int) -> c_int;
+    fn kz_model_range_site_name(model: *const c_void, site: c_int, buf: *mut c_char, len: usize) -> c_int;
+    fn kz_model_range_profile(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, site_max_out: *mut f32, board_max_out: *mut f32) -> c_int;
     fn kz_engine_max_batch(engine: *const c_void) -> c_int;
     fn kz_engine_eval_dense(engine: *mut c_void, input_nchw: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
     fn kz_engine_eval_packed(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
@@ -250,6 +255,79 @@ impl HipModel {
         check(unsafe { kz_model_get_info(ptr, &mut info) });
         HipModel { ptr, info }
     }
+
+    fn adopt(ptr: *mut c_void) -> Self {
+        let mut info = KzModelInfo::default();
+        check(unsafe { kz_model_get_info(ptr, &mut info) });
+        HipModel { ptr, info }
+    }
+
+    /// The same function with a residual stream 2^-k times as large (`kz_model_stream_shift`): f16 and the parity arithmetic
+    /// for a network whose stream leaves +-65504.  k in [-24, 24]; panics where the library refuses.
+    pub fn stream_shift(&self, k: i32) -> HipModel {
+        let mut ptr = std::ptr::null_mut();
+        check(unsafe { kz_model_stream_shift(self.ptr, k as c_int, &mut ptr) });
+        HipModel::adopt(ptr)
+    }
+
+    /// `KZ_HIP_STREAM_SHIFT=<k>` (default 0; read here, never by the library), what `load_graph` applies to every network it
+    /// loads: choose k from a range profile of the network on its own positions (`range_profile`, `shift_for`;
+    /// tools/range_profile.py prints both).
+    pub fn stream_shift_from_env(self) -> HipModel {
+        match std::env::var("KZ_HIP_STREAM_SHIFT") {
+            Err(_) => self,
+            Ok(v) => match v.parse::<i32>() {
+                Ok(0) => self,
+                Ok(k) => self.stream_shift(k),
+                Err(_) => panic!("KZ_HIP_STREAM_SHIFT must be an integer in [-24, 24], got '{}'", v),
+            },
+        }
+    }
+
+    /// The names of the range profile's sites, in order (`kz_model_range_sites`, `kz_model_range_site_name`).
+    pub fn range_sites(&self) -> Vec<String> {
+        let mut n = 0;
+        check(unsafe { kz_model_range_sites(self.ptr, &mut n) });
+        (0..n)
+            .map(|site| {
+                let mut buf = [0 as c_char; 32];
+                check(unsafe { kz_model_range_site_name(self.ptr, site, buf.as_mut_ptr(), buf.len()) });
+                unsafe { CStr::from_ptr(buf.as_ptr()) }.to_string_lossy().into_owned()
+            })
+            .collect()
+    }
+
+    /// max |x| of every stored tower tensor on these packed boards, in exact f32 on `device` (`kz_model_range_profile`):
+    /// (per site over all boards, per board over the sites a shift moves).
+    pub fn range_profile(&self, device: HipDevice, bits: &[u8], bits_stride: usize, scalars_in: &[f32], batch: usize) -> (Vec<f32>, Vec<f32>) {
+        let mut n = 0;
+        check(unsafe { kz_model_range_sites(self.ptr, &mut n) });
+        assert!(bits.len() >= batch * bits_stride && scalars_in.len() >= batch * self.info.input_scalar_channels.max(0) as usize);
+        let (mut site_max, mut board_max) = (vec![0f32; n as usize], vec![0f32; batch]);
+        check(unsafe {
+            kz_model_range_profile(self.ptr, device.0 as c_int, bits.as_ptr(), bits_stride, scalars_in.as_ptr(), batch as c_int, site_max.as_mut_ptr(), board_max.as_mut_ptr())
+        });
+        (site_max, board_max)
+    }
+}
+
+/// The k of `HipModel::stream_shift` for a stream whose shifted sites reach `max_abs` (include/kz_hip.h):
+/// k = max(0, ceil(log2(max_abs / 65504)) + headroom_bits), computed without a floating-point logarithm.
+pub fn shift_for(max_abs: f32, headroom_bits: i32) -> i32 {
+    assert!(max_abs.is_finite() && max_abs >= 0.0, "shift_for: max_abs must be finite and non-negative, got {}", max_abs);
+    if max_abs == 0.0 {
+        return 0;
+    }
+    // the smallest e with max_abs <= 65504 * 2^e
+    let ratio = max_abs as f64 / 65504.0;
+    let mut e = 0;
+    while ratio > (2.0f64).powi(e) {
+        e += 1;
+    }
+    while e > -200 && ratio <= (2.0f64).powi(e - 1) {
+        e -= 1;
+    }
+    (e + headroom_bits).max(0)
 }
 
 impl Drop for HipModel {

@@ -113,7 +113,8 @@ impl<B: Board + Hash, M: BoardMapper<B> + 'static> ZeroSpecialization<B, M> for 
 
     /// The ONNX path of `Command::NewNetwork` (protocol.rs:36) goes straight to the C ABI; the mapper supplies the one
     /// fact the graph does not carry (how many input planes are broadcast scalars).
+    /// `KZ_HIP_STREAM_SHIFT=<k>` (default 0: the network as trained) shifts the residual stream by 2^-k here.
     fn load_graph(&self, path: &str, mapper: M, _: &StartupSettings) -> HipModel {
-        HipModel::load(path, mapper.input_scalar_count())
+        HipModel::load(path, mapper.input_scalar_count()).stream_shift_from_env()
     }
 }

@@ -1,0 +1,188 @@
+#!/usr/bin/env python3
+"""How much f16 headroom a network has, and the stream shift that gives it some (include/kz_hip.h, "stream shift and range
+profile"): runs kz_model_range_profile — max |x| of every tensor an f16 / split16 tower kernel stores, exact f32 on the GPU — on
+the positions of a position file (kzero_amd/position_file.py) or on synthetic boards, prints the per-site table (max, fraction of
+65504) and the suggested k = max(0, ceil(log2(m / 65504)) + headroom_bits), m the maximum over the sites a shift moves.
+
+    python tools/range_profile.py --model net.kzm|net.onnx [--scalar-channels N] --positions games/file [--boards 1024]
+    python tools/range_profile.py --game chess --depth 20 --channels 256 --head attention [--block-gain 64] [--boards 256]
+
+--check  evaluates the boards with the f16 engine of the SHIFTED model (the suggested k, or --k) through the decoded status entry,
+         with the shadow audit against exact f32 on every batch: the status words per kind and the audit's statistics.
+--rate   shifted against unshifted evals/s of the f16 engine (--dtype: another arithmetic) at --batch: the decoded host-boundary
+         rate on the four slots, both models in ONE process, interleaved timed regions, the median of --regions each — and the
+         unshifted model's own max - min spread over its regions, the bar the difference has to clear.
+--profile-time  the wall time of the profile call itself (engine creation included), the median of 5 calls.
+Prints one JSON object; --out writes it too.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+from kzero_amd import benchlib, capi, synth  # noqa: E402
+from kzero_amd.position_file import PositionFile  # noqa: E402
+
+DTYPES = {"f16": capi.KZ_DTYPE_F16, "f32split16": capi.KZ_DTYPE_F32_SPLIT16, "f32": capi.KZ_DTYPE_F32, "bf16": capi.KZ_DTYPE_BF16}
+
+
+class Loop:
+    """One engine's four-slot loop as benchlib's (step, sync) pair (tools/bf16_rate.py)."""
+
+    def __init__(self, eng, bits, scalars, offsets, idx):
+        self.eng, self.args, self.busy = eng, (bits, scalars, offsets, idx), [False] * capi.KZ_ENGINE_SLOTS
+
+    def step(self, i):
+        slot = i % len(self.busy)
+        if self.busy[slot]:
+            self.eng.wait_decoded_view(slot)
+        self.eng.submit_packed_decoded_csr(slot, *self.args)
+        self.busy[slot] = True
+
+    def sync(self):
+        for slot, busy in enumerate(self.busy):
+            if busy:
+                self.eng.wait_decoded_view(slot)
+                self.busy[slot] = False
+
+
+def random_moves(policy_len, n, seed=1):
+    rng = np.random.default_rng(seed)
+    return [rng.permutation(policy_len)[:int(k)].astype(np.int32) for k in rng.integers(1, 61, size=n)]
+
+
+def check(model, k, bits, scalars, moves, device):
+    """The f16 engine of the shifted model on the profiled boards: status words and the audit against exact f32."""
+    eng = capi.Engine(model.stream_shift(k), device, min(len(bits), 256), capi.KZ_DTYPE_F16)
+    audit_boards = min(eng.max_batch, 64)
+    eng.set_audit(capi.KZ_DTYPE_F32, 1, audit_boards)
+    counts = {"ok": 0, "bad_decode": 0, "nonfinite": 0}
+    for lo in range(0, len(bits), eng.max_batch):
+        hi = min(lo + eng.max_batch, len(bits))
+        _, _, status = eng.eval_packed_decoded_status(bits[lo:hi], scalars[lo:hi], moves[lo:hi])
+        counts["ok"] += int((status == 0).sum())
+        counts["bad_decode"] += int(((status & capi.KZ_BOARD_BAD_DECODE) != 0).sum())
+        counts["nonfinite"] += int(((status & capi.KZ_BOARD_NONFINITE) != 0).sum())
+    a = eng.audit_stats()
+    return {"k": k, "tower_path": eng.tower_path, "boards": len(bits), "status": counts,
+            "audit_vs_f32": {"boards": a.boards, "moves": a.moves, "skipped": a.skipped, "max_abs_value": a.max_abs_value.tolist(),
+                             "max_abs_prob": float(a.max_abs_prob), "rms_value": a.rms_value.tolist(), "rms_prob": a.rms_prob}}
+
+
+def rate(model, k, bits, scalars, moves, device, dtype, batch, regions, seconds):
+    pick = np.arange(batch) % len(bits)
+    bits, scalars, moves = np.ascontiguousarray(bits[pick]), np.ascontiguousarray(scalars[pick]), [moves[i] for i in pick]
+    loops, paths = {}, {}
+    for name, m in (("unshifted", model), ("shifted", model.stream_shift(k))):
+        eng = capi.Engine(m, device, batch, DTYPES[dtype])
+        offsets, idx = eng._csr(moves)
+        loops[name], paths[name] = Loop(eng, bits, scalars, offsets, idx), eng.tower_path
+    steps = {}
+    for name, loop in loops.items():
+        t = benchlib.run_timed(loop.step, loop.sync, 8, 8)
+        steps[name] = max(16, int(seconds / (t / 8)))
+    elapsed = {name: [] for name in loops}
+    for _ in range(regions):  # interleaved: both models see the same minutes of the chip
+        for name, loop in loops.items():
+            elapsed[name].append(benchlib.run_timed(loop.step, loop.sync, steps[name], 4))
+    out = {"k": k, "dtype": dtype, "batch": batch, "regions": regions}
+    for name in loops:
+        per_region = [steps[name] * batch / t for t in elapsed[name]]
+        out[name] = {"tower_path": paths[name], "steps_per_region": steps[name],
+                     "evals_per_s_median": round(steps[name] * batch / benchlib.median_region(elapsed[name])),
+                     "evals_per_s_min_max": [round(min(per_region)), round(max(per_region))]}
+    lo, hi = out["unshifted"]["evals_per_s_min_max"]
+    out["unshifted_spread"] = hi - lo
+    out["shifted_minus_unshifted"] = out["shifted"]["evals_per_s_median"] - out["unshifted"]["evals_per_s_median"]
+    out["inside_the_spread"] = abs(out["shifted_minus_unshifted"]) <= out["unshifted_spread"]
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", help="a KZMODEL1 container or an ONNX file")
+    ap.add_argument("--scalar-channels", type=int, help="ONNX: how many input planes are broadcast scalars")
+    ap.add_argument("--positions", help="a position file (path without .json / .bin / .off)")
+    ap.add_argument("--game", default="chess")
+    ap.add_argument("--depth", type=int, default=20)
+    ap.add_argument("--channels", type=int, default=256)
+    ap.add_argument("--head", default="attention")
+    ap.add_argument("--block-gain", type=float, help="synthetic model: synth.random_model's block_gain (a stream that grows)")
+    ap.add_argument("--boards", type=int, default=256, help="positions to profile (the first of the file, or synthetic ones)")
+    ap.add_argument("--headroom", type=int, default=2, help="bits of headroom: unseen positions can be larger than these")
+    ap.add_argument("--k", type=int, help="shift for --check / --rate instead of the suggested one")
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--check", action="store_true")
+    ap.add_argument("--rate", action="store_true")
+    ap.add_argument("--profile-time", action="store_true")
+    ap.add_argument("--dtype", default="f16", choices=sorted(DTYPES))
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--regions", type=int, default=7)
+    ap.add_argument("--seconds", type=float, default=0.5, help="length of a timed region")
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    assert capi.device_count() >= 1, "needs a GPU"
+
+    if args.model:
+        model = capi.Model(path=args.model, onnx_scalar_channels=args.scalar_channels)
+        network = os.path.basename(args.model)
+    else:
+        kw = {"block_gain": args.block_gain} if args.block_gain else {}
+        model = capi.Model(blob=synth.random_model(args.game, args.depth, args.channels, args.head, seed=3, **kw))
+        network = f"{args.game} {args.depth}x{args.channels} (synthetic)"
+    if args.positions:
+        pf = PositionFile(args.positions)
+        bits, scalars, moves = pf.read_boards(range(min(args.boards, len(pf))))
+        source = f"{len(bits)} positions of {args.positions}"
+    else:
+        assert not args.model, "a model file needs --positions (synthetic boards belong to a --game)"
+        bits, scalars = synth.random_boards(args.game, args.boards, seed=2)
+        moves = random_moves(model.info.policy_len, args.boards)
+        source = f"{args.boards} synthetic boards"
+
+    sites = model.range_sites()
+    site_max, board_max = model.range_profile(args.device, bits, scalars)
+    m = float(site_max[:-1].max())
+    suggested = capi.shift_for(m, args.headroom) if np.isfinite(m) else None
+    out = {"tool": "range_profile", "network": network, "boards": source,
+           "sites": [{"site": s, "max_abs": float(v), "of_65504": float(v) / capi.F16_MAX, "shift_moves_it": i < len(sites) - 1}
+                     for i, (s, v) in enumerate(zip(sites, site_max))],
+           "stream_max": m, "boards_beyond_65504": int((board_max > capi.F16_MAX).sum()), "headroom_bits": args.headroom,
+           "suggested_k": suggested}
+    print(f"# {network}, {source}", file=sys.stderr)
+    print(f"# {'site':<14} {'max |x|':>14} {'of 65504':>10}", file=sys.stderr)
+    for row in out["sites"]:
+        print(f"# {row['site']:<14} {row['max_abs']:>14.6g} {row['of_65504']:>10.3g}" + ("" if row["shift_moves_it"] else "   (a shift does not move it)"),
+              file=sys.stderr)
+    print(f"# stream max {m:.6g}, {out['boards_beyond_65504']} of {len(bits)} boards beyond 65504: suggested k = {suggested} "
+          f"({args.headroom} bits of headroom)", file=sys.stderr)
+    if args.profile_time:
+        times = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            model.range_profile(args.device, bits, scalars)
+            times.append(time.perf_counter() - t0)
+        out["profile_call_ms"] = {"boards": len(bits), "median": round(1e3 * float(np.median(times)), 2), "min": round(1e3 * min(times), 2),
+                                  "max": round(1e3 * max(times), 2)}
+    k = args.k if args.k is not None else suggested
+    if args.check or args.rate:
+        assert k is not None, "the stream is not finite on these boards: no shift repairs that"
+    if args.check:
+        out["check"] = check(model, k, bits, scalars, moves, args.device)
+    if args.rate:
+        out["rate"] = rate(model, k, bits, scalars, moves, args.device, args.dtype, args.batch, args.regions, args.seconds)
+    text = json.dumps(out, indent=1)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
