@@ -342,12 +342,25 @@ int kz_engine_audit_stats(kz_engine *engine, void *out, int reset);
  * Choosing k: with m the maximum over the shifted sites (all but the last; = max of board_max_out),
  *     k = max(0, ceil(log2(m / 65504)) + headroom_bits)
  * The library reports and applies, the caller decides; the bindings implement the rule (capi.shift_for, HipNetwork::shift_for,
- * hip.rs shift_for) and the tools default to 2 bits of headroom: positions not yet seen can be larger than the profiled ones. */
+ * hip.rs shift_for) and the tools default to 2 bits of headroom: positions not yet seen can be larger than the profiled ones.
+ *
+ * kz_model_range_profile_fast is the same call — the same sites and names, site_max_out and board_max_out, the same non-finite
+ * rule and refusals — at the rate of the one-launch exact-f32 tower: where that kernel takes the network (128 / 256 tower
+ * channels on a small board: "tower_resident_f32" of kz_model_plan, with or without "+heads") the internal engine runs ONE launch
+ * per chunk, whose epilogues take the maxima of what they store while the tensors are in LDS; no head kernel, no decode and no
+ * copy of the tower output runs, max_batch = min(batch, 256), and the device weight stream is the one ordinary exact-f32 engines
+ * of the model share.  Every other network (Go 19x19, other widths) runs exactly kz_model_range_profile.  On exactly
+ * representable tensors the two entries return the same bits; otherwise they differ as two exact-f32 summation orders do
+ * (1e-4 relative).  kz_model_range_profile_fast_path writes which of the two it is, "tower_resident_f32" or "conv_igemm_f32"
+ * (buf of at least 24 bytes), without touching a GPU; it fails where the profile fails. */
 int kz_model_stream_shift(const kz_model *model, int k, kz_model **out);
 int kz_model_range_sites(const kz_model *model, int *n_sites);
 int kz_model_range_site_name(const kz_model *model, int site, char *buf, size_t len);
 int kz_model_range_profile(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
                            int batch, float *site_max_out, float *board_max_out);
+int kz_model_range_profile_fast(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride,
+                                const float *scalars_in, int batch, float *site_max_out, float *board_max_out);
+int kz_model_range_profile_fast_path(const kz_model *model, char *buf, size_t len);
 
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and

@@ -96,6 +96,9 @@ SIGNATURES = {
     "kz_model_range_site_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),
     "kz_model_range_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
                                          C.c_void_p]),
+    "kz_model_range_profile_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p]),
+    "kz_model_range_profile_fast_path": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "kz_engine_max_batch": (C.c_int, [C.c_void_p]),
     "kz_engine_eval_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "kz_engine_eval_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
@@ -251,6 +254,20 @@ class Model:
     def range_profile(self, device: int, bits: np.ndarray, scalars_in: np.ndarray):
         """max |x| of every stored tower tensor on these boards, in exact f32 on the GPU (kz_model_range_profile):
         (site_max float32 [n_sites], board_max float32 [batch] over the sites a shift moves)."""
+        return self._range_profile("kz_model_range_profile", device, bits, scalars_in)
+
+    def range_profile_fast(self, device: int, bits: np.ndarray, scalars_in: np.ndarray):
+        """The same profile inside the one-launch exact-f32 tower where that kernel takes the network — tens of thousands of
+        boards per second — and exactly range_profile elsewhere (kz_model_range_profile_fast)."""
+        return self._range_profile("kz_model_range_profile_fast", device, bits, scalars_in)
+
+    def range_profile_fast_path(self) -> str:
+        """Where range_profile_fast runs: "tower_resident_f32" or "conv_igemm_f32" — host logic, no GPU needed."""
+        buf = C.create_string_buffer(32)
+        check(load().kz_model_range_profile_fast_path(self._h, buf, len(buf)))
+        return buf.value.decode()
+
+    def _range_profile(self, entry: str, device: int, bits: np.ndarray, scalars_in: np.ndarray):
         n = C.c_int()
         check(load().kz_model_range_sites(self._h, C.byref(n)))
         bits = np.ascontiguousarray(bits, dtype=np.uint8)
@@ -258,8 +275,8 @@ class Model:
         batch = bits.shape[0]
         site_max = np.zeros(n.value, np.float32)
         board_max = np.zeros(max(batch, 1), np.float32)
-        check(load().kz_model_range_profile(self._h, device, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
-                                            scalars_in.ctypes.data, batch, site_max.ctypes.data, board_max.ctypes.data))
+        check(getattr(load(), entry)(self._h, device, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                     scalars_in.ctypes.data, batch, site_max.ctypes.data, board_max.ctypes.data))
         return site_max, board_max[:batch]
 
     def close(self):
@@ -272,6 +289,24 @@ class Model:
             self.close()
         except Exception:
             pass
+
+
+def auto_stream_shift(model: Model, device: int, bits: np.ndarray, scalars_in: np.ndarray, headroom_bits: int = 2):
+    """The shift `model` needs on these sampled positions (HipModel::auto_stream_shift of the C++ mirror): range_profile_fast,
+    m = the largest board_max, k = shift_for(m, headroom_bits).  Returns (model.stream_shift(k) — or `model` itself for
+    k == 0 —, k, m, boards).  No boards: k = 0 and boards = 0, nothing is measured.  m = +inf raises: a network that overflows
+    f32 is not a shift's business."""
+    bits = np.ascontiguousarray(bits, dtype=np.uint8)
+    boards = int(bits.shape[0]) if bits.ndim == 2 else 0
+    if boards == 0:
+        return model, 0, 0.0, 0
+    _, board_max = model.range_profile_fast(device, bits, scalars_in)
+    m = float(board_max.max())
+    if not np.isfinite(m):
+        raise KzError(f"auto_stream_shift: the residual stream is not finite in exact f32 on the {boards} sampled boards: "
+                      f"no shift brings such a network into range")
+    k = shift_for(m, headroom_bits)
+    return (model.stream_shift(k) if k else model), k, m, boards
 
 
 class DeviceBuffer:

@@ -6,6 +6,7 @@
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
+#include <cstdlib>
 #include <exception>
 #include <functional>
 #include <iterator>
@@ -23,6 +24,7 @@
 #include "../../../include/kz_hip.h"
 #include "mapping.hpp"
 #include "network.hpp"
+#include "position_sample.hpp"
 #include "symmetry.hpp"
 
 namespace kz::host {
@@ -125,7 +127,8 @@ inline int shift_for(float max_abs, int headroom_bits = 2) {
 }
 
 // the `Arc<Graph>` of the reference: immutable, shared by every executor
-class HipModel {
+// (auto_stream_shift hands the model itself back when no shift is needed: for that call it must live in a shared_ptr)
+class HipModel : public std::enable_shared_from_this<HipModel> {
     kz_model *ptr_ = nullptr;
 
     explicit HipModel(kz_model *adopted) : ptr_(adopted) { kz_check(kz_model_get_info(ptr_, &info)); }
@@ -175,7 +178,93 @@ class HipModel {
         kz_check(kz_model_range_profile(ptr_, device, bits, bits_stride, scalars_in, batch, r.site_max.data(), r.board_max.data()));
         return r;
     }
+    // The same profile at the rate of the one-launch exact-f32 tower where that kernel takes the network, and exactly
+    // range_profile elsewhere (kz_model_range_profile_fast); range_profile_fast_path says which, without a GPU.
+    RangeProfile range_profile_fast(int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in, int batch) const {
+        int n = 0;
+        kz_check(kz_model_range_sites(ptr_, &n));
+        RangeProfile r{std::vector<float>((size_t)n), std::vector<float>((size_t)std::max(batch, 0))};
+        kz_check(kz_model_range_profile_fast(ptr_, device, bits, bits_stride, scalars_in, batch, r.site_max.data(), r.board_max.data()));
+        return r;
+    }
+    std::string range_profile_fast_path() const {
+        char buf[32];
+        kz_check(kz_model_range_profile_fast_path(ptr_, buf, sizeof buf));
+        return buf;
+    }
+
+    // The shift this network needs on the positions of `sample`: range_profile_fast on a snapshot, m = the largest board_max,
+    // k = shift_for(m, headroom_bits); `model` is stream_shift(k), or this model itself for k == 0.  An empty sample gives
+    // k = 0 and boards == 0 (the first network of a run: pair it with the range fallback).  m = +inf throws: a network that
+    // overflows f32 is not a shift's business.
+    struct AutoShift {
+        std::shared_ptr<const HipModel> model;
+        int k = 0;
+        float max_abs = 0.0f;
+        size_t boards = 0;     // boards profiled; 0: the sample was empty and nothing was measured
+    };
+    AutoShift auto_stream_shift(int device, const PositionSample &sample, int headroom_bits = 2) const {
+        AutoShift r;
+        const PositionSample::Snapshot snap = sample.snapshot();
+        r.boards = snap.boards;
+        if (snap.boards) {
+            if (snap.bits_bytes != (size_t)info.bits_bytes || snap.n_scalar != (size_t)info.input_scalar_channels)
+                throw std::invalid_argument("auto_stream_shift: the sample holds boards of another shape than this model's");
+            const RangeProfile p = range_profile_fast(device, snap.bits.data(), snap.bits_bytes, snap.scalars.data(), (int)snap.boards);
+            r.max_abs = *std::max_element(p.board_max.begin(), p.board_max.end());
+            if (!std::isfinite(r.max_abs))
+                throw std::runtime_error("kzhip: auto_stream_shift: the residual stream is not finite in exact f32 on the " +
+                                         std::to_string(snap.boards) + " sampled boards: no shift brings such a network into range");
+            r.k = shift_for(r.max_abs, headroom_bits);
+        }
+        r.model = r.k ? stream_shift(r.k) : shared_from_this();
+        return r;
+    }
 };
+
+// KZ_HIP_STREAM_SHIFT as the Rust shim reads it (hip.rs: StreamShift::from_env; read here, never by the library): unset or 0:
+// the network as trained; <k>: stream_shift(k); auto[:<headroom>]: the k its own positions ask for (auto_stream_shift).
+struct StreamShiftEnv {
+    bool automatic = false;
+    int k = 0, headroom_bits = 2;
+    static StreamShiftEnv parse(const char *v) {
+        StreamShiftEnv e;
+        if (!v) return e;
+        const std::string s(v);
+        const auto number = [&](const std::string &t, int &out) {
+            size_t used = 0;
+            try {
+                out = std::stoi(t, &used);
+            } catch (const std::exception &) {
+                used = 0;
+            }
+            if (t.empty() || used != t.size())
+                throw std::invalid_argument("KZ_HIP_STREAM_SHIFT must be an integer in [-24, 24] or auto[:<headroom bits>], got '" + s + "'");
+        };
+        if (s == "auto") e.automatic = true;
+        else if (s.rfind("auto:", 0) == 0) {
+            e.automatic = true;
+            number(s.substr(5), e.headroom_bits);
+        } else number(s, e.k);
+        return e;
+    }
+    static StreamShiftEnv from_env() { return parse(std::getenv("KZ_HIP_STREAM_SHIFT")); }
+};
+
+// the sample KZ_HIP_STREAM_SHIFT=auto profiles: process-wide, fed by every HipNetwork (the first 64 boards of every batch, the
+// most recent 16384 kept: 2 MB for chess)
+inline const std::shared_ptr<PositionSample> &process_position_sample() {
+    static const std::shared_ptr<PositionSample> sample = std::make_shared<PositionSample>(16384, 1, 64);
+    return sample;
+}
+
+// What the loader applies to every network it loads (server_hip.rs: load_graph).  The first network of a run, with no
+// positions sampled yet, stays unshifted.
+inline std::shared_ptr<const HipModel> stream_shift_from_env(std::shared_ptr<const HipModel> model, int device) {
+    const StreamShiftEnv e = StreamShiftEnv::from_env();
+    if (e.automatic) return model->auto_stream_shift(device, *process_position_sample(), e.headroom_bits).model;
+    return e.k ? model->stream_shift(e.k) : model;
+}
 
 template <class B, class M>
 class HipNetwork : public Network<B> {
@@ -199,6 +288,11 @@ class HipNetwork : public Network<B> {
     std::vector<uint8_t> sym_ids_;
     // every board under all n_sym_ symmetries, averaged inside the engine (set_average_symmetries)
     bool average_ = false;
+    // the boards just packed are offered to this sample (set_position_sample; null: off)
+    std::shared_ptr<PositionSample> sample_;
+    void offer_sample(size_t bits_bytes, size_t n) {
+        if (sample_) sample_->offer(bits_.data(), bits_bytes, scalars_in_.data(), n);
+    }
 
     // the decoded submit of a prepared batch; with symmetries on, every board gets an id of its own (symmetry.rs:47-52)
     void submit_decoded(int slot, size_t bits_bytes, size_t n) {
@@ -366,12 +460,13 @@ class HipNetwork : public Network<B> {
         if ((size_t)info.policy_len != mapper_.policy_len()) throw std::invalid_argument("Wrong policy shape");
         kz_check(kz_engine_create(model_->get(), device, (int)max_batch_size, dtype, &engine_));
         bits_.resize(max_batch_size * (size_t)info.bits_bytes);
+        if (StreamShiftEnv::from_env().automatic) set_position_sample(process_position_sample());
     }
     HipNetwork(HipNetwork &&o) noexcept
         : mapper_(o.mapper_), model_(std::move(o.model_)), engine_(o.engine_), max_batch_size_(o.max_batch_size_),
           bits_(std::move(o.bits_)), scalars_in_(std::move(o.scalars_in_)), next_slot_(o.next_slot_),
           oldest_slot_(o.oldest_slot_), in_flight_(o.in_flight_), device_decode_(o.device_decode_), n_sym_(o.n_sym_),
-          sym_rng_(o.sym_rng_), average_(o.average_), ranges_(std::move(o.ranges_)), helpers_(std::move(o.helpers_)), wait_cpu_ns(o.wait_cpu_ns),
+          sym_rng_(o.sym_rng_), average_(o.average_), sample_(std::move(o.sample_)), ranges_(std::move(o.ranges_)), helpers_(std::move(o.helpers_)), wait_cpu_ns(o.wait_cpu_ns),
           fell_back_boards(o.fell_back_boards) {
         for (int i = 0; i < KZ_ENGINE_SLOTS; i++) {
             pending_boards_[i] = std::move(o.pending_boards_[i]);
@@ -450,6 +545,15 @@ class HipNetwork : public Network<B> {
         device_decode_ = true;
     }
 
+    // evaluate_batch and submit_batch offer the boards they have just packed to `sample` (PositionSample: the first `take`
+    // boards of every `period`-th call, a memcpy) — what HipModel::auto_stream_shift profiles the next network on.  One sample
+    // for all executors of a process.  Off by default (null turns it off again); KZ_HIP_STREAM_SHIFT=auto turns it on with
+    // process_position_sample().
+    void set_position_sample(std::shared_ptr<PositionSample> sample) {
+        if (sample) sample->bind((size_t)model_->info.bits_bytes, (size_t)model_->info.input_scalar_channels);
+        sample_ = std::move(sample);
+    }
+
     // Helper threads for a batch's host work (encode_input, move lists): 0 = all of it on the calling executor thread like
     // the reference; 1 (hip.rs's default) halves what the executor thread does per batch.  Results are identical.
     void set_prep_helpers(size_t n) {
@@ -479,6 +583,7 @@ class HipNetwork : public Network<B> {
             return out;
         }
         const size_t bits_bytes = prepare(boards, n, device_decode_, &move_offsets_[0]);
+        offer_sample(bits_bytes, n);
         if (device_decode_) {
             const float *values = nullptr, *probs = nullptr;
             submit_decoded(0, bits_bytes, n);
@@ -507,6 +612,7 @@ class HipNetwork : public Network<B> {
         if (in_flight_ == KZ_ENGINE_SLOTS) throw std::logic_error("every engine slot is in flight");
         if (average_ && n * (size_t)n_sym_ > max_batch_size_) throw std::invalid_argument("an averaged batch is at most max_batch_size / n_sym boards");
         const size_t bits_bytes = prepare(boards, n, device_decode_, &move_offsets_[next_slot_]);
+        offer_sample(bits_bytes, n);
         // the engine copies its inputs to pinned staging before submit returns (include/kz_hip.h)
         if (device_decode_) {
             const uint64_t s0 = thread_cpu_ns();

@@ -197,9 +197,12 @@ static bool known_dtype(int dtype) {
     return dtype == KZ_DTYPE_F32 || dtype == KZ_DTYPE_F16 || dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16;
 }
 
-// kz_engine_create; profile: the range profile's internal engine (kz_model_range_profile) — exact f32 on the per-layer
-// implicit GEMM whatever plan_path would choose, no environment switch read, every stash site a range measurement
-static int create_engine(const kz_model *model, int device, int max_batch, int dtype, bool profile, kz_engine **out) {
+// kz_engine_create; profile: the range profile's internal engine — exact f32, no environment switch read, whatever plan_path
+// would choose.  per_layer (kz_model_range_profile): the per-layer implicit GEMM, every stash site a range measurement;
+// resident (kz_model_range_profile_fast where tower32_supported holds): the one-launch f32 tower without heads, whose
+// PROFILE instance measures in its epilogues — the same weight stream as an ordinary exact-f32 engine's (WeightsKey)
+enum class Profile { none, per_layer, resident };
+static int create_engine(const kz_model *model, int device, int max_batch, int dtype, Profile profile, kz_engine **out) {
     {
         if (!model || !out) return fail("kz_engine_create: null argument");
         if (max_batch <= 0) return fail("kz_engine_create: max_batch must be positive");
@@ -227,7 +230,7 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         HIP_TRY(hipSetDevice(device));
 
         std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(new kz_engine(), kz_engine_destroy);
-        e->model = profile ? model->m : effective_model(model, dtype_in, max_batch);
+        e->model = profile != Profile::none ? model->m : effective_model(model, dtype_in, max_batch);
         e->source_model = model->m;
         e->out_channels = model->m->channels;
         const Model &m = *e->model;
@@ -239,10 +242,14 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         e->cp = round_up(m.channels, 32);
         // which kernels run this network: plan_path (kz_plan.hpp) — the table of DESIGN.md §5 is printed from it
         std::string why;
-        if (profile) {
+        if (profile == Profile::per_layer) {
             e->plan = PathPlan();  // (Tower::conv_igemm)
             e->plan.keep = true;
             e->plan.launches = 2 + 2 * m.depth;
+        } else if (profile == Profile::resident) {
+            e->plan = PathPlan();
+            e->plan.tower = Tower::resident_f32;
+            e->plan.launches = 1;
         } else {
             if (!plan_path(m, max_batch, dtype_in, e->plan, why)) return fail("kz_engine_create: " + why);
             experiment_switches(m, dtype, e->cin_p, e->plan);
@@ -328,14 +335,14 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         if (e->dmalloc((void **)&devflag_base, (front + 4) * 4)) return 1;
         HIP_TRY(hipMemset(devflag_base, 0, (front + 4) * 4));
         e->d_devflag = devflag_base + front;
-        if (profile && e->dmalloc((void **)&e->range_out, (size_t)(2 * m.depth + 1) * max_batch * 4)) return 1;
+        if (profile != Profile::none && e->dmalloc((void **)&e->range_out, (size_t)(2 * m.depth + 1) * max_batch * 4)) return 1;
         *out = e.release();
         return 0;
     }
 }
 
 KZ_API int kz_engine_create(const kz_model *model, int device, int max_batch, int dtype, kz_engine **out) {
-    return guarded("kz_engine_create", [&]() -> int { return create_engine(model, device, max_batch, dtype, false, out); });
+    return guarded("kz_engine_create", [&]() -> int { return create_engine(model, device, max_batch, dtype, Profile::none, out); });
 }
 
 KZ_API int kz_model_supports_dtype(const kz_model *model, int dtype) {
@@ -416,56 +423,93 @@ KZ_API int kz_model_range_site_name(const kz_model *model, int site, char *buf, 
     });
 }
 
+// where kz_model_range_profile_fast runs: the one-launch exact-f32 tower wherever the kernel takes the shape
+static bool range_profile_resident(const Model &m) { return kz::tower32_supported(KZ_DTYPE_F32, m.h, m.w, m.channels, m.depth); }
+
+// both profile entries: an internal engine of `mode` with max_batch = min(batch, chunk_max), the boards in chunks of that
+static int range_profile(const std::string &fn, Profile mode, int chunk_max, const kz_model *model, int device, const uint8_t *bits,
+                         size_t bits_stride, const float *scalars_in, int batch, float *site_max_out, float *board_max_out) {
+    int n = 0;
+    if (range_site_count(fn.c_str(), model, n)) return 1;
+    const Model &m = *model->m;
+    if (m.n_scalar < 0)
+        return fail(fn + ": the model was loaded from ONNX without the scalar/bool plane split; load it with "
+                         "kz_model_load_onnx(path, input_scalar_channels) to use packed inputs");
+    if (batch < 1) return fail(fn + ": batch must be positive");
+    if (!bits || (m.n_scalar && !scalars_in) || !site_max_out) return fail(fn + ": null argument");
+    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
+    if (bits_stride < bits_bytes) return fail(fn + ": bits_stride too small");
+    const int chunk = std::min(batch, chunk_max);
+    kz_engine *raw = nullptr;
+    if (create_engine(model, device, chunk, KZ_DTYPE_F32, mode, &raw)) return 1;
+    std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(raw, kz_engine_destroy);
+    kz_engine::Slot &s = e->slots[0];
+    std::vector<float> host((size_t)n * chunk);
+    for (int i = 0; i < n; i++) site_max_out[i] = 0.0f;
+    // (the kernel's values are never NaN: a non-finite board reports +inf)
+    for (int lo = 0; lo < batch; lo += chunk) {
+        const int nb = std::min(chunk, batch - lo);
+        for (int b = 0; b < nb; b++) memcpy(s.h_bits + b * bits_bytes, bits + (size_t)(lo + b) * bits_stride, bits_bytes);
+        if (m.n_scalar) memcpy(s.h_sin, scalars_in + (size_t)lo * m.n_scalar, (size_t)nb * m.n_scalar * 4);
+        HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, nb * bits_bytes, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)nb * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
+        // the tower only: the heads read nothing the profile reports
+        e->arm(s);
+        const kz::PackedBoards in = e->packed_boards(s.d_bits, bits_bytes, s.d_sin);
+        if (mode == Profile::resident) {  // one launch: encode, tower and the maxima
+            if (e->run_tower(nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &in)) return 1;
+        } else {
+            if (e->launch("kz_encode_packed", [&] { kz::launch_encode_packed(e->dtype, in, nb, m.h * m.w, e->x_in, e->cin_p, e->stream); }))
+                return 1;
+            if (e->run_tower(nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+        }
+        if (e->range_site != n) return fail(fn + ": internal error: " + std::to_string(e->range_site) + " sites measured, " + std::to_string(n) + " expected");
+        HIP_TRY(hipMemcpyAsync(host.data(), e->range_out, host.size() * 4, hipMemcpyDeviceToHost, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        for (int b = 0; b < nb; b++) {
+            // behind a non-finite tensor the values are not the network's (ReLU turns a NaN into 0): the board reports +inf
+            // from its first non-finite site on
+            bool nonfinite = false;
+            for (int i = 0; i < n; i++) {
+                nonfinite = nonfinite || host[(size_t)i * chunk + b] == INFINITY;
+                const float v = nonfinite ? INFINITY : host[(size_t)i * chunk + b];
+                site_max_out[i] = std::max(site_max_out[i], v);
+                if (board_max_out && i < n - 1) board_max_out[lo + b] = i == 0 ? v : std::max(board_max_out[lo + b], v);
+            }
+        }
+    }
+    return 0;
+}
+
 KZ_API int kz_model_range_profile(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
                                   int batch, float *site_max_out, float *board_max_out) {
     return guarded("kz_model_range_profile", [&]() -> int {
-        const std::string fn = "kz_model_range_profile";
+        return range_profile("kz_model_range_profile", Profile::per_layer, 64, model, device, bits, bits_stride, scalars_in, batch,
+                             site_max_out, board_max_out);
+    });
+}
+
+KZ_API int kz_model_range_profile_fast(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride,
+                                       const float *scalars_in, int batch, float *site_max_out, float *board_max_out) {
+    return guarded("kz_model_range_profile_fast", [&]() -> int {
+        const std::string fn = "kz_model_range_profile_fast";
         int n = 0;
-        if (range_site_count("kz_model_range_profile", model, n)) return 1;
-        const Model &m = *model->m;
-        if (m.n_scalar < 0)
-            return fail(fn + ": the model was loaded from ONNX without the scalar/bool plane split; load it with "
-                             "kz_model_load_onnx(path, input_scalar_channels) to use packed inputs");
-        if (batch < 1) return fail(fn + ": batch must be positive");
-        if (!bits || (m.n_scalar && !scalars_in) || !site_max_out) return fail(fn + ": null argument");
-        const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
-        if (bits_stride < bits_bytes) return fail(fn + ": bits_stride too small");
-        const int chunk = std::min(batch, 64);
-        kz_engine *raw = nullptr;
-        if (create_engine(model, device, chunk, KZ_DTYPE_F32, true, &raw)) return 1;
-        std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(raw, kz_engine_destroy);
-        kz_engine::Slot &s = e->slots[0];
-        std::vector<float> host((size_t)n * chunk);
-        for (int i = 0; i < n; i++) site_max_out[i] = 0.0f;
-        // (the kernel's values are never NaN: a non-finite board reports +inf)
-        for (int lo = 0; lo < batch; lo += chunk) {
-            const int nb = std::min(chunk, batch - lo);
-            for (int b = 0; b < nb; b++) memcpy(s.h_bits + b * bits_bytes, bits + (size_t)(lo + b) * bits_stride, bits_bytes);
-            if (m.n_scalar) memcpy(s.h_sin, scalars_in + (size_t)lo * m.n_scalar, (size_t)nb * m.n_scalar * 4);
-            HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, nb * bits_bytes, hipMemcpyHostToDevice, e->stream));
-            HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)nb * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
-            // the tower only: the heads read nothing the profile reports
-            e->arm(s);
-            if (e->launch("kz_encode_packed", [&] {
-                    kz::launch_encode_packed(e->dtype, e->packed_boards(s.d_bits, bits_bytes, s.d_sin), nb, m.h * m.w, e->x_in, e->cin_p, e->stream);
-                }))
-                return 1;
-            if (e->run_tower(nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
-            if (e->range_site != n) return fail(fn + ": internal error: " + std::to_string(e->range_site) + " sites measured, " + std::to_string(n) + " expected");
-            HIP_TRY(hipMemcpyAsync(host.data(), e->range_out, host.size() * 4, hipMemcpyDeviceToHost, e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            for (int b = 0; b < nb; b++) {
-                // behind a non-finite tensor the values are not the network's (ReLU turns a NaN into 0): the board reports +inf
-                // from its first non-finite site on
-                bool nonfinite = false;
-                for (int i = 0; i < n; i++) {
-                    nonfinite = nonfinite || host[(size_t)i * chunk + b] == INFINITY;
-                    const float v = nonfinite ? INFINITY : host[(size_t)i * chunk + b];
-                    site_max_out[i] = std::max(site_max_out[i], v);
-                    if (board_max_out && i < n - 1) board_max_out[lo + b] = i == 0 ? v : std::max(board_max_out[lo + b], v);
-                }
-            }
-        }
+        if (range_site_count(fn.c_str(), model, n)) return 1;
+        // elsewhere (Go 19x19, other widths): exactly the per-layer profile
+        const bool resident = range_profile_resident(*model->m);
+        return range_profile(fn, resident ? Profile::resident : Profile::per_layer, resident ? 256 : 64, model, device, bits, bits_stride,
+                             scalars_in, batch, site_max_out, board_max_out);
+    });
+}
+
+KZ_API int kz_model_range_profile_fast_path(const kz_model *model, char *buf, size_t len) {
+    return guarded("kz_model_range_profile_fast_path", [&]() -> int {
+        int n = 0;
+        if (range_site_count("kz_model_range_profile_fast_path", model, n)) return 1;
+        const std::string name = range_profile_resident(*model->m) ? "tower_resident_f32" : "conv_igemm_f32";
+        if (!buf || len < name.size() + 1)
+            return fail("kz_model_range_profile_fast_path: buffer of at least " + std::to_string(name.size() + 1) + " bytes needed");
+        memcpy(buf, name.c_str(), name.size() + 1);
         return 0;
     });
 }

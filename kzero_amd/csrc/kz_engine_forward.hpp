@@ -150,6 +150,11 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.dense3 = plan.t32_dense3;
 #endif
         t.wide = plan.wide;
+        if (range_out) {  // the range profile's engine (resident_f32, no heads): the maxima instead of the tower output
+            t.profile = true;
+            t.y = range_out; t.ldy = max_batch;
+            range_site = 2 * m.depth + 1;  // every epilogue of the launch is a site
+        }
         const bool f16g = plan.tower == Tower::resident_f16g;
         if (launch(split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : "kz_tower_resident_f32", [&] {
                 if (split16()) kz::launch_tower_split(t, stream);

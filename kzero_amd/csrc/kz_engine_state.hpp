@@ -334,6 +334,8 @@ struct kz_engine {
     // the range profile (kz_model_range_profile): a profiling engine — exact f32 on the per-layer path, plan.keep set — takes
     // max |x| per board at every site where run_tower stashes, instead of the copy: range_out [n_sites][max_batch] in device
     // memory, range_site counts the sites of the running pass in stash order (kz_model_range_site_name's order)
+    // (kz_model_range_profile_fast's engine — the one-launch exact-f32 tower — hands range_out to the launch's PROFILE instance
+    // instead, which fills all of it: kz_engine_forward.hpp)
     float *range_out = nullptr;
     int range_site = 0;
 

@@ -347,6 +347,8 @@ struct Tower32Args {
     bool wide = false;    // launch_tower_pairs: twice the boards per workgroup (tower_split_wide_supported) — the engine's
                           // choice at max_batch; a launch whose own batch is too small for it takes the narrow tiles
     bool dense3 = false;  // launch_tower32, experiment build: three 7x7 boards per workgroup (tower32_dense3_supported)
+    bool profile = false; // launch_tower32: the range profile's instance — no heads, no tower output; `y` takes max |x| per
+                          // (site, board), [1 + 2*depth][ldy] with ldy counted in boards (>= batch)
     // launch_tower32 only: the conv policy head (Conv1x1 C->C + ReLU in the weight stream as one more centre-tap layer,
     // then Conv1x1 C->pc, post_act.py:75-110) and the scalar head (post_act.py:8-31) in the same launch — the tower
     // output never leaves LDS and `y` is not written.  tower32_heads_supported says for which models.

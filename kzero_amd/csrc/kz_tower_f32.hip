@@ -63,7 +63,7 @@ struct TowerF32Dev {
     const f32x4 *w;     // fragment-packed: stem steps, then 2*depth layers of 9*C/16 steps (tower32_pack_weights)
     const float *bias;  // [1 + 2*depth][C]
     const float *post_scale, *post_shift;  // final BN [C]
-    float *y;           // tower output [batch*hw][ldy]
+    float *y;           // tower output [batch*hw][ldy]; PROFILE: max |x| per (site, board), [1 + 2*depth][ldy boards]
     int ldx0, ldy, batch, h, w_, hw, depth, stem_groups, nb;
     unsigned inv_w, inv_hw;  // ceil(65536 / w), ceil(65536 / hw): exact quotients for values < 512
     PackedBoards in;  // fused board encode (in.bits != nullptr: x0 is not read)
@@ -81,8 +81,12 @@ struct TowerF32Dev {
 // DENSE: an image holds the workgroup's nb * hw pixel rows and nothing behind them (the rows that fill the last tile up
 // to 16 are not stored: as inputs they are zero rows, as outputs they are not written) — what makes room for THREE 7x7
 // boards (147 rows in ten tiles, 160 KB of LDS to the byte) where the padded image holds two (98 rows in seven tiles).
-template <int C, int NT, bool HEADS, bool DENSE = false>
+// PROFILE (the range profile, kz_model_range_profile_fast): every epilogue is one range site — 0 the stem, then the 2*depth
+// convolutions — and takes max |x| per board of what it stores (kz_range_absmax's rule: `bits & 0x7fffffff` as unsigned,
+// clamped to inf's pattern), one plain store per (site, board) into a.y; the tower output is not written.
+template <int C, int NT, bool HEADS, bool DENSE = false, bool PROFILE = false>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
+    static_assert(!PROFILE || (!HEADS && !DENSE), "the profile instances are the plain tower's");
     constexpr int OT = C / 64;           // 16-channel output tiles per wave
     constexpr int G = C / 16;            // steps per tap in a tower layer
     constexpr int ROWS = NT * 16;
@@ -99,6 +103,9 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
     const int rows_valid = boards * a.hw;
     const int rows_img = DENSE ? a.nb * a.hw : ROWS;  // rows an image holds
     const int IMG1 = IMG0 + rows_img * RS;
+    // PROFILE: per-row maxima of each wave's channels, [2][wave 4][ROWS] words behind the two images — double-buffered by
+    // layer, so that the reduction behind a layer's barrier needs no barrier of its own against the next epilogue
+    const int PMAX = IMG1 + rows_img * RS;
     KZ_STAMP(0);
 
     // zero rows; padding rows of image 0 (their outputs are never stored, but keep them finite)
@@ -178,7 +185,12 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
 #pragma unroll
     for (int nt = 0; nt < NT; nt++) wmask |= (unsigned)(nt * 16 + fr < rows_img) << nt;
     // [relu]; [+ residual from the out image, in place]; [final BN]; 16-byte stores into the out image
+    unsigned rowmax[NT];
     auto epilogue = [&](bool relu, bool residual, bool post) {
+        if constexpr (PROFILE) {
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) rowmax[nt] = 0;
+        }
 #pragma unroll
         for (int ot = 0; ot < OT; ot++) {
             const int oc = (wave * OT + ot) * 16 + kq * 4;
@@ -199,7 +211,35 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
                 if (residual) v += *slot;  // x + relu(bn(conv(.))) (post_act.py:227-228)
                 if (post) v = v * ps + pt;
                 *slot = v;
+                if constexpr (PROFILE) {
+#pragma unroll
+                    for (int j = 0; j < 4; j++) rowmax[nt] = max(rowmax[nt], __float_as_uint(v[j]) & 0x7fffffffu);
+                }
             }
+        }
+    };
+    // PROFILE, site `site`: the epilogue's maxima (a lane's OT tiles are in rowmax already) over the four kq groups, then
+    // per pixel row and wave into LDS ...
+    auto profile_rows = [&](int site) {
+        unsigned *part = reinterpret_cast<unsigned *>(lds + PMAX) + (site & 1) * 4 * ROWS + wave * ROWS;
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++) {
+            unsigned m = rowmax[nt];
+            m = max(m, (unsigned)__shfl_xor((int)m, 16));
+            m = max(m, (unsigned)__shfl_xor((int)m, 32));
+            if (kq == 0) part[nt * 16 + fr] = m;
+        }
+    };
+    // ... and, behind the layer's barrier, over a board's hw rows and the four waves: wave w takes boards w, w + 4, ...
+    // Only the rows of the workgroup's real boards are read: padding rows and the rows of a missing partner count nowhere.
+    auto profile_boards = [&](int site) {
+        const unsigned *part = reinterpret_cast<const unsigned *>(lds + PMAX) + (site & 1) * 4 * ROWS;
+        for (int b = wave; b < boards; b += 4) {
+            unsigned m = 0;
+            for (int i = lane; i < 4 * a.hw; i += 64) m = max(m, part[(i & 3) * ROWS + b * a.hw + (i >> 2)]);
+#pragma unroll
+            for (int off = 32; off; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
+            if (lane == 0) a.y[(size_t)site * a.ldy + board0 + b] = __uint_as_float(min(m, 0x7f800000u));
         }
     };
 
@@ -220,7 +260,9 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
             }
         }
         epilogue(false, false, a.depth == 0);
+        if constexpr (PROFILE) profile_rows(0);
         __syncthreads();
+        if constexpr (PROFILE) profile_boards(0);
         in = IMG1;
         out = IMG0;
     }
@@ -314,15 +356,19 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
         KZ_STAMP(3 * layer);
         const bool second = (layer & 1) == 0;  // the block's second conv: residual add, and the final BN on the last
         epilogue(true, second, second && layer == 2 * a.depth);
+        if constexpr (PROFILE) profile_rows(layer);
         KZ_STAMP(3 * layer + 1);
         __syncthreads();
+        if constexpr (PROFILE) profile_boards(layer);
         KZ_STAMP(3 * layer + 2);
         const int tmp = in;
         in = out;
         out = tmp;
     }
 
-    if constexpr (!HEADS) {
+    if constexpr (PROFILE) {
+        // (the maxima are the launch's whole output)
+    } else if constexpr (!HEADS) {
         // ---- the tower's output (the last `out`, now `in`) -> global, 16 bytes per lane, whole rows ----
         for (int i = tid; i < rows_valid * (C / 4); i += 256) {
             const int r = i / (C / 4), p = i - r * (C / 4);
@@ -344,10 +390,11 @@ int tiles_for(int hw, int channels) {
     return 0;
 }
 
-template <int C, int NT, bool HEADS, bool DENSE = false>
+template <int C, int NT, bool HEADS, bool DENSE = false, bool PROFILE = false>
 void launch1(const TowerF32Dev &d, int grid, hipStream_t stream) {
-    const int LDS_BYTES = (16 + 2 * (DENSE ? d.nb * d.hw : NT * 16)) * (C * 4 + 16);
-    allow_dynamic_lds<kz_tower_resident_f32<C, NT, HEADS, DENSE>>(LDS_BYTES);
+    const int LDS_BYTES = (16 + 2 * (DENSE ? d.nb * d.hw : NT * 16)) * (C * 4 + 16) + (PROFILE ? 2 * 4 * NT * 16 * 4 : 0);
+    static_assert(!PROFILE || (16 + 2 * NT * 16) * (C * 4 + 16) + 2 * 4 * NT * 16 * 4 <= 160 * 1024, "LDS of a workgroup");
+    allow_dynamic_lds<kz_tower_resident_f32<C, NT, HEADS, DENSE, PROFILE>>(LDS_BYTES);
 #ifdef KZ_T32_STAMPS
     static unsigned long long *stamp_buf = nullptr;
     static int launches = 0;
@@ -356,7 +403,7 @@ void launch1(const TowerF32Dev &d, int grid, hipStream_t stream) {
     TowerF32Dev ds = d;
     ds.stamps = stamp_buf;
     if (launches == 20) (void)hipMemsetAsync(stamp_buf, 0, stamp_bytes, stream);
-    kz_tower_resident_f32<C, NT, HEADS, DENSE><<<grid, 256, LDS_BYTES, stream>>>(ds);
+    kz_tower_resident_f32<C, NT, HEADS, DENSE, PROFILE><<<grid, 256, LDS_BYTES, stream>>>(ds);
     if (launches++ == 20 && getenv("KZ_T32_STAMP_FILE")) {
         (void)hipStreamSynchronize(stream);
         std::vector<unsigned long long> host(stamp_bytes / 8);
@@ -367,7 +414,7 @@ void launch1(const TowerF32Dev &d, int grid, hipStream_t stream) {
         }
     }
 #else
-    kz_tower_resident_f32<C, NT, HEADS, DENSE><<<grid, 256, LDS_BYTES, stream>>>(d);
+    kz_tower_resident_f32<C, NT, HEADS, DENSE, PROFILE><<<grid, 256, LDS_BYTES, stream>>>(d);
 #endif
 }
 
@@ -529,6 +576,13 @@ void launch_tower32(const Tower32Args &t, hipStream_t stream) {
     d.scalars = hd.scalars; d.policy = hd.policy; d.nonfinite_flag = hd.nonfinite_flag;
     d.dec = decode_dev(hd.decode, hd.on, hd.policy_len);
     const int grid = (t.batch + d.nb - 1) / d.nb;
+    if (t.profile) {  // the range profile's instances: no heads, y = the maxima [site][ldy boards]
+        if (t.channels == 256) launch1<256, 4, false, false, true>(d, grid, stream);
+        else if (nt == 7) launch1<128, 7, false, false, true>(d, grid, stream);
+        else if (nt == 6) launch1<128, 6, false, false, true>(d, grid, stream);
+        else launch1<128, 4, false, false, true>(d, grid, stream);
+        return;
+    }
     if (t.channels == 256) launch<256, 4>(d, hd.on, grid, stream);
 #ifdef KZ_EXPERIMENTS
     else if (nt == 10) launch<128, 10, true>(d, hd.on, grid, stream);

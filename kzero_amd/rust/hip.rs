@@ -30,7 +30,7 @@ use std::borrow::Borrow;
 use std::ffi::{c_char, c_int, c_void, CStr, CString};
 use std::fmt::{Debug, Formatter};
 use std::marker::PhantomData;
-use std::sync::Arc;
+use std::sync::{Arc, Mutex, OnceLock};
 
 use board_game::board::Board;
 use internal_iterator::InternalIterator;
@@ -119,6 +119,9 @@ extern "C" {
     fn kz_model_range_sites(model: *const c_void, n_sites: *mut c_int) -> c_int;
     fn kz_model_range_site_name(model: *const c_void, site: c_int, buf: *mut c_char, len: usize) -> c_int;
     fn kz_model_range_profile(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, site_max_out: *mut f32, board_max_out: *mut f32) -> c_int;
+    // ... the same profile inside the one-launch exact-f32 tower where that kernel takes the network, and which of the two it is
+    fn kz_model_range_profile_fast(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, site_max_out: *mut f32, board_max_out: *mut f32) -> c_int;
+    fn kz_model_range_profile_fast_path(model: *const c_void, buf: *mut c_char, len: usize) -> c_int;
     fn kz_engine_max_batch(engine: *const c_void) -> c_int;
     fn kz_engine_eval_dense(engine: *mut c_void, input_nchw: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
     fn kz_engine_eval_packed(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
@@ -272,16 +275,37 @@ impl HipModel {
 
     /// `KZ_HIP_STREAM_SHIFT=<k>` (default 0; read here, never by the library), what `load_graph` applies to every network it
     /// loads: choose k from a range profile of the network on its own positions (`range_profile`, `shift_for`;
-    /// tools/range_profile.py prints both).
+    /// tools/range_profile.py prints both) — or let `KZ_HIP_STREAM_SHIFT=auto[:<headroom bits>]` choose it per network
+    /// (`auto_stream_shift` on the process-wide `position_sample()`, which every `HipNetwork` then feeds).  The first
+    /// network of a run, with no positions sampled yet, gets k = 0: pair `auto` with `KZ_HIP_RANGE_FALLBACK=1` for it.
     pub fn stream_shift_from_env(self) -> HipModel {
-        match std::env::var("KZ_HIP_STREAM_SHIFT") {
-            Err(_) => self,
-            Ok(v) => match v.parse::<i32>() {
-                Ok(0) => self,
-                Ok(k) => self.stream_shift(k),
-                Err(_) => panic!("KZ_HIP_STREAM_SHIFT must be an integer in [-24, 24], got '{}'", v),
-            },
+        match StreamShift::from_env() {
+            StreamShift::Fixed(0) => self,
+            StreamShift::Fixed(k) => self.stream_shift(k),
+            StreamShift::Auto(headroom_bits) => {
+                let (shifted, k, max_abs, boards) = self.auto_stream_shift(position_sample(), headroom_bits);
+                eprintln!("kz_hip stream shift: k = {} (max |x| {:e} on {} sampled boards, {} bits of headroom)", k, max_abs, boards, headroom_bits);
+                shifted.unwrap_or(self)
+            }
         }
+    }
+
+    /// The shift this network needs on the positions of `sample` (the C++ mirror's `HipModel::auto_stream_shift`):
+    /// `range_profile_fast` on a snapshot — on the device whose executor offered last —, m = the largest board_max,
+    /// k = `shift_for(m, headroom_bits)`.  Returns (`stream_shift(k)`, or None for k == 0: keep this model; k; m; boards
+    /// profiled).  An empty sample gives k = 0 with boards = 0.  Panics when m is +inf: a network that overflows f32 is not
+    /// a shift's business.
+    pub fn auto_stream_shift(&self, sample: &PositionSample, headroom_bits: i32) -> (Option<HipModel>, i32, f32, usize) {
+        let snap = sample.snapshot();
+        if snap.boards == 0 {
+            return (None, 0, 0.0, 0);
+        }
+        assert_eq!((snap.bits_bytes, snap.n_scalar), (self.info.bits_bytes as usize, self.info.input_scalar_channels.max(0) as usize), "auto_stream_shift: the sample holds boards of another shape than this model's");
+        let (_, board_max) = self.range_profile_fast(snap.device, &snap.bits, snap.bits_bytes, &snap.scalars, snap.boards);
+        let max_abs = board_max.iter().cloned().fold(0f32, f32::max);
+        assert!(max_abs.is_finite(), "auto_stream_shift: the residual stream is not finite in exact f32 on the {} sampled boards: no shift brings such a network into range", snap.boards);
+        let k = shift_for(max_abs, headroom_bits);
+        (if k == 0 { None } else { Some(self.stream_shift(k)) }, k, max_abs, snap.boards)
     }
 
     /// The names of the range profile's sites, in order (`kz_model_range_sites`, `kz_model_range_site_name`).
@@ -309,6 +333,137 @@ impl HipModel {
         });
         (site_max, board_max)
     }
+
+    /// The same profile inside the one-launch exact-f32 tower where that kernel takes the network — tens of thousands of
+    /// boards per second — and exactly `range_profile` elsewhere (`kz_model_range_profile_fast`).
+    pub fn range_profile_fast(&self, device: HipDevice, bits: &[u8], bits_stride: usize, scalars_in: &[f32], batch: usize) -> (Vec<f32>, Vec<f32>) {
+        let mut n = 0;
+        check(unsafe { kz_model_range_sites(self.ptr, &mut n) });
+        assert!(bits.len() >= batch * bits_stride && scalars_in.len() >= batch * self.info.input_scalar_channels.max(0) as usize);
+        let (mut site_max, mut board_max) = (vec![0f32; n as usize], vec![0f32; batch]);
+        check(unsafe {
+            kz_model_range_profile_fast(self.ptr, device.0 as c_int, bits.as_ptr(), bits_stride, scalars_in.as_ptr(), batch as c_int, site_max.as_mut_ptr(), board_max.as_mut_ptr())
+        });
+        (site_max, board_max)
+    }
+
+    /// Where `range_profile_fast` runs: "tower_resident_f32" or "conv_igemm_f32" (`kz_model_range_profile_fast_path`; no GPU).
+    pub fn range_profile_fast_path(&self) -> String {
+        let mut buf = [0 as c_char; 32];
+        check(unsafe { kz_model_range_profile_fast_path(self.ptr, buf.as_mut_ptr(), buf.len()) });
+        unsafe { CStr::from_ptr(buf.as_ptr()) }.to_string_lossy().into_owned()
+    }
+}
+
+/// `KZ_HIP_STREAM_SHIFT`: `<k>` (an integer in [-24, 24]; unset = 0, the network as trained) or `auto[:<headroom bits>]`
+/// (default 2 bits).
+#[derive(Debug, Copy, Clone, Eq, PartialEq)]
+pub enum StreamShift {
+    Fixed(i32),
+    Auto(i32),
+}
+
+impl StreamShift {
+    pub fn parse(v: &str) -> StreamShift {
+        fn usage(v: &str) -> ! {
+            panic!("KZ_HIP_STREAM_SHIFT must be an integer in [-24, 24] or auto[:<headroom bits>], got '{}'", v)
+        }
+        if v == "auto" {
+            return StreamShift::Auto(2);
+        }
+        if let Some(bits) = v.strip_prefix("auto:") {
+            return StreamShift::Auto(bits.parse::<i32>().unwrap_or_else(|_| usage(v)));
+        }
+        StreamShift::Fixed(v.parse::<i32>().unwrap_or_else(|_| usage(v)))
+    }
+    pub fn from_env() -> StreamShift {
+        match std::env::var("KZ_HIP_STREAM_SHIFT") {
+            Err(_) => StreamShift::Fixed(0),
+            Ok(v) => StreamShift::parse(&v),
+        }
+    }
+}
+
+/// The most recent packed boards this process's executors have evaluated (the C++ mirror's host/position_sample.hpp is the
+/// tested statement): `offer` keeps the first `take` boards of every `period`-th call — the audit's deterministic prefix
+/// rule, a memcpy — in a ring of `capacity` boards; `snapshot` copies it out, oldest first.  One instance for all executors,
+/// so that a model is shifted once: a k per executor thread would mean a device weight copy per thread.
+pub struct PositionSample {
+    capacity: usize,
+    period: usize,
+    take: usize,
+    inner: Mutex<SampleRing>,
+}
+
+#[derive(Default)]
+struct SampleRing {
+    bits_bytes: usize,
+    n_scalar: usize,
+    head: usize,
+    size: usize,
+    calls: usize,
+    device: usize,
+    bits: Vec<u8>,
+    scalars: Vec<f32>,
+}
+
+pub struct SampleSnapshot {
+    pub bits: Vec<u8>,
+    pub scalars: Vec<f32>,
+    pub boards: usize,
+    pub bits_bytes: usize,
+    pub n_scalar: usize,
+    /// the device of the executor that offered last
+    pub device: HipDevice,
+}
+
+impl PositionSample {
+    pub fn with_capacity(capacity: usize, period: usize, take: usize) -> Self {
+        assert!(capacity >= 1 && period >= 1 && take >= 1);
+        PositionSample { capacity, period, take, inner: Mutex::new(SampleRing::default()) }
+    }
+
+    /// `batch` packed boards as an engine takes them; boards of another shape than the ones held (another game) empty the ring.
+    pub fn offer(&self, device: HipDevice, bits: &[u8], bits_bytes: usize, scalars: &[f32], n_scalar: usize, batch: usize) {
+        let mut r = self.inner.lock().unwrap();
+        if r.bits_bytes != bits_bytes || r.n_scalar != n_scalar || r.bits.len() != self.capacity * bits_bytes {
+            *r = SampleRing { bits_bytes, n_scalar, bits: vec![0; self.capacity * bits_bytes], scalars: vec![0.0; self.capacity * n_scalar], ..SampleRing::default() };
+        }
+        r.device = device.0;
+        r.calls += 1;
+        if (r.calls - 1) % self.period != 0 {
+            return;
+        }
+        for b in 0..self.take.min(batch) {
+            let at = (r.head + r.size) % self.capacity;
+            r.bits[at * bits_bytes..(at + 1) * bits_bytes].copy_from_slice(&bits[b * bits_bytes..(b + 1) * bits_bytes]);
+            r.scalars[at * n_scalar..(at + 1) * n_scalar].copy_from_slice(&scalars[b * n_scalar..(b + 1) * n_scalar]);
+            if r.size < self.capacity {
+                r.size += 1;
+            } else {
+                r.head = (r.head + 1) % self.capacity;
+            }
+        }
+    }
+
+    pub fn snapshot(&self) -> SampleSnapshot {
+        let r = self.inner.lock().unwrap();
+        let (bb, ns) = (r.bits_bytes, r.n_scalar);
+        let mut snap = SampleSnapshot { bits: Vec::with_capacity(r.size * bb), scalars: Vec::with_capacity(r.size * ns), boards: r.size, bits_bytes: bb, n_scalar: ns, device: HipDevice(r.device) };
+        for i in 0..r.size {
+            let at = (r.head + i) % self.capacity;
+            snap.bits.extend_from_slice(&r.bits[at * bb..(at + 1) * bb]);
+            snap.scalars.extend_from_slice(&r.scalars[at * ns..(at + 1) * ns]);
+        }
+        snap
+    }
+}
+
+/// The sample `KZ_HIP_STREAM_SHIFT=auto` profiles: process-wide, fed by every `HipNetwork` (the first 64 boards of every
+/// batch, the most recent 16384 kept: 2 MB for chess).
+pub fn position_sample() -> &'static PositionSample {
+    static SAMPLE: OnceLock<PositionSample> = OnceLock::new();
+    SAMPLE.get_or_init(|| PositionSample::with_capacity(16384, 1, 64))
 }
 
 /// The k of `HipModel::stream_shift` for a stream whose shifted sites reach `max_abs` (include/kz_hip.h):
@@ -384,6 +539,8 @@ pub struct HipNetwork<B: Board, M: BoardMapper<B>> {
     audit: bool,
     /// `KZ_HIP_PREP_THREADS` (default 0) + 1 ranges of a batch, each prepared by one thread (`prepare`)
     ranges: Vec<PrepRange>,
+    /// `KZ_HIP_STREAM_SHIFT=auto`: the boards `prepare` has just packed are offered to `position_sample()`, from this device
+    sample_from: Option<HipDevice>,
     ph: PhantomData<B>,
 }
 
@@ -520,6 +677,10 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
                 .min(8);
                 (0..helpers + 1).map(|_| PrepRange::default()).collect()
             },
+            sample_from: match StreamShift::from_env() {
+                StreamShift::Auto(_) => Some(device),
+                StreamShift::Fixed(_) => None,
+            },
             ph: PhantomData,
         }
     }
@@ -649,6 +810,9 @@ impl<B: Board, M: BoardMapper<B>> HipNetwork<B, M> {
             }
         }
         assert_eq!(self.scalars_in.len(), n * mapper.input_scalar_count());
+        if let Some(device) = self.sample_from {
+            position_sample().offer(device, &self.bits, bits_bytes, &self.scalars_in, mapper.input_scalar_count(), n);
+        }
         bits_bytes
     }
 

@@ -114,6 +114,9 @@ impl<B: Board + Hash, M: BoardMapper<B> + 'static> ZeroSpecialization<B, M> for 
     /// The ONNX path of `Command::NewNetwork` (protocol.rs:36) goes straight to the C ABI; the mapper supplies the one
     /// fact the graph does not carry (how many input planes are broadcast scalars).
     /// `KZ_HIP_STREAM_SHIFT=<k>` (default 0: the network as trained) shifts the residual stream by 2^-k here.
+    /// `KZ_HIP_STREAM_SHIFT=auto[:<headroom bits>]` chooses k for every network from an exact-f32 range profile on the
+    /// positions the executors have just evaluated (`HipModel::auto_stream_shift`, hip.rs); the first network of a run,
+    /// with none yet, stays unshifted.
     fn load_graph(&self, path: &str, mapper: M, _: &StartupSettings) -> HipModel {
         HipModel::load(path, mapper.input_scalar_count()).stream_shift_from_env()
     }

@@ -13,6 +13,12 @@ the positions of a position file (kzero_amd/position_file.py) or on synthetic bo
          rate on the four slots, both models in ONE process, interleaved timed regions, the median of --regions each — and the
          unshifted model's own max - min spread over its regions, the bar the difference has to clear.
 --profile-time  the wall time of the profile call itself (engine creation included), the median of 5 calls.
+--fast   the table from kz_model_range_profile_fast: the same profile inside the one-launch exact-f32 tower where that kernel
+         takes the network (the JSON names the path).  With --rate it is the PROFILE's rate that is measured instead of an
+         engine's: the fast entry against the per-layer entry on the same boards in one process, interleaved calls (engine
+         creation included), the median of 5 each, boards per second, and whether the fast call's median is below the other's.
+         --hold-f32 keeps an ordinary exact-f32 engine of the model alive meanwhile (what KZ_HIP_RANGE_FALLBACK=1 does in a
+         self-play run): the fast entry's internal engine then finds its weight stream in the cache instead of packing it.
 Prints one JSON object; --out writes it too.
 """
 import argparse
@@ -104,6 +110,28 @@ def rate(model, k, bits, scalars, moves, device, dtype, batch, regions, seconds)
     return out
 
 
+def profile_rate(model, bits, scalars, device, calls=5, hold_f32=False):
+    """Both profile entries on the same boards, interleaved: wall time per call (engine creation included) and boards/s."""
+    held = capi.Engine(model, device, 64, capi.KZ_DTYPE_F32) if hold_f32 else None
+    entries = {"fast": model.range_profile_fast, "per_layer": model.range_profile}
+    for fn in entries.values():  # (code objects loaded, weights packed once: what a second network of a run pays)
+        fn(device, bits, scalars)
+    times = {name: [] for name in entries}
+    for _ in range(calls):
+        for name, fn in entries.items():
+            t0 = time.perf_counter()
+            fn(device, bits, scalars)
+            times[name].append(time.perf_counter() - t0)
+    out = {"boards": len(bits), "calls": calls, "fast_path": model.range_profile_fast_path(),
+           "f32_engine_held": held.tower_path if held else None}
+    for name, t in times.items():
+        med = float(np.median(t))
+        out[name] = {"ms_median": round(1e3 * med, 3), "ms_min": round(1e3 * min(t), 3), "ms_max": round(1e3 * max(t), 3),
+                     "boards_per_s_median": round(len(bits) / med)}
+    out["fast_below_per_layer"] = out["fast"]["ms_median"] < out["per_layer"]["ms_median"]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", help="a KZMODEL1 container or an ONNX file")
@@ -121,6 +149,8 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--rate", action="store_true")
     ap.add_argument("--profile-time", action="store_true")
+    ap.add_argument("--fast", action="store_true", help="profile through kz_model_range_profile_fast; with --rate: the profile's own rate")
+    ap.add_argument("--hold-f32", action="store_true", help="--rate --fast: an exact-f32 engine of the model stays alive (shared weight stream)")
     ap.add_argument("--dtype", default="f16", choices=sorted(DTYPES))
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--regions", type=int, default=7)
@@ -147,7 +177,8 @@ def main():
         source = f"{args.boards} synthetic boards"
 
     sites = model.range_sites()
-    site_max, board_max = model.range_profile(args.device, bits, scalars)
+    profile = model.range_profile_fast if args.fast else model.range_profile
+    site_max, board_max = profile(args.device, bits, scalars)
     m = float(site_max[:-1].max())
     suggested = capi.shift_for(m, args.headroom) if np.isfinite(m) else None
     out = {"tool": "range_profile", "network": network, "boards": source,
@@ -155,6 +186,8 @@ def main():
                      for i, (s, v) in enumerate(zip(sites, site_max))],
            "stream_max": m, "boards_beyond_65504": int((board_max > capi.F16_MAX).sum()), "headroom_bits": args.headroom,
            "suggested_k": suggested}
+    if args.fast:
+        out["profile_path"] = model.range_profile_fast_path()
     print(f"# {network}, {source}", file=sys.stderr)
     print(f"# {'site':<14} {'max |x|':>14} {'of 65504':>10}", file=sys.stderr)
     for row in out["sites"]:
@@ -166,10 +199,13 @@ def main():
         times = []
         for _ in range(5):
             t0 = time.perf_counter()
-            model.range_profile(args.device, bits, scalars)
+            profile(args.device, bits, scalars)
             times.append(time.perf_counter() - t0)
         out["profile_call_ms"] = {"boards": len(bits), "median": round(1e3 * float(np.median(times)), 2), "min": round(1e3 * min(times), 2),
                                   "max": round(1e3 * max(times), 2)}
+    if args.rate and args.fast:
+        out["profile_rate"] = profile_rate(model, bits, scalars, args.device, hold_f32=args.hold_f32)
+        args.rate = False
     k = args.k if args.k is not None else suggested
     if args.check or args.rate:
         assert k is not None, "the stream is not finite on these boards: no shift repairs that"
