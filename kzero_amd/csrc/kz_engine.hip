@@ -162,7 +162,7 @@ KZ_API int kz_model_get_info(const kz_model *model, kz_model_info *out) {
         out->tower_depth = m.depth;
         out->tower_channels = m.channels;
         out->policy_kind = (int)m.policy_kind;
-        out->bits_bytes = m.n_bool < 0 ? -1 : (m.n_bool * m.h * m.w + 7) / 8;
+        out->bits_bytes = m.n_bool < 0 ? -1 : (int)bits_bytes(m);
         out->param_count = m.param_count;
         out->flops_per_eval = m.flops_per_eval;
         return 0;
@@ -290,7 +290,6 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         if (too_large(std::max(h0, h1) * e->esz / max_batch)) return 1;
 
         HIP_TRY(hipStreamCreateWithFlags(&e->slot_stream[0], hipStreamNonBlocking));
-        e->stream = e->slot_stream[0];
         if (plan.heads) {  // one launch per batch that touches nothing but its slot's buffers
             HIP_TRY(hipStreamCreateWithFlags(&e->slot_stream[1], hipStreamNonBlocking));
             for (int i = 2; i < KZ_ENGINE_SLOTS; i++) e->slot_stream[i] = e->slot_stream[i & 1];
@@ -432,13 +431,10 @@ static int range_profile(const std::string &fn, Profile mode, int chunk_max, con
     int n = 0;
     if (range_site_count(fn.c_str(), model, n)) return 1;
     const Model &m = *model->m;
-    if (m.n_scalar < 0)
-        return fail(fn + ": the model was loaded from ONNX without the scalar/bool plane split; load it with "
-                         "kz_model_load_onnx(path, input_scalar_channels) to use packed inputs");
+    if (m.n_scalar < 0) return fail(no_plane_split(fn));
     if (batch < 1) return fail(fn + ": batch must be positive");
     if (!bits || (m.n_scalar && !scalars_in) || !site_max_out) return fail(fn + ": null argument");
-    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
-    if (bits_stride < bits_bytes) return fail(fn + ": bits_stride too small");
+    if (bits_stride < bits_bytes(m)) return fail(fn + ": bits_stride too small");
     const int chunk = std::min(batch, chunk_max);
     kz_engine *raw = nullptr;
     if (create_engine(model, device, chunk, KZ_DTYPE_F32, mode, &raw)) return 1;
@@ -449,23 +445,21 @@ static int range_profile(const std::string &fn, Profile mode, int chunk_max, con
     // (the kernel's values are never NaN: a non-finite board reports +inf)
     for (int lo = 0; lo < batch; lo += chunk) {
         const int nb = std::min(chunk, batch - lo);
-        for (int b = 0; b < nb; b++) memcpy(s.h_bits + b * bits_bytes, bits + (size_t)(lo + b) * bits_stride, bits_bytes);
-        if (m.n_scalar) memcpy(s.h_sin, scalars_in + (size_t)lo * m.n_scalar, (size_t)nb * m.n_scalar * 4);
-        HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, nb * bits_bytes, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)nb * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
+        e->stage_boards(s, bits + (size_t)lo * bits_stride, bits_stride, m.n_scalar ? scalars_in + (size_t)lo * m.n_scalar : nullptr, nb);
+        const Pass p = e->pass_staged(0);
+        if (e->copy_boards_in(p, s, nb)) return 1;
         // the tower only: the heads read nothing the profile reports
-        e->arm(s);
-        const kz::PackedBoards in = e->packed_boards(s.d_bits, bits_bytes, s.d_sin);
+        const kz::PackedBoards in = e->packed_boards(s.d_bits, e->bits_bytes(), s.d_sin);
         if (mode == Profile::resident) {  // one launch: encode, tower and the maxima
-            if (e->run_tower(nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &in)) return 1;
+            if (e->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &in)) return 1;
         } else {
-            if (e->launch("kz_encode_packed", [&] { kz::launch_encode_packed(e->dtype, in, nb, m.h * m.w, e->x_in, e->cin_p, e->stream); }))
+            if (e->launch(p, "kz_encode_packed", [&] { kz::launch_encode_packed(e->dtype, in, nb, m.h * m.w, e->x_in, e->cin_p, p.stream); }))
                 return 1;
-            if (e->run_tower(nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+            if (e->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
         }
         if (e->range_site != n) return fail(fn + ": internal error: " + std::to_string(e->range_site) + " sites measured, " + std::to_string(n) + " expected");
-        HIP_TRY(hipMemcpyAsync(host.data(), e->range_out, host.size() * 4, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
+        HIP_TRY(hipMemcpyAsync(host.data(), e->range_out, host.size() * 4, hipMemcpyDeviceToHost, p.stream));
+        HIP_TRY(hipStreamSynchronize(p.stream));
         for (int b = 0; b < nb; b++) {
             // behind a non-finite tensor the values are not the network's (ReLU turns a NaN into 0): the board reports +inf
             // from its first non-finite site on
@@ -553,18 +547,9 @@ KZ_API int kz_engine_launch_geometry(const kz_engine *e, int batch, int *workgro
 }
 
 static int check_packed(const kz_engine *e, const char *fn) {
-    if (e && e->model->n_scalar < 0)
-        return fail(std::string(fn) + ": the model was loaded from ONNX without the scalar/bool plane split; load it "
-                                      "with kz_model_load_onnx(path, input_scalar_channels) to use packed inputs");
+    if (e && e->model->n_scalar < 0) return fail(no_plane_split(fn));
     return 0;
 }
-
-// a submit runs on its slot's stream (when the slot has one) and puts the engine's own back when it returns
-struct StreamSwap {
-    kz_engine *e;
-    hipStream_t saved;
-    ~StreamSwap() { e->stream = saved; }
-};
 
 static int check_batch(const kz_engine *e, int batch, const char *fn) {
     if (!e) return fail(std::string(fn) + ": null engine");
@@ -574,94 +559,61 @@ static int check_batch(const kz_engine *e, int batch, const char *fn) {
     return 0;
 }
 
-KZ_API int kz_engine_submit_packed(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
-                                   const float *scalars_in, int batch) {
-    return guarded("kz_engine_submit_packed", [&]() -> int {
-        if (check_batch(e, batch, "kz_engine_submit_packed") || check_packed(e, "kz_engine_submit_packed")) return 1;
-        if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail("kz_engine_submit_packed: bad slot");
-        kz_engine::Slot &s = e->slots[slot];
-        if (s.batch >= 0) return fail("kz_engine_submit_packed: slot still in flight (call kz_engine_wait first)");
-        const Model &m = *e->model;
-        const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
-        if (batch > 0 && (!bits || (m.n_scalar && !scalars_in))) return fail("kz_engine_submit_packed: null input");
-        if (batch > 0 && bits_stride < bits_bytes) return fail("kz_engine_submit_packed: bits_stride too small");
-        HIP_TRY(hipSetDevice(e->device));
-        if (batch == 0) {
-            s.batch = 0;
-            return 0;
-        }
-        for (int b = 0; b < batch; b++) memcpy(s.h_bits + b * bits_bytes, bits + b * bits_stride, bits_bytes);
-        if (m.n_scalar) memcpy(s.h_sin, scalars_in, (size_t)batch * m.n_scalar * 4);
-        // on the fused path every slot has its own stream, so two submitted batches run side by side (each resident
-        // launch covers half of the CUs at batch 256); otherwise the slots share the activation buffers and one stream
-        StreamSwap swap{e, e->stream};
-        if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
-        if (e->zero_copy) {
-            // the one launch reads 136 B per board from pinned host memory and writes its 7.5 KB per board there
-            e->arm(s);
-            e->nf_flag = reinterpret_cast<int *>(s.h_sout);
-            if (e->forward_packed(e->packed_boards(s.h_bits, bits_bytes, s.h_sin), batch, s.h_sout + kz_engine::SOUT_HDR, s.h_pol)) return 1;
-            HIP_TRY(hipEventRecord(s.done, e->stream));
-            s.batch = batch;
-            return 0;
-        }
-        HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, batch * bits_bytes, hipMemcpyHostToDevice, e->stream));
-        HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)batch * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
-    #ifdef KZ_EXPERIMENTS
-        if (e->graph_mode()) {
-            s.epoch = kz_engine::GRAPH_EPOCH;
-            e->nf_flag = reinterpret_cast<int *>(s.d_sout);
-            e->nf_epoch = s.epoch;
-            if (e->replay(slot, batch, s.d_bits, bits_bytes, s.d_sin, s.d_sout, s.d_pol, [&]() -> int {
-                    HIP_TRY(hipMemsetAsync(s.d_sout - e->front_words(), 0, ((size_t)e->front_words() + 1) * 4, e->stream));
-                    return e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol);
-                }))
-                return 1;
-        } else
-    #endif
-        {
-            e->arm(s);
-            if (e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
-    #ifdef KZ_EXPERIMENTS
-            e->graph_warm = true;  // (the first pass runs eagerly: lazy per-kernel set-up must not land in a capture)
-    #endif
-        }
-        // (one copy: the batch's per-board range words, the header, the scalars)
-        HIP_TRY(hipMemcpyAsync(s.h_sout - batch, s.d_sout - batch, ((size_t)batch * 6 + kz_engine::SOUT_HDR) * 4, hipMemcpyDeviceToHost,
-                               e->stream));
-        HIP_TRY(hipMemcpyAsync(s.h_pol, s.d_pol, (size_t)batch * m.policy_len * 4, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipEventRecord(s.done, e->stream));
-        s.batch = batch;  // in flight only once the event is recorded: a failed submit leaves the slot free
-        return 0;
-    });
+static int slot_of(const std::string &fn, kz_engine *e, int slot, kz_engine::Slot *&s) {
+    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(fn + ": bad slot");
+    s = &e->slots[slot];
+    return 0;
 }
+
+// what both averaged entries check first: tables set, batch * n_sym within max_batch
+static int check_avg(const char *name, const kz_engine *e, int batch) {
+    const std::string fn = name;
+    if (!e) return fail(fn + ": null engine");
+    if (check_packed(e, name)) return 1;
+    if (!e->n_sym) return fail(fn + ": no tables set (call kz_engine_set_symmetries first)");
+#ifdef KZ_EXPERIMENTS
+    if (e->plan.nb4) return fail(fn + ": the four-board experiment launch takes no symmetry ids");
+#endif
+    const int n = e->n_sym, limit = e->max_batch / n;
+    if (batch < 0 || batch > limit)
+        return fail(fn + ": batch " + std::to_string(batch) + " exceeds max_batch / n_sym = " + std::to_string(limit) + " (" +
+                    std::to_string(n) + " symmetries: the network runs on batch * n_sym boards, max_batch " + std::to_string(e->max_batch) + ")");
+    return 0;
+}
+
+// The host-pointer entries by what they submit (`decoded` with ids is the `_sym` entry), and what each checks first.
+enum class Entry { raw, decoded, averaged };
+static int check_entry(const char *fn, Entry kind, const kz_engine *e, int batch) {
+    return kind == Entry::averaged ? check_avg(fn, e, batch) : check_batch(e, batch, fn) || check_packed(e, fn);
+}
+static int submit(const char *name, Entry kind, kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                  int batch, const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices);  // (below)
 
 // ------------------------------------------------------------------------------------------------
 // Per-board status (KZ_BOARD_*) and the range fallback: what the calls that return a batch do once its event has been waited for
 // ------------------------------------------------------------------------------------------------
-// The status of the first `batch` boards of a finished slot, from the per-board words the launches wrote (kz_kernels.hpp),
-// into s.status.  Where this batch's range words are: in front of the slot's pinned header when its results came through that
-// header — raw rows, or a decode inside the launch (an averaged launch's words count VIRTUAL boards: kz_sym_average has folded
-// them) —, and beside the decode's words otherwise (kz_decode_output / kz_sym_average copied them there).
-static void board_status(kz_engine::Slot &s, int batch, bool decoded) {
+// The status of the boards of a finished batch `f` of slot `s`, from the per-board words the launches wrote (kz_kernels.hpp),
+// into s.status: the decode's words, and the range words in front of the pinned header where they are this batch's
+// (InFlight::words_in_front).
+static void board_status(kz_engine::Slot &s, const InFlight &f) {
     const int *nf = reinterpret_cast<const int *>(s.h_sout);
-    const bool nf_front = !decoded || (s.in_launch && !s.avg);
-    for (int b = 0; b < batch; b++) {
+    const bool front = f.words_in_front();
+    for (int b = 0; b < f.batch; b++) {
         uint8_t st = KZ_BOARD_OK;
-        if (decoded) {
+        if (f.is_decoded()) {
             if (s.h_err[kz::ERR_HDR + 2 * b]) st |= KZ_BOARD_BAD_DECODE;
             if (s.h_err[kz::ERR_HDR + 2 * b + 1]) st |= KZ_BOARD_NONFINITE;
         }
-        if (nf_front && nf[-1 - b] == s.epoch) st |= KZ_BOARD_NONFINITE;
+        if (front && nf[-1 - b] == f.epoch) st |= KZ_BOARD_NONFINITE;
         s.status[b] = st;
     }
 }
 
-// `n` boards of a slot's pinned input staging, picked by index into one contiguous batch for a sibling's submit: bits, scalars
-// and — decoded — the CSR move lists, with the symmetry ids when `ids`.  The one gather of the range fallback and the audit.
-static void gather_boards(const kz_engine *e, const kz_engine::Slot &s, const int *boards, int n, bool decoded, bool ids, BoardGather &g) {
-    const Model &m = *e->model;
-    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8, ns = (size_t)std::max(m.n_scalar, 0);
+// `n` boards of batch `f` in slot `s`'s pinned input staging, picked by index into one contiguous batch for a sibling's submit:
+// bits, scalars and — decoded — the CSR move lists, with the symmetry ids where they travel.  The one gather of the range
+// fallback and the audit.
+static void gather_boards(const kz_engine *e, const kz_engine::Slot &s, const InFlight &f, const int *boards, int n, BoardGather &g) {
+    const size_t bits_bytes = e->bits_bytes(), ns = (size_t)std::max(e->model->n_scalar, 0);
     g.bits.resize((size_t)n * bits_bytes);
     g.sin.resize((size_t)n * ns);
     g.sym.resize((size_t)n);
@@ -671,54 +623,59 @@ static void gather_boards(const kz_engine *e, const kz_engine::Slot &s, const in
         const int b = boards[i];
         memcpy(g.bits.data() + (size_t)i * bits_bytes, s.h_bits + (size_t)b * bits_bytes, bits_bytes);
         if (ns) memcpy(g.sin.data() + (size_t)i * ns, s.h_sin + (size_t)b * ns, ns * 4);
-        if (!decoded) continue;
-        if (ids) g.sym[i] = s.h_sym[b];
+        if (!f.is_decoded()) continue;
+        if (f.ids_travel()) g.sym[i] = s.h_sym[b];
         if (s.h_moff[b + 1] > s.h_moff[b]) g.midx.insert(g.midx.end(), s.h_midx + s.h_moff[b], s.h_midx + s.h_moff[b + 1]);
         g.moff.push_back((int64_t)g.midx.size());
     }
     g.midx.push_back(0);  // (never read: a non-null pointer for an empty list)
 }
 
-// A gathered batch submitted to slot `slot` of sibling `f` through the entry that matches the slot's own submit: raw rows,
-// decoded with the same symmetry ids (or none), or averaged.
-static int submit_gathered(kz_engine *e, const kz_engine::Slot &s, kz_engine *f, int slot, int n, bool decoded, const BoardGather &g) {
-    const Model &m = *e->model;
-    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
-    if (!decoded) return kz_engine_submit_packed(f, slot, g.bits.data(), bits_bytes, g.sin.data(), n);
-    if (s.avg) return kz_engine_submit_packed_decoded_avg(f, slot, g.bits.data(), bits_bytes, g.sin.data(), n, g.moff.data(), g.midx.data());
-    return kz_engine_submit_packed_decoded_sym(f, slot, g.bits.data(), bits_bytes, g.sin.data(), n, s.with_sym ? g.sym.data() : nullptr,
-                                               g.moff.data(), g.midx.data());
+// A gathered batch submitted to slot `slot` of sibling `sib` as the entry that matches batch `f`'s own would: raw rows, decoded
+// with the same symmetry ids (or none), or averaged.
+static int submit_gathered(kz_engine *sib, int slot, const InFlight &f, int n, const BoardGather &g) {
+    const Entry kind = !f.is_decoded() ? Entry::raw : f.avg ? Entry::averaged : Entry::decoded;
+    const char *name = kind == Entry::raw        ? "kz_engine_submit_packed"
+                       : kind == Entry::averaged ? "kz_engine_submit_packed_decoded_avg"
+                                                 : "kz_engine_submit_packed_decoded_sym";
+    return guarded(name, [&]() -> int {
+        return submit(name, kind, sib, slot, g.bits.data(), sib->bits_bytes(), g.sin.data(), n, f.ids_travel() ? g.sym.data() : nullptr,
+                      g.moff.data(), g.midx.data());
+    });
 }
 
-// The boards of a finished slot that carry KZ_BOARD_NONFINITE, re-evaluated through the sibling engine's matching entry (raw
+// A sibling's slot is waited for through its event, not through the sibling's entries: its per-board verdict is what is wanted
+// (in fs.status; the results stay in its pinned staging).
+static int wait_sibling(kz_engine::Slot &fs) {
+    const InFlight f = fs.take();
+    HIP_TRY(hipEventSynchronize(fs.done));
+    board_status(fs, f);
+    return 0;
+}
+
+// The boards of a finished batch that carry KZ_BOARD_NONFINITE, re-evaluated through the sibling engine's matching entry (raw
 // rows, decoded with the same symmetry ids, or averaged) from the slot's pinned input staging, in chunks of the sibling's
 // max_batch; its results go over those boards' rows and ranges of the slot's output staging and their status becomes
 // KZ_BOARD_FELL_BACK (a board still bad in exact f32 keeps its bits beside it).  Host-driven, inside the returning call.
-static int range_fallback(kz_engine *e, kz_engine::Slot &s, int batch, bool decoded) {
-    kz_engine *f = e->fallback;
+static int range_fallback(kz_engine *e, kz_engine::Slot &s, const InFlight &f) {
+    kz_engine *sib = e->fallback;
     std::vector<int> bad;
-    for (int b = 0; b < batch; b++)
+    for (int b = 0; b < f.batch; b++)
         if (s.status[b] & KZ_BOARD_NONFINITE) bad.push_back(b);
     if (bad.empty()) return 0;
     const size_t plen = (size_t)e->model->policy_len;
-    const bool avg = decoded && s.avg;
-    const size_t per = avg ? (size_t)(f->max_batch / std::max(e->n_sym, 1)) : (size_t)f->max_batch;
+    const size_t per = f.avg ? (size_t)(sib->max_batch / std::max(e->n_sym, 1)) : (size_t)sib->max_batch;
     if (per < 1) return 0;  // (more symmetries than the sibling holds boards: such an averaged batch keeps its verdict)
-    kz_engine::Slot &fs = f->slots[0];
+    kz_engine::Slot &fs = sib->slots[0];
     BoardGather g;
     for (size_t lo = 0; lo < bad.size(); lo += per) {
         const int n = (int)std::min(per, bad.size() - lo);
-        gather_boards(e, s, bad.data() + lo, n, decoded, s.with_sym && !avg, g);
-        if (submit_gathered(e, s, f, 0, n, decoded, g)) return 1;
+        gather_boards(e, s, f, bad.data() + lo, n, g);
+        if (submit_gathered(sib, 0, f, n, g) || wait_sibling(fs)) return 1;
         const std::vector<int64_t> &moff = g.moff;
-        // the sibling's slot is waited for here, not through its entries: its per-board verdict is what is wanted
-        fs.batch = -1;
-        fs.decoded = false;
-        HIP_TRY(hipEventSynchronize(fs.done));
-        board_status(fs, n, decoded);
         for (int i = 0; i < n; i++) {
             const int b = bad[lo + i];
-            if (!decoded) {
+            if (!f.is_decoded()) {
                 memcpy(s.h_sout + kz_engine::SOUT_HDR + (size_t)b * 5, fs.h_sout + kz_engine::SOUT_HDR + (size_t)i * 5, 20);
                 memcpy(s.h_pol + (size_t)b * plen, fs.h_pol + (size_t)i * plen, plen * 4);
             } else {
@@ -736,35 +693,31 @@ static int range_fallback(kz_engine *e, kz_engine::Slot &s, int batch, bool deco
 // The shadow audit (kz_engine_set_audit): a sample of the decoded batches, evaluated a second time by a sibling engine in a
 // <= 1e-4 arithmetic and compared on the host.  Nothing of the batch itself is touched.
 // ------------------------------------------------------------------------------------------------
-// The tail of every decoded submit while the audit is on, once the batch's own launches are enqueued and the slot is in
-// flight: counts the submit and, every period-th time, hands the first k boards of the slot's input staging to the sibling's
-// slot of the same index, where they run on the sibling's own stream beside the batch.  A failing sibling submit fails this
-// submit with the sibling's message, and the slot is free again.
-static int audit_submit(kz_engine *e, int slot) {
+// The tail of every decoded submit while the audit is on, once the batch's own launches and event are enqueued and before its
+// record `f` goes into the slot: counts the submit and, every period-th time, hands the first k boards of the slot's input
+// staging to the sibling's slot of the same index, where they run on the sibling's own stream beside the batch; f.audit_k = k.
+// A failing sibling submit fails this submit with the sibling's message, and the slot stays free.
+static int audit_submit(kz_engine *e, int slot, InFlight &f) {
     kz_engine::Audit &a = *e->audit;
     kz_engine::Slot &s = e->slots[slot];
-    s.audit_k = 0;
     if (a.submits++ % a.period) return 0;
-    int k = std::min(a.boards, s.batch);
-    if (s.avg) k = std::min(k, a.sibling->max_batch / std::max(e->n_sym, 1));
+    int k = std::min(a.boards, f.batch);
+    if (f.avg) k = std::min(k, a.sibling->max_batch / std::max(e->n_sym, 1));
     if (k < 1) return 0;
     kz_engine::Slot &fs = a.sibling->slots[slot];
-    if (fs.batch >= 0) {  // (left behind by a returning call that failed before its comparison)
+    if (fs.fly.busy()) {  // (left behind by a returning call that failed before its comparison)
         (void)hipEventSynchronize(fs.done);
-        fs.batch = -1;
-        fs.decoded = false;
+        fs.take();
     }
     std::vector<int> &first = a.first;
     if ((int)first.size() < k)
         for (int b = (int)first.size(); b < k; b++) first.push_back(b);
-    gather_boards(e, s, first.data(), k, true, s.with_sym && !s.avg, a.gather);
-    if (submit_gathered(e, s, a.sibling, slot, k, true, a.gather)) {
-        (void)hipEventSynchronize(s.done);
-        s.batch = -1;
-        s.decoded = false;
+    gather_boards(e, s, f, first.data(), k, a.gather);
+    if (submit_gathered(a.sibling, slot, f, k, a.gather)) {
+        (void)hipEventSynchronize(s.done);  // (the batch's own launches still use the staging of the slot that stays free)
         return 1;
     }
-    s.audit_k = k;
+    f.audit_k = k;
     return 0;
 }
 
@@ -774,21 +727,15 @@ static void audit_accumulate(float engine, float sibling, float &max_abs, double
     sum_sq += (double)d * (double)d;
 }
 
-// The returning call's half, after the status and the fallback: waits for the sibling's slot (its event, not its entries: the
-// per-board verdict is wanted), then compares the boards whose status is 0 on both sides, in batch order — the five values,
-// then the probabilities in the caller's move order.
-static int audit_compare(kz_engine *e, kz_engine::Slot &s) {
+// The returning call's half, after the status and the fallback: waits for the sibling's slot, then compares the boards whose
+// status is 0 on both sides, in batch order — the five values, then the probabilities in the caller's move order.
+static int audit_compare(kz_engine *e, kz_engine::Slot &s, const InFlight &f) {
     kz_engine::Audit &a = *e->audit;
-    const int k = s.audit_k;
-    s.audit_k = 0;
     kz_engine::Slot &fs = a.sibling->slots[&s - e->slots];
-    fs.batch = -1;
-    fs.decoded = false;
-    HIP_TRY(hipEventSynchronize(fs.done));
-    board_status(fs, k, true);
+    if (wait_sibling(fs)) return 1;
     kz_audit_stats &st = a.stats;
     st.batches++;
-    for (int b = 0; b < k; b++) {
+    for (int b = 0; b < f.audit_k; b++) {
         if (s.status[b] != KZ_BOARD_OK || fs.status[b] != KZ_BOARD_OK) {
             st.skipped++;
             continue;
@@ -802,22 +749,22 @@ static int audit_compare(kz_engine *e, kz_engine::Slot &s) {
     return 0;
 }
 
-// What every call that returns a batch does after the slot's event: the per-board status, the fallback where it is on, and —
-// judge = true, the entries without a status output — the verdict those entries have always given, with their messages.
-// Without a fell-back board the verdict is read from the per-batch words exactly as before; with one, from the boards' status
-// (the per-batch words still hold what the replaced results raised).
-static int finish_batch(const char *name, kz_engine *e, kz_engine::Slot &s, int batch, bool decoded, bool judge) {
+// What every call that returns a batch does after the slot's event, with the record it took from the slot: the per-board
+// status, the fallback where it is on, and — judge = true, the entries without a status output — the verdict those entries
+// have always given, with their messages.  Without a fell-back board the verdict is read from the per-batch words exactly as
+// before; with one, from the boards' status (the per-batch words still hold what the replaced results raised).
+static int finish_batch(const char *name, kz_engine *e, kz_engine::Slot &s, const InFlight &f, bool judge) {
     const std::string fn = name;
-    board_status(s, batch, decoded);
-    if (e->fallback && range_fallback(e, s, batch, decoded)) return 1;
-    if (e->audit && decoded && s.audit_k && audit_compare(e, s)) return 1;
+    board_status(s, f);
+    if (e->fallback && range_fallback(e, s, f)) return 1;
+    if (e->audit && f.audit_k && audit_compare(e, s, f)) return 1;
     if (!judge) return 0;
     const auto softmax_message = [&] {
         return fn + ": Softmax input sum must be strictly positive (or a move index is out of range" +
-               (s.with_sym ? ", a symmetry id is not below n_sym, or a listed move has no image under its board's symmetry)" : ")");
+               (f.symmetries_involved() ? ", a symmetry id is not below n_sym, or a listed move has no image under its board's symmetry)" : ")");
     };
     bool fell_back = false, nonfinite = false, bad_decode = false;
-    for (int b = 0; b < batch; b++) {
+    for (int b = 0; b < f.batch; b++) {
         fell_back |= (s.status[b] & KZ_BOARD_FELL_BACK) != 0;
         nonfinite |= (s.status[b] & KZ_BOARD_NONFINITE) != 0;
         bad_decode |= (s.status[b] & KZ_BOARD_BAD_DECODE) != 0;
@@ -827,67 +774,23 @@ static int finish_batch(const char *name, kz_engine *e, kz_engine::Slot &s, int 
         if (bad_decode) return fail(softmax_message());
         return 0;
     }
-    if (!decoded) return kz_engine::slot_nonfinite(s) ? fail(kz_engine::nonfinite_message(name)) : 0;
-    if (s.in_launch && kz_engine::slot_nonfinite(s)) return fail(kz_engine::nonfinite_message(name));
+    if (f.flag_in_header() && kz_engine::slot_nonfinite(s, f.epoch)) return fail(kz_engine::nonfinite_message(name));
+    if (!f.is_decoded()) return 0;
     if (s.h_err[1]) return fail(kz_engine::nonfinite_message(name));
     if (s.h_err[0]) return fail(softmax_message());
     return 0;
 }
 
-KZ_API int kz_engine_wait(kz_engine *e, int slot, float *scalars_out, float *policy_out) {
-    return guarded("kz_engine_wait", [&]() -> int {
-        if (!e) return fail("kz_engine_wait: null engine");
-        if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail("kz_engine_wait: bad slot");
-        kz_engine::Slot &s = e->slots[slot];
-        if (s.batch < 0 || s.decoded) return fail("kz_engine_wait: nothing submitted on this slot");
-        const int batch = s.batch;
-        s.batch = -1;
-        if (batch == 0) return 0;
-        if (!scalars_out || !policy_out) return fail("kz_engine_wait: null output");
-        HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipEventSynchronize(s.done));
-        const int rc = finish_batch("kz_engine_wait", e, s, batch, false, true);
-        memcpy(scalars_out, s.h_sout + kz_engine::SOUT_HDR, (size_t)batch * 5 * 4);
-        memcpy(policy_out, s.h_pol, (size_t)batch * e->model->policy_len * 4);
-        return rc;
-    });
-}
-
-KZ_API int kz_engine_wait_view(kz_engine *e, int slot, const float **scalars_out, const float **policy_out) {
-    return guarded("kz_engine_wait_view", [&]() -> int {
-        if (!e) return fail("kz_engine_wait_view: null engine");
-        if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail("kz_engine_wait_view: bad slot");
-        if (!scalars_out || !policy_out) return fail("kz_engine_wait_view: null output");
-        kz_engine::Slot &s = e->slots[slot];
-        if (s.batch < 0 || s.decoded) return fail("kz_engine_wait_view: nothing submitted on this slot");
-        const int batch = s.batch;
-        s.batch = -1;
-        *scalars_out = s.h_sout + kz_engine::SOUT_HDR;
-        *policy_out = s.h_pol;
-        if (batch == 0) return 0;
-        HIP_TRY(hipSetDevice(e->device));
-        HIP_TRY(hipEventSynchronize(s.done));
-        return finish_batch("kz_engine_wait_view", e, s, batch, false, true);
-    });
-}
-
-KZ_API int kz_engine_eval_packed(kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
-                                 int batch, float *scalars_out, float *policy_out) {
-    return guarded("kz_engine_eval_packed", [&]() -> int {
-        if (kz_engine_submit_packed(e, 0, bits, bits_stride, scalars_in, batch)) return 1;
-        return kz_engine_wait(e, 0, scalars_out, policy_out);
-    });
-}
-
+// ------------------------------------------------------------------------------------------------
+// Submit: every host-pointer entry is one body
+// ------------------------------------------------------------------------------------------------
 // A decoded submit's arguments (batch > 0) checked, then the boards and the CSR move lists copied into the slot's pinned
-// staging (allocated and grown here); the error words cleared.  Shared by every decoded submit.
+// staging (allocated and grown here); the error words cleared.
 static int stage_decoded(const char *fn, kz_engine *e, kz_engine::Slot &s, const uint8_t *bits, size_t bits_stride,
                          const float *scalars_in, int batch, const int64_t *move_offsets, const int32_t *move_indices, size_t &total_out) {
     if (!bits || !move_offsets) return fail(std::string(fn) + ": null argument");
-    const Model &m = *e->model;
-    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
-    if (bits_stride < bits_bytes) return fail(std::string(fn) + ": bits_stride too small");
-    if (m.n_scalar && !scalars_in) return fail(std::string(fn) + ": null scalars");
+    if (bits_stride < e->bits_bytes()) return fail(std::string(fn) + ": bits_stride too small");
+    if (e->model->n_scalar && !scalars_in) return fail(std::string(fn) + ": null scalars");
     if (move_offsets[0] != 0) return fail(std::string(fn) + ": move_offsets[0] must be 0");
     for (int b = 0; b < batch; b++)
         if (move_offsets[b + 1] < move_offsets[b]) return fail(std::string(fn) + ": move_offsets must be non-decreasing");
@@ -904,8 +807,7 @@ static int stage_decoded(const char *fn, kz_engine *e, kz_engine::Slot &s, const
         if (e->hmalloc((void **)&s.h_midx, cap * 4) || e->hmalloc((void **)&s.h_probs, cap * 4)) return 1;
         s.move_cap = cap;
     }
-    for (int b = 0; b < batch; b++) memcpy(s.h_bits + b * bits_bytes, bits + b * bits_stride, bits_bytes);
-    if (m.n_scalar) memcpy(s.h_sin, scalars_in, (size_t)batch * m.n_scalar * 4);
+    e->stage_boards(s, bits, bits_stride, scalars_in, batch);
     memcpy(s.h_moff, move_offsets, (size_t)(batch + 1) * 8);
     if (total) memcpy(s.h_midx, move_indices, total * 4);
     memset(s.h_err, 0, kz::error_flag_words(batch) * 4);  // the per-batch words and this batch's per-board ones: cleared per submit
@@ -913,102 +815,12 @@ static int stage_decoded(const char *fn, kz_engine *e, kz_engine::Slot &s, const
     return 0;
 }
 
-// kz_engine_submit_packed_decoded and, with sym, kz_engine_submit_packed_decoded_sym
-static int submit_decoded(const char *fn, kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
-                          int batch, const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices) {
-    if (check_batch(e, batch, fn) || check_packed(e, fn)) return 1;
-    if (sym && !e->n_sym) return fail(std::string(fn) + ": symmetry ids given but no tables set (call kz_engine_set_symmetries first)");
-#ifdef KZ_EXPERIMENTS
-    if (sym && e->plan.nb4) return fail(std::string(fn) + ": the four-board experiment launch takes no symmetry ids");
-#endif
-    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(std::string(fn) + ": bad slot");
-    kz_engine::Slot &s = e->slots[slot];
-    if (s.batch >= 0) return fail(std::string(fn) + ": slot still in flight (call kz_engine_wait_decoded first)");
-    if (batch == 0) {
-        s.batch = 0;
-        s.decoded = true;
-        s.with_sym = false;
-        s.moves = 0;
-        return 0;
-    }
-    size_t total = 0;
-    if (stage_decoded(fn, e, s, bits, bits_stride, scalars_in, batch, move_offsets, move_indices, total)) return 1;
-    const Model &m = *e->model;
-    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
-    const uint8_t *ids = nullptr;  // the launches read the ids from the slot's pinned staging, like the move lists
-    if (sym) {
-        memcpy(s.h_sym, sym, (size_t)batch);
-        ids = s.h_sym;
-    }
-    s.with_sym = sym != nullptr;
-    s.avg = false;
-    StreamSwap swap{e, e->stream};
-    if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
-    if (e->zero_copy && e->plan.heads) {
-        // ONE launch and no copy operation: it reads the packed boards and the move lists from the slot's pinned staging
-        // and writes the decoded values and the available moves' probabilities there (0.2 KB per chess evaluation cross
-        // PCIe); decode_output (common.rs:16-100) is the launch's last step.  The conv policy heads keep their logits in
-        // device memory (s.d_pol) for the gather; the attention network's never leave LDS.
-        e->arm(s);
-        e->nf_flag = reinterpret_cast<int *>(s.h_sout);
-        kz::DecodeArgs dec{s.h_moff, s.h_midx, s.h_values, s.h_probs, s.h_err};
-        if (ids) {
-            dec.sym = ids;
-            dec.policy_map = e->d_policy_map;
-            dec.n_sym = e->n_sym;
-        }
-        if (e->forward_packed(e->packed_boards(s.h_bits, bits_bytes, s.h_sin, ids), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &dec)) return 1;
-        HIP_TRY(hipEventRecord(s.done, e->stream));
-        s.batch = batch;
-        s.decoded = s.in_launch = true;
-        s.moves = total;
-        return e->audit ? audit_submit(e, slot) : 0;
-    }
-    // heads in launches of their own: the network leaves scalars and logits in device memory, the stand-alone decode kernel
-    // reads the move lists from and writes values / probabilities / flags to the slot's pinned staging directly (every word
-    // once): the two input copies are the only copy operations of the batch
-    HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, batch * bits_bytes, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)batch * m.n_scalar * 4, hipMemcpyHostToDevice, e->stream));
-    e->arm(s);
-    if (e->forward_packed(e->packed_boards(s.d_bits, bits_bytes, s.d_sin, ids), batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
-    if (e->launch("kz_decode_output", [&] {
-            kz::launch_decode_output(s.d_sout + kz_engine::SOUT_HDR, s.d_pol, batch, m.policy_len, s.h_moff, s.h_midx, s.h_values,
-                                     s.h_probs, s.h_err, reinterpret_cast<const int *>(s.d_sout), s.epoch, e->stream, ids,
-                                     e->d_policy_map, e->n_sym);
-        }))
-        return 1;
-    HIP_TRY(hipEventRecord(s.done, e->stream));
-    s.batch = batch;
-    s.decoded = true;
-    s.in_launch = false;
-    s.moves = total;
-    return e->audit ? audit_submit(e, slot) : 0;
-}
-
-KZ_API int kz_engine_submit_packed_decoded(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
-                                           const float *scalars_in, int batch, const int64_t *move_offsets,
-                                           const int32_t *move_indices) {
-    return guarded("kz_engine_submit_packed_decoded", [&]() -> int {
-        return submit_decoded("kz_engine_submit_packed_decoded", e, slot, bits, bits_stride, scalars_in, batch, nullptr, move_offsets,
-                              move_indices);
-    });
-}
-
-KZ_API int kz_engine_submit_packed_decoded_sym(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
-                                               const float *scalars_in, int batch, const uint8_t *sym,
-                                               const int64_t *move_offsets, const int32_t *move_indices) {
-    return guarded("kz_engine_submit_packed_decoded_sym", [&]() -> int {
-        return submit_decoded("kz_engine_submit_packed_decoded_sym", e, slot, bits, bits_stride, scalars_in, batch, sym, move_offsets,
-                              move_indices);
-    });
-}
-
 // The virtual batch's device scratch of a slot (kz_engine::Slot::Virtual): everything sized by max_batch at the first averaged
 // submit, the two move arrays for n_sym * total moves, grown the way move_cap grows.  Every buffer stays below 2 GiB.
-static int virtual_scratch(const char *fn, kz_engine *e, kz_engine::Slot &s, size_t bits_bytes, size_t vmoves) {
+static int virtual_scratch(const char *fn, kz_engine *e, kz_engine::Slot &s, size_t vmoves) {
     const Model &m = *e->model;
     kz_engine::Slot::Virtual &v = s.virt;
-    const size_t limit = ((size_t)1 << 31) - 1, mb = (size_t)e->max_batch;
+    const size_t limit = ((size_t)1 << 31) - 1, mb = (size_t)e->max_batch, bits_bytes = e->bits_bytes();
     const auto too_large = [&](size_t bytes) {
         return bytes > limit && fail(std::string(fn) + ": a scratch buffer of the virtual batch would need " + std::to_string(bytes) +
                                      " bytes (every engine tensor must stay below 2 GiB)");
@@ -1029,92 +841,197 @@ static int virtual_scratch(const char *fn, kz_engine *e, kz_engine::Slot &s, siz
     return 0;
 }
 
-// what both averaged entries check first: tables set, batch * n_sym within max_batch
-static int check_avg(const char *name, const kz_engine *e, int batch) {
+// kz_engine_submit_packed (raw), _decoded, _decoded_sym (decoded with sym) and _decoded_avg (averaged): the boards into the
+// slot's pinned staging, one network pass on the slot's stream, the slot in flight.
+//   direct ("+heads" launches, zero copy): ONE launch and no copy operation.  It reads the packed boards and the move lists
+//     from the pinned staging and writes there — raw rows (136 B in, 7.5 KB out per chess board), or, decode_output
+//     (common.rs:16-100) being its last step, the decoded values and the available moves' probabilities (0.2 KB per chess
+//     evaluation cross PCIe; the conv policy heads keep their logits in s.d_pol for the gather, the attention network's never
+//     leave LDS).
+//   otherwise: the boards are copied in, the network leaves scalars and logits in device memory, and either both are copied
+//     back (raw) or the stand-alone kz_decode_output reads the move lists from and writes values / probabilities / flags to
+//     the pinned staging directly.
+//   averaged (kz_symmetry_avg.hip): kz_sym_fan_out builds the VIRTUAL batch — every board under every symmetry, ids = k — from
+//     the pinned staging in device scratch, the unchanged pass and decode run over it, kz_sym_average folds it into the
+//     pinned staging.
+static int submit(const char *name, Entry kind, kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                  int batch, const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices) {
     const std::string fn = name;
-    if (!e) return fail(fn + ": null engine");
-    if (check_packed(e, name)) return 1;
-    if (!e->n_sym) return fail(fn + ": no tables set (call kz_engine_set_symmetries first)");
+    const bool raw = kind == Entry::raw, avg = kind == Entry::averaged;
+    if (check_entry(name, kind, e, batch)) return 1;
+    if (sym && !e->n_sym) return fail(fn + ": symmetry ids given but no tables set (call kz_engine_set_symmetries first)");
 #ifdef KZ_EXPERIMENTS
-    if (e->plan.nb4) return fail(fn + ": the four-board experiment launch takes no symmetry ids");
+    if (sym && e->plan.nb4) return fail(fn + ": the four-board experiment launch takes no symmetry ids");
 #endif
-    const int n = e->n_sym, limit = e->max_batch / n;
-    if (batch < 0 || batch > limit)
-        return fail(fn + ": batch " + std::to_string(batch) + " exceeds max_batch / n_sym = " + std::to_string(limit) + " (" +
-                    std::to_string(n) + " symmetries: the network runs on batch * n_sym boards, max_batch " + std::to_string(e->max_batch) + ")");
+    kz_engine::Slot *slot_ptr = nullptr;
+    if (slot_of(fn, e, slot, slot_ptr)) return 1;
+    kz_engine::Slot &s = *slot_ptr;
+    if (s.fly.busy()) return fail(fn + ": slot still in flight (call " + (raw ? "kz_engine_wait" : "kz_engine_wait_decoded") + " first)");
+    InFlight f;  // goes into the slot whole, once the event is recorded: a failed submit leaves the slot free
+    f.kind = raw ? InFlight::raw : InFlight::decoded;
+    f.batch = batch;
+    if (batch == 0) {
+        s.fly = f;
+        return 0;
+    }
+    const Model &m = *e->model;
+    const size_t bits_bytes = e->bits_bytes();
+    if (raw) {
+        if (!bits || (m.n_scalar && !scalars_in)) return fail(fn + ": null input");
+        if (bits_stride < bits_bytes) return fail(fn + ": bits_stride too small");
+        HIP_TRY(hipSetDevice(e->device));
+        e->stage_boards(s, bits, bits_stride, scalars_in, batch);
+    } else {
+        if (stage_decoded(name, e, s, bits, bits_stride, scalars_in, batch, move_offsets, move_indices, f.moves)) return 1;
+        if (sym) memcpy(s.h_sym, sym, (size_t)batch);  // the launches read the ids from the pinned staging, like the move lists
+    }
+    f.avg = avg;
+    f.with_sym = sym != nullptr;
+    const bool direct = e->zero_copy && e->plan.heads;
+    f.in_launch = direct && !raw;
+#ifdef KZ_EXPERIMENTS
+    const bool replayed = raw && !direct && e->graph_mode();
+    const Pass p = replayed ? e->pass_replayed(slot) : direct ? e->pass_pinned(slot) : e->pass_staged(slot);
+#else
+    const Pass p = direct ? e->pass_pinned(slot) : e->pass_staged(slot);
+#endif
+    f.epoch = p.nf_epoch;
+    // where the network reads `n` boards and their ids, and where the decode reads lists and writes values, probs and err:
+    // the pinned staging, the device copies, or the virtual batch
+    int n = batch;
+    kz::PackedBoards in;
+    kz::DecodeArgs dec;
+    if (avg) {
+        n = batch * e->n_sym;
+        if (virtual_scratch(name, e, s, (size_t)e->n_sym * f.moves)) return 1;
+        const kz_engine::Slot::Virtual &v = s.virt;
+        const kz::SymFanOutArgs fan{s.h_bits, bits_bytes, s.h_sin, m.n_scalar, batch, e->n_sym, s.h_moff, s.h_midx,
+                                    v.bits, v.sin, v.sym, v.moff, v.midx, v.err};
+        if (e->launch(p, "kz_sym_fan_out", [&] { kz::launch_sym_fan_out(fan, p.stream); })) return 1;
+        in = e->packed_boards(v.bits, bits_bytes, v.sin, v.sym);
+        dec = kz::DecodeArgs{v.moff, v.midx, v.values, v.probs, v.err, v.sym, e->d_policy_map, e->n_sym};
+    } else {
+        const uint8_t *ids = sym ? s.h_sym : nullptr;
+        if (!direct && e->copy_boards_in(p, s, batch)) return 1;
+        in = direct ? e->packed_boards(s.h_bits, bits_bytes, s.h_sin, ids) : e->packed_boards(s.d_bits, bits_bytes, s.d_sin, ids);
+        if (!raw) dec = kz::DecodeArgs{s.h_moff, s.h_midx, s.h_values, s.h_probs, s.h_err, ids, ids ? e->d_policy_map : nullptr, ids ? e->n_sym : 0};
+    }
+    // raw rows of a direct launch go to the pinned staging; everything else the network writes stays in device memory
+    float *sout = (raw && direct ? s.h_sout : s.d_sout) + kz_engine::SOUT_HDR, *pol = raw && direct ? s.h_pol : s.d_pol;
+    const auto network = [&]() -> int { return e->forward_packed(p, in, n, sout, pol, f.in_launch ? &dec : nullptr); };
+#ifdef KZ_EXPERIMENTS
+    if (replayed) {
+        if (e->replay(p, slot, batch, s.d_bits, bits_bytes, s.d_sin, s.d_sout, s.d_pol, [&]() -> int {
+                HIP_TRY(hipMemsetAsync(s.d_sout - e->front_words(), 0, ((size_t)e->front_words() + 1) * 4, p.stream));
+                return network();
+            }))
+            return 1;
+    } else
+#endif
+    if (network()) return 1;
+#ifdef KZ_EXPERIMENTS
+    if (raw && !direct) e->graph_warm = true;  // (the first pass runs eagerly: lazy per-kernel set-up must not land in a capture)
+#endif
+    if (raw && !direct) {
+        // (one copy: the batch's per-board range words, the header, the scalars)
+        HIP_TRY(hipMemcpyAsync(s.h_sout - batch, s.d_sout - batch, ((size_t)batch * 6 + kz_engine::SOUT_HDR) * 4, hipMemcpyDeviceToHost, p.stream));
+        HIP_TRY(hipMemcpyAsync(s.h_pol, s.d_pol, (size_t)batch * m.policy_len * 4, hipMemcpyDeviceToHost, p.stream));
+    }
+    if (!raw && !direct &&
+        e->launch(p, "kz_decode_output", [&] {
+            kz::launch_decode_output(sout, pol, n, m.policy_len, dec.move_offsets, dec.move_indices, dec.values, dec.probs, dec.error_flag,
+                                     p.nf_flag, p.nf_epoch, p.stream, dec.sym, dec.policy_map, dec.n_sym);
+        }))
+        return 1;
+    if (avg) {
+        // (a direct launch stamped its virtual boards' range words in front of the pinned header; the stand-alone decode has
+        // already copied them into v.err)
+        const kz::SymAverageArgs fold{dec.values, dec.probs, dec.move_offsets, dec.error_flag, batch, e->n_sym, s.h_values, s.h_probs, s.h_err,
+                                      direct ? p.nf_flag : nullptr, p.nf_epoch};
+        if (e->launch(p, "kz_sym_average", [&] { kz::launch_sym_average(fold, p.stream); })) return 1;
+    }
+    HIP_TRY(hipEventRecord(s.done, p.stream));
+    if (!raw && e->audit && audit_submit(e, slot, f)) return 1;
+    s.fly = f;
     return 0;
 }
 
-// kz_engine_submit_packed_decoded_avg: every board under every symmetry of the tables, averaged (kz_symmetry_avg.hip).  Three
-// launches on the slot's stream: the fan-out from the pinned staging into the virtual batch, the unchanged network pass over
-// it (ids = k; decode inside the launch on the "+heads" paths, kz_decode_output elsewhere) into device scratch, the average
-// into the pinned staging.
-static int submit_decoded_avg(const char *name, kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
-                              int batch, const int64_t *move_offsets, const int32_t *move_indices) {
-    const std::string fn = name;
-    if (check_avg(name, e, batch)) return 1;
-    const int n = e->n_sym;
-    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(fn + ": bad slot");
-    kz_engine::Slot &s = e->slots[slot];
-    if (s.batch >= 0) return fail(fn + ": slot still in flight (call kz_engine_wait_decoded first)");
-    if (batch == 0) {
-        s.batch = 0;
-        s.decoded = true;
-        s.with_sym = false;
-        s.moves = 0;
-        return 0;
-    }
-    size_t total = 0;
-    if (stage_decoded(name, e, s, bits, bits_stride, scalars_in, batch, move_offsets, move_indices, total)) return 1;
-    const Model &m = *e->model;
-    const size_t bits_bytes = (size_t)(m.n_bool * m.h * m.w + 7) / 8;
-    if (virtual_scratch(name, e, s, bits_bytes, (size_t)n * total)) return 1;
-    const kz_engine::Slot::Virtual &v = s.virt;
-    const int vbatch = batch * n;
-    s.with_sym = true;  // (the batch's errors are those of the `_sym` entries)
-    s.avg = true;
-    StreamSwap swap{e, e->stream};
-    if (e->slot_stream[slot]) e->stream = e->slot_stream[slot];
-    const kz::SymFanOutArgs fan{s.h_bits, bits_bytes, s.h_sin, m.n_scalar, batch, n, s.h_moff, s.h_midx,
-                                v.bits, v.sin, v.sym, v.moff, v.midx, v.err};
-    if (e->launch("kz_sym_fan_out", [&] { kz::launch_sym_fan_out(fan, e->stream); })) return 1;
-    const kz::PackedBoards boards = e->packed_boards(v.bits, bits_bytes, v.sin, v.sym);
-    const bool in_launch = e->zero_copy && e->plan.heads;
-    e->arm(s);
-    if (in_launch) {
-        e->nf_flag = reinterpret_cast<int *>(s.h_sout);  // the range check reports into the slot's header, as for every decoded submit
-        kz::DecodeArgs dec{v.moff, v.midx, v.values, v.probs, v.err};
-        dec.sym = v.sym;
-        dec.policy_map = e->d_policy_map;
-        dec.n_sym = n;
-        if (e->forward_packed(boards, vbatch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &dec)) return 1;
-    } else {
-        if (e->forward_packed(boards, vbatch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
-        if (e->launch("kz_decode_output", [&] {
-                kz::launch_decode_output(s.d_sout + kz_engine::SOUT_HDR, s.d_pol, vbatch, m.policy_len, v.moff, v.midx, v.values, v.probs,
-                                         v.err, reinterpret_cast<const int *>(s.d_sout), s.epoch, e->stream, v.sym, e->d_policy_map, n);
-            }))
-            return 1;
-    }
-    // (the "+heads" launch stamped its virtual boards' range words in front of the slot's pinned header; the stand-alone
-    // decode has already copied them into v.err)
-    const kz::SymAverageArgs avg{v.values, v.probs, v.moff, v.err, batch, n, s.h_values, s.h_probs, s.h_err,
-                                 in_launch ? reinterpret_cast<const int *>(s.h_sout) : nullptr, s.epoch};
-    if (e->launch("kz_sym_average", [&] { kz::launch_sym_average(avg, e->stream); })) return 1;
-    HIP_TRY(hipEventRecord(s.done, e->stream));
-    s.batch = batch;
-    s.decoded = true;
-    s.in_launch = in_launch;
-    s.moves = total;
-    return e->audit ? audit_submit(e, slot) : 0;
+KZ_API int kz_engine_submit_packed(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
+                                   const float *scalars_in, int batch) {
+    return guarded("kz_engine_submit_packed", [&]() -> int {
+        return submit("kz_engine_submit_packed", Entry::raw, e, slot, bits, bits_stride, scalars_in, batch, nullptr, nullptr, nullptr);
+    });
+}
+
+KZ_API int kz_engine_submit_packed_decoded(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
+                                           const float *scalars_in, int batch, const int64_t *move_offsets,
+                                           const int32_t *move_indices) {
+    return guarded("kz_engine_submit_packed_decoded", [&]() -> int {
+        return submit("kz_engine_submit_packed_decoded", Entry::decoded, e, slot, bits, bits_stride, scalars_in, batch, nullptr, move_offsets,
+                      move_indices);
+    });
+}
+
+KZ_API int kz_engine_submit_packed_decoded_sym(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
+                                               const float *scalars_in, int batch, const uint8_t *sym,
+                                               const int64_t *move_offsets, const int32_t *move_indices) {
+    return guarded("kz_engine_submit_packed_decoded_sym", [&]() -> int {
+        return submit("kz_engine_submit_packed_decoded_sym", Entry::decoded, e, slot, bits, bits_stride, scalars_in, batch, sym, move_offsets,
+                      move_indices);
+    });
 }
 
 KZ_API int kz_engine_submit_packed_decoded_avg(kz_engine *e, int slot, const uint8_t *bits, size_t bits_stride,
                                                const float *scalars_in, int batch, const int64_t *move_offsets,
                                                const int32_t *move_indices) {
     return guarded("kz_engine_submit_packed_decoded_avg", [&]() -> int {
-        return submit_decoded_avg("kz_engine_submit_packed_decoded_avg", e, slot, bits, bits_stride, scalars_in, batch, move_offsets,
-                                  move_indices);
+        return submit("kz_engine_submit_packed_decoded_avg", Entry::averaged, e, slot, bits, bits_stride, scalars_in, batch, nullptr,
+                      move_offsets, move_indices);
+    });
+}
+
+KZ_API int kz_engine_wait(kz_engine *e, int slot, float *scalars_out, float *policy_out) {
+    return guarded("kz_engine_wait", [&]() -> int {
+        if (!e) return fail("kz_engine_wait: null engine");
+        kz_engine::Slot *sp = nullptr;
+        if (slot_of("kz_engine_wait", e, slot, sp)) return 1;
+        kz_engine::Slot &s = *sp;
+        if (s.fly.kind != InFlight::raw) return fail("kz_engine_wait: nothing submitted on this slot");
+        const InFlight f = s.take();
+        if (f.batch == 0) return 0;
+        if (!scalars_out || !policy_out) return fail("kz_engine_wait: null output");
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipEventSynchronize(s.done));
+        const int rc = finish_batch("kz_engine_wait", e, s, f, true);
+        memcpy(scalars_out, s.h_sout + kz_engine::SOUT_HDR, (size_t)f.batch * 5 * 4);
+        memcpy(policy_out, s.h_pol, (size_t)f.batch * e->model->policy_len * 4);
+        return rc;
+    });
+}
+
+KZ_API int kz_engine_wait_view(kz_engine *e, int slot, const float **scalars_out, const float **policy_out) {
+    return guarded("kz_engine_wait_view", [&]() -> int {
+        if (!e) return fail("kz_engine_wait_view: null engine");
+        kz_engine::Slot *sp = nullptr;
+        if (slot_of("kz_engine_wait_view", e, slot, sp)) return 1;
+        if (!scalars_out || !policy_out) return fail("kz_engine_wait_view: null output");
+        kz_engine::Slot &s = *sp;
+        if (s.fly.kind != InFlight::raw) return fail("kz_engine_wait_view: nothing submitted on this slot");
+        const InFlight f = s.take();
+        *scalars_out = s.h_sout + kz_engine::SOUT_HDR;
+        *policy_out = s.h_pol;
+        if (f.batch == 0) return 0;
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipEventSynchronize(s.done));
+        return finish_batch("kz_engine_wait_view", e, s, f, true);
+    });
+}
+
+KZ_API int kz_engine_eval_packed(kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                 int batch, float *scalars_out, float *policy_out) {
+    return guarded("kz_engine_eval_packed", [&]() -> int {
+        if (kz_engine_submit_packed(e, 0, bits, bits_stride, scalars_in, batch)) return 1;
+        return kz_engine_wait(e, 0, scalars_out, policy_out);
     });
 }
 
@@ -1143,8 +1060,7 @@ KZ_API int kz_engine_set_symmetries(kz_engine *e, int n_sym, const int32_t *squa
                                 " is outside -1.." + std::to_string(plen - 1));
             }
         }
-        for (const auto &s : e->slots)
-            if (s.batch >= 0) return fail(fn + ": a batch is in flight (wait for every slot first)");
+        if (e->idle(fn)) return 1;
         HIP_TRY(hipSetDevice(e->device));
         if (e->sync_all()) return 1;
         if (!e->slots[0].h_sym)
@@ -1172,20 +1088,19 @@ KZ_API int kz_engine_set_symmetries(kz_engine *e, int n_sym, const int32_t *squa
 static int wait_decoded(const char *name, kz_engine *e, int slot, const float **values_out, const float **probs_out, void **status_out) {
     const std::string fn = name;
     if (!e) return fail(fn + ": null engine");
-    if (slot < 0 || slot >= KZ_ENGINE_SLOTS) return fail(fn + ": bad slot");
+    kz_engine::Slot *sp = nullptr;
+    if (slot_of(fn, e, slot, sp)) return 1;
     if (!values_out || !probs_out) return fail(fn + ": null output");
-    kz_engine::Slot &s = e->slots[slot];
-    if (s.batch < 0 || !s.decoded) return fail(fn + ": nothing submitted with a move list on this slot");
-    const int batch = s.batch;
-    s.batch = -1;
-    s.decoded = false;
+    kz_engine::Slot &s = *sp;
+    if (!s.fly.is_decoded()) return fail(fn + ": nothing submitted with a move list on this slot");
+    const InFlight f = s.take();
     *values_out = s.h_values;
     *probs_out = s.h_probs;
     if (status_out) *status_out = s.status.data();
-    if (batch == 0) return 0;
+    if (f.batch == 0) return 0;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipEventSynchronize(s.done));
-    return finish_batch(name, e, s, batch, true, status_out == nullptr);
+    return finish_batch(name, e, s, f, status_out == nullptr);
 }
 
 KZ_API int kz_engine_wait_decoded(kz_engine *e, int slot, const float **values_out, const float **probs_out) {
@@ -1199,6 +1114,20 @@ KZ_API int kz_engine_wait_decoded_status(kz_engine *e, int slot, const float **v
     });
 }
 
+// A sibling of `e` (the range fallback's, the audit's): the model as loaded, the same device, `dtype`, a small max_batch of its
+// own, its own streams, slots and staging, and the engine's symmetry tables.
+static int create_sibling(const kz_engine *e, int dtype, int max_batch, kz_engine **out) {
+    const kz_model source(e->source_model);
+    kz_engine *f = nullptr;
+    if (kz_engine_create(&source, e->device, max_batch, dtype, &f)) return 1;
+    if (e->n_sym && kz_engine_set_symmetries(f, e->n_sym, e->h_square_src.data(), e->h_policy_map.data())) {
+        kz_engine_destroy(f);
+        return 1;
+    }
+    *out = f;
+    return 0;
+}
+
 KZ_API int kz_engine_set_range_fallback(kz_engine *e, int dtype) {
     return guarded("kz_engine_set_range_fallback", [&]() -> int {
         const std::string fn = "kz_engine_set_range_fallback";
@@ -1206,24 +1135,15 @@ KZ_API int kz_engine_set_range_fallback(kz_engine *e, int dtype) {
         if (dtype != KZ_DTYPE_F32 && dtype != -1) return fail(fn + ": dtype must be KZ_DTYPE_F32 (on) or -1 (off), got " + std::to_string(dtype));
         if (e->dtype == KZ_DTYPE_F32 && !e->split16() && !e->bf16())
             return fail(fn + ": this engine evaluates in KZ_DTYPE_F32 already (exact f32 has no f16 range to fall back from)");
-        for (const auto &s : e->slots)
-            if (s.batch >= 0) return fail(fn + ": a batch is in flight (wait for every slot first)");
+        if (e->idle(fn)) return 1;
         if (dtype == -1) {
             kz_engine_destroy(e->fallback);
             e->fallback = nullptr;
             return 0;
         }
         if (e->fallback) return 0;
-        // the sibling: same model and device, exact f32, a small max_batch of its own (flagged boards go through it in chunks)
-        const kz_model source(e->source_model);
-        kz_engine *f = nullptr;
-        if (kz_engine_create(&source, e->device, std::min(e->max_batch, 64), KZ_DTYPE_F32, &f)) return 1;
-        if (e->n_sym && kz_engine_set_symmetries(f, e->n_sym, e->h_square_src.data(), e->h_policy_map.data())) {
-            kz_engine_destroy(f);
-            return 1;
-        }
-        e->fallback = f;
-        return 0;
+        // exact f32; flagged boards go through it in chunks
+        return create_sibling(e, KZ_DTYPE_F32, std::min(e->max_batch, 64), &e->fallback);
     });
 }
 
@@ -1238,8 +1158,7 @@ KZ_API int kz_engine_set_audit(kz_engine *e, int dtype, int period, int boards) 
                         std::to_string(dtype));
         if (dtype == e->public_dtype())
             return fail(fn + ": this engine evaluates in that dtype already (an audit against its own arithmetic compares nothing)");
-        for (const auto &s : e->slots)
-            if (s.batch >= 0) return fail(fn + ": a batch is in flight (wait for every slot first)");
+        if (e->idle(fn)) return 1;
         if (dtype == -1) {
             if (e->audit) kz_engine_destroy(e->audit->sibling);
             delete e->audit;
@@ -1255,13 +1174,8 @@ KZ_API int kz_engine_set_audit(kz_engine *e, int dtype, int period, int boards) 
         if (dtype == KZ_DTYPE_F32_SPLIT16 && kz_model_supports_dtype(&source, dtype) != 1)
             return fail(fn + ": this model has no KZ_DTYPE_F32_SPLIT16 kernels (kz_model_supports_dtype is 0): audit it against KZ_DTYPE_F32");
         if (!e->audit || e->audit->dtype != dtype) {
-            // the sibling: same model and device, `dtype`, a small max_batch of its own; created before the old one goes
-            kz_engine *f = nullptr;
-            if (kz_engine_create(&source, e->device, sibling_batch, dtype, &f)) return 1;
-            if (e->n_sym && kz_engine_set_symmetries(f, e->n_sym, e->h_square_src.data(), e->h_policy_map.data())) {
-                kz_engine_destroy(f);
-                return 1;
-            }
+            kz_engine *f = nullptr;  // created before the old one goes
+            if (create_sibling(e, dtype, sibling_batch, &f)) return 1;
             if (!e->audit) e->audit = new kz_engine::Audit();
             kz_engine_destroy(e->audit->sibling);
             e->audit->sibling = f;
@@ -1272,7 +1186,6 @@ KZ_API int kz_engine_set_audit(kz_engine *e, int dtype, int period, int boards) 
         a.boards = boards;
         a.submits = 0;
         a.stats = kz_audit_stats{};
-        for (auto &s : e->slots) s.audit_k = 0;
         return 0;
     });
 }
@@ -1284,25 +1197,25 @@ KZ_API int kz_engine_audit_stats(kz_engine *e, void *out, int reset) {
         if (!out) return fail(fn + ": null output");
         if (!e->audit) return fail(fn + ": the audit is off (call kz_engine_set_audit first)");
         for (const auto &s : e->slots)
-            if (s.batch >= 0 && s.decoded && s.audit_k) return fail(fn + ": an audited batch is in flight (wait for it first)");
+            if (s.fly.audit_k) return fail(fn + ": an audited batch is in flight (wait for it first)");
         memcpy(out, &e->audit->stats, sizeof(kz_audit_stats));
         if (reset) e->audit->stats = kz_audit_stats{};
         return 0;
     });
 }
 
-// kz_engine_eval_packed_decoded and, with sym, kz_engine_eval_packed_decoded_sym
-static int eval_decoded(const char *name, kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in, int batch,
-                        const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices, float *values_out, float *probs_out,
-                        void *status_out = nullptr, bool with_status = false) {
+// the blocking decoded entries: a submit of `kind` on slot 0 and its wait (without a status output, under kz_engine_wait_decoded's name)
+static int eval_decoded(const char *name, Entry kind, kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                        int batch, const uint8_t *sym, const int64_t *move_offsets, const int32_t *move_indices, float *values_out,
+                        float *probs_out, void *status_out = nullptr, bool with_status = false) {
     const std::string fn = name;
-    if (check_batch(e, batch, name) || check_packed(e, name)) return 1;
+    if (check_entry(name, kind, e, batch)) return 1;
     if (batch == 0) return 0;
     if (!values_out || (with_status && !status_out)) return fail(fn + ": null argument");
-    if (move_offsets && batch > 0 && move_offsets[batch] > 0 && !probs_out) return fail(fn + ": null move list");
-    if (submit_decoded(name, e, 0, bits, bits_stride, scalars_in, batch, sym, move_offsets, move_indices)) return 1;
+    if (move_offsets && move_offsets[batch] > 0 && !probs_out) return fail(fn + ": null move list");
+    if (submit(name, kind, e, 0, bits, bits_stride, scalars_in, batch, sym, move_offsets, move_indices)) return 1;
     const float *values = nullptr, *probs = nullptr;
-    const size_t total = e->slots[0].moves;
+    const size_t total = e->slots[0].fly.moves;
     void *status = nullptr;
     if (wait_decoded(with_status ? name : "kz_engine_wait_decoded", e, 0, &values, &probs, with_status ? &status : nullptr)) return 1;
     memcpy(values_out, values, (size_t)batch * 20);
@@ -1315,7 +1228,7 @@ KZ_API int kz_engine_eval_packed_decoded_status(kz_engine *e, const uint8_t *bit
                                                 int batch, const uint8_t *sym, const int64_t *move_offsets,
                                                 const int32_t *move_indices, float *values_out, float *probs_out, void *status_out) {
     return guarded("kz_engine_eval_packed_decoded_status", [&]() -> int {
-        return eval_decoded("kz_engine_eval_packed_decoded_status", e, bits, bits_stride, scalars_in, batch, sym, move_offsets,
+        return eval_decoded("kz_engine_eval_packed_decoded_status", Entry::decoded, e, bits, bits_stride, scalars_in, batch, sym, move_offsets,
                             move_indices, values_out, probs_out, status_out, true);
     });
 }
@@ -1324,7 +1237,7 @@ KZ_API int kz_engine_eval_packed_decoded(kz_engine *e, const uint8_t *bits, size
                                          int batch, const int64_t *move_offsets, const int32_t *move_indices,
                                          float *values_out, float *probs_out) {
     return guarded("kz_engine_eval_packed_decoded", [&]() -> int {
-        return eval_decoded("kz_engine_eval_packed_decoded", e, bits, bits_stride, scalars_in, batch, nullptr, move_offsets, move_indices,
+        return eval_decoded("kz_engine_eval_packed_decoded", Entry::decoded, e, bits, bits_stride, scalars_in, batch, nullptr, move_offsets, move_indices,
                             values_out, probs_out);
     });
 }
@@ -1333,7 +1246,7 @@ KZ_API int kz_engine_eval_packed_decoded_sym(kz_engine *e, const uint8_t *bits, 
                                              int batch, const uint8_t *sym, const int64_t *move_offsets,
                                              const int32_t *move_indices, float *values_out, float *probs_out) {
     return guarded("kz_engine_eval_packed_decoded_sym", [&]() -> int {
-        return eval_decoded("kz_engine_eval_packed_decoded_sym", e, bits, bits_stride, scalars_in, batch, sym, move_offsets,
+        return eval_decoded("kz_engine_eval_packed_decoded_sym", Entry::decoded, e, bits, bits_stride, scalars_in, batch, sym, move_offsets,
                             move_indices, values_out, probs_out);
     });
 }
@@ -1342,19 +1255,8 @@ KZ_API int kz_engine_eval_packed_decoded_avg(kz_engine *e, const uint8_t *bits, 
                                              int batch, const int64_t *move_offsets, const int32_t *move_indices,
                                              float *values_out, float *probs_out) {
     return guarded("kz_engine_eval_packed_decoded_avg", [&]() -> int {
-        const char *name = "kz_engine_eval_packed_decoded_avg";
-        const std::string fn = name;
-        if (check_avg(name, e, batch)) return 1;
-        if (batch == 0) return 0;
-        if (!values_out) return fail(fn + ": null argument");
-        if (move_offsets && move_offsets[batch] > 0 && !probs_out) return fail(fn + ": null move list");
-        if (submit_decoded_avg(name, e, 0, bits, bits_stride, scalars_in, batch, move_offsets, move_indices)) return 1;
-        const float *values = nullptr, *probs = nullptr;
-        const size_t total = e->slots[0].moves;
-        if (kz_engine_wait_decoded(e, 0, &values, &probs)) return 1;
-        memcpy(values_out, values, (size_t)batch * 20);
-        if (total) memcpy(probs_out, probs, total * 4);
-        return 0;
+        return eval_decoded("kz_engine_eval_packed_decoded_avg", Entry::averaged, e, bits, bits_stride, scalars_in, batch, nullptr,
+                            move_offsets, move_indices, values_out, probs_out);
     });
 }
 
@@ -1365,7 +1267,7 @@ KZ_API int kz_engine_eval_dense(kz_engine *e, const float *input_nchw, int batch
         if (batch == 0) return 0;
         if (!input_nchw || !scalars_out || !policy_out) return fail("kz_engine_eval_dense: null argument");
         kz_engine::Slot &s = e->slots[0];
-        if (s.batch >= 0) return fail("kz_engine_eval_dense: slot 0 still in flight");
+        if (s.fly.busy()) return fail("kz_engine_eval_dense: slot 0 still in flight");
         const Model &m = *e->model;
         HIP_TRY(hipSetDevice(e->device));
         const size_t per = (size_t)m.c_in * m.h * m.w * 4;
@@ -1374,16 +1276,15 @@ KZ_API int kz_engine_eval_dense(kz_engine *e, const float *input_nchw, int batch
                 return 1;
         }
         memcpy(e->h_dense, input_nchw, batch * per);
-        HIP_TRY(hipMemcpyAsync(e->d_dense, e->h_dense, batch * per, hipMemcpyHostToDevice, e->stream));
-        e->arm(s);
-        if (e->forward_dense(e->d_dense, batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
-        HIP_TRY(hipMemcpyAsync(s.h_sout, s.d_sout, ((size_t)batch * 5 + kz_engine::SOUT_HDR) * 4, hipMemcpyDeviceToHost,
-                               e->stream));
-        HIP_TRY(hipMemcpyAsync(s.h_pol, s.d_pol, (size_t)batch * m.policy_len * 4, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
+        const Pass p = e->pass_staged(0);
+        HIP_TRY(hipMemcpyAsync(e->d_dense, e->h_dense, batch * per, hipMemcpyHostToDevice, p.stream));
+        if (e->forward_dense(p, e->d_dense, batch, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+        HIP_TRY(hipMemcpyAsync(s.h_sout, s.d_sout, ((size_t)batch * 5 + kz_engine::SOUT_HDR) * 4, hipMemcpyDeviceToHost, p.stream));
+        HIP_TRY(hipMemcpyAsync(s.h_pol, s.d_pol, (size_t)batch * m.policy_len * 4, hipMemcpyDeviceToHost, p.stream));
+        HIP_TRY(hipStreamSynchronize(p.stream));
         memcpy(scalars_out, s.h_sout + kz_engine::SOUT_HDR, (size_t)batch * 5 * 4);
         memcpy(policy_out, s.h_pol, (size_t)batch * m.policy_len * 4);
-        if (kz_engine::slot_nonfinite(s)) return fail(kz_engine::nonfinite_message("kz_engine_eval_dense"));
+        if (kz_engine::slot_nonfinite(s, p.nf_epoch)) return fail(kz_engine::nonfinite_message("kz_engine_eval_dense"));
         return 0;
     });
 }
@@ -1396,21 +1297,18 @@ KZ_API int kz_engine_enqueue_packed_device(kz_engine *e, const void *d_bits, siz
             return 1;
         if (batch == 0) return 0;
         if (!d_bits || !d_scalars_out || !d_policy_out) return fail("kz_engine_enqueue_packed_device: null argument");
-        const Model &m = *e->model;
-        if (bits_stride < (size_t)(m.n_bool * m.h * m.w + 7) / 8)
-            return fail("kz_engine_enqueue_packed_device: bits_stride too small");
+        if (bits_stride < e->bits_bytes()) return fail("kz_engine_enqueue_packed_device: bits_stride too small");
         HIP_TRY(hipSetDevice(e->device));
-        e->arm_device();
+        const kz::PackedBoards in = e->packed_boards(d_bits, bits_stride, d_scalars_in);
     #ifdef KZ_EXPERIMENTS
         if (e->graph_mode()) {
-            e->nf_epoch = kz_engine::GRAPH_EPOCH;
-            return e->replay(-1, batch, d_bits, bits_stride, d_scalars_in, d_scalars_out, d_policy_out, [&]() -> int {
-                return e->forward_packed(e->packed_boards(d_bits, bits_stride, d_scalars_in), batch, d_scalars_out, d_policy_out);
-            });
+            const Pass p = e->pass_replayed(-1);
+            return e->replay(p, -1, batch, d_bits, bits_stride, d_scalars_in, d_scalars_out, d_policy_out,
+                             [&]() -> int { return e->forward_packed(p, in, batch, d_scalars_out, d_policy_out); });
         }
         e->graph_warm = true;
     #endif
-        return e->forward_packed(e->packed_boards(d_bits, bits_stride, d_scalars_in), batch, d_scalars_out, d_policy_out);
+        return e->forward_packed(e->pass_resident(), in, batch, d_scalars_out, d_policy_out);
     });
 }
 
@@ -1421,8 +1319,7 @@ KZ_API int kz_engine_enqueue_dense_device(kz_engine *e, const void *d_input_nchw
         if (batch == 0) return 0;
         if (!d_input_nchw || !d_scalars_out || !d_policy_out) return fail("kz_engine_enqueue_dense_device: null argument");
         HIP_TRY(hipSetDevice(e->device));
-        e->arm_device();
-        return e->forward_dense(d_input_nchw, batch, d_scalars_out, d_policy_out);
+        return e->forward_dense(e->pass_resident(), d_input_nchw, batch, d_scalars_out, d_policy_out);
     });
 }
 

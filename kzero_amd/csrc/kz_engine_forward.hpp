@@ -1,9 +1,9 @@
 // kz_engine_forward.hpp — the forward pass of an engine: which kernels run for its plan (kz_engine::plan, kz_plan.hpp: the
-// tower family, heads inside its launch or not), in which order, on the engine's current stream.  Out-of-class definitions of the members kz_engine_state.hpp declares;
+// tower family, heads inside its launch or not), in which order, on the stream of the Pass it is given.  Out-of-class definitions of the members kz_engine_state.hpp declares;
 // included ONCE, by kz_engine.hip.
 #pragma once
 
-inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, int ldy, int M, int relu, const void *res, bool post,
+inline int kz_engine::conv(const Pass &p, const DevConv &w, const void *x, int ldx, void *y, int ldy, int M, int relu, const void *res, bool post,
          int h, int wd, int group, int src_group, int src_off, float *y32, int ldy32) {
     if (w.bws) {  // whole boards as LDS-resident spatial tiles, split arithmetic: (hi, lo) rows of 2 C halves
         kz::BoardConvArgs b{};
@@ -12,7 +12,7 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
         b.post_scale = post ? wts->post_scale : nullptr;
         b.post_shift = post ? wts->post_shift : nullptr;
         b.boards = M / (h * wd); b.h = h; b.w = wd; b.cin = w.cin_p; b.cout = w.cout; b.relu = relu;
-        return launch("kz_board_conv_split16", [&] { kz::launch_board_conv_split(b, stream); });
+        return launch(p, "kz_board_conv_split16", [&] { kz::launch_board_conv_split(b, p.stream); });
     }
     if (w.bw) {  // whole boards as LDS-resident spatial tiles
         kz::BoardConvArgs b{};
@@ -21,12 +21,12 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
         b.post_shift = post ? wts->post_shift : nullptr;
         b.boards = M / (h * wd); b.h = h; b.w = wd; b.cin = w.cin_p; b.cout = w.cout; b.relu = relu;
         b.rowmap = wts->bc_rowmap; b.halo = wts->bc_halo; b.n_halo = wts->bc_n_halo;
-        return launch("kz_board_conv_f16", [&] {
+        return launch(p, "kz_board_conv_f16", [&] {
 #ifdef KZ_EXPERIMENTS
-            if (w.bw2) kz::launch_board_conv2(b, stream);
+            if (w.bw2) kz::launch_board_conv2(b, p.stream);
             else
 #endif
-            kz::launch_board_conv(b, stream);
+            kz::launch_board_conv(b, p.stream);
         });
     }
     if (w.sw && y && !res && !post && !y32 && ldx >= w.cin_p) {  // 1x1 head convolution: split16 or any f16 path
@@ -35,7 +35,7 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
         c.x = x; c.ldx = ldx; c.weights = w.sw; c.bias = w.b; c.y = y; c.ldy = ldy;
         c.M = M; c.cin_p = w.cin_p; c.cout_p = w.cout_p; c.relu = relu;
         c.group = group; c.src_group = src_group; c.src_off = src_off;
-        return launch("kz_conv1x1_split", [&] { kz::launch_conv1x1_split(c, stream); });
+        return launch(p, "kz_conv1x1_split", [&] { kz::launch_conv1x1_split(c, p.stream); });
     }
     kz::ConvArgs a{};
     a.x = x; a.ldx = ldx; a.w = w.w; a.bias = w.b; a.res = res; a.ldres = ldy;
@@ -44,13 +44,13 @@ inline int kz_engine::conv(const DevConv &w, const void *x, int ldx, void *y, in
     a.y = y; a.y32 = y32; a.ldy = ldy; a.ldy32 = ldy32;
     a.M = M; a.h = h; a.w_ = wd; a.group = group; a.src_group = src_group; a.src_off = src_off;
     a.cin_p = w.cin_p; a.cout_p = w.cout_p; a.cout = w.cout; a.k = w.k; a.relu = relu;
-    return launch(kz::conv_kernel_name(dtype), [&] { kz::launch_conv(dtype, a, stream); });
+    return launch(p, kz::conv_kernel_name(dtype), [&] { kz::launch_conv(dtype, a, p.stream); });
 }
 
 // packed != nullptr (encodes_boards(plan) only): the launch encodes the boards itself.  The "+heads" launches (plan.heads) can
 // end in decode_output (kz_decode_dev.hpp): with `dec` nothing but the decoded values and the available moves' probabilities
 // leave the launch
-inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, const kz::PackedBoards *packed,
+inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, float *d_policy, const kz::PackedBoards *packed,
               const kz::DecodeArgs *dec) {
     const Model &m = *model;
     const int hw = m.h * m.w, M = batch * hw;
@@ -60,8 +60,8 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.depth = m.depth; t.res = m.dn_res ? 1 : 0; t.policy_len = m.policy_len;
         t.w_in = wts->dn_w_in; t.b_in = wts->dn_b_in; t.blocks = wts->dn_blocks; t.sf = wts->dn_sf; t.tf = wts->dn_tf;
         t.w_out = wts->dn_w_out; t.b_out = wts->dn_b_out; t.scalars = d_scalars; t.policy = d_policy;
-        t.nonfinite_flag = nf_flag; t.epoch = nf_epoch;
-        if (launch("kz_dense_network", [&] { kz::launch_dense_network(t, stream); })) return 1;
+        t.nonfinite_flag = p.nf_flag; t.epoch = p.nf_epoch;
+        if (launch(p, "kz_dense_network", [&] { kz::launch_dense_network(t, p.stream); })) return 1;
         tower_out = 0;
         return 0;
     }
@@ -72,7 +72,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.w_layers = wts->att16_layers; t.y = act[0]; t.batch = batch; t.depth = m.depth; t.d_model = m.channels;
         t.d_ff = m.att_dff; t.alpha = m.att_alpha; t.eps = m.ln_eps;
         if (packed) t.in = *packed;  // fused board encode
-        if (launch(t.f32 ? "kz_att_tower_f32" : "kz_att_tower_f16", [&] { kz::launch_att_tower16(t, stream); })) return 1;
+        if (launch(p, t.f32 ? "kz_att_tower_f32" : "kz_att_tower_f16", [&] { kz::launch_att_tower16(t, p.stream); })) return 1;
         tower_out = 0;
         return 0;
     }
@@ -83,7 +83,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.y = act[0]; t.ldy = cp; t.out_f16 = dtype == KZ_DTYPE_F16;
         t.batch = batch; t.h = m.h; t.w = m.w; t.depth = m.depth; t.d_model = m.channels; t.heads = m.att_heads;
         t.d_k = m.att_dk; t.d_v = m.att_dv; t.d_ff = m.att_dff; t.alpha = m.att_alpha; t.eps = m.ln_eps;
-        if (launch("kz_att_tower_f32_valu", [&] { kz::launch_att_tower(t, stream); })) return 1;
+        if (launch(p, "kz_att_tower_f32_valu", [&] { kz::launch_att_tower(t, p.stream); })) return 1;
         tower_out = 0;
         return 0;
     }
@@ -98,17 +98,17 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         t.sh_w0 = wts->sh_w0; t.sh_b0 = wts->sh_b0; t.sh_w1 = wts->sh_w1; t.sh_b1 = wts->sh_b1;
         t.sh_w2 = wts->sh_w2; t.sh_b2 = wts->sh_b2; t.att_idx = wts->att_idx;
         t.scalars = d_scalars; t.policy = d_policy;
-        t.nonfinite_flag = nf_flag; t.epoch = nf_epoch;
+        t.nonfinite_flag = p.nf_flag; t.epoch = p.nf_epoch;
         if (dec && plan.heads) t.decode = *dec;
 #ifdef KZ_EXPERIMENTS
         t.prev = plan.tower_prev;
 #endif
-        if (launch("kz_tower_resident_f16", [&] {
+        if (launch(p, "kz_tower_resident_f16", [&] {
 #ifdef KZ_EXPERIMENTS
-                if (plan.nb4) kz::launch_tower_resident4(t, xres, stream);
+                if (plan.nb4) kz::launch_tower_resident4(t, xres, p.stream);
                 else
 #endif
-                kz::launch_tower_resident(t, stream);
+                kz::launch_tower_resident(t, p.stream);
             }))
             return 1;
         tower_out = 0;
@@ -128,7 +128,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
             hd.sh_w2 = wts->sh_w2; hd.sh_b2 = wts->sh_b2; hd.att_idx = wts->att_idx;
             hd.policy_len = m.policy_len;
             hd.scalars = d_scalars; hd.policy = d_policy;
-            hd.nonfinite_flag = nf_flag; hd.epoch = nf_epoch;
+            hd.nonfinite_flag = p.nf_flag; hd.epoch = p.nf_epoch;
         }
         if (plan.heads && m.policy_kind != kz::POLICY_ATTENTION) {  // conv policy heads: the f32 tail
             kz::Tower32Args::Heads &hd = t.heads;
@@ -143,7 +143,7 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
                 hd.pe_bc = wts->pe_bc; hd.pe_wl = wts->pe_wl; hd.pe_bl = wts->pe_bl;
             }
             hd.scalars = d_scalars; hd.policy = d_policy;
-            hd.nonfinite_flag = nf_flag; hd.epoch = nf_epoch;
+            hd.nonfinite_flag = p.nf_flag; hd.epoch = p.nf_epoch;
         }
         if (dec && t.heads.on) t.heads.decode = *dec;
 #ifdef KZ_EXPERIMENTS
@@ -156,11 +156,11 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
             range_site = 2 * m.depth + 1;  // every epilogue of the launch is a site
         }
         const bool f16g = plan.tower == Tower::resident_f16g;
-        if (launch(split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : "kz_tower_resident_f32", [&] {
-                if (split16()) kz::launch_tower_split(t, stream);
-                else if (bf16()) kz::launch_tower_bf16(t, stream);  // f32 tensors, like the split launch
-                else if (f16g) kz::launch_tower_pairs(t, false, stream);  // f16 tensors behind the same pointers
-                else kz::launch_tower32(t, stream);
+        if (launch(p, split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : "kz_tower_resident_f32", [&] {
+                if (split16()) kz::launch_tower_split(t, p.stream);
+                else if (bf16()) kz::launch_tower_bf16(t, p.stream);  // f32 tensors, like the split launch
+                else if (f16g) kz::launch_tower_pairs(t, false, p.stream);  // f16 tensors behind the same pointers
+                else kz::launch_tower32(t, p.stream);
             }))
             return 1;
         tower_out = 0;
@@ -171,18 +171,18 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
         // (hi, lo) tensor of the same shape have the same size, so the three activation buffers serve both —, the
         // 2·depth tower convolutions in split arithmetic, the last one writing f32 for the heads
         if (wts->stem_split) {  // encoded f32 planes [M][32] -> (hi, lo) rows -> the board-tile kernel, one chunk
-            if (launch("kz_split_rows", [&] { kz::launch_split_rows((const float *)x_in, act[2], (size_t)M, cin_p, stream); })) return 1;
-            if (conv(wts->tower[0], act[2], cin_p, act[0], cp, M, 0, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
+            if (launch(p, "kz_split_rows", [&] { kz::launch_split_rows((const float *)x_in, act[2], (size_t)M, cin_p, p.stream); })) return 1;
+            if (conv(p, wts->tower[0], act[2], cin_p, act[0], cp, M, 0, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
         } else {
-            if (conv(wts->tower[0], x_in, cin_p, act[2], cp, M, 0, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
-            if (launch("kz_split_rows", [&] { kz::launch_split_rows((const float *)act[2], act[0], (size_t)M, cp, stream); })) return 1;
+            if (conv(p, wts->tower[0], x_in, cin_p, act[2], cp, M, 0, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
+            if (launch(p, "kz_split_rows", [&] { kz::launch_split_rows((const float *)act[2], act[0], (size_t)M, cp, p.stream); })) return 1;
         }
         int cur = 0;
         for (int i = 1; i <= m.depth; i++) {
             const int mid = (cur + 1) % 3, nxt = (cur + 2) % 3;
             const bool last = i == m.depth;
-            if (conv(wts->tower[2 * i - 1], act[cur], cp, act[mid], cp, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
-            if (conv(wts->tower[2 * i], act[mid], cp, last ? nullptr : act[nxt], cp, M, 1, act[cur], last, m.h, m.w, hw, hw, 0,
+            if (conv(p, wts->tower[2 * i - 1], act[cur], cp, act[mid], cp, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
+            if (conv(p, wts->tower[2 * i], act[mid], cp, last ? nullptr : act[nxt], cp, M, 1, act[cur], last, m.h, m.w, hw, hw, 0,
                      last ? (float *)act[nxt] : nullptr, cp))
                 return 1;
             cur = nxt;
@@ -192,19 +192,19 @@ inline int kz_engine::run_tower(int batch, float *d_scalars, float *d_policy, co
     }
     // stem: conv + bias, no activation (post_act.py:205)
     range_site = 0;
-    if (conv(wts->tower[0], x_in, cin_p, act[0], cp, M, 0, nullptr, m.depth == 0, m.h, m.w, hw, hw, 0)) return 1;
-    if (stash(m.depth == 0 ? "tower.1" : "tower.0", act[0], batch)) return 1;
+    if (conv(p, wts->tower[0], x_in, cin_p, act[0], cp, M, 0, nullptr, m.depth == 0, m.h, m.w, hw, hw, 0)) return 1;
+    if (stash(p, m.depth == 0 ? "tower.1" : "tower.0", act[0], batch)) return 1;
     int cur = 0;
     for (int i = 1; i <= m.depth; i++) {
         const int mid = (cur + 1) % 3, nxt = (cur + 2) % 3;
         const bool last = i == m.depth;
-        if (conv(wts->tower[2 * i - 1], act[cur], cp, act[mid], cp, M, 1, nullptr, false, m.h, m.w, hw, hw, 0))
+        if (conv(p, wts->tower[2 * i - 1], act[cur], cp, act[mid], cp, M, 1, nullptr, false, m.h, m.w, hw, hw, 0))
             return 1;
-        if (stash("tower." + std::to_string(i) + ".mid", act[mid], batch)) return 1;
+        if (stash(p, "tower." + std::to_string(i) + ".mid", act[mid], batch)) return 1;
         // x + relu(bn(conv(mid))) (post_act.py:227-228); the tower's final BN rides on the last block
-        if (conv(wts->tower[2 * i], act[mid], cp, act[nxt], cp, M, 1, act[cur], last, m.h, m.w, hw, hw, 0))
+        if (conv(p, wts->tower[2 * i], act[mid], cp, act[nxt], cp, M, 1, act[cur], last, m.h, m.w, hw, hw, 0))
             return 1;
-        if (stash("tower." + std::to_string(last ? i + 1 : i), act[nxt], batch)) return 1;
+        if (stash(p, "tower." + std::to_string(last ? i + 1 : i), act[nxt], batch)) return 1;
         cur = nxt;
     }
     tower_out = cur;
@@ -217,7 +217,7 @@ inline bool kz_engine::extra_in_scalar_head() const {
            kz::scalar_head_takes_extra(dtype == KZ_DTYPE_F32 ? 0 : 1, cp, m.sh_conv.cout);
 }
 
-inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
+inline int kz_engine::run_heads(const Pass &p, int batch, float *d_scalars, float *d_policy) {
     if (plan.heads || plan.tower == Tower::dense_net) return 0;  // written by the tower launch
     const Model &m = *model;
     const int hw = m.h * m.w, M = batch * hw;
@@ -229,20 +229,20 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
         a.weights = wts->ah_w; a.bias = wts->ah_bias;
         a.w1 = wts->sh_w1; a.b1 = wts->sh_b1; a.w2 = wts->sh_w2; a.b2 = wts->sh_b2;
         a.flat_to_att = wts->flat_to_att; a.scalars = d_scalars; a.policy = d_policy;
-        a.nonfinite_flag = nf_flag; a.epoch = nf_epoch;
-        return launch("kz_att_heads_f16", [&] { kz::launch_att_heads(a, stream); });
+        a.nonfinite_flag = p.nf_flag; a.epoch = p.nf_epoch;
+        return launch(p, "kz_att_heads_f16", [&] { kz::launch_att_heads(a, p.stream); });
     }
     {
         kz::ScalarHeadArgs a{x, cp, batch, hw, m.channels, m.sh_conv.cout, m.sh_fc0.out,
                              wts->sh_w0, wts->sh_b0, wts->sh_w1, wts->sh_b1, wts->sh_w2, wts->sh_b2, d_scalars,
-                             nf_flag, nf_epoch, wts->sh_w1t};
+                             p.nf_flag, p.nf_epoch, wts->sh_w1t};
         // ConvPolicyHead's extra moves read the same tower output: one pass for both (post_act.py:63-67)
         if (extra_in_scalar_head()) {
             a.extra = m.policy_extra_moves;
             a.w0x = wts->sh_w0x; a.pe_bc = wts->pe_bc; a.pe_wl = wts->pe_wl; a.pe_bl = wts->pe_bl;
             a.policy = d_policy; a.policy_len = m.policy_len; a.policy_offset = m.policy_conv_channels * hw;
         }
-        if (launch("kz_scalar_head", [&] { kz::launch_scalar_head(dtype, a, stream); })) return 1;
+        if (launch(p, "kz_scalar_head", [&] { kz::launch_scalar_head(dtype, a, p.stream); })) return 1;
     }
     switch (m.policy_kind) {
         case kz::POLICY_ATAXX_CONV:
@@ -258,46 +258,46 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
                 c.M = M; c.cin_p = c0.cin_p; c.cout_p = c0.cout_p; c.relu = 1;
                 c.group = hw; c.src_group = hw; c.src_off = 0;
                 c.pw1 = wts->p_w1; c.pb1 = wts->p_b1; c.policy = d_policy; c.policy_len = m.policy_len; c.hw = hw;
-                if (launch("kz_conv1x1_split", [&] { kz::launch_conv1x1_split(c, stream); })) return 1;
+                if (launch(p, "kz_conv1x1_split", [&] { kz::launch_conv1x1_split(c, p.stream); })) return 1;
             } else {
-                if (conv(c0, x, cp, head0, c0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
+                if (conv(p, c0, x, cp, head0, c0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
                 kz::PolicyConvArgs a{head0, c0.cout_p, batch, hw, m.channels, pc, wts->p_w1, wts->p_b1,
                                      d_policy, m.policy_len, m.policy_kind == kz::POLICY_ATAXX_CONV ? 1 : 0};
-                if (launch("kz_policy_conv", [&] { kz::launch_policy_conv(dtype, a, stream); })) return 1;
+                if (launch(p, "kz_policy_conv", [&] { kz::launch_policy_conv(dtype, a, p.stream); })) return 1;
             }
             if (m.policy_kind == kz::POLICY_CONV && m.policy_extra_moves && !extra_in_scalar_head()) {
                 kz::PolicyExtraArgs e{x, cp, batch, hw, m.channels, m.policy_extra_moves, wts->pe_wc, wts->pe_bc,
                                       wts->pe_wl, wts->pe_bl, d_policy, m.policy_len, pc * hw};
-                if (launch("kz_policy_extra", [&] { kz::launch_policy_extra(dtype, e, stream); })) return 1;
+                if (launch(p, "kz_policy_extra", [&] { kz::launch_policy_extra(dtype, e, p.stream); })) return 1;
             }
             break;
         }
         case kz::POLICY_ARIMAA: {
             // ArimaaPolicyHead (post_act.py:144-173): policy = concat(scalar(common) [1 + 6], flatten(bulk(common)) [4 * hw])
             const DevConv &c0 = wts->p_conv0;
-            if (conv(c0, x, cp, head0, c0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
+            if (conv(p, c0, x, cp, head0, c0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
             kz::PolicyConvArgs a{head0, c0.cout_p, batch, hw, m.channels, 4, wts->p_w1, wts->p_b1,
                                  d_policy + 7, m.policy_len, 0};  // (the four planes start behind the seven scalars)
-            if (launch("kz_policy_conv", [&] { kz::launch_policy_conv(dtype, a, stream); })) return 1;
+            if (launch(p, "kz_policy_conv", [&] { kz::launch_policy_conv(dtype, a, p.stream); })) return 1;
             // the scalar branch has the ScalarHead's shape: the same kernel, seven outputs into the policy rows
             kz::ScalarHeadArgs sa{x, cp, batch, hw, m.channels, m.arimaa_hidden_channels, m.arimaa_hidden_size,
                                   wts->pa_w0, wts->pa_b0, wts->pa_w1, wts->pa_b1, wts->pa_w2, wts->pa_b2, d_policy,
                                   nullptr, 0, wts->pa_w1t};
             sa.n_out = 7;
             sa.out_ld = m.policy_len;
-            if (launch("kz_scalar_head", [&] { kz::launch_scalar_head(dtype, sa, stream); })) return 1;
+            if (launch(p, "kz_scalar_head", [&] { kz::launch_scalar_head(dtype, sa, p.stream); })) return 1;
             break;
         }
         case kz::POLICY_ATTENTION: {
             // bulk = conv_bulk(common) on all 64 squares; under = conv_under(common[:, :, 7, None, :]) on the
             // 8 squares of rank index 7 (post_act.py:128-129): source rows 56..63 of each board
-            if (conv(wts->p_bulk, x, cp, head0, wts->p_bulk.cout_p, M, 0, nullptr, false, m.h, m.w, hw, hw, 0))
+            if (conv(p, wts->p_bulk, x, cp, head0, wts->p_bulk.cout_p, M, 0, nullptr, false, m.h, m.w, hw, hw, 0))
                 return 1;
-            if (conv(wts->p_under, x, cp, head1, wts->p_under.cout_p, batch * 8, 0, nullptr, false, 1, 8, 8, hw, 56))
+            if (conv(p, wts->p_under, x, cp, head1, wts->p_under.cout_p, batch * 8, 0, nullptr, false, 1, 8, 8, hw, 56))
                 return 1;
             kz::AttentionArgs a{head0, head1, wts->p_bulk.cout_p, wts->p_under.cout_p, batch,
                                 m.policy_query_channels, wts->flat_to_att, d_policy, m.policy_len};
-            if (launch("kz_attention_gather", [&] { kz::launch_attention(dtype, a, stream); })) return 1;
+            if (launch(p, "kz_attention_gather", [&] { kz::launch_attention(dtype, a, p.stream); })) return 1;
             break;
         }
         case kz::POLICY_NONE: break;
@@ -305,20 +305,20 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
             const void *flat = x;
             int flat_ld = hw * cp;
             if (m.dense_hidden_channels) {
-                if (conv(wts->p_conv0, x, cp, head0, wts->p_conv0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0))
+                if (conv(p, wts->p_conv0, x, cp, head0, wts->p_conv0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0))
                     return 1;
                 flat = head0;
                 flat_ld = hw * wts->p_conv0.cout_p;
             }
             // Flatten + Linear: one GEMM row per board
             if (m.dense_hidden_size) {
-                if (conv(wts->p_fc0, flat, flat_ld, head1, wts->p_fc0.cout_p, batch, 1, nullptr, false, 1, 1, 1, 1, 0))
+                if (conv(p, wts->p_fc0, flat, flat_ld, head1, wts->p_fc0.cout_p, batch, 1, nullptr, false, 1, 1, 1, 1, 0))
                     return 1;
-                if (conv(wts->p_fc1, head1, wts->p_fc0.cout_p, nullptr, 0, batch, 0, nullptr, false, 1, 1, 1, 1, 0,
+                if (conv(p, wts->p_fc1, head1, wts->p_fc0.cout_p, nullptr, 0, batch, 0, nullptr, false, 1, 1, 1, 1, 0,
                          d_policy, m.policy_len))
                     return 1;
             } else {
-                if (conv(wts->p_fc1, flat, flat_ld, nullptr, 0, batch, 0, nullptr, false, 1, 1, 1, 1, 0, d_policy,
+                if (conv(p, wts->p_fc1, flat, flat_ld, nullptr, 0, batch, 0, nullptr, false, 1, 1, 1, 1, 0, d_policy,
                          m.policy_len))
                     return 1;
             }
@@ -329,21 +329,21 @@ inline int kz_engine::run_heads(int batch, float *d_scalars, float *d_policy) {
 }
 
 // dec (plan.heads only): the launch ends in decode_output and writes dec->values / dec->probs
-inline int kz_engine::forward_packed(const kz::PackedBoards &in, int batch, void *d_sout, void *d_pol, const kz::DecodeArgs *dec) {
+inline int kz_engine::forward_packed(const Pass &p, const kz::PackedBoards &in, int batch, void *d_sout, void *d_pol, const kz::DecodeArgs *dec) {
     const Model &m = *model;
     if (encodes_boards(plan)) {
-        if (run_tower(batch, (float *)d_sout, (float *)d_pol, &in, dec)) return 1;
-        return run_heads(batch, (float *)d_sout, (float *)d_pol);
+        if (run_tower(p, batch, (float *)d_sout, (float *)d_pol, &in, dec)) return 1;
+        return run_heads(p, batch, (float *)d_sout, (float *)d_pol);
     }
-    if (launch("kz_encode_packed", [&] { kz::launch_encode_packed(dtype, in, batch, m.h * m.w, x_in, cin_p, stream); })) return 1;
-    if (run_tower(batch, (float *)d_sout, (float *)d_pol)) return 1;
-    return run_heads(batch, (float *)d_sout, (float *)d_pol);
+    if (launch(p, "kz_encode_packed", [&] { kz::launch_encode_packed(dtype, in, batch, m.h * m.w, x_in, cin_p, p.stream); })) return 1;
+    if (run_tower(p, batch, (float *)d_sout, (float *)d_pol)) return 1;
+    return run_heads(p, batch, (float *)d_sout, (float *)d_pol);
 }
 
-inline int kz_engine::forward_dense(const void *d_nchw, int batch, void *d_sout, void *d_pol) {
+inline int kz_engine::forward_dense(const Pass &p, const void *d_nchw, int batch, void *d_sout, void *d_pol) {
     const Model &m = *model;
-    if (launch("kz_encode_dense", [&] { kz::launch_encode_dense(dtype, (const float *)d_nchw, batch, m.c_in, m.h * m.w, x_in, cin_p, stream); }))
+    if (launch(p, "kz_encode_dense", [&] { kz::launch_encode_dense(dtype, (const float *)d_nchw, batch, m.c_in, m.h * m.w, x_in, cin_p, p.stream); }))
         return 1;
-    if (run_tower(batch, (float *)d_sout, (float *)d_pol)) return 1;
-    return run_heads(batch, (float *)d_sout, (float *)d_pol);
+    if (run_tower(p, batch, (float *)d_sout, (float *)d_pol)) return 1;
+    return run_heads(p, batch, (float *)d_sout, (float *)d_pol);
 }

@@ -1,6 +1,6 @@
 // kz_engine_state.hpp — what an engine IS: the per-launch profiler, the model handle, and `struct kz_engine` with its
 // path (one PathPlan of kz_plan.hpp, asked whenever a kernel choice depends on it), streams, slots (pinned staging + device
-// buffers), range-check epochs and allocation bookkeeping.  The forward pass over
+// buffers + the one InFlight record), range-check epochs, the Pass a forward pass is given, and allocation bookkeeping.  The forward pass over
 // that state — which kernels run, in which order — is declared here and defined in kz_engine_forward.hpp; the `extern "C"`
 // entry points that drive both are kz_engine.hip.  Included ONCE, by kz_engine.hip, inside its anonymous namespace (the
 // first part) — the same arrangement as kz_engine_util.hpp / kz_plan.hpp / kz_device_weights.hpp.
@@ -101,13 +101,50 @@ struct BoardGather {
     std::vector<int32_t> midx;
 };
 
+// Where a forward pass is enqueued and where its range check reports (kz::ScalarHeadArgs: a kernel that meets a non-finite
+// activation raises *nf_flag to nf_epoch, and the per-board word in front of it).  Made by kz_engine's pass_* methods, one per
+// origin, and handed down through forward_* / run_tower / run_heads / conv / launch / stash: nothing else says where a pass goes.
+struct Pass {
+    hipStream_t stream;
+    int *nf_flag;
+    int nf_epoch;
+};
+
+// What a slot has in flight.  ONE record: assigned whole by the submit once its event is recorded (a submit that fails
+// leaves the slot free), and handed whole to the call that returns the batch by Slot::take(), which frees the slot.
+struct InFlight {
+    enum Kind : uint8_t { none, raw, decoded } kind = none;  // raw: scalars and policy rows; decoded: submitted with a move list
+    int batch = 0;
+    bool in_launch = false;  // decoded by the network's own launch ("+heads", zero copy), not by a kz_decode_output behind it
+    bool avg = false;        // an averaged submit: the network ran on batch * n_sym virtual boards
+    bool with_sym = false;   // the caller gave symmetry ids
+    size_t moves = 0;        // decoded: move_offsets[batch]
+    int audit_k = 0;         // the first audit_k boards also run on the audit's sibling (same slot index)
+    int epoch = 0;           // what the range words read where this batch met a non-finite activation (Pass::nf_epoch)
+    bool busy() const { return kind != none; }
+    bool is_decoded() const { return kind == decoded; }
+    // the per-batch range word of this batch is the pinned header's: the raw rows come with that header, and a decode inside
+    // the launch leaves the word where the launch reported (pass_pinned); a stand-alone decode copies it into h_err[1]
+    bool flag_in_header() const { return kind == raw || in_launch; }
+    // ... and so are the per-board words in front of it — but an averaged launch's count VIRTUAL boards, which
+    // kz_sym_average has folded into the decode's words like kz_decode_output does on the other paths
+    bool words_in_front() const { return kind == raw || (in_launch && !avg); }
+    // a sibling's submit of boards of this batch carries their ids (an averaged batch makes its own: 0 .. n_sym-1 per board)
+    bool ids_travel() const { return with_sym && !avg; }
+    // a decode error of this batch may be a symmetry's (an id not below n_sym, a move without an image): the error's wording
+    bool symmetries_involved() const { return with_sym || avg; }
+};
+
+// bytes of one board's packed bool planes
+inline size_t bits_bytes(const Model &m) { return (size_t)(m.n_bool * m.h * m.w + 7) / 8; }
+
 struct kz_engine {
     std::shared_ptr<Model> model;
     std::shared_ptr<DeviceWeights> wts;
     int device = 0, dtype = 0, max_batch = 0;
     int out_channels = 0;  // the network's own tower channels (model->channels may be widened: effective_model)
     size_t esz = 4;
-    hipStream_t stream = nullptr;          // the stream the forward pass is currently enqueued on
+    size_t bits_bytes() const { return ::bits_bytes(*model); }
     // [0] = the main stream.  On the fused path (one launch per batch, which touches nothing but its slot's buffers) slots
     // alternate over TWO streams — a batch of 256 is half a chip of workgroups, so two launches run side by side and the
     // next launch of a stream starts the moment the previous one ends — and the launch reads the packed boards from and
@@ -146,22 +183,21 @@ struct kz_engine {
         float *d_sout = nullptr, *h_sout = nullptr;
         float *d_pol = nullptr, *h_pol = nullptr;
         hipEvent_t done = nullptr;
-        int batch = -1;
-        int epoch = 0;  // what the flag reads when this submission saw a non-finite activation
+        InFlight fly;  // what `done` stands for; kind none: the slot is free
+        InFlight take() {
+            const InFlight f = fly;
+            fly = InFlight();
+            return f;
+        }
         // device-side decode (N2): CSR move lists, decoded values, probabilities, error flag; grown on demand
-        bool decoded = false;  // what is in flight was submitted with a move list
-        bool in_launch = false;  // ... and decoded by the network's own launch (the range check reports in h_sout's header)
-        size_t move_cap = 0, moves = 0;
+        size_t move_cap = 0;
         int64_t *h_moff = nullptr;
         int32_t *h_midx = nullptr;
         float *h_values = nullptr, *h_probs = nullptr;
         int *h_err = nullptr;  // [0] softmax sum / move index, [1] range check, then two words per board (kz_kernels.hpp:
                                // launch_decode_output, error_flag_words(max_batch)); cleared per submit by stage_decoded
-        bool avg = false;      // what is in flight is an averaged submit (the launches' range words count virtual boards)
         std::vector<uint8_t> status;  // [max_batch] KZ_BOARD_* of the batch last waited for (kz_engine_wait_decoded_status's view)
         uint8_t *h_sym = nullptr;  // [max_batch] symmetry ids of the batch (pinned, read by the launches; set_symmetries allocates it)
-        bool with_sym = false;     // what is in flight was submitted with symmetry ids
-        int audit_k = 0;           // the first audit_k boards of what is in flight also run on the audit's sibling (same slot index)
         // every board under every symmetry (the `_avg` entries, kz_symmetry_avg.hip): the VIRTUAL batch in device memory —
         // what kz_sym_fan_out writes and the network reads, what the decode writes and kz_sym_average reads.  Allocated at
         // the slot's first averaged submit, for max_batch virtual boards; the two move arrays grow like move_cap
@@ -206,8 +242,6 @@ struct kz_engine {
     // Epochs run 1 .. GRAPH_EPOCH-1 and start over (0 is the cleared word, GRAPH_EPOCH the replayed passes' constant):
     // at ~2k submissions/s an int would overflow after 12 days of self-play.
     int epoch = 0;
-    int *nf_flag = nullptr;  // what the running forward pass writes to
-    int nf_epoch = 0;
     int *d_devflag = nullptr;  // flag of the device-resident entry points, checked by kz_engine_synchronize
     int dev_epoch_enqueued = 0;  // epoch of the last device-resident enqueue (slot submissions do not touch d_devflag)
     int dev_epoch_checked = 0;
@@ -219,11 +253,10 @@ struct kz_engine {
             // the slots' own flag words too: a slot that once recorded a non-finite batch at epoch X keeps X in its header,
             // and X is about to be issued again (everything is idle here: sync_all above)
             for (auto &s : slots) {
-                if (s.batch >= 0) continue;  // (a finished batch nobody has waited for yet keeps its verdict)
+                if (s.fly.busy()) continue;  // (a finished batch nobody has waited for yet keeps its verdict)
                 // (with their per-board words in front: epoch-stamped like the flag itself)
                 if (s.d_sout) (void)hipMemset(s.d_sout - front_words(), 0, ((size_t)front_words() + 1) * 4);
                 if (s.h_sout) memset(s.h_sout - front_words(), 0, ((size_t)front_words() + 1) * 4);
-                s.epoch = 0;
             }
             epoch = dev_epoch_enqueued = dev_epoch_checked = 0;
         }
@@ -236,9 +269,17 @@ struct kz_engine {
         if (hipMemcpy(&v, d_devflag, 4, hipMemcpyDeviceToHost) == hipSuccess && v != GRAPH_EPOCH && v > dev_epoch_checked)
             wrap_nonfinite_pending = true;
     }
-    void arm_device() {  // the forward pass enqueued next reports into the device-resident flag
-        nf_flag = d_devflag;
-        nf_epoch = dev_epoch_enqueued = next_epoch();
+    // ---- the passes, by origin.  A slot's pass runs on the slot's stream: its own on the fused path, so that two submitted
+    // batches run side by side; otherwise the slots share the activation buffers and the main stream ----
+    hipStream_t stream_of(int slot) const { return slot_stream[slot] ? slot_stream[slot] : slot_stream[0]; }
+    // a slot whose results are copied back: the flag is the device header's, fetched with the scalars (or read by kz_decode_output)
+    Pass pass_staged(int slot) { return Pass{stream_of(slot), reinterpret_cast<int *>(slots[slot].d_sout), next_epoch()}; }
+    // a slot whose launch writes its pinned staging itself (zero copy): the flag is the pinned header's
+    Pass pass_pinned(int slot) { return Pass{stream_of(slot), reinterpret_cast<int *>(slots[slot].h_sout), next_epoch()}; }
+    // the device-resident entry points: the main stream, the flag kz_engine_synchronize checks
+    Pass pass_resident() {
+        dev_epoch_enqueued = next_epoch();
+        return Pass{slot_stream[0], d_devflag, dev_epoch_enqueued};
     }
 
     // hipGraph replay of the forward pass (KZ_HIP_GRAPH=1; multi-launch paths only — the one-launch paths have nothing to
@@ -261,9 +302,15 @@ struct kz_engine {
     };
     std::vector<GraphEntry> graphs;
     bool graph_mode() const { return plan.graph && graph_warm && !prof.on && !plan.keep; }
-    // runs `body` (which enqueues on `stream`) through the graph of this key: captured at first sight
+    // a replayed pass: slot `kind`'s device header, or (-1) the device-resident flag with its enqueue noted, at the constant epoch
+    Pass pass_replayed(int kind) {
+        if (kind < 0) dev_epoch_enqueued = next_epoch();
+        return Pass{kind < 0 ? slot_stream[0] : stream_of(kind), kind < 0 ? d_devflag : reinterpret_cast<int *>(slots[kind].d_sout), GRAPH_EPOCH};
+    }
+    // runs `body` (which enqueues on p.stream) through the graph of this key: captured at first sight
     template <class Body>
-    int replay(int kind, int batch, const void *bits, size_t stride, const void *sin, void *sout, void *pol, Body body) {
+    int replay(const Pass &p, int kind, int batch, const void *bits, size_t stride, const void *sin, void *sout, void *pol, Body body) {
+        hipStream_t stream = p.stream;
         for (const GraphEntry &g : graphs)
             if (g.kind == kind && g.batch == batch && g.bits == bits && g.stride == stride && g.sin == sin && g.sout == sout &&
                 g.pol == pol) {
@@ -288,12 +335,13 @@ struct kz_engine {
         return 0;
     }
 #endif
-    void arm(Slot &s) {  // the forward pass enqueued next reports into this slot's header
-        s.epoch = next_epoch();
-        nf_flag = reinterpret_cast<int *>(s.d_sout);
-        nf_epoch = s.epoch;
+    static bool slot_nonfinite(const Slot &s, int epoch) { return *reinterpret_cast<const int *>(s.h_sout) == epoch; }
+    // "a batch is in flight": what the calls that change something every slot depends on ask first
+    int idle(const std::string &fn) const {
+        for (const auto &s : slots)
+            if (s.fly.busy()) return fail(fn + ": a batch is in flight (wait for every slot first)");
+        return 0;
     }
-    static bool slot_nonfinite(const Slot &s) { return *reinterpret_cast<const int *>(s.h_sout) == s.epoch; }
     int check_devflag() {
         if (wrap_nonfinite_pending) {
             wrap_nonfinite_pending = false;
@@ -339,32 +387,32 @@ struct kz_engine {
     float *range_out = nullptr;
     int range_site = 0;
 
-    int stash(const std::string &name, const void *src, int batch) {
+    int stash(const Pass &p, const std::string &name, const void *src, int batch) {
         if (!plan.keep) return 0;
         if (range_out) {
             float *out = range_out + (size_t)range_site++ * max_batch;
-            return launch("kz_range_absmax", [&] {
-                kz::launch_range_absmax((const float *)src, batch, model->h * model->w, model->channels, cp, out, stream);
+            return launch(p, "kz_range_absmax", [&] {
+                kz::launch_range_absmax((const float *)src, batch, model->h * model->w, model->channels, cp, out, p.stream);
             });
         }
         const size_t bytes = (size_t)batch * model->h * model->w * cp * esz;
         auto it = kept.find(name);
         if (it == kept.end()) {
-            void *p = nullptr;
-            if (dmalloc(&p, (size_t)max_batch * model->h * model->w * cp * esz)) return 1;
-            it = kept.emplace(name, p).first;
+            void *buf = nullptr;
+            if (dmalloc(&buf, (size_t)max_batch * model->h * model->w * cp * esz)) return 1;
+            it = kept.emplace(name, buf).first;
         }
-        HIP_TRY(hipMemcpyAsync(it->second, src, bytes, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(it->second, src, bytes, hipMemcpyDeviceToDevice, p.stream));
         return 0;
     }
 
     // ---- the forward pass (kz_engine_forward.hpp) ----
-    // the bracket of every launch: `enqueue` starts kernel `name` (the profiler's and kz_engine_kernel_time's name) on `stream`
+    // the bracket of every launch: `enqueue` starts kernel `name` (the profiler's and kz_engine_kernel_time's name) on p.stream
     template <class F>
-    int launch(const char *name, F &&enqueue) {
-        prof.begin(name, stream);
+    int launch(const Pass &p, const char *name, F &&enqueue) {
+        prof.begin(name, p.stream);
         enqueue();
-        prof.end(stream);
+        prof.end(p.stream);
         HIP_TRY(hipGetLastError());
         return 0;
     }
@@ -379,13 +427,25 @@ struct kz_engine {
         }
         return in;
     }
-    int conv(const DevConv &w, const void *x, int ldx, void *y, int ldy, int M, int relu, const void *res, bool post,
+    // the caller's boards into a slot's pinned input staging, rows packed to bits_bytes()
+    void stage_boards(Slot &s, const uint8_t *bits, size_t stride, const float *scalars, int batch) const {
+        const size_t bb = bits_bytes();
+        for (int b = 0; b < batch; b++) memcpy(s.h_bits + b * bb, bits + b * stride, bb);
+        if (model->n_scalar) memcpy(s.h_sin, scalars, (size_t)batch * model->n_scalar * 4);
+    }
+    // ... and, where the launches do not read the pinned staging themselves, on to the slot's device copies
+    int copy_boards_in(const Pass &p, Slot &s, int batch) const {
+        HIP_TRY(hipMemcpyAsync(s.d_bits, s.h_bits, batch * bits_bytes(), hipMemcpyHostToDevice, p.stream));
+        HIP_TRY(hipMemcpyAsync(s.d_sin, s.h_sin, (size_t)batch * model->n_scalar * 4, hipMemcpyHostToDevice, p.stream));
+        return 0;
+    }
+    int conv(const Pass &p, const DevConv &w, const void *x, int ldx, void *y, int ldy, int M, int relu, const void *res, bool post,
              int h, int wd, int group, int src_group, int src_off, float *y32 = nullptr, int ldy32 = 0);
     // packed: boards still to be encoded (the one-launch towers encode inside the launch)
-    int run_tower(int batch, float *d_scalars, float *d_policy, const kz::PackedBoards *packed = nullptr,
+    int run_tower(const Pass &p, int batch, float *d_scalars, float *d_policy, const kz::PackedBoards *packed = nullptr,
                   const kz::DecodeArgs *dec = nullptr);
     bool extra_in_scalar_head() const;
-    int run_heads(int batch, float *d_scalars, float *d_policy);
-    int forward_packed(const kz::PackedBoards &in, int batch, void *d_sout, void *d_pol, const kz::DecodeArgs *dec = nullptr);
-    int forward_dense(const void *d_nchw, int batch, void *d_sout, void *d_pol);
+    int run_heads(const Pass &p, int batch, float *d_scalars, float *d_policy);
+    int forward_packed(const Pass &p, const kz::PackedBoards &in, int batch, void *d_sout, void *d_pol, const kz::DecodeArgs *dec = nullptr);
+    int forward_dense(const Pass &p, const void *d_nchw, int batch, void *d_sout, void *d_pol);
 };

@@ -10,6 +10,12 @@ int fail(const std::string &msg) {
     return 1;
 }
 
+// what every packed-input entry tells the owner of an ONNX model whose planes it cannot tell apart
+std::string no_plane_split(const std::string &fn) {
+    return fn + ": the model was loaded from ONNX without the scalar/bool plane split; load it with "
+                "kz_model_load_onnx(path, input_scalar_channels) to use packed inputs";
+}
+
 // No C++ exception may cross the C ABI: the host on the other side is Rust (kzero_amd/rust/hip.rs), where an unwinding
 // foreign exception is undefined behaviour / an abort.  Every `extern "C"` entry point of kz_engine.hip runs its body through
 // this: std::bad_alloc / std::length_error from host-side packing or an absurd max_batch become a non-zero return with a
