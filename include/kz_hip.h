@@ -362,6 +362,37 @@ int kz_model_range_profile_fast(const kz_model *model, int device, const uint8_t
                                 const float *scalars_in, int batch, float *site_max_out, float *board_max_out);
 int kz_model_range_profile_fast_path(const kz_model *model, char *buf, size_t len);
 
+/* ---- range histogram: how much of every stored tower tensor sits in each binade ----
+ * The profile above measures one end of the distribution, max |x|.  The histogram counts every stored value of every site by
+ * binade, exactly, so that for any shift k and any arithmetic the caller can read off the share of stored values that overflow
+ * f16, become f16 subnormals, flush to zero, or lose the lo half of a split16 pair (the bindings' shift_report does the sums).
+ * The bins, KZ_RANGE_BINS of them.  For a stored f32 value with bit pattern u, let a = u & 0x7fffffff and e = a >> 23:
+ *   a == 0 (+-0)             bin 0
+ *   e == 255 (inf or NaN)    bin 95
+ *   otherwise                E = e - 127 (an f32 subnormal counts as E = -127); bin = clamp(E, -50, 43) + 51:
+ *                            bin b in 2 .. 93 holds 2^(b-51) <= |x| < 2^(b-50), bin 1 holds 0 < |x| < 2^-49, bin 94 holds
+ *                            finite |x| >= 2^43
+ * This resolves f16's whole window under every k in [-24, 24]: the smallest subnormal half, 2^-25, at k = -24 is bin 2, and
+ * 2^16 at k = 24 is bin 91.  The binning is integer arithmetic on the bit pattern, never a floating comparison.
+ * kz_model_range_histogram has kz_model_range_profile's contract — the same sites in the same order, the same refusals (each
+ * in this function's name), the same internal exact-f32 per-layer engine and chunks — and fills hist_out [n_sites][KZ_RANGE_BINS]:
+ * the number of elements of each site's tensors, over all boards and over real channels only, per bin.  Every element is
+ * counted once: a site's 96 counts sum to batch * h * w * tower_channels.  What is counted is the value that is stored (after
+ * ReLU, the residual add and the final BatchNorm), as for the maxima.  The counts are integers: they do not depend on the batch
+ * split, a board's place, or scheduling.  A non-finite value lands in bin 95; what the later sites hold for THAT board is
+ * unspecified (ReLU turns a NaN into 0), its elements are still counted once per site, and no other board's counts change.
+ * kz_model_range_histogram_fast is the same call inside the one-launch exact-f32 tower wherever
+ * kz_model_range_profile_fast_path says "tower_resident_f32" (the epilogues bin what they store while it is in LDS; the device
+ * weight stream is the one ordinary exact-f32 engines of the model share), and exactly kz_model_range_histogram elsewhere.  On
+ * exactly representable tensors the two return the same counts; otherwise they differ where two exact-f32 summation orders
+ * put a value on different sides of a binade boundary.  (hist_out: uint64_t [n_sites][KZ_RANGE_BINS], typed void like the
+ * status bytes of kz_engine_wait_status.) */
+#define KZ_RANGE_BINS 96
+int kz_model_range_histogram(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                             int batch, void *hist_out);
+int kz_model_range_histogram_fast(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride,
+                                  const float *scalars_in, int batch, void *hist_out);
+
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and
  * returns; kz_engine_synchronize waits. */

@@ -99,6 +99,8 @@ SIGNATURES = {
     "kz_model_range_profile_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p]),
     "kz_model_range_profile_fast_path": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
+    "kz_model_range_histogram": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "kz_model_range_histogram_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "kz_engine_max_batch": (C.c_int, [C.c_void_p]),
     "kz_engine_eval_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "kz_engine_eval_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
@@ -197,6 +199,48 @@ def shift_for(max_abs: float, headroom_bits: int = 2) -> int:
     return max(0, ceil_log2 + int(headroom_bits))
 
 
+KZ_RANGE_BINS = 96  # include/kz_hip.h: bin 0 +-0, bin 95 inf / NaN, bin b in 1 .. 94 the binade E = b - 51 (the ends clamped)
+SHIFT_REPORT_FIELDS = ("total", "zero", "nonfinite", "f16_over", "f16_top", "f16_subnormal", "f16_flushed", "split_lo_subnormal",
+                       "clamped_low", "clamped_high")
+
+
+def shift_report(hist: np.ndarray, k: int) -> dict:
+    """What a stream shift of k does to the stored values a range histogram counted (Model.range_histogram; hist
+    [n_sites, 96]): per site E' = E - k on the shifted sites and E' = E on the last one, and the counts — uint64 [n_sites] each —
+      total, zero, nonfinite                  all elements; +-0; inf or NaN
+      f16_over, f16_top                       E' >= 16: beyond f16; E' = 15: the binade that holds 65504 .. 65536
+      f16_subnormal, f16_flushed              -25 <= E' <= -15; E' < -25: rounds to zero or to the smallest subnormal
+      split_lo_subnormal                      E' <= -3: the lo half of a split16 pair is subnormal or gone
+      clamped_low, clamped_high               the two end bins (E <= -50, E >= 43) as they are: for every k in [-24, 24] they lie
+                                              in f16_flushed (and split_lo_subnormal) and in f16_over, so nothing is guessed
+    Pure integer arithmetic: the library reports, the caller decides, as for shift_for."""
+    hist = np.asarray(hist)
+    if hist.ndim != 2 or hist.shape[1] != KZ_RANGE_BINS or hist.shape[0] < 1:
+        raise KzError(f"shift_report: hist must be [n_sites, {KZ_RANGE_BINS}], got {hist.shape}")
+    k = int(k)
+    if not -24 <= k <= 24:
+        raise KzError(f"shift_report: k = {k} out of range [-24, 24]")
+    hist = hist.astype(np.uint64)
+    n = hist.shape[0]
+    out = {name: np.zeros(n, np.uint64) for name in SHIFT_REPORT_FIELDS}
+    for site in range(n):
+        row = [int(v) for v in hist[site]]
+        shift = k if site < n - 1 else 0  # (the last site is behind the final BatchNorm: a shift does not move it)
+        r = dict.fromkeys(SHIFT_REPORT_FIELDS, 0)
+        r["total"], r["zero"], r["nonfinite"] = sum(row), row[0], row[KZ_RANGE_BINS - 1]
+        r["clamped_low"], r["clamped_high"] = row[1], row[KZ_RANGE_BINS - 2]
+        for b in range(1, KZ_RANGE_BINS - 1):
+            e = b - 51 - shift  # (bin 1: at most this; bin 94: at least this — the classes below hold for both)
+            r["f16_over"] += row[b] if e >= 16 else 0
+            r["f16_top"] += row[b] if e == 15 else 0
+            r["f16_subnormal"] += row[b] if -25 <= e <= -15 else 0
+            r["f16_flushed"] += row[b] if e < -25 else 0
+            r["split_lo_subnormal"] += row[b] if e <= -3 else 0
+        for name in SHIFT_REPORT_FIELDS:
+            out[name][site] = r[name]
+    return out
+
+
 class Model:
     """`Arc<Graph>`: immutable, shareable across engines, threads and devices."""
 
@@ -266,6 +310,20 @@ class Model:
         buf = C.create_string_buffer(32)
         check(load().kz_model_range_profile_fast_path(self._h, buf, len(buf)))
         return buf.value.decode()
+
+    def range_histogram(self, device: int, bits: np.ndarray, scalars_in: np.ndarray, fast: bool = True) -> np.ndarray:
+        """How many stored values of every site lie in each binade on these boards, counted in exact f32 on the GPU: uint64
+        [n_sites, 96], every row summing to batch * h * w * tower_channels (kz_model_range_histogram_fast: inside the one-launch
+        tower where range_profile_fast_path says so; fast=False: kz_model_range_histogram, per layer).  shift_report reads it."""
+        n = C.c_int()
+        check(load().kz_model_range_sites(self._h, C.byref(n)))
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        hist = np.zeros((n.value, KZ_RANGE_BINS), np.uint64)
+        entry = load().kz_model_range_histogram_fast if fast else load().kz_model_range_histogram
+        check(entry(self._h, device, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0, scalars_in.ctypes.data,
+                    bits.shape[0], hist.ctypes.data))
+        return hist
 
     def _range_profile(self, entry: str, device: int, bits: np.ndarray, scalars_in: np.ndarray):
         n = C.c_int()

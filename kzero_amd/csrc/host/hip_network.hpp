@@ -126,6 +126,43 @@ inline int shift_for(float max_abs, int headroom_bits = 2) {
     return std::max(0, ceil_log2 + headroom_bits);
 }
 
+// What a stream shift of k does to the stored values a range histogram counted (HipModel::range_histogram: hist
+// [n_sites][KZ_RANGE_BINS], include/kz_hip.h), per site: E' = E - k on the shifted sites, E' = E on the last one.
+//   f16_over E' >= 16; f16_top E' = 15 (the binade of 65504 .. 65536); f16_subnormal -25 <= E' <= -15; f16_flushed E' < -25;
+//   split_lo_subnormal E' <= -3 (the lo half of a split16 pair is subnormal or gone)
+//   clamped_low, clamped_high: the two end bins (E <= -50, E >= 43) as they are — for every k in [-24, 24] they lie in
+//   f16_flushed (and split_lo_subnormal) and in f16_over, so nothing is guessed
+// Integer arithmetic only; the library reports, the caller decides.
+struct ShiftReport {
+    uint64_t total = 0, zero = 0, nonfinite = 0, f16_over = 0, f16_top = 0, f16_subnormal = 0, f16_flushed = 0,
+             split_lo_subnormal = 0, clamped_low = 0, clamped_high = 0;
+};
+inline std::vector<ShiftReport> shift_report(const std::vector<uint64_t> &hist, int k) {
+    if (hist.empty() || hist.size() % KZ_RANGE_BINS) throw std::invalid_argument("shift_report: hist must be [n_sites][96]");
+    if (k < -24 || k > 24) throw std::invalid_argument("shift_report: k out of range [-24, 24]");
+    const size_t n = hist.size() / KZ_RANGE_BINS;
+    std::vector<ShiftReport> out(n);
+    for (size_t site = 0; site < n; site++) {
+        const uint64_t *row = hist.data() + site * KZ_RANGE_BINS;
+        const int shift = site + 1 < n ? k : 0;
+        ShiftReport &r = out[site];
+        for (int b = 0; b < KZ_RANGE_BINS; b++) r.total += row[b];
+        r.zero = row[0];
+        r.nonfinite = row[KZ_RANGE_BINS - 1];
+        r.clamped_low = row[1];
+        r.clamped_high = row[KZ_RANGE_BINS - 2];
+        for (int b = 1; b < KZ_RANGE_BINS - 1; b++) {
+            const int e = b - 51 - shift;  // (bin 1: at most this; bin 94: at least this — the classes hold for both)
+            if (e >= 16) r.f16_over += row[b];
+            if (e == 15) r.f16_top += row[b];
+            if (e >= -25 && e <= -15) r.f16_subnormal += row[b];
+            if (e < -25) r.f16_flushed += row[b];
+            if (e <= -3) r.split_lo_subnormal += row[b];
+        }
+    }
+    return out;
+}
+
 // the `Arc<Graph>` of the reference: immutable, shared by every executor
 // (auto_stream_shift hands the model itself back when no shift is needed: for that call it must live in a shared_ptr)
 class HipModel : public std::enable_shared_from_this<HipModel> {
@@ -186,6 +223,18 @@ class HipModel : public std::enable_shared_from_this<HipModel> {
         RangeProfile r{std::vector<float>((size_t)n), std::vector<float>((size_t)std::max(batch, 0))};
         kz_check(kz_model_range_profile_fast(ptr_, device, bits, bits_stride, scalars_in, batch, r.site_max.data(), r.board_max.data()));
         return r;
+    }
+    // How many stored values of every site lie in each binade, counted in exact f32 on `device`: [n_sites][KZ_RANGE_BINS], every
+    // site summing to batch * h * w * tower_channels (kz_model_range_histogram_fast: inside the one-launch tower where
+    // range_profile_fast_path says so; fast = false: kz_model_range_histogram, per layer).  shift_report reads it.
+    std::vector<uint64_t> range_histogram(int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in, int batch,
+                                          bool fast = true) const {
+        int n = 0;
+        kz_check(kz_model_range_sites(ptr_, &n));
+        std::vector<uint64_t> hist((size_t)n * KZ_RANGE_BINS);
+        kz_check((fast ? kz_model_range_histogram_fast : kz_model_range_histogram)(ptr_, device, bits, bits_stride, scalars_in, batch,
+                                                                                  (void *)hist.data()));
+        return hist;
     }
     std::string range_profile_fast_path() const {
         char buf[32];

@@ -200,8 +200,11 @@ static bool known_dtype(int dtype) {
 // kz_engine_create; profile: the range profile's internal engine — exact f32, no environment switch read, whatever plan_path
 // would choose.  per_layer (kz_model_range_profile): the per-layer implicit GEMM, every stash site a range measurement;
 // resident (kz_model_range_profile_fast where tower32_supported holds): the one-launch f32 tower without heads, whose
-// PROFILE instance measures in its epilogues — the same weight stream as an ordinary exact-f32 engine's (WeightsKey)
-enum class Profile { none, per_layer, resident };
+// PROFILE instance measures in its epilogues — the same weight stream as an ordinary exact-f32 engine's (WeightsKey).
+// per_layer_hist, resident_hist (kz_model_range_histogram, _fast): the same two engines counting binades instead of taking maxima
+enum class Profile { none, per_layer, resident, per_layer_hist, resident_hist };
+static bool profile_per_layer(Profile p) { return p == Profile::per_layer || p == Profile::per_layer_hist; }
+static bool profile_hist(Profile p) { return p == Profile::per_layer_hist || p == Profile::resident_hist; }
 static int create_engine(const kz_model *model, int device, int max_batch, int dtype, Profile profile, kz_engine **out) {
     {
         if (!model || !out) return fail("kz_engine_create: null argument");
@@ -242,11 +245,11 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         e->cp = round_up(m.channels, 32);
         // which kernels run this network: plan_path (kz_plan.hpp) — the table of DESIGN.md §5 is printed from it
         std::string why;
-        if (profile == Profile::per_layer) {
+        if (profile_per_layer(profile)) {
             e->plan = PathPlan();  // (Tower::conv_igemm)
             e->plan.keep = true;
             e->plan.launches = 2 + 2 * m.depth;
-        } else if (profile == Profile::resident) {
+        } else if (profile != Profile::none) {
             e->plan = PathPlan();
             e->plan.tower = Tower::resident_f32;
             e->plan.launches = 1;
@@ -334,7 +337,14 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         if (e->dmalloc((void **)&devflag_base, (front + 4) * 4)) return 1;
         HIP_TRY(hipMemset(devflag_base, 0, (front + 4) * 4));
         e->d_devflag = devflag_base + front;
-        if (profile != Profile::none && e->dmalloc((void **)&e->range_out, (size_t)(2 * m.depth + 1) * max_batch * 4)) return 1;
+        if (profile_hist(profile)) {
+            const size_t bytes = (size_t)(2 * m.depth + 1) * kz::RANGE_BINS * sizeof(unsigned long long);
+            if (e->dmalloc(&e->range_out, bytes)) return 1;
+            HIP_TRY(hipMemset(e->range_out, 0, bytes));
+            e->range_hist = true;
+        } else if (profile != Profile::none && e->dmalloc(&e->range_out, (size_t)(2 * m.depth + 1) * max_batch * 4)) {
+            return 1;
+        }
         *out = e.release();
         return 0;
     }
@@ -425,23 +435,29 @@ KZ_API int kz_model_range_site_name(const kz_model *model, int site, char *buf, 
 // where kz_model_range_profile_fast runs: the one-launch exact-f32 tower wherever the kernel takes the shape
 static bool range_profile_resident(const Model &m) { return kz::tower32_supported(KZ_DTYPE_F32, m.h, m.w, m.channels, m.depth); }
 
-// both profile entries: an internal engine of `mode` with max_batch = min(batch, chunk_max), the boards in chunks of that
+// the profile and histogram entries: an internal engine of `mode` with max_batch = min(batch, chunk_max), the boards in chunks
+// of that.  A histogram mode fills hist_out [n_sites][KZ_RANGE_BINS] — the engine's counters add up over the chunks and are
+// read once — and the two maxima pointers are null.
+static_assert(KZ_RANGE_BINS == kz::RANGE_BINS, "the kernels' bins are the header's");
 static int range_profile(const std::string &fn, Profile mode, int chunk_max, const kz_model *model, int device, const uint8_t *bits,
-                         size_t bits_stride, const float *scalars_in, int batch, float *site_max_out, float *board_max_out) {
+                         size_t bits_stride, const float *scalars_in, int batch, float *site_max_out, float *board_max_out,
+                         uint64_t *hist_out = nullptr) {
+    const bool hist = profile_hist(mode);
     int n = 0;
     if (range_site_count(fn.c_str(), model, n)) return 1;
     const Model &m = *model->m;
     if (m.n_scalar < 0) return fail(no_plane_split(fn));
     if (batch < 1) return fail(fn + ": batch must be positive");
-    if (!bits || (m.n_scalar && !scalars_in) || !site_max_out) return fail(fn + ": null argument");
+    if (!bits || (m.n_scalar && !scalars_in) || !(hist ? (const void *)hist_out : (const void *)site_max_out)) return fail(fn + ": null argument");
     if (bits_stride < bits_bytes(m)) return fail(fn + ": bits_stride too small");
     const int chunk = std::min(batch, chunk_max);
     kz_engine *raw = nullptr;
-    if (create_engine(model, device, chunk, KZ_DTYPE_F32, mode, &raw)) return 1;
+    // (a histogram entry's every failure is in its own name; the maxima entries keep the engine's message as it is)
+    if (create_engine(model, device, chunk, KZ_DTYPE_F32, mode, &raw)) return hist ? fail(fn + ": " + std::string(g_err)) : 1;
     std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(raw, kz_engine_destroy);
     kz_engine::Slot &s = e->slots[0];
-    std::vector<float> host((size_t)n * chunk);
-    for (int i = 0; i < n; i++) site_max_out[i] = 0.0f;
+    std::vector<float> host(hist ? 0 : (size_t)n * chunk);
+    for (int i = 0; i < n && !hist; i++) site_max_out[i] = 0.0f;
     // (the kernel's values are never NaN: a non-finite board reports +inf)
     for (int lo = 0; lo < batch; lo += chunk) {
         const int nb = std::min(chunk, batch - lo);
@@ -450,7 +466,7 @@ static int range_profile(const std::string &fn, Profile mode, int chunk_max, con
         if (e->copy_boards_in(p, s, nb)) return 1;
         // the tower only: the heads read nothing the profile reports
         const kz::PackedBoards in = e->packed_boards(s.d_bits, e->bits_bytes(), s.d_sin);
-        if (mode == Profile::resident) {  // one launch: encode, tower and the maxima
+        if (!profile_per_layer(mode)) {  // one launch: encode, tower and the maxima
             if (e->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &in)) return 1;
         } else {
             if (e->launch(p, "kz_encode_packed", [&] { kz::launch_encode_packed(e->dtype, in, nb, m.h * m.w, e->x_in, e->cin_p, p.stream); }))
@@ -458,8 +474,9 @@ static int range_profile(const std::string &fn, Profile mode, int chunk_max, con
             if (e->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
         }
         if (e->range_site != n) return fail(fn + ": internal error: " + std::to_string(e->range_site) + " sites measured, " + std::to_string(n) + " expected");
-        HIP_TRY(hipMemcpyAsync(host.data(), e->range_out, host.size() * 4, hipMemcpyDeviceToHost, p.stream));
-        HIP_TRY(hipStreamSynchronize(p.stream));
+        if (!hist) HIP_TRY(hipMemcpyAsync(host.data(), e->range_out, host.size() * 4, hipMemcpyDeviceToHost, p.stream));
+        HIP_TRY(hipStreamSynchronize(p.stream));  // (the staging is free for the next chunk)
+        if (hist) continue;
         for (int b = 0; b < nb; b++) {
             // behind a non-finite tensor the values are not the network's (ReLU turns a NaN into 0): the board reports +inf
             // from its first non-finite site on
@@ -471,6 +488,11 @@ static int range_profile(const std::string &fn, Profile mode, int chunk_max, con
                 if (board_max_out && i < n - 1) board_max_out[lo + b] = i == 0 ? v : std::max(board_max_out[lo + b], v);
             }
         }
+    }
+    if (hist) {
+        static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "the counters");
+        const size_t bytes = (size_t)n * kz::RANGE_BINS * sizeof(uint64_t);
+        HIP_TRY(hipMemcpy(hist_out, e->range_out, bytes, hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -493,6 +515,26 @@ KZ_API int kz_model_range_profile_fast(const kz_model *model, int device, const 
         const bool resident = range_profile_resident(*model->m);
         return range_profile(fn, resident ? Profile::resident : Profile::per_layer, resident ? 256 : 64, model, device, bits, bits_stride,
                              scalars_in, batch, site_max_out, board_max_out);
+    });
+}
+
+KZ_API int kz_model_range_histogram(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                                    int batch, void *hist_out) {
+    return guarded("kz_model_range_histogram", [&]() -> int {
+        return range_profile("kz_model_range_histogram", Profile::per_layer_hist, 64, model, device, bits, bits_stride, scalars_in, batch,
+                             nullptr, nullptr, (uint64_t *)hist_out);
+    });
+}
+
+KZ_API int kz_model_range_histogram_fast(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride,
+                                         const float *scalars_in, int batch, void *hist_out) {
+    return guarded("kz_model_range_histogram_fast", [&]() -> int {
+        const std::string fn = "kz_model_range_histogram_fast";
+        int n = 0;
+        if (range_site_count(fn.c_str(), model, n)) return 1;
+        const bool resident = range_profile_resident(*model->m);
+        return range_profile(fn, resident ? Profile::resident_hist : Profile::per_layer_hist, resident ? 256 : 64, model, device, bits,
+                             bits_stride, scalars_in, batch, nullptr, nullptr, (uint64_t *)hist_out);
     });
 }
 

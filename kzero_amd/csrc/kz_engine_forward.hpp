@@ -152,7 +152,8 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         t.wide = plan.wide;
         if (range_out) {  // the range profile's engine (resident_f32, no heads): the maxima instead of the tower output
             t.profile = true;
-            t.y = range_out; t.ldy = max_batch;
+            if (range_hist) t.hist = (unsigned long long *)range_out;  // (the counts instead of the maxima)
+            else { t.y = (float *)range_out; t.ldy = max_batch; }
             range_site = 2 * m.depth + 1;  // every epilogue of the launch is a site
         }
         const bool f16g = plan.tower == Tower::resident_f16g;

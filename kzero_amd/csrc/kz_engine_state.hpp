@@ -384,13 +384,22 @@ struct kz_engine {
     // memory, range_site counts the sites of the running pass in stash order (kz_model_range_site_name's order)
     // (kz_model_range_profile_fast's engine — the one-launch exact-f32 tower — hands range_out to the launch's PROFILE instance
     // instead, which fills all of it: kz_engine_forward.hpp)
-    float *range_out = nullptr;
+    // range_hist (kz_model_range_histogram and _fast): the same engines in histogram mode — range_out holds 64-bit counters
+    // [n_sites][KZ_RANGE_BINS] instead, zero at creation, and every pass ADDS the binade counts of what it stores
+    void *range_out = nullptr;
+    bool range_hist = false;
     int range_site = 0;
 
     int stash(const Pass &p, const std::string &name, const void *src, int batch) {
         if (!plan.keep) return 0;
+        if (range_hist) {
+            unsigned long long *out = (unsigned long long *)range_out + (size_t)range_site++ * kz::RANGE_BINS;
+            return launch(p, "kz_range_histogram", [&] {
+                kz::launch_range_histogram((const float *)src, batch, model->h * model->w, model->channels, cp, out, p.stream);
+            });
+        }
         if (range_out) {
-            float *out = range_out + (size_t)range_site++ * max_batch;
+            float *out = (float *)range_out + (size_t)range_site++ * max_batch;
             return launch(p, "kz_range_absmax", [&] {
                 kz::launch_range_absmax((const float *)src, batch, model->h * model->w, model->channels, cp, out, p.stream);
             });

@@ -59,6 +59,19 @@ void launch_encode_dense(int dtype, const float *nchw, int batch, int c, int hw,
 // cp floats (a multiple of 32: rows are 128-byte aligned); +inf for a board with any non-finite value.  One workgroup per board.
 void launch_range_absmax(const float *x, int boards, int hw, int channels, int cp, float *out, hipStream_t stream);
 
+// The range histogram's bin of a stored f32 value with bit pattern u (include/kz_hip.h: KZ_RANGE_BINS): integer arithmetic
+// on the pattern — 0: +-0; 95: inf or NaN; otherwise the biased exponent clamped to [77, 170] (E = e - 127 in [-50, 43],
+// an f32 subnormal far below) less 76.
+constexpr int RANGE_BINS = 96;
+__host__ __device__ inline unsigned range_bin(unsigned u) {
+    const unsigned a = u & 0x7fffffffu, e = a >> 23;
+    const unsigned b = (e < 77u ? 77u : e > 170u ? 170u : e) - 76u;
+    return a == 0 ? 0u : e == 255u ? 95u : b;
+}
+// hist[bin] += the number of values of that bin among the boards * hw rows of `channels` real f32 values (row stride cp floats,
+// as above).  hist: RANGE_BINS 64-bit counters in device memory, added to with integer atomics (kz_range_profile.hip).
+void launch_range_histogram(const float *x, int boards, int hw, int channels, int cp, unsigned long long *hist, hipStream_t stream);
+
 // Implicit-GEMM convolution, kernel k in {1,3}, pad k/2, fused epilogue:
 //   v = acc + bias[oc];  if (relu) v = max(v, 0);  if (res) v += res[row][oc];
 //   if (post_scale) v = v * post_scale[oc] + post_shift[oc];  y[row][oc] = v
@@ -349,6 +362,8 @@ struct Tower32Args {
     bool dense3 = false;  // launch_tower32, experiment build: three 7x7 boards per workgroup (tower32_dense3_supported)
     bool profile = false; // launch_tower32: the range profile's instance — no heads, no tower output; `y` takes max |x| per
                           // (site, board), [1 + 2*depth][ldy] with ldy counted in boards (>= batch)
+    unsigned long long *hist = nullptr;  // with profile: the range histogram's instance instead — `y` is not written, and
+                          // hist [1 + 2*depth][RANGE_BINS] (device memory) is ADDED to with integer atomics
     // launch_tower32 only: the conv policy head (Conv1x1 C->C + ReLU in the weight stream as one more centre-tap layer,
     // then Conv1x1 C->pc, post_act.py:75-110) and the scalar head (post_act.py:8-31) in the same launch — the tower
     // output never leaves LDS and `y` is not written.  tower32_heads_supported says for which models.

@@ -63,7 +63,7 @@ struct TowerF32Dev {
     const f32x4 *w;     // fragment-packed: stem steps, then 2*depth layers of 9*C/16 steps (tower32_pack_weights)
     const float *bias;  // [1 + 2*depth][C]
     const float *post_scale, *post_shift;  // final BN [C]
-    float *y;           // tower output [batch*hw][ldy]; PROFILE: max |x| per (site, board), [1 + 2*depth][ldy boards]
+    float *y;           // tower output [batch*hw][ldy]; Prof::max: max |x| per (site, board), [1 + 2*depth][ldy boards]
     int ldx0, ldy, batch, h, w_, hw, depth, stem_groups, nb;
     unsigned inv_w, inv_hw;  // ceil(65536 / w), ceil(65536 / hw): exact quotients for values < 512
     PackedBoards in;  // fused board encode (in.bits != nullptr: x0 is not read)
@@ -75,18 +75,27 @@ struct TowerF32Dev {
     int *nonfinite_flag;
     DecodeDev dec;  // dec.move_offsets set: decode_output inside the launch (policy must be device memory then)
     unsigned long long *stamps;  // (diagnostic build)
+    unsigned long long *hist;    // Prof::histogram: [1 + 2*depth][RANGE_BINS] counters, added to
 };
 
 
 // DENSE: an image holds the workgroup's nb * hw pixel rows and nothing behind them (the rows that fill the last tile up
 // to 16 are not stored: as inputs they are zero rows, as outputs they are not written) — what makes room for THREE 7x7
 // boards (147 rows in ten tiles, 160 KB of LDS to the byte) where the padded image holds two (98 rows in seven tiles).
-// PROFILE (the range profile, kz_model_range_profile_fast): every epilogue is one range site — 0 the stem, then the 2*depth
+// PROFILE = Prof::max (the range profile, kz_model_range_profile_fast): every epilogue is one range site — 0 the stem, then the 2*depth
 // convolutions — and takes max |x| per board of what it stores (kz_range_absmax's rule: `bits & 0x7fffffff` as unsigned,
 // clamped to inf's pattern), one plain store per (site, board) into a.y; the tower output is not written.
-template <int C, int NT, bool HEADS, bool DENSE = false, bool PROFILE = false>
+// Prof::histogram (the range histogram, kz_model_range_histogram_fast): every epilogue bins what it stores for the rows of the
+// workgroup's real boards (range_bin) into LDS histograms private to the wave — HSUB copies, chosen by lane: a wave's values
+// sit in a handful of bins, and 64 lanes on one LDS word would queue 64 deep —, and each wave adds its non-empty bins to
+// a.hist[site] once per site, with integer atomics whose result nobody reads: no barrier, no order between workgroups.
+enum class Prof { none, max, histogram };
+constexpr int HSUB = 8, HSTRIDE = RANGE_BINS + 1;  // (97 words: the copies of one bin lie in different banks)
+constexpr int profile_lds(Prof p, int nt) { return p == Prof::max ? 2 * 4 * nt * 16 * 4 : p == Prof::histogram ? 4 * HSUB * HSTRIDE * 4 : 0; }
+
+template <int C, int NT, bool HEADS, bool DENSE = false, Prof PROFILE = Prof::none>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
-    static_assert(!PROFILE || (!HEADS && !DENSE), "the profile instances are the plain tower's");
+    static_assert(PROFILE == Prof::none || (!HEADS && !DENSE), "the profile instances are the plain tower's");
     constexpr int OT = C / 64;           // 16-channel output tiles per wave
     constexpr int G = C / 16;            // steps per tap in a tower layer
     constexpr int ROWS = NT * 16;
@@ -103,9 +112,14 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
     const int rows_valid = boards * a.hw;
     const int rows_img = DENSE ? a.nb * a.hw : ROWS;  // rows an image holds
     const int IMG1 = IMG0 + rows_img * RS;
-    // PROFILE: per-row maxima of each wave's channels, [2][wave 4][ROWS] words behind the two images — double-buffered by
+    // Prof::max: per-row maxima of each wave's channels, [2][wave 4][ROWS] words behind the two images — double-buffered by
     // layer, so that the reduction behind a layer's barrier needs no barrier of its own against the next epilogue
+    // (Prof::histogram: the waves' histograms, [wave 4][HSUB][HSTRIDE] words, in the same place)
     const int PMAX = IMG1 + rows_img * RS;
+    unsigned *const hmine = reinterpret_cast<unsigned *>(lds + PMAX) + wave * HSUB * HSTRIDE;
+    if constexpr (PROFILE == Prof::histogram) {
+        for (int i = lane; i < HSUB * HSTRIDE; i += 64) hmine[i] = 0;
+    }
     KZ_STAMP(0);
 
     // zero rows; padding rows of image 0 (their outputs are never stored, but keep them finite)
@@ -186,8 +200,13 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
     for (int nt = 0; nt < NT; nt++) wmask |= (unsigned)(nt * 16 + fr < rows_img) << nt;
     // [relu]; [+ residual from the out image, in place]; [final BN]; 16-byte stores into the out image
     unsigned rowmax[NT];
+    // Prof::histogram: the rows this lane counts (bit nt: row fr of tile nt belongs to a real board) and its copy
+    unsigned cmask = 0;
+#pragma unroll
+    for (int nt = 0; nt < NT; nt++) cmask |= (unsigned)(nt * 16 + fr < rows_valid) << nt;
+    unsigned *const hcopy = hmine + (lane & (HSUB - 1)) * HSTRIDE;
     auto epilogue = [&](bool relu, bool residual, bool post) {
-        if constexpr (PROFILE) {
+        if constexpr (PROFILE == Prof::max) {
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) rowmax[nt] = 0;
         }
@@ -211,14 +230,20 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
                 if (residual) v += *slot;  // x + relu(bn(conv(.))) (post_act.py:227-228)
                 if (post) v = v * ps + pt;
                 *slot = v;
-                if constexpr (PROFILE) {
+                if constexpr (PROFILE == Prof::max) {
 #pragma unroll
                     for (int j = 0; j < 4; j++) rowmax[nt] = max(rowmax[nt], __float_as_uint(v[j]) & 0x7fffffffu);
+                }
+                if constexpr (PROFILE == Prof::histogram) {
+                    if ((cmask >> nt) & 1) {
+#pragma unroll
+                        for (int j = 0; j < 4; j++) atomicAdd(hcopy + range_bin(__float_as_uint(v[j])), 1u);
+                    }
                 }
             }
         }
     };
-    // PROFILE, site `site`: the epilogue's maxima (a lane's OT tiles are in rowmax already) over the four kq groups, then
+    // Prof::max, site `site`: the epilogue's maxima (a lane's OT tiles are in rowmax already) over the four kq groups, then
     // per pixel row and wave into LDS ...
     auto profile_rows = [&](int site) {
         unsigned *part = reinterpret_cast<unsigned *>(lds + PMAX) + (site & 1) * 4 * ROWS + wave * ROWS;
@@ -243,6 +268,25 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
         }
     };
 
+    // Prof::histogram, site `site`: the wave's own copies, summed per bin (lane: bins lane and lane + 64), cleared for the next
+    // site and added to the global counters.  Only this wave touches its copies, and a wave's LDS operations complete in order.
+    auto profile_flush = [&](int site) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int bin = lane; bin < RANGE_BINS; bin += 64) {
+            unsigned n = 0;
+#pragma unroll
+            for (int c = 0; c < HSUB; c++) {
+                n += hmine[c * HSTRIDE + bin];
+                hmine[c * HSTRIDE + bin] = 0;
+            }
+            if (n) atomicAdd(a.hist + (size_t)site * RANGE_BINS + bin, (unsigned long long)n);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+
     // ---- stem: conv + bias, no activation (post_act.py:205); stem_groups steps of 16 channels per tap ----
     {
         init_acc(0);
@@ -260,9 +304,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
             }
         }
         epilogue(false, false, a.depth == 0);
-        if constexpr (PROFILE) profile_rows(0);
+        if constexpr (PROFILE == Prof::max) profile_rows(0);
+        if constexpr (PROFILE == Prof::histogram) profile_flush(0);
         __syncthreads();
-        if constexpr (PROFILE) profile_boards(0);
+        if constexpr (PROFILE == Prof::max) profile_boards(0);
         in = IMG1;
         out = IMG0;
     }
@@ -356,18 +401,19 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
         KZ_STAMP(3 * layer);
         const bool second = (layer & 1) == 0;  // the block's second conv: residual add, and the final BN on the last
         epilogue(true, second, second && layer == 2 * a.depth);
-        if constexpr (PROFILE) profile_rows(layer);
+        if constexpr (PROFILE == Prof::max) profile_rows(layer);
+        if constexpr (PROFILE == Prof::histogram) profile_flush(layer);
         KZ_STAMP(3 * layer + 1);
         __syncthreads();
-        if constexpr (PROFILE) profile_boards(layer);
+        if constexpr (PROFILE == Prof::max) profile_boards(layer);
         KZ_STAMP(3 * layer + 2);
         const int tmp = in;
         in = out;
         out = tmp;
     }
 
-    if constexpr (PROFILE) {
-        // (the maxima are the launch's whole output)
+    if constexpr (PROFILE != Prof::none) {
+        // (the maxima, or the counts, are the launch's whole output)
     } else if constexpr (!HEADS) {
         // ---- the tower's output (the last `out`, now `in`) -> global, 16 bytes per lane, whole rows ----
         for (int i = tid; i < rows_valid * (C / 4); i += 256) {
@@ -390,10 +436,10 @@ int tiles_for(int hw, int channels) {
     return 0;
 }
 
-template <int C, int NT, bool HEADS, bool DENSE = false, bool PROFILE = false>
+template <int C, int NT, bool HEADS, bool DENSE = false, Prof PROFILE = Prof::none>
 void launch1(const TowerF32Dev &d, int grid, hipStream_t stream) {
-    const int LDS_BYTES = (16 + 2 * (DENSE ? d.nb * d.hw : NT * 16)) * (C * 4 + 16) + (PROFILE ? 2 * 4 * NT * 16 * 4 : 0);
-    static_assert(!PROFILE || (16 + 2 * NT * 16) * (C * 4 + 16) + 2 * 4 * NT * 16 * 4 <= 160 * 1024, "LDS of a workgroup");
+    const int LDS_BYTES = (16 + 2 * (DENSE ? d.nb * d.hw : NT * 16)) * (C * 4 + 16) + profile_lds(PROFILE, NT);
+    static_assert(PROFILE == Prof::none || (16 + 2 * NT * 16) * (C * 4 + 16) + profile_lds(PROFILE, NT) <= 160 * 1024, "LDS of a workgroup");
     allow_dynamic_lds<kz_tower_resident_f32<C, NT, HEADS, DENSE, PROFILE>>(LDS_BYTES);
 #ifdef KZ_T32_STAMPS
     static unsigned long long *stamp_buf = nullptr;
@@ -553,6 +599,7 @@ void launch_tower32(const Tower32Args &t, hipStream_t stream) {
     d.post_scale = t.post_scale;
     d.post_shift = t.post_shift;
     d.y = t.y;
+    d.hist = t.hist;
     d.ldx0 = t.ldx0;
     d.ldy = t.ldy;
     d.batch = t.batch;
@@ -576,11 +623,18 @@ void launch_tower32(const Tower32Args &t, hipStream_t stream) {
     d.scalars = hd.scalars; d.policy = hd.policy; d.nonfinite_flag = hd.nonfinite_flag;
     d.dec = decode_dev(hd.decode, hd.on, hd.policy_len);
     const int grid = (t.batch + d.nb - 1) / d.nb;
+    if (t.profile && t.hist) {  // the range histogram's instances: no heads, hist += the counts [site][bin]
+        if (t.channels == 256) launch1<256, 4, false, false, Prof::histogram>(d, grid, stream);
+        else if (nt == 7) launch1<128, 7, false, false, Prof::histogram>(d, grid, stream);
+        else if (nt == 6) launch1<128, 6, false, false, Prof::histogram>(d, grid, stream);
+        else launch1<128, 4, false, false, Prof::histogram>(d, grid, stream);
+        return;
+    }
     if (t.profile) {  // the range profile's instances: no heads, y = the maxima [site][ldy boards]
-        if (t.channels == 256) launch1<256, 4, false, false, true>(d, grid, stream);
-        else if (nt == 7) launch1<128, 7, false, false, true>(d, grid, stream);
-        else if (nt == 6) launch1<128, 6, false, false, true>(d, grid, stream);
-        else launch1<128, 4, false, false, true>(d, grid, stream);
+        if (t.channels == 256) launch1<256, 4, false, false, Prof::max>(d, grid, stream);
+        else if (nt == 7) launch1<128, 7, false, false, Prof::max>(d, grid, stream);
+        else if (nt == 6) launch1<128, 6, false, false, Prof::max>(d, grid, stream);
+        else launch1<128, 4, false, false, Prof::max>(d, grid, stream);
         return;
     }
     if (t.channels == 256) launch<256, 4>(d, hd.on, grid, stream);

@@ -122,6 +122,9 @@ extern "C" {
     // ... the same profile inside the one-launch exact-f32 tower where that kernel takes the network, and which of the two it is
     fn kz_model_range_profile_fast(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, site_max_out: *mut f32, board_max_out: *mut f32) -> c_int;
     fn kz_model_range_profile_fast_path(model: *const c_void, buf: *mut c_char, len: usize) -> c_int;
+    // the range histogram: binade counts of every stored tower tensor, hist_out u64 [n_sites][KZ_RANGE_BINS]
+    fn kz_model_range_histogram(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, hist_out: *mut c_void) -> c_int;
+    fn kz_model_range_histogram_fast(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, hist_out: *mut c_void) -> c_int;
     fn kz_engine_max_batch(engine: *const c_void) -> c_int;
     fn kz_engine_eval_dense(engine: *mut c_void, input_nchw: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
     fn kz_engine_eval_packed(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
@@ -347,6 +350,25 @@ impl HipModel {
         (site_max, board_max)
     }
 
+    /// How many stored values of every site lie in each binade, counted in exact f32 on `device`: `[n_sites][KZ_RANGE_BINS]`
+    /// flat, every site summing to batch * h * w * tower_channels (`kz_model_range_histogram_fast`: inside the one-launch tower where
+    /// `range_profile_fast_path` says so; `fast = false`: `kz_model_range_histogram`, per layer).  `shift_report` reads it.
+    pub fn range_histogram(&self, device: HipDevice, bits: &[u8], bits_stride: usize, scalars_in: &[f32], batch: usize, fast: bool) -> Vec<u64> {
+        let mut n = 0;
+        check(unsafe { kz_model_range_sites(self.ptr, &mut n) });
+        assert!(bits.len() >= batch * bits_stride && scalars_in.len() >= batch * self.info.input_scalar_channels.max(0) as usize);
+        let mut hist = vec![0u64; n as usize * KZ_RANGE_BINS];
+        let out = hist.as_mut_ptr() as *mut c_void;
+        check(unsafe {
+            if fast {
+                kz_model_range_histogram_fast(self.ptr, device.0 as c_int, bits.as_ptr(), bits_stride, scalars_in.as_ptr(), batch as c_int, out)
+            } else {
+                kz_model_range_histogram(self.ptr, device.0 as c_int, bits.as_ptr(), bits_stride, scalars_in.as_ptr(), batch as c_int, out)
+            }
+        });
+        hist
+    }
+
     /// Where `range_profile_fast` runs: "tower_resident_f32" or "conv_igemm_f32" (`kz_model_range_profile_fast_path`; no GPU).
     pub fn range_profile_fast_path(&self) -> String {
         let mut buf = [0 as c_char; 32];
@@ -457,6 +479,66 @@ impl PositionSample {
         }
         snap
     }
+}
+
+/// The bins of `HipModel::range_histogram` (include/kz_hip.h): 0 is +-0, 95 inf or NaN, b in 1..=94 the binade E = b - 51
+/// with the two ends clamped.
+pub const KZ_RANGE_BINS: usize = 96;
+
+/// What a stream shift of k does to the stored values of one site of a range histogram (`shift_report`).
+#[derive(Debug, Clone, Copy, Default, PartialEq, Eq)]
+pub struct ShiftReport {
+    pub total: u64,
+    pub zero: u64,
+    pub nonfinite: u64,
+    /// E' >= 16: beyond f16
+    pub f16_over: u64,
+    /// E' = 15: the binade that holds 65504 .. 65536
+    pub f16_top: u64,
+    /// -25 <= E' <= -15
+    pub f16_subnormal: u64,
+    /// E' < -25
+    pub f16_flushed: u64,
+    /// E' <= -3: the lo half of a split16 pair is subnormal or gone
+    pub split_lo_subnormal: u64,
+    /// the two end bins (E <= -50, E >= 43) as they are: for every k in [-24, 24] they lie in `f16_flushed` (and
+    /// `split_lo_subnormal`) and in `f16_over`, so nothing is guessed
+    pub clamped_low: u64,
+    pub clamped_high: u64,
+}
+
+/// Per site of `hist` (`[n_sites][KZ_RANGE_BINS]` flat, as `HipModel::range_histogram` returns it): E' = E - k on the shifted sites, E' = E on the last one.  Integer arithmetic only; the library
+/// reports, the caller decides, as for `shift_for`.
+pub fn shift_report(hist: &[u64], k: i32) -> Vec<ShiftReport> {
+    assert!(!hist.is_empty() && hist.len() % KZ_RANGE_BINS == 0, "shift_report: hist must be [n_sites][96]");
+    assert!((-24..=24).contains(&k), "shift_report: k = {} out of range [-24, 24]", k);
+    let n = hist.len() / KZ_RANGE_BINS;
+    hist.chunks(KZ_RANGE_BINS)
+        .enumerate()
+        .map(|(site, row)| {
+            let shift = if site + 1 < n { k } else { 0 };
+            let mut r = ShiftReport { total: row.iter().sum(), zero: row[0], nonfinite: row[KZ_RANGE_BINS - 1], clamped_low: row[1], clamped_high: row[KZ_RANGE_BINS - 2], ..Default::default() };
+            for b in 1..KZ_RANGE_BINS - 1 {
+                let e = b as i32 - 51 - shift; // (bin 1: at most this; bin 94: at least this: the classes hold for both)
+                if e >= 16 {
+                    r.f16_over += row[b];
+                }
+                if e == 15 {
+                    r.f16_top += row[b];
+                }
+                if (-25..=-15).contains(&e) {
+                    r.f16_subnormal += row[b];
+                }
+                if e < -25 {
+                    r.f16_flushed += row[b];
+                }
+                if e <= -3 {
+                    r.split_lo_subnormal += row[b];
+                }
+            }
+            r
+        })
+        .collect()
 }
 
 /// The sample `KZ_HIP_STREAM_SHIFT=auto` profiles: process-wide, fed by every `HipNetwork` (the first 64 boards of every

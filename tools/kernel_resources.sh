@@ -21,7 +21,8 @@ for blk in re.split(r"\n\s+- \.agpr_count:", txt)[1:]:
     blk = ".agpr_count:" + blk
     g = lambda k: (re.search(r"\." + k + r":\s+(\S+)", blk) or [None, "?"])[1]
     dem = subprocess.run(["c++filt", g("name")], capture_output=True, text=True).stdout.strip()
-    dem = re.sub(r"\(.*\)$", "", dem.replace("kz::(anonymous namespace)::", "")).replace("void ", "")
+    # (the trailing parameter list only: a template argument of enum type is printed with parentheses of its own)
+    dem = re.sub(r"\([^()]*\)$", "", dem.replace("kz::(anonymous namespace)::", "")).replace("void ", "")
     if not re.search(flt, dem): continue
     print("%-62s vgpr %4s (agpr %4s) sgpr %4s spilled v %3s s %3s scratch %5s lds %6s" % (dem, g("vgpr_count"), g("agpr_count"),
           g("sgpr_count"), g("vgpr_spill_count"), g("sgpr_spill_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size")))

@@ -19,6 +19,13 @@ the positions of a position file (kzero_amd/position_file.py) or on synthetic bo
          creation included), the median of 5 each, boards per second, and whether the fast call's median is below the other's.
          --hold-f32 keeps an ordinary exact-f32 engine of the model alive meanwhile (what KZ_HIP_RANGE_FALLBACK=1 does in a
          self-play run): the fast entry's internal engine then finds its weight stream in the cache instead of packing it.
+--hist   the range histogram (kz_model_range_histogram; with --fast kz_model_range_histogram_fast): per site, what
+         capi.shift_report says of the rule's k and of k - 2 and k + 2 — the shares of the stored values that are zero, beyond
+         f16, in f16's top binade, f16 subnormals, flushed, and without a split16 lo half.  With --rate the four entries are
+         timed instead of an engine: both histogram entries next to both max entries on the same boards in one process,
+         interleaved calls, the median of 5 each, with an exact-f32 engine of the model alive (the weights are cached).
+         --max-lib takes the two max entries from ANOTHER build of the library (tools/build_rev_lib.sh: the parent commit's),
+         loaded beside this one with a model and a held engine of its own.
 Prints one JSON object; --out writes it too.
 """
 import argparse
@@ -132,6 +139,81 @@ def profile_rate(model, bits, scalars, device, calls=5, hold_f32=False):
     return out
 
 
+SHARES = ("zero", "nonfinite", "f16_over", "f16_top", "f16_subnormal", "f16_flushed", "split_lo_subnormal", "clamped_low",
+          "clamped_high")
+
+
+def hist_report(hist, sites, k):
+    """shift_report for k - 2, k, k + 2 (inside [-24, 24]) as shares of each site's elements."""
+    out = []
+    for kk in sorted({max(-24, min(24, k + d)) for d in (-2, 0, 2)}):
+        r = capi.shift_report(hist, kk)
+        out.append({"k": kk, "sites": [{"site": s, "elements": int(r["total"][i]),
+                                        **{f: float(r[f][i]) / max(int(r["total"][i]), 1) for f in SHARES}}
+                                       for i, s in enumerate(sites)]})
+    return out
+
+
+class OtherLib:
+    """The two max entries of another build of the library: its own model of the same blob and its own held exact-f32 engine."""
+
+    def __init__(self, path, blob, device):
+        C = capi.C
+        self.lib, self.device = C.CDLL(path), device
+        for name in ("kz_model_load_memory", "kz_model_range_sites", "kz_model_range_profile", "kz_model_range_profile_fast",
+                     "kz_engine_create"):
+            fn = getattr(self.lib, name)
+            fn.restype, fn.argtypes = capi.SIGNATURES[name]
+        self.lib.kz_last_error.restype = C.c_char_p
+        self.model, self.engine = C.c_void_p(), C.c_void_p()
+        self.check(self.lib.kz_model_load_memory(blob, len(blob), C.byref(self.model)))
+        self.check(self.lib.kz_engine_create(self.model, device, 64, capi.KZ_DTYPE_F32, C.byref(self.engine)))
+        n = C.c_int()
+        self.check(self.lib.kz_model_range_sites(self.model, C.byref(n)))
+        self.site_max = np.zeros(n.value, np.float32)
+
+    def check(self, rc):
+        assert rc == 0, self.lib.kz_last_error().decode()
+
+    def entry(self, name):
+        fn = getattr(self.lib, name)
+
+        def call(device, bits, scalars):
+            self.check(fn(self.model, device, bits.ctypes.data, bits.shape[1], scalars.ctypes.data, bits.shape[0],
+                          self.site_max.ctypes.data, None))
+        return call
+
+
+def hist_rate(model, blob, bits, scalars, device, max_lib=None, calls=5):
+    """The two histogram entries and the two max entries on the same boards, interleaved, an exact-f32 engine held: wall time
+    per call (engine creation included) and boards/s."""
+    held = capi.Engine(model, device, 64, capi.KZ_DTYPE_F32)
+    bits, scalars = np.ascontiguousarray(bits, np.uint8), np.ascontiguousarray(scalars, np.float32)
+    other = OtherLib(max_lib, blob, device) if max_lib else None
+    entries = {"hist_fast": lambda d, b, s: model.range_histogram(d, b, s, fast=True),
+               "hist_per_layer": lambda d, b, s: model.range_histogram(d, b, s, fast=False),
+               "max_fast": other.entry("kz_model_range_profile_fast") if other else model.range_profile_fast,
+               "max_per_layer": other.entry("kz_model_range_profile") if other else model.range_profile}
+    for fn in entries.values():
+        fn(device, bits, scalars)
+    times = {name: [] for name in entries}
+    for _ in range(calls):
+        for name, fn in entries.items():
+            t0 = time.perf_counter()
+            fn(device, bits, scalars)
+            times[name].append(time.perf_counter() - t0)
+    out = {"boards": len(bits), "calls": calls, "fast_path": model.range_profile_fast_path(), "f32_engine_held": held.tower_path,
+           "max_entries_from": max_lib or "this library"}
+    for name, t in times.items():
+        med = float(np.median(t))
+        out[name] = {"ms_median": round(1e3 * med, 3), "ms_min": round(1e3 * min(t), 3), "ms_max": round(1e3 * max(t), 3),
+                     "boards_per_s_median": round(len(bits) / med)}
+    out["hist_fast_below_max_per_layer"] = out["hist_fast"]["ms_median"] < out["max_per_layer"]["ms_median"]
+    out["hist_fast_over_max_fast"] = round(out["hist_fast"]["ms_median"] / out["max_fast"]["ms_median"], 3)
+    out["hist_per_layer_over_max_per_layer"] = round(out["hist_per_layer"]["ms_median"] / out["max_per_layer"]["ms_median"], 3)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", help="a KZMODEL1 container or an ONNX file")
@@ -151,6 +233,8 @@ def main():
     ap.add_argument("--profile-time", action="store_true")
     ap.add_argument("--fast", action="store_true", help="profile through kz_model_range_profile_fast; with --rate: the profile's own rate")
     ap.add_argument("--hold-f32", action="store_true", help="--rate --fast: an exact-f32 engine of the model stays alive (shared weight stream)")
+    ap.add_argument("--hist", action="store_true", help="the range histogram and what shift_report says of k - 2, k, k + 2; with --rate: the entries' rates")
+    ap.add_argument("--max-lib", help="--hist --rate: another build of the library for the two max entries (the parent commit's)")
     ap.add_argument("--dtype", default="f16", choices=sorted(DTYPES))
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--regions", type=int, default=7)
@@ -161,10 +245,11 @@ def main():
 
     if args.model:
         model = capi.Model(path=args.model, onnx_scalar_channels=args.scalar_channels)
-        network = os.path.basename(args.model)
+        network, blob = os.path.basename(args.model), None
     else:
         kw = {"block_gain": args.block_gain} if args.block_gain else {}
-        model = capi.Model(blob=synth.random_model(args.game, args.depth, args.channels, args.head, seed=3, **kw))
+        blob = synth.random_model(args.game, args.depth, args.channels, args.head, seed=3, **kw)
+        model = capi.Model(blob=blob)
         network = f"{args.game} {args.depth}x{args.channels} (synthetic)"
     if args.positions:
         pf = PositionFile(args.positions)
@@ -195,6 +280,21 @@ def main():
               file=sys.stderr)
     print(f"# stream max {m:.6g}, {out['boards_beyond_65504']} of {len(bits)} boards beyond 65504: suggested k = {suggested} "
           f"({args.headroom} bits of headroom)", file=sys.stderr)
+    if args.hist:
+        k_for = args.k if args.k is not None else suggested if suggested is not None else 0
+        hist = model.range_histogram(args.device, bits, scalars, fast=args.fast)
+        out["histogram"] = {"entry": "kz_model_range_histogram_fast" if args.fast else "kz_model_range_histogram", "k": k_for,
+                            "reports": hist_report(hist, sites, k_for)}
+        for rep in out["histogram"]["reports"]:
+            print(f"# k = {rep['k']}: share of each site's stored values", file=sys.stderr)
+            print(f"# {'site':<14} " + " ".join(f"{f[:13]:>13}" for f in SHARES), file=sys.stderr)
+            for row in rep["sites"]:
+                print(f"# {row['site']:<14} " + " ".join(f"{row[f]:>13.3g}" for f in SHARES), file=sys.stderr)
+        if args.rate:
+            if args.max_lib and blob is None:
+                blob = open(args.model, "rb").read()
+            out["histogram_rate"] = hist_rate(model, blob, bits, scalars, args.device, args.max_lib)
+            args.rate = False
     if args.profile_time:
         times = []
         for _ in range(5):
