@@ -936,15 +936,19 @@ KZO_EXPORT int kzo_max_threads(void) {
 /* decode_output — rust/kz-core/src/network/common.rs:16-114                    */
 /* ------------------------------------------------------------------------- */
 
-/* softmax_in_place (common.rs:102-114). Returns -1 where the reference asserts (sum must be > 0). */
+/* softmax_in_place (common.rs:102-114). Returns -1 where the reference asserts (sum must be > 0).
+ * The exponentials are f32 like the reference's; their sum is accumulated in double and rounded once: a serial f32 fold is
+ * off by up to n ulp (measured 23 u at 63 moves, 197 u at 1154 against a float64 softmax, tests/test_decode_nets.py), more
+ * than the decode under test, whose lanes add n / 64 terms each — a yardstick must not be the coarser of the two. */
 KZO_EXPORT int kzo_softmax_in_place(float *v, int n) {
     float max = -INFINITY;
     for (int i = 0; i < n; i++) max = v[i] > max ? v[i] : max; /* fold(NEG_INFINITY, max) */
-    float sum = 0.0f;
+    double acc = 0.0;
     for (int i = 0; i < n; i++) {
         v[i] = expf(v[i] - max);
-        sum += v[i];
+        acc += v[i];
     }
+    const float sum = (float)acc;
     if (!(sum > 0.0f)) return fail("Softmax input sum must be strictly positive");
     for (int i = 0; i < n; i++) v[i] /= sum;
     return 0;

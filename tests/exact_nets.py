@@ -35,6 +35,10 @@ value, the same in any summation order, so the result is still a matter of bits.
 `sums` as above, with the steps of the rounded operands.  The report counts, per site, the ties that go down, the ties that
 go up and the values that are no tie: tests/test_round_nets.py holds floors on them and shows that references which round
 otherwise, elsewhere, once more or once less return other outputs.
+
+The scaled family (`build_scaled`) is a narrow network with the layers that write its outputs times powers of two: still
+exact, logits of any spread.  With `decode_ref`, a float64 decode_output, it is the reference of the launches' decode
+(tests/decode_cases.py, tests/test_decode_nets.py, tests/test_gpu_decode_exact.py).
 """
 import numpy as np
 
@@ -878,3 +882,73 @@ def run_mutant(b, rounding):
     base, mine = kept(b.report), kept(rep)
     applies = any(not np.array_equal(mine[k], base[k]) for k in mine if k in base)
     return s.astype(np.float32), p.astype(np.float32), applies
+
+
+# ---- the scaled family: exact logits of any spread, for the decode (tests/decode_cases.py) ----
+
+def logit_layers(meta, tensors):
+    """[(layer, rows)] of every layer that writes a policy logit (rows None: all of them).  Conv and dense heads: the last
+    layer (Go: the pass move's as well); the attention head: the q_from rows of conv_bulk — a logit is q_from . q_to / sqrt(q),
+    linear in either operand."""
+    kind = meta["policy_kind"]
+    if kind in ("ataxx_conv", "conv"):
+        return [("policy_head.seq.2", None)] + ([("policy_head.seq_extra.2", None)] if kind == "conv" and meta.get("policy_extra_moves", 0) else [])
+    if kind == "attention":
+        return [("policy_head.conv_bulk", _side_rows("policy_head.conv_bulk", meta["policy_query_channels"], "from"))]
+    if kind == "dense":
+        idx = (2 if meta.get("policy_dense_hidden_channels", 0) else 0) + 1 + (2 if meta.get("policy_dense_hidden_size", 0) else 0)
+        return [(f"policy_head.seq.{idx}", None)]
+    raise ValueError(f"no scaled family for policy head '{kind}'")
+
+
+_SCACHE = {}
+
+
+def build_scaled(net, k_policy, k_value, k_wdl):
+    """`build(net, None)` with the layers that write the outputs times a power of two — exact, so the outputs are the base
+    network's times that power, bit for bit, and a float64 softmax of them is a reference without logit error: every layer
+    of `logit_layers` times 2^k_policy (weights and bias; a tuple: one exponent per layer, in that order), the rows of scalar_head.seq.5 times 2^k_value (row 0: value),
+    2^k_wdl (rows 1-3) and 1 (row 4: moves left).  A Built with the base's boards, the reference rerun on the scaled tensors
+    (`ref_scalars`, `ref_policy`, `report`), the base (`base`) and the exponents (`k`)."""
+    key = (net, k_policy, k_value, k_wdl)
+    if key not in _SCACHE:
+        while len(_SCACHE) >= 6:
+            _SCACHE.pop(next(iter(_SCACHE)))
+        base = build(net, None)
+        t = {k: v.copy() for k, v in base.tensors.items()}
+        layers = logit_layers(base.meta, t)
+        ks = k_policy if isinstance(k_policy, tuple) else (k_policy,) * len(layers)
+        assert len(ks) == len(layers)
+        for (p, rows), k in zip(layers, ks):
+            rows = slice(None) if rows is None else rows
+            t[p + ".weight"][rows] *= np.float32(2.0 ** k)
+            t[p + ".bias"][rows] *= np.float32(2.0 ** k)
+        f = np.array([2.0 ** k_value] + 3 * [2.0 ** k_wdl] + [1.0], np.float32)
+        t["scalar_head.seq.5.weight"] *= f[:, None]
+        t["scalar_head.seq.5.bias"] *= f
+        b = Built()
+        b.base, b.k, b.meta, b.tensors, b.seed = base, (k_policy, k_value, k_wdl), base.meta, t, base.seed
+        b.bits, b.scalars_in, b.x, b.layers = base.bits, base.scalars_in, base.x, base.layers
+        s, p, b.report = reference(t, b.meta, b.x)
+        b.ref_scalars, b.ref_policy = s.astype(np.float32), p.astype(np.float32)
+        b.blob = write_model(b.meta, t)
+        _SCACHE[key] = b
+    return _SCACHE[key]
+
+
+def decode_ref(scalars, logits, move_lists):
+    """decode_output (rust/kz-core/src/network/common.rs:16-100) in float64, from the definition: values [B, 5] =
+    tanh(s0), softmax(s1..s3), s4 and per board the softmax over logits[moves] in the order given, the maximum subtracted,
+    the sums by math.fsum (exactly rounded).  An empty list gives an empty array."""
+    import math
+    scalars, logits = np.asarray(scalars, np.float64), np.asarray(logits, np.float64)
+
+    def softmax(v):
+        e = np.exp(v - v.max())
+        return e / math.fsum(e.tolist())
+    values = np.empty((len(scalars), 5))
+    values[:, 0] = np.tanh(scalars[:, 0])
+    for b in range(len(scalars)):
+        values[b, 1:4] = softmax(scalars[b, 1:4])
+    values[:, 4] = scalars[:, 4]
+    return values, [softmax(logits[b][np.asarray(m, np.int64)]) if len(m) else np.zeros(0) for b, m in enumerate(move_lists)]

@@ -1,6 +1,7 @@
 """Zero-tolerance parity: every kernel instance with addressing of its own evaluates the exactly representable networks of
-tests/exact_nets.py and must return the bits of the float64 reference — raw scalars and logits through eval_packed, the
-inexact tanh / softmax of the decode stay out.  On these networks no arithmetic of the library rounds (weights, inputs and
+tests/exact_nets.py and must return the bits of the float64 reference — raw scalars and logits through eval_packed; the
+inexact tanh / softmax of the decode are held to a float64 softmax of the same exact logits, within derived bounds, by
+tests/test_gpu_decode_exact.py.  On these networks no arithmetic of the library rounds (weights, inputs and
 stored intermediates are short dyadic numbers within half of f16's integer range, every sum stays within 2^22 steps:
 tests/test_exact_nets.py holds both for every case here), so any difference is a wrong address, pad, pack or batch
 offset: exactly the errors that sit below the f16 bounds of tests/test_gpu_parity.py.
