@@ -123,7 +123,7 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         if (packed) t.in = *packed;  // fused board encode
         if (plan.heads && m.policy_kind == kz::POLICY_ATTENTION) {  // (the split launch only)
             kz::Tower32Args::Heads &hd = t.heads;
-            hd.on = true;
+            hd.kind = kz::Tower32Args::Heads::Kind::attention;
             hd.sh_w0 = wts->sh_w0; hd.sh_b0 = wts->sh_b0; hd.sh_w1 = wts->sh_w1; hd.sh_b1 = wts->sh_b1;
             hd.sh_w2 = wts->sh_w2; hd.sh_b2 = wts->sh_b2; hd.att_idx = wts->att_idx;
             hd.policy_len = m.policy_len;
@@ -132,7 +132,7 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         }
         if (plan.heads && m.policy_kind != kz::POLICY_ATTENTION) {  // conv policy heads: the f32 tail
             kz::Tower32Args::Heads &hd = t.heads;
-            hd.on = true;
+            hd.kind = kz::Tower32Args::Heads::Kind::conv;
             hd.hc = m.sh_conv.cout; hd.hs = m.sh_fc0.out;
             hd.small_w = wts->h32_small; hd.sh_b0 = wts->sh_b0; hd.sh_w1t = wts->sh_w1t; hd.sh_b1 = wts->sh_b1;
             hd.sh_w2 = wts->sh_w2; hd.sh_b2 = wts->sh_b2;
@@ -145,7 +145,7 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
             hd.scalars = d_scalars; hd.policy = d_policy;
             hd.nonfinite_flag = p.nf_flag; hd.epoch = p.nf_epoch;
         }
-        if (dec && t.heads.on) t.heads.decode = *dec;
+        if (dec && plan.heads) t.heads.decode = *dec;
 #ifdef KZ_EXPERIMENTS
         t.dense3 = plan.t32_dense3;
 #endif
@@ -157,13 +157,19 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
             range_site = 2 * m.depth + 1;  // every epilogue of the launch is a site
         }
         const bool f16g = plan.tower == Tower::resident_f16g;
-        if (launch(p, split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : "kz_tower_resident_f32", [&] {
-                if (split16()) kz::launch_tower_split(t, p.stream);
-                else if (bf16()) kz::launch_tower_bf16(t, p.stream);  // f32 tensors, like the split launch
-                else if (f16g) kz::launch_tower_pairs(t, false, p.stream);  // f16 tensors behind the same pointers
-                else kz::launch_tower32(t, p.stream);
+        const char *name = split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : "kz_tower_resident_f32";
+        bool launched = false;  // (the family has a fixed table of instances: a shape outside it launches nothing)
+        int nt = 0;
+        if (launch(p, name, [&] {
+                if (split16()) launched = kz::launch_tower_split(t, p.stream, &nt);
+                else if (bf16()) launched = kz::launch_tower_bf16(t, p.stream, &nt);  // f32 tensors, like the split launch
+                else if (f16g) launched = kz::launch_tower_pairs(t, p.stream, &nt);  // f16 tensors behind the same pointers
+                else launched = kz::launch_tower32(t, p.stream, &nt);
             }))
             return 1;
+        if (!launched)
+            return fail(std::string(name) + ": no instance for " + std::to_string(m.channels) + " channels and nt = " + std::to_string(nt) +
+                        " tiles of 16 rows" + (plan.heads ? " with the heads inside the launch" : ""));
         tower_out = 0;
         return 0;
     }

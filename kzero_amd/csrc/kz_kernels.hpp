@@ -368,7 +368,9 @@ struct Tower32Args {
     // then Conv1x1 C->pc, post_act.py:75-110) and the scalar head (post_act.py:8-31) in the same launch — the tower
     // output never leaves LDS and `y` is not written.  tower32_heads_supported says for which models.
     struct Heads {
-        bool on = false;
+        // which heads run inside the launch: the chess attention heads (launch_tower_split only) or the conv policy heads
+        enum class Kind { none, attention, conv };
+        Kind kind = Kind::none;
         // (the split launch's attention heads, kz_tower_split.hip: the scalar head's matrices as they are, the gather table)
         const float *sh_w0 = nullptr, *sh_w1 = nullptr;
         const int32_t *att_idx = nullptr;  // [1880]: (flat_to_att / 88) * 96 + flat_to_att % 88
@@ -406,7 +408,9 @@ int tower32_boards_per_workgroup(int h, int w, int channels);
 size_t tower32_weight_elems(int c_in, int channels, int depth);
 size_t tower32_weight_pad_elems(int channels);  // zeros the stream must end with (the launch's weight ring reads ahead)
 void tower32_pack_weights(const float *oihw, int cout, int cin, bool stem, float *dst);
-void launch_tower32(const Tower32Args &a, hipStream_t stream);
+// The four one-launch towers of a Tower32Args exist as a fixed table of instances each.  A launcher returns false, and has
+// launched nothing, when (channels, tiles of 16 rows, kind of heads) is none of them; *nt (if given) takes the tile count asked for.
+bool launch_tower32(const Tower32Args &a, hipStream_t stream, int *nt = nullptr);
 
 // ---- the same tower with f32-equivalent results on the f16 matrix cores (kz_tower_split.hip): activations and weights
 // as (hi, lo) f16 pairs, three MFMAs per product.  Shapes of the exact-f32 launch with c_in <= channels; same Tower32Args
@@ -419,17 +423,17 @@ bool tower_split_wide_supported(int h, int w, int channels, int max_batch);
 size_t tower_split_stem_elems(int channels, int c_in, bool split);              // f16 elements of the 9 * ceil(c_in / 32) stem k-steps
 size_t tower_split_weight_elems(int channels, int depth, int c_in, bool split);  // f16 elements: stem + 2 * depth layers
 void tower_split_pack_weights(const float *oihw, int cout, int cin, int hw, bool stem, bool split, uint16_t *dst, bool bf16 = false);
-void launch_tower_split(const Tower32Args &a, hipStream_t stream);
-// the chess attention network's heads inside that launch (a.heads.on; scalars and policy are then its only output)
+bool launch_tower_split(const Tower32Args &a, hipStream_t stream, int *nt = nullptr);
+// the chess attention network's heads inside that launch (a.heads.kind == attention; scalars and policy are then its only output)
 bool tower_split_heads_supported(int policy_kind, int query_channels, int policy_len, int h, int w, int channels, int sh_channels,
                                  int sh_size);
 size_t tower_split_heads_weight_elems();  // f16 elements behind the tower's k-steps
 void tower_split_pack_heads(const float *w_bulk, const float *b_bulk, const float *w_under, const float *b_under, uint16_t *dst,
                             float *bias5 /* [5][256] behind the tower's bias rows */);
 // ... and for the conv policy heads (Ataxx, Go 9x9) at 128 / 256 channels: the policy head's Conv1x1 C->C rides behind the
-// tower as one more pass (its bias as one more bias row), the rest is the exact-f32 launch's tail (Tower32Args::Heads with
-// small_w set, as for launch_tower32) on f32 copies of the LDS images
-// (split = false: the plain-f16 launch, launch_tower_pairs(t, false): "tower_resident_f16g+heads" — the same tail with its
+// tower as one more pass (its bias as one more bias row), the rest is the exact-f32 launch's tail (Tower32Args::Heads of
+// kind conv, as for launch_tower32) on f32 copies of the LDS images
+// (split = false: the plain-f16 launch, launch_tower_pairs: "tower_resident_f16g+heads" — the same tail with its
 // two small convolutions as f16 MFMAs on the f16 images: Heads::small_w = tower_split_pack_small_weights16; wide: with
 // Tower32Args::wide)
 bool tower_split_conv_heads_supported(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs,
@@ -441,12 +445,12 @@ size_t tower_split_conv_heads_weight_elems(int channels, bool split);
 void tower_split_pack_conv_heads(const float *w /* [C][C] */, int channels, bool split, uint16_t *dst, bool bf16 = false);
 // the same launch without the lo halves (split = false): plain f16 arithmetic, x0 and y are f16 tensors behind the
 // float pointers of Tower32Args — the board-resident f16 tower for the shapes kz_tower.hip does not take
-void launch_tower_pairs(const Tower32Args &a, bool split, hipStream_t stream);
+bool launch_tower_pairs(const Tower32Args &a, hipStream_t stream, int *nt = nullptr);
 // the plain launch on bf16 elements (kz_tower_bf16g.hip: bf16 x bf16 products, f32 accumulation; f32's exponent, 8 significant
-// bits): the shapes, tiles and wide tiles of launch_tower_pairs(t, false) (tower_split_supported / tower_split_wide_supported /
+// bits): the shapes, tiles and wide tiles of launch_tower_pairs (tower_split_supported / tower_split_wide_supported /
 // tower_split_conv_heads_supported with split = false) with the split launch's tensors — f32 x0 and y (or packed boards in) —,
 // `weights` = the split = false stream packed with bf16 = true, Heads::small_w = tower32_pack_small_weights (the tail is exact f32)
-void launch_tower_bf16(const Tower32Args &a, hipStream_t stream);
+bool launch_tower_bf16(const Tower32Args &a, hipStream_t stream, int *nt = nullptr);
 
 // ---- 1x1 convolution in the same split arithmetic (the head convolutions behind the split tower), f32 in and out:
 // y[r][0..cout_p) = [relu](bias + W x[row(r)]), row(r) = (r / group) * src_group + src_off + r % group ----

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <iterator>  // std::size, std::index_sequence: the launchers fold over their instance tables
+#include <utility>
+
 namespace kz {
 
 // A kernel that takes more than 64 KB of dynamic LDS must be allowed to, per device: call this before every launch of

@@ -813,6 +813,24 @@ void launch_instance(const TowerDev &d, int grid, int bytes, hipStream_t stream)
     allow_dynamic_lds<Kernel>(bytes);
     Kernel<<<grid, 256, bytes, stream>>>(d);
 }
+
+// The six instances and the choice among them (PREV, experiment build: the same six with the round-6 address arithmetic)
+template <bool PREV>
+void launch_chess(const TowerDev &d, const TowerArgs &t, hipStream_t stream) {
+    const bool heads = t.fused_heads;
+    if (t.cin_p > 32) {  // (ChessHistoryMapper: 34 / 47 / 60 planes; always two boards per workgroup)
+        const int grid = (t.batch + 1) / 2;
+        if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, true, PREV>>(d, grid, Layout<2>::BYTES, stream);
+        else launch_instance<kz_tower_resident<2, false, PF_NB2, true, PREV>>(d, grid, Layout<2>::BYTES, stream);
+    } else if (t.boards_per_wg == 1) {
+        if (heads) launch_instance<kz_tower_resident<1, true, PF_NB1, false, PREV>>(d, t.batch, Layout<1>::BYTES, stream);
+        else launch_instance<kz_tower_resident<1, false, PF_NB1, false, PREV>>(d, t.batch, Layout<1>::BYTES, stream);
+    } else {
+        const int grid = (t.batch + 1) / 2;
+        if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, false, PREV>>(d, grid, Layout<2>::BYTES, stream);
+        else launch_instance<kz_tower_resident<2, false, PF_NB2, false, PREV>>(d, grid, Layout<2>::BYTES, stream);
+    }
+}
 }  // namespace
 
 void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
@@ -835,35 +853,10 @@ void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
     d.nonfinite_flag = t.nonfinite_flag;
     d.epoch = t.epoch;
     d.dec = decode_dev(t.decode, t.fused_heads, POLICY);
-    const bool heads = t.fused_heads;
 #ifdef KZ_EXPERIMENTS
-    if (t.prev) {  // (the round-6 instances: tests/test_tower_overlap.py)
-        const int grid = (t.batch + 1) / 2;
-        if (t.cin_p > 32) {
-            if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, true, true>>(d, grid, Layout<2>::BYTES, stream);
-            else launch_instance<kz_tower_resident<2, false, PF_NB2, true, true>>(d, grid, Layout<2>::BYTES, stream);
-        } else if (t.boards_per_wg == 1) {
-            if (heads) launch_instance<kz_tower_resident<1, true, PF_NB1, false, true>>(d, t.batch, Layout<1>::BYTES, stream);
-            else launch_instance<kz_tower_resident<1, false, PF_NB1, false, true>>(d, t.batch, Layout<1>::BYTES, stream);
-        } else {
-            if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, false, true>>(d, grid, Layout<2>::BYTES, stream);
-            else launch_instance<kz_tower_resident<2, false, PF_NB2, false, true>>(d, grid, Layout<2>::BYTES, stream);
-        }
-        return;
-    }
+    if (t.prev) return launch_chess<true>(d, t, stream);  // (the round-6 instances: tests/test_tower_overlap.py)
 #endif
-    if (t.cin_p > 32) {  // (ChessHistoryMapper: 34 / 47 / 60 planes; always two boards per workgroup)
-        const int grid = (t.batch + 1) / 2;
-        if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, true>>(d, grid, Layout<2>::BYTES, stream);
-        else launch_instance<kz_tower_resident<2, false, PF_NB2, true>>(d, grid, Layout<2>::BYTES, stream);
-    } else if (t.boards_per_wg == 1) {
-        if (heads) launch_instance<kz_tower_resident<1, true, PF_NB1>>(d, t.batch, Layout<1>::BYTES, stream);
-        else launch_instance<kz_tower_resident<1, false, PF_NB1>>(d, t.batch, Layout<1>::BYTES, stream);
-    } else {
-        const int grid = (t.batch + 1) / 2;
-        if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2>>(d, grid, Layout<2>::BYTES, stream);
-        else launch_instance<kz_tower_resident<2, false, PF_NB2>>(d, grid, Layout<2>::BYTES, stream);
-    }
+    launch_chess<false>(d, t, stream);
 }
 
 }  // namespace kz

@@ -430,11 +430,30 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
     KZ_STAMP(62);
 }
 
-int tiles_for(int hw, int channels) {
+constexpr int tiles_for(int hw, int channels) {
     if (channels == 256) return hw <= 64 ? 4 : 0;
     if (channels == 128) return hw * 2 <= 112 ? 7 : hw <= 64 ? 4 : hw <= 96 ? 6 : 0;
     return 0;
 }
+
+// The instances: every row is compiled plain, with the conv heads, as Prof::max and as Prof::histogram, and launch_row folds
+// over the rows — a row is an instance and nothing else is.  Every tile count tiles_for returns has its row:
+struct F32Row {
+    int c, nt;
+};
+constexpr F32Row F32_ROWS[] = {{256, 4}, {128, 7}, {128, 6}, {128, 4}};
+constexpr bool f32_has_row(int channels, int nt) {
+    for (const F32Row &r : F32_ROWS)
+        if (r.c == channels && r.nt == nt) return true;
+    return false;
+}
+constexpr bool f32_rule_has_rows() {
+    for (int channels = 32; channels <= 512; channels += 32)
+        for (int hw = 1; hw <= 512; hw++)
+            if (const int nt = tiles_for(hw, channels); nt && !f32_has_row(channels, nt)) return false;
+    return true;
+}
+static_assert(f32_rule_has_rows(), "tiles_for returns a tile count that has no instance");
 
 template <int C, int NT, bool HEADS, bool DENSE = false, Prof PROFILE = Prof::none>
 void launch1(const TowerF32Dev &d, int grid, hipStream_t stream) {
@@ -464,10 +483,12 @@ void launch1(const TowerF32Dev &d, int grid, hipStream_t stream) {
 #endif
 }
 
-template <int C, int NT, bool DENSE = false>
-void launch(const TowerF32Dev &d, bool heads, int grid, hipStream_t stream) {
-    if (heads) launch1<C, NT, true, DENSE>(d, grid, stream);
-    else launch1<C, NT, false, DENSE>(d, grid, stream);
+// The instance of (channels, nt) among F32_ROWS in one mode: the row that matches supplies the template arguments, and no
+// row = no launch (false)
+template <bool HEADS, Prof PROFILE, size_t... I>
+bool launch_row(std::index_sequence<I...>, int channels, int nt, const TowerF32Dev &d, int grid, hipStream_t stream) {
+    return (... || (F32_ROWS[I].c == channels && F32_ROWS[I].nt == nt &&
+                    (launch1<F32_ROWS[I].c, F32_ROWS[I].nt, HEADS, false, PROFILE>(d, grid, stream), true)));
 }
 
 }  // namespace
@@ -591,7 +612,8 @@ void tower32_pack_weights(const float *oihw, int cout, int cin, bool stem, float
                         }
 }
 
-void launch_tower32(const Tower32Args &t, hipStream_t stream) {
+bool launch_tower32(const Tower32Args &t, hipStream_t stream, int *nt_out) {
+    using Kind = Tower32Args::Heads::Kind;
     TowerF32Dev d;
     d.x0 = t.x0;
     d.w = static_cast<const f32x4 *>(t.weights);
@@ -609,6 +631,8 @@ void launch_tower32(const Tower32Args &t, hipStream_t stream) {
     d.depth = t.depth;
     d.stem_groups = (t.c_in + 15) / 16;
     const int nt = t.dense3 ? 10 : tiles_for(d.hw, t.channels);
+    if (nt_out) *nt_out = nt;
+    if (!nt) return false;
     d.nb = nt * 16 / d.hw;
     d.inv_w = (65536u + (unsigned)t.w - 1) / (unsigned)t.w;
     d.inv_hw = (65536u + (unsigned)d.hw - 1) / (unsigned)d.hw;
@@ -621,29 +645,24 @@ void launch_tower32(const Tower32Args &t, hipStream_t stream) {
     d.small_w = static_cast<const f32x4 *>(static_cast<const void *>(hd.small_w));
     d.stamps = nullptr;
     d.scalars = hd.scalars; d.policy = hd.policy; d.nonfinite_flag = hd.nonfinite_flag;
-    d.dec = decode_dev(hd.decode, hd.on, hd.policy_len);
+    d.dec = decode_dev(hd.decode, hd.kind != Kind::none, hd.policy_len);
     const int grid = (t.batch + d.nb - 1) / d.nb;
-    if (t.profile && t.hist) {  // the range histogram's instances: no heads, hist += the counts [site][bin]
-        if (t.channels == 256) launch1<256, 4, false, false, Prof::histogram>(d, grid, stream);
-        else if (nt == 7) launch1<128, 7, false, false, Prof::histogram>(d, grid, stream);
-        else if (nt == 6) launch1<128, 6, false, false, Prof::histogram>(d, grid, stream);
-        else launch1<128, 4, false, false, Prof::histogram>(d, grid, stream);
-        return;
-    }
-    if (t.profile) {  // the range profile's instances: no heads, y = the maxima [site][ldy boards]
-        if (t.channels == 256) launch1<256, 4, false, false, Prof::max>(d, grid, stream);
-        else if (nt == 7) launch1<128, 7, false, false, Prof::max>(d, grid, stream);
-        else if (nt == 6) launch1<128, 6, false, false, Prof::max>(d, grid, stream);
-        else launch1<128, 4, false, false, Prof::max>(d, grid, stream);
-        return;
-    }
-    if (t.channels == 256) launch<256, 4>(d, hd.on, grid, stream);
+    const auto rows = std::make_index_sequence<std::size(F32_ROWS)>{};
+    // the range histogram's instances: no heads, hist += the counts [site][bin]; the range profile's: y = the maxima [site][ldy boards]
+    if (t.profile && t.hist) return launch_row<false, Prof::histogram>(rows, t.channels, nt, d, grid, stream);
+    if (t.profile) return launch_row<false, Prof::max>(rows, t.channels, nt, d, grid, stream);
+    if (hd.kind == Kind::attention) return false;  // (the attention heads are the split launch's)
+    const bool heads = hd.kind == Kind::conv;
 #ifdef KZ_EXPERIMENTS
-    else if (nt == 10) launch<128, 10, true>(d, hd.on, grid, stream);
+    if (t.dense3) {  // (tower32_dense3_supported)
+        if (t.channels != 128) return false;
+        if (heads) launch1<128, 10, true, true>(d, grid, stream);
+        else launch1<128, 10, false, true>(d, grid, stream);
+        return true;
+    }
 #endif
-    else if (nt == 7) launch<128, 7>(d, hd.on, grid, stream);
-    else if (nt == 6) launch<128, 6>(d, hd.on, grid, stream);
-    else launch<128, 4>(d, hd.on, grid, stream);
+    return heads ? launch_row<true, Prof::none>(rows, t.channels, nt, d, grid, stream)
+                 : launch_row<false, Prof::none>(rows, t.channels, nt, d, grid, stream);
 }
 
 }  // namespace kz

@@ -4,7 +4,7 @@
 //   kz_tower_split.hip  SPLIT = true   "tower_resident_split16[+heads]"  (KZ_DTYPE_F32_SPLIT16)
 //   kz_tower_f16g.hip   SPLIT = false  "tower_resident_f16g[+heads]"      (KZ_DTYPE_F16 on the shapes kz_tower.hip does not take)
 //   kz_tower_bf16g.hip  BF = true      "tower_resident_bf16g[+heads]"     (KZ_DTYPE_BF16: the plain arithmetic on bf16 elements)
-// Host-side weight packing and the support predicates: kz_tower_pairs_pack.hip; instance selection: kz_tower_pairs_shapes.hpp.
+// Host-side weight packing and the support predicates: kz_tower_pairs_pack.hip; the tile rules and the tables of instances: kz_tower_pairs_shapes.hpp; launch_pairs (at the end) folds over a table.
 //
 // every weight is carried as a pair of f16 values (hi = f16(v), lo = f16(v - hi): 22 significant bits) and every product
 // is three MFMAs, hi*hi + hi*lo + lo*hi, accumulated in f32 (the lo*lo term is below 2^-22 of the product).  Same
@@ -48,7 +48,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-#include "kz_tower_pairs_shapes.hpp"  // HEAD_PASSES, POLICY, LOGIT_LD, split_tiles_for, split_wide_tiles_for
+#include "kz_tower_pairs_shapes.hpp"  // HEAD_PASSES, POLICY, LOGIT_LD, pairs_tiles, PLAIN_ROWS, SPLIT_ROWS, SPLIT_ATTENTION
 
 #include "kz_decode_dev.hpp"  // DecodeDev, decode_board_wave: decode_output as the last step of a launch with the heads inside
 #include "kz_conv_heads.hpp"  // conv_heads_f32: the conv policy heads and the scalar head on f32 row images in LDS
@@ -886,22 +886,21 @@ inline SplitDev make_split_dev(const Tower32Args &t, bool split, int &nt, int &g
     d.w_ = t.w;
     d.hw = t.h * t.w;
     d.stem_chunks = (t.c_in + 31) / 32;
-    // (an engine that takes the wide tiles still launches the narrow ones for a batch too small to fill 128 wide workgroups:
-    // the same weight stream, twice the workgroups, half the time per workgroup)
-    nt = !split && t.wide ? split_wide_tiles_for(d.hw, t.channels, t.batch) : 0;  // (the widest level this batch fills the chip with)
-    if (!nt) nt = split_tiles_for(d.hw, t.channels, split);
+    nt = pairs_tiles(d.hw, t.channels, split, t.wide ? t.batch : 0);
+    if (!nt) return d;  // (no instance takes this shape: nothing to size)
     d.nb = nt * 16 / d.hw;
     d.inv_w = (65536u + (unsigned)t.w - 1) / (unsigned)t.w;
     d.inv_hw = (65536u + (unsigned)d.hw - 1) / (unsigned)d.hw;
     grid = (t.batch + d.nb - 1) / d.nb;
-    if (t.heads.on && (split || t.heads.small_w)) {  // (the engine asked tower_split_[conv_]heads_supported)
-        const Tower32Args::Heads &hd = t.heads;
+    const Tower32Args::Heads &hd = t.heads;
+    if (hd.kind != Tower32Args::Heads::Kind::none) {  // (the engine asked tower_split_[conv_]heads_supported)
+        const bool conv = hd.kind == Tower32Args::Heads::Kind::conv;
         d.sh_w0 = hd.sh_w0; d.sh_b0 = hd.sh_b0; d.sh_w1 = hd.sh_w1; d.sh_b1 = hd.sh_b1; d.sh_w2 = hd.sh_w2; d.sh_b2 = hd.sh_b2;
         d.att_idx = hd.att_idx;
         d.scalars = hd.scalars; d.policy = hd.policy;
         d.nonfinite_flag = hd.nonfinite_flag; d.epoch = hd.epoch;
-        d.dec = decode_dev(hd.decode, true, hd.small_w ? hd.policy_len : POLICY);
-        if (hd.small_w) {  // conv policy heads (tower_split_conv_heads_supported)
+        d.dec = decode_dev(hd.decode, true, conv ? hd.policy_len : POLICY);
+        if (conv) {  // conv policy heads (tower_split_conv_heads_supported)
             d.hc = hd.hc; d.hs = hd.hs; d.pc = hd.pc; d.policy_len = hd.policy_len; d.zero_tail = hd.zero_tail; d.extra = hd.extra;
             d.sh_w1t = hd.sh_w1t; d.p_b1 = hd.p_b1; d.pe_bc = hd.pe_bc; d.pe_wl = hd.pe_wl; d.pe_bl = hd.pe_bl;
             d.small_w = reinterpret_cast<const f32x4 *>(hd.small_w);
@@ -909,6 +908,49 @@ inline SplitDev make_split_dev(const Tower32Args &t, bool split, int &nt, int &g
         }
     }
     return d;
+}
+
+// The instance of (channels, nt) among ROWS (kz_tower_pairs_shapes.hpp), with the conv heads' tail if asked for: the row that
+// matches supplies the template arguments, and no row = no launch (false)
+template <const auto &ROWS, bool SPLIT, bool BF, size_t... I>
+bool launch_row(std::index_sequence<I...>, int channels, int nt, bool conv_heads, const SplitDev &d, int grid, hipStream_t stream) {
+    return (... || [&] {
+        constexpr PairsRow R = ROWS[I];
+        if (R.c != channels || R.nt != nt) return false;
+        if (!conv_heads) launch<R.c, R.nt, SPLIT, 0, BF>(d, grid, stream);
+        else if constexpr (R.conv_heads) launch<R.c, R.nt, SPLIT, 2, BF>(d, grid, stream);
+        return !conv_heads || R.conv_heads;
+    }());
+}
+
+// What launch_tower_split (SPLIT), launch_tower_pairs and launch_tower_bf16 (BF) are: the arguments, then the one instance
+// the tile rules chose for this shape and batch (nt_out: the tile count asked for).  false: there is no such instance.
+template <bool SPLIT, bool BF = false>
+bool launch_pairs(const Tower32Args &t, hipStream_t stream, int *nt_out) {
+    using Kind = Tower32Args::Heads::Kind;
+    int nt = 0, grid = 0;
+    const SplitDev d = make_split_dev(t, SPLIT, nt, grid);
+    if (nt_out) *nt_out = nt;
+    if (!nt) return false;
+    if (t.heads.kind == Kind::attention) {  // the chess attention network (the engine asked tower_split_heads_supported)
+        if constexpr (SPLIT) {
+            if (t.channels != SPLIT_ATTENTION.c || nt != SPLIT_ATTENTION.nt) return false;
+            launch<SPLIT_ATTENTION.c, SPLIT_ATTENTION.nt, true, 1>(d, grid, stream);
+            return true;
+        }
+        return false;
+    }
+#ifdef KZ_EXPERIMENTS
+    if constexpr (!BF) {
+        if (t.heads.kind == Kind::none && split_uses_32x32(t.channels, nt, SPLIT)) {
+            launch32<SPLIT>(d, grid, stream);
+            return true;
+        }
+    }
+#endif
+    const bool conv_heads = t.heads.kind == Kind::conv;  // "...+heads" (the engine asked tower_split_conv_heads_supported)
+    if constexpr (SPLIT) return launch_row<SPLIT_ROWS, true, false>(std::make_index_sequence<std::size(SPLIT_ROWS)>{}, t.channels, nt, conv_heads, d, grid, stream);
+    else return launch_row<PLAIN_ROWS, false, BF>(std::make_index_sequence<std::size(PLAIN_ROWS)>{}, t.channels, nt, conv_heads, d, grid, stream);
 }
 
 }  // namespace

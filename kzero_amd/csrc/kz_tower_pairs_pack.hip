@@ -1,6 +1,7 @@
 // kz_tower_pairs_pack.hip — host side of the one-launch (hi, lo) / plain-f16 / bf16 towers (kz_tower_pairs.hpp): which shapes they
 // take, the weight streams in MFMA fragment order, the heads' weights.  No kernel in this file.
 #include <cstdlib>
+#include <utility>
 #include <vector>
 
 #include "kz_kernels.hpp"
@@ -37,8 +38,7 @@ bool tower_split_supported(int h, int w, int channels, int depth, int c_in, bool
 }
 
 int tower_split_boards_per_workgroup(int h, int w, int channels, bool split, int wide_batch) {
-    int nt = !split && wide_batch ? split_wide_tiles_for(h * w, channels, wide_batch) : 0;
-    if (!nt) nt = split_tiles_for(h * w, channels, split);
+    const int nt = pairs_tiles(h * w, channels, split, wide_batch);
     return nt ? nt * 16 / (h * w) : 0;
 }
 
@@ -178,14 +178,12 @@ void tower_split_pack_heads(const float *w_bulk, const float *b_bulk, const floa
 // ---- conv policy heads in the split launch: the shapes of the exact-f32 launch's fused heads at 128 / 256 channels ----
 bool tower_split_conv_heads_supported(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs,
                                       bool split, int wide_batch) {
-    if (channels != 128 && channels != 256) return false;
     // (wide_batch: the engine's max_batch when it takes the wide tiles — a launch with a smaller batch takes a narrower level,
     // whose fewer boards need less of the tail's scratch)
-    int nt = !split && wide_batch ? split_wide_tiles_for(h * w, channels, wide_batch) : 0;
-    if (!nt) nt = split_tiles_for(h * w, channels, split);
-    // instances: <256, 4> and <128, 4 / 6 / 7> (plain f16: <128, 8 / 11 / 13> too).  Split arithmetic: the f32 row images of the
-    // tail must fit the LDS next to nothing else; plain f16: the tail's scratch behind the launch's own images.
-    if (nt == 0 || (channels == 256 && nt != 4)) return false;
+    const int nt = pairs_tiles(h * w, channels, split, wide_batch);
+    if (!pairs_has_instance(channels, nt, split, true)) return false;  // (the rows with conv_heads, kz_tower_pairs_shapes.hpp)
+    // Split arithmetic: the f32 row images of the tail must fit the LDS next to nothing else; plain f16: the tail's scratch
+    // behind the launch's own images.
     if (split && (size_t)(16 + 2 * nt * 16) * (channels * 4 + 16) > (size_t)160 * 1024) return false;
     return conv_heads_fit(nt, policy_kind, extra_moves, pc, h, w, channels, hc, hs,
                           split ? 0 : (size_t)pairs_f16_tail_scratch_bytes(channels, nt));
