@@ -28,7 +28,7 @@ namespace {
 
 #include "kz_engine_util.hpp"     // g_err, fail, guarded, HIP_TRY
 #include "kz_plan.hpp"            // Tower, PathPlan, plan_path: which kernels run a network
-#include "kz_device_weights.hpp"  // DevConv, DeviceWeights::build(model, plan), the cache by WeightsKey
+#include "kz_device_weights.hpp"  // DevConv, DeviceWeights::build(model, spec), the cache by WeightsKey
 
 #include "kz_engine_state.hpp"    // Prof, kz_model, effective_model, struct kz_engine: streams, slots, staging (closes the namespace itself)
 #include "kz_engine_forward.hpp"  // kz_engine::run_tower / run_heads / forward_*: the launches of a forward pass
@@ -200,7 +200,7 @@ static bool known_dtype(int dtype) {
 // kz_engine_create; profile: the range profile's internal engine — exact f32, no environment switch read, whatever plan_path
 // would choose.  per_layer (kz_model_range_profile): the per-layer implicit GEMM, every stash site a range measurement;
 // resident (kz_model_range_profile_fast where tower32_supported holds): the one-launch f32 tower without heads, whose
-// PROFILE instance measures in its epilogues — the same weight stream as an ordinary exact-f32 engine's (WeightsKey).
+// PROFILE instance measures in its epilogues — the same weight stream as an ordinary exact-f32 engine's (weights_spec).
 // per_layer_hist, resident_hist (kz_model_range_histogram, _fast): the same two engines counting binades instead of taking maxima
 enum class Profile { none, per_layer, resident, per_layer_hist, resident_hist };
 static bool profile_per_layer(Profile p) { return p == Profile::per_layer || p == Profile::per_layer_hist; }
@@ -260,14 +260,14 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         const PathPlan &plan = e->plan;
         {
             std::lock_guard<std::mutex> lock(g_cache_mutex);
-            const WeightsKey key(e->model.get(), device, dtype, plan);
+            const WeightsKey key{e->model.get(), device, dtype, weights_spec(m, plan)};
             auto it = g_cache.find(key);
             if (it != g_cache.end()) e->wts = it->second.lock();
             if (!e->wts) {
                 auto w = std::make_shared<DeviceWeights>();
                 w->device = device;
                 w->dtype = dtype;
-                if (w->build(m, plan)) return 1;
+                if (w->build(m, key.spec)) return 1;
                 g_cache[key] = w;
                 e->wts = w;
             }
@@ -279,15 +279,15 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         if (!plan.heads && !plan.att_heads) switch (m.policy_kind) {
             case kz::POLICY_ATAXX_CONV:
             case kz::POLICY_ARIMAA:
-            case kz::POLICY_CONV: h0 = rows * w.p_conv0.cout_p; break;
+            case kz::POLICY_CONV: h0 = rows * w.pol.conv0.cout_p; break;
             case kz::POLICY_ATTENTION:
-                h0 = rows * w.p_bulk.cout_p;
-                h1 = (size_t)max_batch * 8 * w.p_under.cout_p;
+                h0 = rows * w.pol.bulk.cout_p;
+                h1 = (size_t)max_batch * 8 * w.pol.under.cout_p;
                 break;
             case kz::POLICY_NONE: break;
             case kz::POLICY_DENSE:
-                if (m.dense_hidden_channels) h0 = rows * w.p_conv0.cout_p;
-                if (m.dense_hidden_size) h1 = (size_t)max_batch * w.p_fc0.cout_p;
+                if (m.dense_hidden_channels) h0 = rows * w.pol.conv0.cout_p;
+                if (m.dense_hidden_size) h1 = (size_t)max_batch * w.pol.fc0.cout_p;
                 break;
         }
         if (too_large(std::max(h0, h1) * e->esz / max_batch)) return 1;

@@ -58,8 +58,8 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         kz::DenseNetArgs t{};
         t.x0 = x_in; t.in_f16 = dtype == KZ_DTYPE_F16; t.batch = batch; t.hw = hw; t.cin_p = cin_p; t.size = m.channels;
         t.depth = m.depth; t.res = m.dn_res ? 1 : 0; t.policy_len = m.policy_len;
-        t.w_in = wts->dn_w_in; t.b_in = wts->dn_b_in; t.blocks = wts->dn_blocks; t.sf = wts->dn_sf; t.tf = wts->dn_tf;
-        t.w_out = wts->dn_w_out; t.b_out = wts->dn_b_out; t.scalars = d_scalars; t.policy = d_policy;
+        t.w_in = wts->dn.w_in; t.b_in = wts->dn.b_in; t.blocks = wts->dn.blocks; t.sf = wts->dn.sf; t.tf = wts->dn.tf;
+        t.w_out = wts->dn.w_out; t.b_out = wts->dn.b_out; t.scalars = d_scalars; t.policy = d_policy;
         t.nonfinite_flag = p.nf_flag; t.epoch = p.nf_epoch;
         if (launch(p, "kz_dense_network", [&] { kz::launch_dense_network(t, p.stream); })) return 1;
         tower_out = 0;
@@ -68,8 +68,8 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
     if (plan.tower == Tower::att_mfma) {  // AttentionTower on the matrix cores, in the engine's arithmetic
         kz::AttTower16Args t{};
         t.f32 = dtype == KZ_DTYPE_F32;
-        t.x0 = x_in; t.cin_p = cin_p; t.w_expand = wts->att16_expand; t.embedding = wts->att_embedding;
-        t.w_layers = wts->att16_layers; t.y = act[0]; t.batch = batch; t.depth = m.depth; t.d_model = m.channels;
+        t.x0 = x_in; t.cin_p = cin_p; t.w_expand = wts->att.expand16; t.embedding = wts->att.embedding;
+        t.w_layers = wts->att.layers16; t.y = act[0]; t.batch = batch; t.depth = m.depth; t.d_model = m.channels;
         t.d_ff = m.att_dff; t.alpha = m.att_alpha; t.eps = m.ln_eps;
         if (packed) t.in = *packed;  // fused board encode
         if (launch(p, t.f32 ? "kz_att_tower_f32" : "kz_att_tower_f16", [&] { kz::launch_att_tower16(t, p.stream); })) return 1;
@@ -79,7 +79,7 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
     if (plan.tower == Tower::att_valu) {  // AttentionTower: encoded planes in x_in -> tower output rows in act[0], one launch
         kz::AttTowerArgs t{};
         t.x0 = x_in; t.ldx0 = cin_p; t.in_f16 = dtype == KZ_DTYPE_F16; t.c_in = m.c_in;
-        t.expand = wts->att_expand; t.embedding = wts->att_embedding; t.layers = wts->att_layers;
+        t.expand = wts->att.expand; t.embedding = wts->att.embedding; t.layers = wts->att.layers;
         t.y = act[0]; t.ldy = cp; t.out_f16 = dtype == KZ_DTYPE_F16;
         t.batch = batch; t.h = m.h; t.w = m.w; t.depth = m.depth; t.d_model = m.channels; t.heads = m.att_heads;
         t.d_k = m.att_dk; t.d_v = m.att_dv; t.d_ff = m.att_dff; t.alpha = m.att_alpha; t.eps = m.ln_eps;
@@ -90,13 +90,13 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
     if (plan.tower == Tower::resident_f16) {
         kz::TowerArgs t{};
         if (packed) t.in = *packed;  // fused board encode
-        t.x0 = x_in; t.cin_p = cin_p; t.w_stem = wts->res_w_stem; t.w_tower = wts->res_w_tower;
-        t.bias = wts->res_bias; t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
+        t.x0 = x_in; t.cin_p = cin_p; t.w_stem = wts->res.w_stem; t.w_tower = wts->res.w_tower;
+        t.bias = wts->res.bias; t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
         t.y = act[0]; t.batch = batch; t.h = m.h; t.w = m.w; t.depth = m.depth;
         t.boards_per_wg = plan.tower_nb;
         t.fused_heads = plan.heads;
-        t.sh_w0 = wts->sh_w0; t.sh_b0 = wts->sh_b0; t.sh_w1 = wts->sh_w1; t.sh_b1 = wts->sh_b1;
-        t.sh_w2 = wts->sh_w2; t.sh_b2 = wts->sh_b2; t.att_idx = wts->att_idx;
+        t.sh_w0 = wts->sh.w0; t.sh_b0 = wts->sh.b0; t.sh_w1 = wts->sh.w1; t.sh_b1 = wts->sh.b1;
+        t.sh_w2 = wts->sh.w2; t.sh_b2 = wts->sh.b2; t.att_idx = wts->res.att_idx;
         t.scalars = d_scalars; t.policy = d_policy;
         t.nonfinite_flag = p.nf_flag; t.epoch = p.nf_epoch;
         if (dec && plan.heads) t.decode = *dec;
@@ -116,34 +116,32 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
     }
     if (!per_layer(plan)) {  // resident_f32, resident_split16, resident_f16g, resident_bf16g
         kz::Tower32Args t{};
-        t.x0 = (const float *)x_in; t.ldx0 = cin_p; t.c_in = m.c_in; t.weights = wts->res32_w; t.bias = wts->res_bias;
+        t.x0 = (const float *)x_in; t.ldx0 = cin_p; t.c_in = m.c_in; t.weights = wts->res.w32; t.bias = wts->res.bias;
         t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
         t.y = (float *)act[0]; t.ldy = cp; t.batch = batch; t.h = m.h; t.w = m.w; t.channels = m.channels;
         t.depth = m.depth;
         if (packed) t.in = *packed;  // fused board encode
-        if (plan.heads && m.policy_kind == kz::POLICY_ATTENTION) {  // (the split launch only)
+        if (plan.heads) {  // the scalar head's matrices for either kind of heads, then the kind's own
             kz::Tower32Args::Heads &hd = t.heads;
-            hd.kind = kz::Tower32Args::Heads::Kind::attention;
-            hd.sh_w0 = wts->sh_w0; hd.sh_b0 = wts->sh_b0; hd.sh_w1 = wts->sh_w1; hd.sh_b1 = wts->sh_b1;
-            hd.sh_w2 = wts->sh_w2; hd.sh_b2 = wts->sh_b2; hd.att_idx = wts->att_idx;
+            const ScalarBranch &sh = wts->sh;
+            hd.sh_b0 = sh.b0; hd.sh_b1 = sh.b1; hd.sh_w2 = sh.w2; hd.sh_b2 = sh.b2;
             hd.policy_len = m.policy_len;
             hd.scalars = d_scalars; hd.policy = d_policy;
             hd.nonfinite_flag = p.nf_flag; hd.epoch = p.nf_epoch;
-        }
-        if (plan.heads && m.policy_kind != kz::POLICY_ATTENTION) {  // conv policy heads: the f32 tail
-            kz::Tower32Args::Heads &hd = t.heads;
-            hd.kind = kz::Tower32Args::Heads::Kind::conv;
-            hd.hc = m.sh_conv.cout; hd.hs = m.sh_fc0.out;
-            hd.small_w = wts->h32_small; hd.sh_b0 = wts->sh_b0; hd.sh_w1t = wts->sh_w1t; hd.sh_b1 = wts->sh_b1;
-            hd.sh_w2 = wts->sh_w2; hd.sh_b2 = wts->sh_b2;
-            hd.pc = m.policy_conv_channels; hd.p_b1 = wts->p_b1;
-            hd.policy_len = m.policy_len; hd.zero_tail = m.policy_kind == kz::POLICY_ATAXX_CONV ? 1 : 0;
-            if (m.policy_kind == kz::POLICY_CONV && m.policy_extra_moves) {
-                hd.extra = m.policy_extra_moves;
-                hd.pe_bc = wts->pe_bc; hd.pe_wl = wts->pe_wl; hd.pe_bl = wts->pe_bl;
+            if (m.policy_kind == kz::POLICY_ATTENTION) {  // (the split launch only)
+                hd.kind = kz::Tower32Args::Heads::Kind::attention;
+                hd.sh_w0 = sh.w0; hd.sh_w1 = sh.w1; hd.att_idx = wts->res.att_idx;
+            } else {  // conv policy heads: the f32 tail
+                hd.kind = kz::Tower32Args::Heads::Kind::conv;
+                hd.hc = m.sh_conv.cout; hd.hs = m.sh_fc0.out;
+                hd.small_w = wts->res.small; hd.sh_w1t = sh.w1t;
+                hd.pc = m.policy_conv_channels; hd.p_b1 = wts->pol.b1;
+                hd.zero_tail = m.policy_kind == kz::POLICY_ATAXX_CONV ? 1 : 0;
+                if (m.policy_kind == kz::POLICY_CONV && m.policy_extra_moves) {
+                    hd.extra = m.policy_extra_moves;
+                    hd.pe_bc = wts->pol.pe_bc; hd.pe_wl = wts->pol.pe_wl; hd.pe_bl = wts->pol.pe_bl;
+                }
             }
-            hd.scalars = d_scalars; hd.policy = d_policy;
-            hd.nonfinite_flag = p.nf_flag; hd.epoch = p.nf_epoch;
         }
         if (dec && plan.heads) t.heads.decode = *dec;
 #ifdef KZ_EXPERIMENTS
@@ -220,8 +218,13 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
 
 inline bool kz_engine::extra_in_scalar_head() const {
     const Model &m = *model;
-    return m.policy_kind == kz::POLICY_CONV && m.policy_extra_moves > 0 && wts->sh_w0x &&
+    return m.policy_kind == kz::POLICY_CONV && m.policy_extra_moves > 0 && wts->pol.w0x &&
            kz::scalar_head_takes_extra(dtype == KZ_DTYPE_F32 ? 0 : 1, cp, m.sh_conv.cout);
+}
+
+// a ScalarHead-shaped branch over the tower output x: hc 1x1 filters, hs hidden units, the outputs to `out`
+inline kz::ScalarHeadArgs kz_engine::scalar_head_args(const ScalarBranch &s, const void *x, int batch, int hc, int hs, float *out) const {
+    return kz::ScalarHeadArgs{x, cp, batch, model->h * model->w, model->channels, hc, hs, s.w0, s.b0, s.w1, s.b1, s.w2, s.b2, out, nullptr, 0, s.w1t};
 }
 
 inline int kz_engine::run_heads(const Pass &p, int batch, float *d_scalars, float *d_policy) {
@@ -233,20 +236,19 @@ inline int kz_engine::run_heads(const Pass &p, int batch, float *d_scalars, floa
         kz::AttHeadsArgs a{};
         a.x = x; a.ldx = cp; a.batch = batch; a.channels = m.channels; a.q = m.policy_query_channels;
         a.hc = m.sh_conv.cout; a.hs = m.sh_fc0.out; a.policy_len = m.policy_len;
-        a.weights = wts->ah_w; a.bias = wts->ah_bias;
-        a.w1 = wts->sh_w1; a.b1 = wts->sh_b1; a.w2 = wts->sh_w2; a.b2 = wts->sh_b2;
-        a.flat_to_att = wts->flat_to_att; a.scalars = d_scalars; a.policy = d_policy;
+        a.weights = wts->pol.ah_w; a.bias = wts->pol.ah_bias;
+        a.w1 = wts->sh.w1; a.b1 = wts->sh.b1; a.w2 = wts->sh.w2; a.b2 = wts->sh.b2;
+        a.flat_to_att = wts->pol.flat_to_att; a.scalars = d_scalars; a.policy = d_policy;
         a.nonfinite_flag = p.nf_flag; a.epoch = p.nf_epoch;
         return launch(p, "kz_att_heads_f16", [&] { kz::launch_att_heads(a, p.stream); });
     }
     {
-        kz::ScalarHeadArgs a{x, cp, batch, hw, m.channels, m.sh_conv.cout, m.sh_fc0.out,
-                             wts->sh_w0, wts->sh_b0, wts->sh_w1, wts->sh_b1, wts->sh_w2, wts->sh_b2, d_scalars,
-                             p.nf_flag, p.nf_epoch, wts->sh_w1t};
+        kz::ScalarHeadArgs a = scalar_head_args(wts->sh, x, batch, m.sh_conv.cout, m.sh_fc0.out, d_scalars);
+        a.nonfinite_flag = p.nf_flag; a.epoch = p.nf_epoch;
         // ConvPolicyHead's extra moves read the same tower output: one pass for both (post_act.py:63-67)
         if (extra_in_scalar_head()) {
             a.extra = m.policy_extra_moves;
-            a.w0x = wts->sh_w0x; a.pe_bc = wts->pe_bc; a.pe_wl = wts->pe_wl; a.pe_bl = wts->pe_bl;
+            a.w0x = wts->pol.w0x; a.pe_bc = wts->pol.pe_bc; a.pe_wl = wts->pol.pe_wl; a.pe_bl = wts->pol.pe_bl;
             a.policy = d_policy; a.policy_len = m.policy_len; a.policy_offset = m.policy_conv_channels * hw;
         }
         if (launch(p, "kz_scalar_head", [&] { kz::launch_scalar_head(dtype, a, p.stream); })) return 1;
@@ -255,7 +257,7 @@ inline int kz_engine::run_heads(const Pass &p, int batch, float *d_scalars, floa
         case kz::POLICY_ATAXX_CONV:
         case kz::POLICY_CONV: {
             const int pc = m.policy_conv_channels;
-            const DevConv &c0 = wts->p_conv0;
+            const DevConv &c0 = wts->pol.conv0;
             if (m.policy_kind == kz::POLICY_CONV && c0.sw && cp >= c0.cin_p &&
                 kz::conv1x1_policy_epilogue_supported(c0.cin_p, c0.cout_p, c0.cout, pc)) {
                 // Conv1x1 C->C + ReLU + Conv1x1 C->1 in one launch: the hidden layer never goes to memory
@@ -264,32 +266,30 @@ inline int kz_engine::run_heads(const Pass &p, int batch, float *d_scalars, floa
                 c.x = x; c.ldx = cp; c.weights = c0.sw; c.bias = c0.b; c.y = nullptr; c.ldy = 0;
                 c.M = M; c.cin_p = c0.cin_p; c.cout_p = c0.cout_p; c.relu = 1;
                 c.group = hw; c.src_group = hw; c.src_off = 0;
-                c.pw1 = wts->p_w1; c.pb1 = wts->p_b1; c.policy = d_policy; c.policy_len = m.policy_len; c.hw = hw;
+                c.pw1 = wts->pol.w1; c.pb1 = wts->pol.b1; c.policy = d_policy; c.policy_len = m.policy_len; c.hw = hw;
                 if (launch(p, "kz_conv1x1_split", [&] { kz::launch_conv1x1_split(c, p.stream); })) return 1;
             } else {
                 if (conv(p, c0, x, cp, head0, c0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
-                kz::PolicyConvArgs a{head0, c0.cout_p, batch, hw, m.channels, pc, wts->p_w1, wts->p_b1,
+                kz::PolicyConvArgs a{head0, c0.cout_p, batch, hw, m.channels, pc, wts->pol.w1, wts->pol.b1,
                                      d_policy, m.policy_len, m.policy_kind == kz::POLICY_ATAXX_CONV ? 1 : 0};
                 if (launch(p, "kz_policy_conv", [&] { kz::launch_policy_conv(dtype, a, p.stream); })) return 1;
             }
             if (m.policy_kind == kz::POLICY_CONV && m.policy_extra_moves && !extra_in_scalar_head()) {
-                kz::PolicyExtraArgs e{x, cp, batch, hw, m.channels, m.policy_extra_moves, wts->pe_wc, wts->pe_bc,
-                                      wts->pe_wl, wts->pe_bl, d_policy, m.policy_len, pc * hw};
+                kz::PolicyExtraArgs e{x, cp, batch, hw, m.channels, m.policy_extra_moves, wts->pol.pe_wc, wts->pol.pe_bc,
+                                      wts->pol.pe_wl, wts->pol.pe_bl, d_policy, m.policy_len, pc * hw};
                 if (launch(p, "kz_policy_extra", [&] { kz::launch_policy_extra(dtype, e, p.stream); })) return 1;
             }
             break;
         }
         case kz::POLICY_ARIMAA: {
             // ArimaaPolicyHead (post_act.py:144-173): policy = concat(scalar(common) [1 + 6], flatten(bulk(common)) [4 * hw])
-            const DevConv &c0 = wts->p_conv0;
+            const DevConv &c0 = wts->pol.conv0;
             if (conv(p, c0, x, cp, head0, c0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0)) return 1;
-            kz::PolicyConvArgs a{head0, c0.cout_p, batch, hw, m.channels, 4, wts->p_w1, wts->p_b1,
+            kz::PolicyConvArgs a{head0, c0.cout_p, batch, hw, m.channels, 4, wts->pol.w1, wts->pol.b1,
                                  d_policy + 7, m.policy_len, 0};  // (the four planes start behind the seven scalars)
             if (launch(p, "kz_policy_conv", [&] { kz::launch_policy_conv(dtype, a, p.stream); })) return 1;
             // the scalar branch has the ScalarHead's shape: the same kernel, seven outputs into the policy rows
-            kz::ScalarHeadArgs sa{x, cp, batch, hw, m.channels, m.arimaa_hidden_channels, m.arimaa_hidden_size,
-                                  wts->pa_w0, wts->pa_b0, wts->pa_w1, wts->pa_b1, wts->pa_w2, wts->pa_b2, d_policy,
-                                  nullptr, 0, wts->pa_w1t};
+            kz::ScalarHeadArgs sa = scalar_head_args(wts->pol.arimaa, x, batch, m.arimaa_hidden_channels, m.arimaa_hidden_size, d_policy);
             sa.n_out = 7;
             sa.out_ld = m.policy_len;
             if (launch(p, "kz_scalar_head", [&] { kz::launch_scalar_head(dtype, sa, p.stream); })) return 1;
@@ -298,12 +298,12 @@ inline int kz_engine::run_heads(const Pass &p, int batch, float *d_scalars, floa
         case kz::POLICY_ATTENTION: {
             // bulk = conv_bulk(common) on all 64 squares; under = conv_under(common[:, :, 7, None, :]) on the
             // 8 squares of rank index 7 (post_act.py:128-129): source rows 56..63 of each board
-            if (conv(p, wts->p_bulk, x, cp, head0, wts->p_bulk.cout_p, M, 0, nullptr, false, m.h, m.w, hw, hw, 0))
+            if (conv(p, wts->pol.bulk, x, cp, head0, wts->pol.bulk.cout_p, M, 0, nullptr, false, m.h, m.w, hw, hw, 0))
                 return 1;
-            if (conv(p, wts->p_under, x, cp, head1, wts->p_under.cout_p, batch * 8, 0, nullptr, false, 1, 8, 8, hw, 56))
+            if (conv(p, wts->pol.under, x, cp, head1, wts->pol.under.cout_p, batch * 8, 0, nullptr, false, 1, 8, 8, hw, 56))
                 return 1;
-            kz::AttentionArgs a{head0, head1, wts->p_bulk.cout_p, wts->p_under.cout_p, batch,
-                                m.policy_query_channels, wts->flat_to_att, d_policy, m.policy_len};
+            kz::AttentionArgs a{head0, head1, wts->pol.bulk.cout_p, wts->pol.under.cout_p, batch,
+                                m.policy_query_channels, wts->pol.flat_to_att, d_policy, m.policy_len};
             if (launch(p, "kz_attention_gather", [&] { kz::launch_attention(dtype, a, p.stream); })) return 1;
             break;
         }
@@ -312,20 +312,20 @@ inline int kz_engine::run_heads(const Pass &p, int batch, float *d_scalars, floa
             const void *flat = x;
             int flat_ld = hw * cp;
             if (m.dense_hidden_channels) {
-                if (conv(p, wts->p_conv0, x, cp, head0, wts->p_conv0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0))
+                if (conv(p, wts->pol.conv0, x, cp, head0, wts->pol.conv0.cout_p, M, 1, nullptr, false, m.h, m.w, hw, hw, 0))
                     return 1;
                 flat = head0;
-                flat_ld = hw * wts->p_conv0.cout_p;
+                flat_ld = hw * wts->pol.conv0.cout_p;
             }
             // Flatten + Linear: one GEMM row per board
             if (m.dense_hidden_size) {
-                if (conv(p, wts->p_fc0, flat, flat_ld, head1, wts->p_fc0.cout_p, batch, 1, nullptr, false, 1, 1, 1, 1, 0))
+                if (conv(p, wts->pol.fc0, flat, flat_ld, head1, wts->pol.fc0.cout_p, batch, 1, nullptr, false, 1, 1, 1, 1, 0))
                     return 1;
-                if (conv(p, wts->p_fc1, head1, wts->p_fc0.cout_p, nullptr, 0, batch, 0, nullptr, false, 1, 1, 1, 1, 0,
+                if (conv(p, wts->pol.fc1, head1, wts->pol.fc0.cout_p, nullptr, 0, batch, 0, nullptr, false, 1, 1, 1, 1, 0,
                          d_policy, m.policy_len))
                     return 1;
             } else {
-                if (conv(p, wts->p_fc1, flat, flat_ld, nullptr, 0, batch, 0, nullptr, false, 1, 1, 1, 1, 0, d_policy,
+                if (conv(p, wts->pol.fc1, flat, flat_ld, nullptr, 0, batch, 0, nullptr, false, 1, 1, 1, 1, 0, d_policy,
                          m.policy_len))
                     return 1;
             }

@@ -454,6 +454,7 @@ struct kz_engine {
     int run_tower(const Pass &p, int batch, float *d_scalars, float *d_policy, const kz::PackedBoards *packed = nullptr,
                   const kz::DecodeArgs *dec = nullptr);
     bool extra_in_scalar_head() const;
+    kz::ScalarHeadArgs scalar_head_args(const ScalarBranch &s, const void *x, int batch, int hc, int hs, float *out) const;
     int run_heads(const Pass &p, int batch, float *d_scalars, float *d_policy);
     int forward_packed(const Pass &p, const kz::PackedBoards &in, int batch, void *d_sout, void *d_pol, const kz::DecodeArgs *dec = nullptr);
     int forward_dense(const Pass &p, const void *d_nchw, int batch, void *d_sout, void *d_pol);

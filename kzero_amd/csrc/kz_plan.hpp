@@ -7,7 +7,7 @@
 // kz_engine_create and kz_model_plan — DESIGN.md §5 prints its table from it and tests/test_path_table.py holds it, and
 // the environment switches' effect on it, to tests/golden/path_table.json without a GPU.  plan_path is the first-match
 // chain below; its answer, one PathPlan, is the tower's kernel family plus the few choices independent of it.  The engine
-// keeps the plan and asks it (the functions below) whatever depends on it; DeviceWeights::build reads it too.
+// keeps the plan and asks it (the functions below) whatever depends on it; DeviceWeights::build reads its WeightsSpec.
 //
 //   dtype f16:         8x8, 256 channels, <= 224 planes          -> tower_resident_f16 [+heads: attention head, Q = 256]
 //                      else a shape of kz_tower_split.hip        -> tower_resident_f16g [+heads: conv heads at 128 / 256]
@@ -59,7 +59,38 @@ struct PathPlan {
 };
 
 // KZ_DTYPE_F32_SPLIT16: the f32 engine (dtype KZ_DTYPE_F32) with split arithmetic in the tower and the 1x1 head convolutions
-bool split_arithmetic(const PathPlan &p) { return p.tower == Tower::resident_split16 || p.tower == Tower::board_conv_split16; }
+bool split_arithmetic(Tower t) { return t == Tower::resident_split16 || t == Tower::board_conv_split16; }
+bool split_arithmetic(const PathPlan &p) { return split_arithmetic(p.tower); }
+
+// What the device weights depend on of a plan — all that DeviceWeights::build (kz_device_weights.hpp) is given of it, and with
+// the model, the device and the dtype the key of the weights cache: plans of equal spec share one set of streams.
+enum class StreamHeads { none, attention, conv };  // the heads whose weights ride in the one-launch tower's stream
+struct WeightsSpec {
+    Tower tower = Tower::conv_igemm;
+    StreamHeads heads = StreamHeads::none;
+    bool att_heads = false;              // PathPlan::att_heads: the attention policy head packed for kz_att_heads.hip
+    bool conv2 = false, nb4 = false;     // PathPlan::conv2, nb4 (the experiment build; false in the product)
+    auto fields() const { return std::tie(tower, heads, att_heads, conv2, nb4); }
+    bool operator<(const WeightsSpec &o) const { return fields() < o.fields(); }
+};
+WeightsSpec weights_spec(const Model &m, const PathPlan &p) {
+    WeightsSpec s;
+    s.tower = p.tower;
+    if (p.heads) s.heads = m.policy_kind == kz::POLICY_ATTENTION ? StreamHeads::attention : StreamHeads::conv;
+    // the exact-f32 stream carries the conv heads wherever the kernel can run them, whether the launch does or not: one
+    // stream for "+heads", for KZ_NO_FUSED_HEADS and for the range profile's engine
+    if (p.tower == Tower::resident_f32)
+        s.heads = kz::tower32_heads_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels, m.h, m.w, m.channels,
+                                              m.sh_conv.cout, m.sh_fc0.out)
+                      ? StreamHeads::conv
+                      : StreamHeads::none;
+    s.att_heads = p.att_heads;
+#ifdef KZ_EXPERIMENTS
+    s.conv2 = p.conv2;
+    s.nb4 = p.nb4;
+#endif
+    return s;
+}
 
 // one launch per layer (stem + 2·depth convolutions) through three rotating activation buffers; else one launch, one buffer
 bool per_layer(const PathPlan &p) {
