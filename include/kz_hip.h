@@ -393,6 +393,48 @@ int kz_model_range_histogram(const kz_model *model, int device, const uint8_t *b
 int kz_model_range_histogram_fast(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride,
                                   const float *scalars_in, int batch, void *hist_out);
 
+/* ---- tower taps and error profile: what the one-launch towers store, and how far it is from exact f32 ----
+ * The profile and the histogram above run in exact f32: they say what a 16-bit store WOULD do.  A tap is what the kernel that
+ * ships DID store.  Every one-launch ResTower ("tower_resident_f16", "_f16g", "_bf16g", "_split16", "_f32" of kz_model_plan) has
+ * a tap instance per geometry: the same template arguments, the same arithmetic in the same order, and one more store — the lane
+ * that writes its four channels of a pixel to the LDS image writes the same elements, as rounded for that store (f16, bf16, the
+ * (hi, lo) pair, f32), to a tensor in device memory, at every range site (kz_model_range_site_name's sites and order).  The last
+ * site is what the plain tower hands on: f32 where its output tensor is f32 (split16, bf16, f32), f16 in the two f16 launches.
+ * Only rows of real boards are written — not the rows that fill a 16-row tile, a missing partner board, or tiles past `batch`.
+ * A tap instance is the plain tower: no heads, no decode.
+ *
+ * kz_model_tower_taps_path(model, max_batch, dtype, buf, len) writes the kernel a tap call runs — kz_model_plan(model, max_batch,
+ * dtype)'s tower_path without "+heads" — without touching a GPU (buf of at least 32 bytes).  max_batch chooses the instance as it
+ * does for an engine (boards per workgroup, wide tiles), and the environment switches act as they do for kz_engine_create; a tap
+ * call runs THAT geometry on however few boards it is given.
+ * kz_model_tower_taps is synchronous: an internal engine of the model on `device`, the boards (packed as for
+ * kz_engine_eval_packed) in chunks, every device tensor below 2 GiB.  out: f32 [n_sites][batch][tower_channels][h][w] for the
+ * sites [site_first, site_first + n_sites); an element is the stored value widened exactly, (float)hi + (float)lo for a pair.
+ * A stream-shifted model's taps are in shifted units.
+ * kz_model_error_profile fills out [kz_model_range_sites] of kz_site_error (typed void like hist_out): dtype's taps against exact
+ * f32 on the same boards, reduced on the device.  a = the tap, r = the reference; an element where either is not finite counts
+ * in `nonfinite` and in no other field.  The reference is the one-launch f32 tower's own taps where kz_model_range_profile_fast_path
+ * says "tower_resident_f32", and kz_model_range_profile's per-layer exact-f32 engine at its sites elsewhere.  max_abs_err, max_abs_ref,
+ * count and nonfinite do not depend on scheduling; the two sums are f64 and depend on the order of addition in their last bits.
+ * dtype: KZ_DTYPE_F16, KZ_DTYPE_F32_SPLIT16 or bf16 (3); KZ_DTYPE_F32 is refused (a profile against itself compares nothing).
+ * All three fail, each with a message of its own in the function's name: null arguments; an AttentionTower network; a
+ * DenseNetwork; a tower without blocks; a dtype the model does not support; a network whose plan at (max_batch, dtype) runs per
+ * layer (read those with KZ_KEEP_ACTIVATIONS and kz_engine_read_activation); a site range outside 0 .. n_sites; batch < 1 or
+ * batch > max_batch; a bits_stride below kz_model_info.bits_bytes.  Those checks need no GPU. */
+typedef struct kz_site_error {
+    double   max_abs_err; /* max |a - r|, the difference taken in f64 */
+    double   sum_sq_err;  /* sum (a - r)^2 */
+    double   sum_sq_ref;  /* sum r^2 */
+    double   max_abs_ref; /* max |r| */
+    uint64_t count;       /* elements compared: batch * tower_channels * h * w less nonfinite */
+    uint64_t nonfinite;   /* elements where a or r is inf or NaN */
+} kz_site_error; /* 48 bytes */
+int kz_model_tower_taps_path(const kz_model *model, int max_batch, int dtype, char *buf, size_t len);
+int kz_model_tower_taps(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
+                        const float *scalars_in, int batch, int site_first, int n_sites, float *out);
+int kz_model_error_profile(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
+                           const float *scalars_in, int batch, void *out);
+
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and
  * returns; kz_engine_synchronize waits. */

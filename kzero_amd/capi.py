@@ -76,6 +76,18 @@ class AuditResult:
                 f"rms_value={self.rms_value.tolist()}, rms_prob={self.rms_prob})")
 
 
+class SiteError(C.Structure):
+    """kz_site_error (include/kz_hip.h): one range site of kz_model_error_profile, 48 bytes."""
+    _fields_ = [("max_abs_err", C.c_double), ("sum_sq_err", C.c_double), ("sum_sq_ref", C.c_double), ("max_abs_ref", C.c_double),
+                ("count", C.c_uint64), ("nonfinite", C.c_uint64)]
+
+
+# the same record as a numpy dtype, with the site's name in front (Model.error_profile)
+SITE_ERROR_DTYPE = np.dtype([("max_abs_err", np.float64), ("sum_sq_err", np.float64), ("sum_sq_ref", np.float64),
+                             ("max_abs_ref", np.float64), ("count", np.uint64), ("nonfinite", np.uint64)])
+assert C.sizeof(SiteError) == SITE_ERROR_DTYPE.itemsize == 48
+
+
 # name -> (restype, argtypes); every symbol include/kz_hip.h declares
 SIGNATURES = {
     "kz_last_error": (C.c_char_p, []),
@@ -101,6 +113,11 @@ SIGNATURES = {
     "kz_model_range_profile_fast_path": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t]),
     "kz_model_range_histogram": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     "kz_model_range_histogram_fast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "kz_model_tower_taps_path": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "kz_model_tower_taps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                                      C.c_int, C.c_void_p]),
+    "kz_model_error_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                         C.c_void_p]),
     "kz_engine_max_batch": (C.c_int, [C.c_void_p]),
     "kz_engine_eval_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "kz_engine_eval_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
@@ -324,6 +341,53 @@ class Model:
         check(entry(self._h, device, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0, scalars_in.ctypes.data,
                     bits.shape[0], hist.ctypes.data))
         return hist
+
+    def tower_taps_path(self, max_batch: int, dtype: int) -> str:
+        """The kernel a tap call runs: plan(max_batch, dtype)'s tower without "+heads" (kz_model_tower_taps_path) — host logic,
+        no GPU needed; fails where the taps fail."""
+        buf = C.create_string_buffer(64)
+        check(load().kz_model_tower_taps_path(self._h, max_batch, dtype, buf, len(buf)))
+        return buf.value.decode()
+
+    def tower_taps(self, device: int, max_batch: int, dtype: int, bits: np.ndarray, scalars_in: np.ndarray, site_first: int = 0,
+                   n_sites: int = None, out: np.ndarray = None) -> dict:
+        """What the one-launch tower of an engine of (max_batch, dtype) stores at the range sites [site_first, site_first +
+        n_sites) on these boards, as the kernel rounds it (kz_model_tower_taps): {site name: float32 [batch, C, H, W]}.
+        out: a float32 array of [n_sites, batch, C, H, W] elements to fill instead of a new one (the dict's arrays are views)."""
+        if n_sites is None:
+            n_sites = len(self.range_sites()) - site_first
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        batch = bits.shape[0]
+        shape = (max(n_sites, 0), batch, self.info.tower_channels, self.info.board_h, self.info.board_w)
+        if out is None:
+            out = np.zeros(shape, np.float32)
+        if out.dtype != np.float32 or not out.flags.c_contiguous or out.size < int(np.prod(shape)):
+            raise KzError(f"tower_taps: out must be a C-contiguous float32 array of at least {int(np.prod(shape))} elements")
+        check(load().kz_model_tower_taps(self._h, device, max_batch, dtype, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                         scalars_in.ctypes.data, batch, site_first, n_sites, out.ctypes.data))
+        names = self.range_sites()
+        view = out.reshape(-1)[:int(np.prod(shape))].reshape(shape)
+        return {names[site_first + i]: view[i] for i in range(n_sites)}
+
+    def error_profile(self, device: int, max_batch: int, dtype: int, bits: np.ndarray, scalars_in: np.ndarray) -> np.ndarray:
+        """Per range site, how far that tower's stored tensors are from exact f32 on these boards, reduced on the GPU
+        (kz_model_error_profile): a structured array [n_sites] with the fields site (the name), max_abs_err, sum_sq_err,
+        sum_sq_ref, max_abs_ref, count, nonfinite.  rms error relative to the reference's rms: sqrt(sum_sq_err / sum_sq_ref)."""
+        try:
+            names = self.range_sites()
+        except KzError:
+            names = [""]  # (a network without range sites: the call below says so in its own name)
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        raw = np.zeros(len(names), SITE_ERROR_DTYPE)
+        check(load().kz_model_error_profile(self._h, device, max_batch, dtype, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                            scalars_in.ctypes.data, bits.shape[0], raw.ctypes.data))
+        out = np.zeros(len(names), np.dtype([("site", "U24")] + SITE_ERROR_DTYPE.descr))
+        out["site"] = names
+        for f in SITE_ERROR_DTYPE.names:
+            out[f] = raw[f]
+        return out
 
     def _range_profile(self, entry: str, device: int, bits: np.ndarray, scalars_in: np.ndarray):
         n = C.c_int()

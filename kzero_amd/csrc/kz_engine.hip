@@ -202,10 +202,16 @@ static bool known_dtype(int dtype) {
 // resident (kz_model_range_profile_fast where tower32_supported holds): the one-launch f32 tower without heads, whose
 // PROFILE instance measures in its epilogues — the same weight stream as an ordinary exact-f32 engine's (weights_spec).
 // per_layer_hist, resident_hist (kz_model_range_histogram, _fast): the same two engines counting binades instead of taking maxima
-enum class Profile { none, per_layer, resident, per_layer_hist, resident_hist };
-static bool profile_per_layer(Profile p) { return p == Profile::per_layer || p == Profile::per_layer_hist; }
+// taps (kz_model_tower_taps, kz_model_error_profile): the engine kz_engine_create would make for (max_batch, dtype) — the
+// effective model, plan_path with the environment switches — but never with the heads inside the launch, and with a tap buffer
+// for tap_boards boards, which makes run_tower launch the tap instance.  taps_reference: the same on the one-launch exact-f32
+// tower whatever plan_path says (no switch read), the error profile's reference where that kernel takes the shape;
+// per_layer_deviation: its reference elsewhere, the range profile's per-layer engine whose stash sites are compared on the device
+enum class Profile { none, per_layer, resident, per_layer_hist, resident_hist, taps, taps_reference, per_layer_deviation };
+static bool profile_per_layer(Profile p) { return p == Profile::per_layer || p == Profile::per_layer_hist || p == Profile::per_layer_deviation; }
 static bool profile_hist(Profile p) { return p == Profile::per_layer_hist || p == Profile::resident_hist; }
-static int create_engine(const kz_model *model, int device, int max_batch, int dtype, Profile profile, kz_engine **out) {
+static bool profile_taps(Profile p) { return p == Profile::taps || p == Profile::taps_reference; }
+static int create_engine(const kz_model *model, int device, int max_batch, int dtype, Profile profile, kz_engine **out, int tap_boards = 0) {
     {
         if (!model || !out) return fail("kz_engine_create: null argument");
         if (max_batch <= 0) return fail("kz_engine_create: max_batch must be positive");
@@ -233,7 +239,7 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         HIP_TRY(hipSetDevice(device));
 
         std::unique_ptr<kz_engine, void (*)(kz_engine *)> e(new kz_engine(), kz_engine_destroy);
-        e->model = profile != Profile::none ? model->m : effective_model(model, dtype_in, max_batch);
+        e->model = profile != Profile::none && profile != Profile::taps ? model->m : effective_model(model, dtype_in, max_batch);
         e->source_model = model->m;
         e->out_channels = model->m->channels;
         const Model &m = *e->model;
@@ -249,6 +255,10 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
             e->plan = PathPlan();  // (Tower::conv_igemm)
             e->plan.keep = true;
             e->plan.launches = 2 + 2 * m.depth;
+        } else if (profile == Profile::taps) {  // (the caller has asked plan_path already: a one-launch ResTower)
+            if (!plan_path(m, max_batch, dtype_in, e->plan, why)) return fail("kz_engine_create: " + why);
+            e->plan.heads = false;
+            e->plan.launches = 1;
         } else if (profile != Profile::none) {
             e->plan = PathPlan();
             e->plan.tower = Tower::resident_f32;
@@ -342,7 +352,13 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
             if (e->dmalloc(&e->range_out, bytes)) return 1;
             HIP_TRY(hipMemset(e->range_out, 0, bytes));
             e->range_hist = true;
-        } else if (profile != Profile::none && e->dmalloc(&e->range_out, (size_t)(2 * m.depth + 1) * max_batch * 4)) {
+        } else if (profile_taps(profile)) {
+            // every site's tensor for tap_boards boards, all of them together below 2 GiB
+            const size_t per_board = (size_t)(2 * m.depth + 1) * hw * m.channels * 4;
+            e->tap_boards = (int)std::min<size_t>((size_t)std::min(max_batch, std::max(tap_boards, 1)), std::max<size_t>(((((size_t)1 << 31) - 1) / per_board), 1));
+            if (e->dmalloc((void **)&e->tap_out, per_board * e->tap_boards)) return 1;
+        } else if ((profile == Profile::per_layer || profile == Profile::resident) &&
+                   e->dmalloc(&e->range_out, (size_t)(2 * m.depth + 1) * max_batch * 4)) {
             return 1;
         }
         *out = e.release();
@@ -546,6 +562,196 @@ KZ_API int kz_model_range_profile_fast_path(const kz_model *model, char *buf, si
         if (!buf || len < name.size() + 1)
             return fail("kz_model_range_profile_fast_path: buffer of at least " + std::to_string(name.size() + 1) + " bytes needed");
         memcpy(buf, name.c_str(), name.size() + 1);
+        return 0;
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Tower taps and error profile (include/kz_hip.h): every stored tensor of the one-launch tower an engine of (max_batch, dtype)
+// runs, as the kernel rounds it, and its deviation from exact f32 per site
+// ------------------------------------------------------------------------------------------------
+
+// What a tap call runs: kz_model_plan's tower for (max_batch, dtype), never with the heads inside.  Host logic only (plan_path),
+// so every refusal below needs no GPU.  n: the range sites.
+static int tap_plan(const std::string &fn, const kz_model *model, int max_batch, int dtype, PathPlan &plan, int &n) {
+    if (!model) return fail(fn + ": null argument");
+    const Model &m = *model->m;
+    if (m.tower_kind == kz::TOWER_ATTENTION)
+        return fail(fn + ": an AttentionTower network has no range sites to tap: the taps are the one-launch ResTower's stored tensors");
+    if (m.tower_kind == kz::TOWER_DENSE_NET) return fail(fn + ": a DenseNetwork has no tower, and its one launch has no tap instance");
+    if (m.depth < 1) return fail(fn + ": a tower without blocks has no residual stream to tap");
+    n = 2 * m.depth + 1;
+    if (max_batch <= 0) return fail(fn + ": max_batch must be positive");
+    if (!known_dtype(dtype)) return fail(fn + ": unknown dtype " + std::to_string(dtype));
+    std::string why;
+    if (!plan_path(*effective_model(model, dtype, max_batch), max_batch, dtype, plan, why))
+        return fail(fn + ": this model does not run in dtype " + std::to_string(dtype) + ": " + why);
+    if (per_layer(plan))
+        return fail(fn + ": at max_batch " + std::to_string(max_batch) + " this network runs one launch per layer (" + path_name(plan, dtype) +
+                    "), which keeps its activations in device memory already: read those with KZ_KEEP_ACTIVATIONS=1 and "
+                    "kz_engine_read_activation; the taps are the one-launch towers'");
+    plan.heads = false;
+    return 0;
+}
+
+// the argument checks the two evaluating entries share, after tap_plan
+static int tap_arguments(const std::string &fn, const Model &m, int max_batch, const uint8_t *bits, size_t bits_stride, const float *scalars_in,
+                         int batch) {
+    if (m.n_scalar < 0) return fail(no_plane_split(fn));
+    if (m.n_scalar && !scalars_in) return fail(fn + ": null argument");
+    if (batch < 1 || batch > max_batch)
+        return fail(fn + ": batch " + std::to_string(batch) + " out of range: 1 .. max_batch (" + std::to_string(max_batch) + "), the batch size whose geometry is tapped");
+    if (bits_stride < bits_bytes(m)) return fail(fn + ": bits_stride too small (" + std::to_string(bits_stride) + " < " + std::to_string(bits_bytes(m)) + " bytes per board)");
+    return 0;
+}
+
+using EnginePtr = std::unique_ptr<kz_engine, void (*)(kz_engine *)>;
+static int tap_engine(const std::string &fn, const kz_model *model, int device, int max_batch, int dtype, Profile mode, int tap_boards, EnginePtr &e) {
+    kz_engine *raw = nullptr;
+    if (create_engine(model, device, max_batch, dtype, mode, &raw, tap_boards)) return fail(fn + ": " + std::string(g_err));
+    e.reset(raw);
+    return 0;
+}
+
+// one pass of a tap engine over nb <= tap_boards boards: the tap buffer to NaN patterns, then the launch; returns with the
+// stream idle
+static int tap_pass(kz_engine *e, const uint8_t *bits, size_t bits_stride, const float *scalars_in, int nb) {
+    kz_engine::Slot &s = e->slots[0];
+    const Model &m = *e->model;
+    e->stage_boards(s, bits, bits_stride, scalars_in, nb);
+    const Pass p = e->pass_staged(0);
+    if (e->copy_boards_in(p, s, nb)) return 1;
+    HIP_TRY(hipMemsetAsync(e->tap_out, 0xff, (size_t)(2 * m.depth + 1) * e->tap_site_bytes(), p.stream));
+    const kz::PackedBoards in = e->packed_boards(s.d_bits, e->bits_bytes(), s.d_sin);
+    e->range_site = 0;
+    if (e->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &in)) return 1;
+    if (e->range_site != 2 * m.depth + 1) return fail("internal error: the planned tower has no tap instance");
+    HIP_TRY(hipStreamSynchronize(p.stream));
+    return 0;
+}
+
+KZ_API int kz_model_tower_taps_path(const kz_model *model, int max_batch, int dtype, char *buf, size_t len) {
+    return guarded("kz_model_tower_taps_path", [&]() -> int {
+        const std::string fn = "kz_model_tower_taps_path";
+        PathPlan plan;
+        int n = 0;
+        if (tap_plan(fn, model, max_batch, dtype, plan, n)) return 1;
+        const std::string name = path_name(plan, dtype);
+        if (!buf || len < name.size() + 1) return fail(fn + ": buffer of at least " + std::to_string(name.size() + 1) + " bytes needed");
+        memcpy(buf, name.c_str(), name.size() + 1);
+        return 0;
+    });
+}
+
+KZ_API int kz_model_tower_taps(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
+                               const float *scalars_in, int batch, int site_first, int n_sites, float *out) {
+    return guarded("kz_model_tower_taps", [&]() -> int {
+        const std::string fn = "kz_model_tower_taps";
+        if (!model || !bits || !out) return fail(fn + ": null argument");
+        PathPlan plan;
+        int n = 0;
+        if (tap_plan(fn, model, max_batch, dtype, plan, n)) return 1;
+        if (site_first < 0 || n_sites < 1 || site_first > n - n_sites)
+            return fail(fn + ": sites [" + std::to_string(site_first) + ", " + std::to_string((long long)site_first + n_sites) + ") out of range (" +
+                        std::to_string(n) + " sites)");
+        const Model &src = *model->m;
+        if (tap_arguments(fn, src, max_batch, bits, bits_stride, scalars_in, batch)) return 1;
+        EnginePtr e(nullptr, kz_engine_destroy);
+        if (tap_engine(fn, model, device, max_batch, dtype, Profile::taps, batch, e)) return 1;
+        // The host loop converts: a site's rows come back as the kernel stored them (NHWC, the site's element) and are widened
+        // and transposed here — no second device tensor, and this is no hot path.  (e->model may be the widened network: its
+        // zero channels behind the model's own are not returned.)
+        const size_t hw = (size_t)src.h * src.w, ld = (size_t)e->model->channels, channels = (size_t)e->out_channels;
+        std::vector<unsigned char> host((size_t)e->tap_boards * hw * ld * 4);
+        for (int lo = 0; lo < batch; lo += e->tap_boards) {
+            const int nb = std::min(e->tap_boards, batch - lo);
+            if (tap_pass(e.get(), bits + (size_t)lo * bits_stride, bits_stride, src.n_scalar ? scalars_in + (size_t)lo * src.n_scalar : nullptr, nb))
+                return fail(fn + ": " + std::string(g_err));
+            const size_t rows = (size_t)nb * hw;
+            for (int si = 0; si < n_sites; si++) {
+                const int site = site_first + si;
+                const kz::TapFormat f = e->tap_format(site);
+                const size_t esz = f == kz::TapFormat::f32 ? 4 : 2;
+                HIP_TRY(hipMemcpy(host.data(), e->tap_site(site), rows * ld * esz, hipMemcpyDeviceToHost));
+                if (f == kz::TapFormat::split16)
+                    HIP_TRY(hipMemcpy(host.data() + rows * ld * 2, e->tap_site(site) + e->tap_site_bytes() / 2, rows * ld * 2, hipMemcpyDeviceToHost));
+                const float *h32 = reinterpret_cast<const float *>(host.data());
+                const _Float16 *h16 = reinterpret_cast<const _Float16 *>(host.data()), *l16 = h16 + rows * ld;
+                const uint16_t *b16 = reinterpret_cast<const uint16_t *>(host.data());
+                for (size_t r = 0; r < rows; r++) {
+                    float *dst = out + (((size_t)si * batch + lo) * channels) * hw + (r / hw) * channels * hw + r % hw;
+                    for (size_t c = 0; c < channels; c++) {
+                        const size_t i = r * ld + c;
+                        float v;
+                        if (f == kz::TapFormat::f32) v = h32[i];
+                        else if (f == kz::TapFormat::f16) v = (float)h16[i];
+                        else if (f == kz::TapFormat::split16) v = (float)h16[i] + (float)l16[i];
+                        else {
+                            const uint32_t u = (uint32_t)b16[i] << 16;
+                            memcpy(&v, &u, 4);
+                        }
+                        dst[c * hw] = v;
+                    }
+                }
+            }
+        }
+        return 0;
+    });
+}
+
+static_assert(sizeof(kz_site_error) == 48 && sizeof(kz::TapDeviation) == sizeof(kz_site_error), "a device record is a kz_site_error: the two maxima as the bit patterns of non-negative doubles");
+KZ_API int kz_model_error_profile(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
+                                  const float *scalars_in, int batch, void *out) {
+    return guarded("kz_model_error_profile", [&]() -> int {
+        const std::string fn = "kz_model_error_profile";
+        if (!model || !bits || !out) return fail(fn + ": null argument");
+        PathPlan plan;
+        int n = 0;
+        if (tap_plan(fn, model, max_batch, dtype, plan, n)) return 1;
+        if (dtype == KZ_DTYPE_F32) return fail(fn + ": KZ_DTYPE_F32 is the reference: a profile of exact f32 against itself compares nothing");
+        const Model &src = *model->m;
+        if (tap_arguments(fn, src, max_batch, bits, bits_stride, scalars_in, batch)) return 1;
+        // the reference: the one-launch f32 tower's own taps where that kernel takes the shape, else the per-layer exact-f32
+        // engine (kz_model_range_profile's), whose stash sites are compared as they are produced
+        const bool resident = range_profile_resident(src);
+        EnginePtr e(nullptr, kz_engine_destroy), ref(nullptr, kz_engine_destroy);
+        if (tap_engine(fn, model, device, max_batch, dtype, Profile::taps, resident ? batch : std::min(batch, 64), e)) return 1;
+        const int chunk = std::min(batch, e->tap_boards);
+        if (tap_engine(fn, model, device, chunk, KZ_DTYPE_F32, resident ? Profile::taps_reference : Profile::per_layer_deviation, chunk, ref)) return 1;
+        kz::TapDeviation *dev = nullptr;
+        if (e->dmalloc((void **)&dev, (size_t)n * sizeof(kz::TapDeviation))) return fail(fn + ": " + std::string(g_err));
+        HIP_TRY(hipMemset(dev, 0, (size_t)n * sizeof(kz::TapDeviation)));
+        HIP_TRY(hipDeviceSynchronize());  // (the engines' streams do not wait for the null stream)
+        if (!resident) {
+            ref->tap_peer = e.get();
+            ref->deviation = dev;
+        }
+        for (int lo = 0; lo < batch; lo += chunk) {
+            const int nb = std::min(chunk, batch - lo);
+            const uint8_t *b = bits + (size_t)lo * bits_stride;
+            const float *sc = src.n_scalar ? scalars_in + (size_t)lo * src.n_scalar : nullptr;
+            if (tap_pass(e.get(), b, bits_stride, sc, nb)) return fail(fn + ": " + std::string(g_err));
+            if (resident) {
+                if (tap_pass(ref.get(), b, bits_stride, sc, nb)) return fail(fn + ": " + std::string(g_err));
+                const Pass p = ref->pass_staged(0);
+                for (int site = 0; site < n; site++)
+                    if (e->tap_deviation(p, site, reinterpret_cast<const float *>(ref->tap_site(site)), ref->model->channels, nb, dev + site))
+                        return fail(fn + ": " + std::string(g_err));
+                HIP_TRY(hipStreamSynchronize(p.stream));
+            } else {
+                kz_engine::Slot &s = ref->slots[0];
+                ref->stage_boards(s, b, bits_stride, sc, nb);
+                const Pass p = ref->pass_staged(0);
+                if (ref->copy_boards_in(p, s, nb)) return fail(fn + ": " + std::string(g_err));
+                const kz::PackedBoards in = ref->packed_boards(s.d_bits, ref->bits_bytes(), s.d_sin);
+                if (ref->launch(p, "kz_encode_packed", [&] { kz::launch_encode_packed(ref->dtype, in, nb, src.h * src.w, ref->x_in, ref->cin_p, p.stream); }) ||
+                    ref->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol))
+                    return fail(fn + ": " + std::string(g_err));
+                if (ref->range_site != n) return fail(fn + ": internal error: " + std::to_string(ref->range_site) + " sites compared, " + std::to_string(n) + " expected");
+                HIP_TRY(hipStreamSynchronize(p.stream));
+            }
+        }
+        HIP_TRY(hipMemcpy(out, dev, (size_t)n * sizeof(kz_site_error), hipMemcpyDeviceToHost));
         return 0;
     });
 }

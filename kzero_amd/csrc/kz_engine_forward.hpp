@@ -100,6 +100,10 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         t.scalars = d_scalars; t.policy = d_policy;
         t.nonfinite_flag = p.nf_flag; t.epoch = p.nf_epoch;
         if (dec && plan.heads) t.decode = *dec;
+        if (tap_out) {  // a tap engine (no heads in its plan): the tap instance of the same geometry, every site's tensor to tap_out
+            t.taps = taps();
+            range_site = 2 * m.depth + 1;
+        }
 #ifdef KZ_EXPERIMENTS
         t.prev = plan.tower_prev;
 #endif
@@ -153,6 +157,11 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
             if (range_hist) t.hist = (unsigned long long *)range_out;  // (the counts instead of the maxima)
             else { t.y = (float *)range_out; t.ldy = max_batch; }
             range_site = 2 * m.depth + 1;  // every epilogue of the launch is a site
+        }
+        if (tap_out) {  // a tap engine (no heads in its plan): the tap instance of the geometry max_batch plans
+            t.taps = taps();
+            t.tap_wide_batch = max_batch;
+            range_site = 2 * m.depth + 1;
         }
         const bool f16g = plan.tower == Tower::resident_f16g;
         const char *name = split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : "kz_tower_resident_f32";

@@ -390,8 +390,43 @@ struct kz_engine {
     bool range_hist = false;
     int range_site = 0;
 
+    // the tower taps (kz_model_tower_taps, kz_model_error_profile): a tap engine — the planned one-launch tower, never with its
+    // heads — hands tap_out to the launch's tap instance, which stores every site's tensor there as its epilogue rounds it
+    // (kz_kernels.hpp: TapOut): [n_sites] tensors of tap_boards boards, tap_site_bytes() apart whatever the element.  Filled with
+    // 0xff bytes before every pass — a NaN in each of the four elements —, so an element no lane wrote reads as NaN.
+    unsigned char *tap_out = nullptr;
+    int tap_boards = 0;
+    size_t tap_site_bytes() const { return (size_t)tap_boards * model->h * model->w * model->channels * 4; }
+    kz::TapOut taps() const { return kz::TapOut{tap_out, tap_site_bytes()}; }
+    // the element of a site's tensor: the family's, and at the last site what the plain tower hands on
+    kz::TapFormat tap_format(int site) const {
+        const bool last = site == 2 * model->depth;
+        switch (plan.tower) {
+            case Tower::resident_f32: return kz::TapFormat::f32;
+            case Tower::resident_split16: return last ? kz::TapFormat::f32 : kz::TapFormat::split16;
+            case Tower::resident_bf16g: return last ? kz::TapFormat::f32 : kz::TapFormat::bf16;
+            default: return kz::TapFormat::f16;  // resident_f16, resident_f16g
+        }
+    }
+    const unsigned char *tap_site(int site) const { return tap_out + (size_t)site * tap_site_bytes(); }
+    // site `site` of this tap engine's last pass (`boards` boards) against the same rows in exact f32 (row stride ref_ld floats)
+    int tap_deviation(const Pass &p, int site, const float *ref, int ref_ld, int boards, kz::TapDeviation *out) const {
+        kz::launch_tap_deviation(tap_site(site), tap_format(site), tap_site_bytes() / 2, model->channels, ref, ref_ld,
+                                 (size_t)boards * model->h * model->w, out_channels, out, p.stream);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
+    // the error profile's per-layer reference (an exact-f32 profiling engine): instead of a maximum, every stash site is compared
+    // with tap_peer's tap of that site (tap_peer has finished its pass), into deviation [n_sites] in device memory
+    const kz_engine *tap_peer = nullptr;
+    kz::TapDeviation *deviation = nullptr;
+
     int stash(const Pass &p, const std::string &name, const void *src, int batch) {
         if (!plan.keep) return 0;
+        if (tap_peer) {
+            const int site = range_site++;
+            return tap_peer->tap_deviation(p, site, (const float *)src, cp, batch, deviation + site);
+        }
         if (range_hist) {
             unsigned long long *out = (unsigned long long *)range_out + (size_t)range_site++ * kz::RANGE_BINS;
             return launch(p, "kz_range_histogram", [&] {

@@ -72,6 +72,59 @@ __host__ __device__ inline unsigned range_bin(unsigned u) {
 // as above).  hist: RANGE_BINS 64-bit counters in device memory, added to with integer atomics (kz_range_profile.hip).
 void launch_range_histogram(const float *x, int boards, int hw, int channels, int cp, unsigned long long *hist, hipStream_t stream);
 
+// Tower taps (kz_model_tower_taps, kz_model_error_profile): the tap instance of a one-launch tower writes every range site's
+// tensor, as its epilogue rounds it for the LDS store, to `base` + site * site_bytes: NHWC rows [board * hw + pixel][channels]
+// of the site's element — a lane's four consecutive channels of a pixel are one vector store.  Only rows of real boards are
+// written (the histogram instances' rule).  A (hi, lo) site is two such f16 tensors, lo site_bytes / 2 behind hi.
+// site_bytes = boards the buffer holds * hw * channels * 4, whatever the element.
+enum class TapFormat : int { f32 = 0, f16 = 1, split16 = 2, bf16 = 3 };
+struct TapOut {
+    unsigned char *base = nullptr;  // nullptr: no taps (the product instance runs)
+    size_t site_bytes = 0;
+};
+// The device side: every tower template has a compile-time tap mode (`TAP` as the last template argument of kz_tower_resident and
+// kz_tower_resident_split, Prof::taps of kz_tower_resident_f32; the plain tower only: no heads, no decode), and behind the LDS
+// store of its one epilogue stands `if constexpr (TAP) tap_put(a, site, live, element, v)`: in a tap instance the four elements
+// that went to the LDS image go to the site's tensor as well — site 0 the stem, then the 2 * depth convolutions in order, the
+// last one behind the final BN; `element` = tap_elem(...): row * channels + the lane's first channel; `live`: the row belongs to
+// a real board; `behind`: bytes from the tensor's start (tap_pair: the lo tensor of a pair).  A product instance discards the
+// statement and compiles to the code it was.  `a` is the kernel's argument struct, where the buffer's two words (tap_base,
+// tap_site_bytes) share the words of the heads' two outputs — a tap instance has no heads —, so no product instance's argument moves.
+__device__ __forceinline__ size_t tap_elem(int board0, int hw, int row, int channels, int channel) {
+    return ((size_t)board0 * hw + row) * channels + channel;
+}
+template <class A, class V4>
+__device__ __forceinline__ void tap_put(const A &a, int site, bool live, size_t element, V4 v, size_t behind = 0) {
+    if (live) *reinterpret_cast<V4 *>(a.tap_base + (size_t)site * a.tap_site_bytes + behind + element * (sizeof(V4) / 4)) = v;
+}
+template <class A, class V4>
+__device__ __forceinline__ void tap_pair(const A &a, int site, bool live, size_t element, V4 hi, V4 lo) {
+    tap_put(a, site, live, element, hi);
+    tap_put(a, site, live, element, lo, a.tap_site_bytes / 2);
+}
+// kz_tower.hip's rows: lane row fr of pixel tile mt is pixel 16 mt + fr of the workgroup's one board, or with line tiles (two
+// boards) pixel 8 mt + (fr & 7) of board fr >> 3, which counts only if the batch has it
+template <bool LINE_TILES>
+__device__ __forceinline__ bool tap_chess_live(int board0, int fr, int batch) { return board0 + (LINE_TILES ? fr >> 3 : 0) < batch; }
+template <bool LINE_TILES>
+__device__ __forceinline__ size_t tap_chess_row(int board0, int fr, int mt) {
+    return (size_t)board0 * 64 + (LINE_TILES ? (fr >> 3) * 64 + mt * 8 + (fr & 7) : mt * 16 + fr);
+}
+// One record per site (kz_tower_taps.hip: kz_tap_deviation ADDS to it — zero it first): a = the tap's value ((float)hi +
+// (float)lo for a pair), r = the exact-f32 reference's; the maxima as the bit patterns of non-negative f64 values (a - r taken
+// in f64), the sums in f64; an element where a or r is not finite counts in `nonfinite` and nowhere else.  Field for field
+// kz_site_error (include/kz_hip.h).
+struct TapDeviation {
+    unsigned long long max_abs_err_bits;
+    double sum_sq_err, sum_sq_ref;
+    unsigned long long max_abs_ref_bits, count, nonfinite;
+};
+// tap: `rows` rows of a site in `format` (row stride tap_ld elements, lo_bytes from hi to lo for a pair); ref: the same rows in
+// f32, row stride ref_ld floats (the per-layer engine's padded NHWC rows, or an f32 tap); the first `channels` of every row
+// are compared.  tap_ld and ref_ld are multiples of 8: every load is 16 bytes.
+void launch_tap_deviation(const void *tap, TapFormat format, size_t lo_bytes, int tap_ld, const float *ref, int ref_ld, size_t rows,
+                          int channels, TapDeviation *out, hipStream_t stream);
+
 // Implicit-GEMM convolution, kernel k in {1,3}, pad k/2, fused epilogue:
 //   v = acc + bias[oc];  if (relu) v = max(v, 0);  if (res) v += res[row][oc];
 //   if (post_scale) v = v * post_scale[oc] + post_shift[oc];  y[row][oc] = v
@@ -364,6 +417,11 @@ struct Tower32Args {
                           // (site, board), [1 + 2*depth][ldy] with ldy counted in boards (>= batch)
     unsigned long long *hist = nullptr;  // with profile: the range histogram's instance instead — `y` is not written, and
                           // hist [1 + 2*depth][RANGE_BINS] (device memory) is ADDED to with integer atomics
+    // all four launchers: taps.base set — the tap instance of the plain tower (heads.kind must be none; `y` is written as the
+    // product instance writes it).  tap_wide_batch (launch_tower_pairs / _bf16 with `wide`): the batch the tile rule is asked
+    // with instead of this launch's own — a tap runs the geometry of the engine's max_batch on however few boards
+    TapOut taps;
+    int tap_wide_batch = 0;
     // launch_tower32 only: the conv policy head (Conv1x1 C->C + ReLU in the weight stream as one more centre-tap layer,
     // then Conv1x1 C->pc, post_act.py:75-110) and the scalar head (post_act.py:8-31) in the same launch — the tower
     // output never leaves LDS and `y` is not written.  tower32_heads_supported says for which models.
@@ -496,6 +554,7 @@ struct TowerArgs {
     int epoch;
     DecodeArgs decode;    // fused heads only; set: decode_output inside the launch, scalars / policy are not written
     bool prev;            // experiment build only: the round-6 instance of the kernel (bit-identity reference)
+    TapOut taps;          // base set: the tap instance of the plain tower (fused_heads must be false; `y` is written as usual)
 };
 bool tower_resident_supported(int dtype, int h, int w, int channels, int depth, int c_in);
 bool tower_heads_supported(int policy_kind, int query_channels, int policy_len, int sh_channels, int sh_size);

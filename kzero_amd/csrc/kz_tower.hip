@@ -62,7 +62,7 @@ struct TowerDev {
     // fused heads
     const float *sh_w0, *sh_b0, *sh_w1, *sh_b1, *sh_w2, *sh_b2;
     const int32_t *att_idx;  // [1880]: (flat_to_att / 88) * 96 + flat_to_att % 88
-    float *scalars, *policy;
+    union { float *scalars; unsigned char *tap_base; }; union { float *policy; size_t tap_site_bytes; };  // (a tap instance — no heads — keeps its buffer in the heads' two output words: kz_kernels.hpp, tap_put)
     int *nonfinite_flag;  // range check (fused heads), see ScalarHeadArgs in kz_kernels.hpp
     int epoch;
     DecodeDev dec;        // dec.move_offsets set: values / probabilities of the available moves instead of scalars / policy
@@ -120,12 +120,12 @@ constexpr int SG_VALU = 0x2, SG_SALU = 0x4, SG_MFMA = 0x8, SG_VMEM_READ = 0x20, 
 // chunk count in the benchmark's instance cost 0.3 %)
 // PREV: the round-6 address arithmetic (per-lane 64-bit weight addresses with a clamp at the end of the stream, tap rows
 // through short-circuit conditions) and one LDS read per (tap, tile) fragment, in the same k-step order — instantiated
-// only in the experiment build, as the bit-identity reference
-template <int NB, bool HEADS, int PF, bool WIDE = false, bool PREV = false>
+// only in the experiment build, as the bit-identity reference.  TAP: the tap instance of the plain tower (kz_kernels.hpp, tap_put)
+template <int NB, bool HEADS, int PF, bool WIDE = false, bool PREV = false, bool TAP = false>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     using L = Layout<NB>;
     constexpr int M = L::M, MT = L::MT;
-    static_assert(PF <= TOWER_PF_MAX, "the refills past the end of the stream must land in its padding");
+    static_assert(PF <= TOWER_PF_MAX, "the refills past the end of the stream must land in its padding"); static_assert(!TAP || (!HEADS && !PREV), "the tap instances are the plain tower's");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
     const int tid = threadIdx.x;
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     // this lane's slice of the LDS image: its pixel row of tile 0, channels [64*wave + 4*kq, +4) of oc-tile 0
     const int epi_base = lane_row + (wave * 64 + kq * 4) * 2;
     // epilogue: [relu]; [+ residual X]; [final BN]; -> f16 -> LDS image at dst_off.  Flags are compile-time.
-    auto epilogue = [&](int dst_off, auto relu, auto residual, auto post) __attribute__((always_inline)) {
+    auto epilogue = [&](int dst_off, auto relu, auto residual, auto post, int site = 0) __attribute__((always_inline)) {
 #pragma unroll
         for (int nt = 0; nt < 4; nt++) {
             h16x4 rx[MT];
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
                     for (int j = 0; j < 4; j++) v[j] += (float)rx[mt][j];
                 }
                 if constexpr (decltype(post)::value) v = v * post_s[nt] + post_t[nt];
-                *reinterpret_cast<h16x4 *>(lds + dst_off + off) = to_h4(v);
+                *reinterpret_cast<h16x4 *>(lds + dst_off + off) = to_h4(v); if constexpr (TAP) tap_put(a, site, tap_chess_live<L::LINE_TILES>(board0, fr, a.batch), tap_chess_row<L::LINE_TILES>(board0, fr, mt) * C + wave * 64 + nt * 16 + kq * 4, to_h4(v));
             }
         }
     };
@@ -525,9 +525,9 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
             }
         }
         conv_3x3(is_b ? L::Y_OFF : L::X_OFF);
-        if (!is_b) epilogue(L::Y_OFF, YES, NO, NO);
-        else if (layer != layers) epilogue(L::X_OFF, YES, YES, NO);
-        else epilogue(L::X_OFF, YES, YES, YES);
+        if (!is_b) epilogue(L::Y_OFF, YES, NO, NO, layer);
+        else if (layer != layers) epilogue(L::X_OFF, YES, YES, NO, layer);
+        else epilogue(L::X_OFF, YES, YES, YES, layer);
         __syncthreads();
     }
 
@@ -818,6 +818,14 @@ void launch_instance(const TowerDev &d, int grid, int bytes, hipStream_t stream)
 template <bool PREV>
 void launch_chess(const TowerDev &d, const TowerArgs &t, hipStream_t stream) {
     const bool heads = t.fused_heads;
+    if constexpr (!PREV) {
+        if (t.taps.base && !heads) {  // the tap instances: the plain tower of the same geometry (d.tap_base is set)
+            if (t.cin_p > 32) launch_instance<kz_tower_resident<2, false, PF_NB2, true, false, true>>(d, (t.batch + 1) / 2, Layout<2>::BYTES, stream);
+            else if (t.boards_per_wg == 1) launch_instance<kz_tower_resident<1, false, PF_NB1, false, false, true>>(d, t.batch, Layout<1>::BYTES, stream);
+            else launch_instance<kz_tower_resident<2, false, PF_NB2, false, false, true>>(d, (t.batch + 1) / 2, Layout<2>::BYTES, stream);
+            return;
+        }
+    }
     if (t.cin_p > 32) {  // (ChessHistoryMapper: 34 / 47 / 60 planes; always two boards per workgroup)
         const int grid = (t.batch + 1) / 2;
         if (heads) launch_instance<kz_tower_resident<2, true, PF_NB2, true, PREV>>(d, grid, Layout<2>::BYTES, stream);
@@ -853,6 +861,10 @@ void launch_tower_resident(const TowerArgs &t, hipStream_t stream) {
     d.nonfinite_flag = t.nonfinite_flag;
     d.epoch = t.epoch;
     d.dec = decode_dev(t.decode, t.fused_heads, POLICY);
+    if (t.taps.base && !t.fused_heads) {  // (with the heads inside there is no tap instance: the product instance runs)
+        d.tap_base = t.taps.base;
+        d.tap_site_bytes = t.taps.site_bytes;
+    }
 #ifdef KZ_EXPERIMENTS
     if (t.prev) return launch_chess<true>(d, t, stream);  // (the round-6 instances: tests/test_tower_overlap.py)
 #endif

@@ -71,7 +71,7 @@ struct TowerF32Dev {
     int hc, hs, pc, policy_len, zero_tail, extra, epoch;
     const float *sh_b0, *sh_w1t, *sh_b1, *sh_w2, *sh_b2, *p_b1, *pe_bc, *pe_wl, *pe_bl;
     const f32x4 *small_w;  // tower32_pack_small_weights: [over x: scalar-head conv rows, extra-move conv row][over hidden: policy conv]
-    float *scalars, *policy;
+    union { float *scalars; unsigned char *tap_base; }; union { float *policy; size_t tap_site_bytes; };  // (a tap instance — no heads — keeps its buffer in the heads' two output words: kz_kernels.hpp, tap_put)
     int *nonfinite_flag;
     DecodeDev dec;  // dec.move_offsets set: decode_output inside the launch (policy must be device memory then)
     unsigned long long *stamps;  // (diagnostic build)
@@ -89,7 +89,7 @@ struct TowerF32Dev {
 // workgroup's real boards (range_bin) into LDS histograms private to the wave — HSUB copies, chosen by lane: a wave's values
 // sit in a handful of bins, and 64 lanes on one LDS word would queue 64 deep —, and each wave adds its non-empty bins to
 // a.hist[site] once per site, with integer atomics whose result nobody reads: no barrier, no order between workgroups.
-enum class Prof { none, max, histogram };
+enum class Prof { none, max, histogram, taps };  // taps: the tap instance of the plain tower (kz_kernels.hpp, tap_put), f32 rows; a.y is not written
 constexpr int HSUB = 8, HSTRIDE = RANGE_BINS + 1;  // (97 words: the copies of one bin lie in different banks)
 constexpr int profile_lds(Prof p, int nt) { return p == Prof::max ? 2 * 4 * nt * 16 * 4 : p == Prof::histogram ? 4 * HSUB * HSTRIDE * 4 : 0; }
 
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
 #pragma unroll
     for (int nt = 0; nt < NT; nt++) cmask |= (unsigned)(nt * 16 + fr < rows_valid) << nt;
     unsigned *const hcopy = hmine + (lane & (HSUB - 1)) * HSTRIDE;
-    auto epilogue = [&](bool relu, bool residual, bool post) {
+    auto epilogue = [&](bool relu, bool residual, bool post, int site = 0) {
         if constexpr (PROFILE == Prof::max) {
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) rowmax[nt] = 0;
@@ -229,7 +229,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
                 }
                 if (residual) v += *slot;  // x + relu(bn(conv(.))) (post_act.py:227-228)
                 if (post) v = v * ps + pt;
-                *slot = v;
+                *slot = v; if constexpr (PROFILE == Prof::taps) tap_put(a, site, (cmask >> nt) & 1, tap_elem(board0, a.hw, nt * 16 + fr, C, oc), v);
                 if constexpr (PROFILE == Prof::max) {
 #pragma unroll
                     for (int j = 0; j < 4; j++) rowmax[nt] = max(rowmax[nt], __float_as_uint(v[j]) & 0x7fffffffu);
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_f32(TowerF32Dev a) {
         }
         KZ_STAMP(3 * layer);
         const bool second = (layer & 1) == 0;  // the block's second conv: residual add, and the final BN on the last
-        epilogue(true, second, second && layer == 2 * a.depth);
+        epilogue(true, second, second && layer == 2 * a.depth, layer);
         if constexpr (PROFILE == Prof::max) profile_rows(layer);
         if constexpr (PROFILE == Prof::histogram) profile_flush(layer);
         KZ_STAMP(3 * layer + 1);
@@ -646,11 +646,17 @@ bool launch_tower32(const Tower32Args &t, hipStream_t stream, int *nt_out) {
     d.stamps = nullptr;
     d.scalars = hd.scalars; d.policy = hd.policy; d.nonfinite_flag = hd.nonfinite_flag;
     d.dec = decode_dev(hd.decode, hd.kind != Kind::none, hd.policy_len);
+    if (t.taps.base && hd.kind == Kind::none) {  // (a tap instance is the plain tower's)
+        d.tap_base = t.taps.base;
+        d.tap_site_bytes = t.taps.site_bytes;
+    }
     const int grid = (t.batch + d.nb - 1) / d.nb;
     const auto rows = std::make_index_sequence<std::size(F32_ROWS)>{};
     // the range histogram's instances: no heads, hist += the counts [site][bin]; the range profile's: y = the maxima [site][ldy boards]
     if (t.profile && t.hist) return launch_row<false, Prof::histogram>(rows, t.channels, nt, d, grid, stream);
     if (t.profile) return launch_row<false, Prof::max>(rows, t.channels, nt, d, grid, stream);
+    // the tap instances: the plain tower, every site's tensor to t.taps
+    if (t.taps.base) return hd.kind == Kind::none && !t.dense3 && launch_row<false, Prof::taps>(rows, t.channels, nt, d, grid, stream);
     if (hd.kind == Kind::attention) return false;  // (the attention heads are the split launch's)
     const bool heads = hd.kind == Kind::conv;
 #ifdef KZ_EXPERIMENTS

@@ -136,7 +136,7 @@ struct SplitDev {
     const float *sh_w1t, *p_b1, *pe_bc, *pe_wl, *pe_bl;
     const f32x4 *small_w;
     const uint4 *small_w16;  // plain f16: the two small convolutions as f16 fragments (tower_split_pack_small_weights16)
-    float *scalars, *policy;
+    union { float *scalars; unsigned char *tap_base; }; union { float *policy; size_t tap_site_bytes; };  // (a tap instance — no heads — keeps its buffer in the heads' two output words: kz_kernels.hpp, tap_put)
     int *nonfinite_flag;
     int epoch;
     DecodeDev dec;  // dec.move_offsets set (fused heads only): decode_output inside the launch
@@ -162,12 +162,12 @@ __device__ __forceinline__ f32x4 mfma_16x16x32(V8 a, V8 b, f32x4 c) {
 
 // HEADS: 0 = the tower alone; 1 = + the chess attention network's heads; 2 = + conv policy heads and the scalar head
 // BF: the plain arithmetic (SPLIT = false) on bf16 elements — the images, the weight fragments and the MFMA — with the split
-// launch's f32 tensors in and out
-template <int C, int NT, bool SPLIT, int HEADS = 0, bool BF = false>
+// launch's f32 tensors in and out.  TAP: the tap instance of the plain tower (kz_kernels.hpp, tap_put): every site in its element, the last one as the launch hands it on
+template <int C, int NT, bool SPLIT, int HEADS = 0, bool BF = false, bool TAP = false>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
     static_assert(HEADS != 1 || (C == 256 && NT == 4 && SPLIT), "attention heads: the chess network in split arithmetic");
     static_assert(HEADS != 2 || C == 256 || C == 128, "conv heads: a channel count of kz_tower_f32.hip");
-    static_assert(!(BF && SPLIT), "bf16 is a plain arithmetic: one image per activation");
+    static_assert(!(BF && SPLIT), "bf16 is a plain arithmetic: one image per activation"); static_assert(!TAP || HEADS == 0, "the tap instances are the plain tower's");
     using E = std::conditional_t<BF, __bf16, h16>;  // the element of an image and of a weight fragment
     using e16x8 = E __attribute__((ext_vector_type(8)));
     using e16x4 = E __attribute__((ext_vector_type(4)));
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
         else return epi_base + nt * 16 * RS + ot * 32;
     };
     // epilogue: [relu]; [+ residual X]; -> (hi, lo) -> the image pair at dst_h
-    auto epilogue = [&](int dst_h, bool relu, bool residual) __attribute__((always_inline)) {
+    auto epilogue = [&](int dst_h, bool relu, bool residual, int site = 0) __attribute__((always_inline)) {
 #pragma unroll
         for (int ot = 0; ot < OT; ot++)
 #pragma unroll
@@ -372,9 +372,9 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
                     e16x4 hi, lo;
                     split4<E>(v, hi, lo);
                     *reinterpret_cast<e16x4 *>(lds + dst_h + off) = hi;
-                    *reinterpret_cast<e16x4 *>(lds + dst_h + DELTA + off) = lo;
+                    *reinterpret_cast<e16x4 *>(lds + dst_h + DELTA + off) = lo; if constexpr (TAP) tap_pair(a, site, nt * 16 + fr < rows_valid, tap_elem(board0, a.hw, nt * 16 + fr, C, (wave * OT + ot) * 16 + kq * 4), hi, lo);
                 } else {
-                    *reinterpret_cast<e16x4 *>(lds + dst_h + off) = e16x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]};
+                    *reinterpret_cast<e16x4 *>(lds + dst_h + off) = e16x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]}; if constexpr (TAP) tap_put(a, site, nt * 16 + fr < rows_valid, tap_elem(board0, a.hw, nt * 16 + fr, C, (wave * OT + ot) * 16 + kq * 4), e16x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]});
                 }
             }
     };
@@ -452,9 +452,9 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
         fetch_bias(layer + 1);
         conv_3x3(is_b ? YH : XH);
         if (!is_b) {
-            epilogue(YH, true, false);
+            epilogue(YH, true, false, layer);
         } else if (layer != layers) {
-            epilogue(XH, true, true);
+            epilogue(XH, true, true, layer);
         } else {
             // last layer: ReLU, residual, final BN -> f32 rows of the tower output in global memory
 #pragma unroll
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
                     }
                     const int r = nt * 16 + fr;
                     const size_t o = ((size_t)board0 * a.hw + r) * a.ldy + oc;
-                    if (r < rows_valid) {
+                    if (r < rows_valid) {  if constexpr (TAP) { if constexpr (F32_IO) tap_put(a, layers, true, tap_elem(board0, a.hw, r, C, oc), v); else tap_put(a, layers, true, tap_elem(board0, a.hw, r, C, oc), e16x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]}); }  // (the last site: what the launch hands on)
                         if constexpr (F32_IO) *reinterpret_cast<f32x4 *>(static_cast<float *>(a.y) + o) = v;
                         else *reinterpret_cast<e16x4 *>(static_cast<h16 *>(a.y) + o) = e16x4{(E)v[0], (E)v[1], (E)v[2], (E)v[3]};
                     }
@@ -853,7 +853,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_split(SplitDev a) {
 #endif
 
 // BF (with SPLIT = false): the bf16 instances — the plain-f16 instance's LDS, conv heads' tail scratch included
-template <int C, int NT, bool SPLIT, int HEADS = 0, bool BF = false>
+template <int C, int NT, bool SPLIT, int HEADS = 0, bool BF = false, bool TAP = false>
 void launch(const SplitDev &d, int grid, hipStream_t stream) {
     // (the conv heads' tail: the split launch wants the two images as f32 rows; the plain-f16 launch the tail's scratch,
     // F16_TAIL_SCRATCH_BYTES, behind its own images)
@@ -861,8 +861,8 @@ void launch(const SplitDev &d, int grid, hipStream_t stream) {
     static_assert(OWN == pairs_own_lds_bytes(C, NT, SPLIT), "the host's restatement of the LDS geometry");
     constexpr int LDS = HEADS != 2 ? OWN : !SPLIT ? OWN + pairs_f16_tail_scratch_bytes(C, NT) : F32_IMAGES > OWN ? F32_IMAGES : OWN;
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    allow_dynamic_lds<kz_tower_resident_split<C, NT, SPLIT, HEADS, BF>>(LDS);
-    kz_tower_resident_split<C, NT, SPLIT, HEADS, BF><<<grid, 256, LDS, stream>>>(d);
+    allow_dynamic_lds<kz_tower_resident_split<C, NT, SPLIT, HEADS, BF, TAP>>(LDS);
+    kz_tower_resident_split<C, NT, SPLIT, HEADS, BF, TAP><<<grid, 256, LDS, stream>>>(d);
 }
 
 
@@ -886,7 +886,8 @@ inline SplitDev make_split_dev(const Tower32Args &t, bool split, int &nt, int &g
     d.w_ = t.w;
     d.hw = t.h * t.w;
     d.stem_chunks = (t.c_in + 31) / 32;
-    nt = pairs_tiles(d.hw, t.channels, split, t.wide ? t.batch : 0);
+    // (a tap launch asks the tile rule with the engine's max_batch: the geometry of a full batch on however few boards)
+    nt = pairs_tiles(d.hw, t.channels, split, t.wide ? (t.taps.base && t.tap_wide_batch ? t.tap_wide_batch : t.batch) : 0);
     if (!nt) return d;  // (no instance takes this shape: nothing to size)
     d.nb = nt * 16 / d.hw;
     d.inv_w = (65536u + (unsigned)t.w - 1) / (unsigned)t.w;
@@ -913,11 +914,12 @@ inline SplitDev make_split_dev(const Tower32Args &t, bool split, int &nt, int &g
 // The instance of (channels, nt) among ROWS (kz_tower_pairs_shapes.hpp), with the conv heads' tail if asked for: the row that
 // matches supplies the template arguments, and no row = no launch (false)
 template <const auto &ROWS, bool SPLIT, bool BF, size_t... I>
-bool launch_row(std::index_sequence<I...>, int channels, int nt, bool conv_heads, const SplitDev &d, int grid, hipStream_t stream) {
+bool launch_row(std::index_sequence<I...>, int channels, int nt, bool conv_heads, bool tap, const SplitDev &d, int grid, hipStream_t stream) {
     return (... || [&] {
         constexpr PairsRow R = ROWS[I];
         if (R.c != channels || R.nt != nt) return false;
-        if (!conv_heads) launch<R.c, R.nt, SPLIT, 0, BF>(d, grid, stream);
+        if (!conv_heads && tap) launch<R.c, R.nt, SPLIT, 0, BF, true>(d, grid, stream);  // (every row has its tap instance)
+        else if (!conv_heads) launch<R.c, R.nt, SPLIT, 0, BF>(d, grid, stream);
         else if constexpr (R.conv_heads) launch<R.c, R.nt, SPLIT, 2, BF>(d, grid, stream);
         return !conv_heads || R.conv_heads;
     }());
@@ -929,9 +931,15 @@ template <bool SPLIT, bool BF = false>
 bool launch_pairs(const Tower32Args &t, hipStream_t stream, int *nt_out) {
     using Kind = Tower32Args::Heads::Kind;
     int nt = 0, grid = 0;
-    const SplitDev d = make_split_dev(t, SPLIT, nt, grid);
+    SplitDev d = make_split_dev(t, SPLIT, nt, grid);
     if (nt_out) *nt_out = nt;
     if (!nt) return false;
+    const bool tap = t.taps.base != nullptr;
+    if (tap) {  // (a tap instance is the plain tower's)
+        if (t.heads.kind != Kind::none) return false;
+        d.tap_base = t.taps.base;
+        d.tap_site_bytes = t.taps.site_bytes;
+    }
     if (t.heads.kind == Kind::attention) {  // the chess attention network (the engine asked tower_split_heads_supported)
         if constexpr (SPLIT) {
             if (t.channels != SPLIT_ATTENTION.c || nt != SPLIT_ATTENTION.nt) return false;
@@ -942,15 +950,15 @@ bool launch_pairs(const Tower32Args &t, hipStream_t stream, int *nt_out) {
     }
 #ifdef KZ_EXPERIMENTS
     if constexpr (!BF) {
-        if (t.heads.kind == Kind::none && split_uses_32x32(t.channels, nt, SPLIT)) {
+        if (t.heads.kind == Kind::none && !tap && split_uses_32x32(t.channels, nt, SPLIT)) {
             launch32<SPLIT>(d, grid, stream);
             return true;
         }
     }
 #endif
     const bool conv_heads = t.heads.kind == Kind::conv;  // "...+heads" (the engine asked tower_split_conv_heads_supported)
-    if constexpr (SPLIT) return launch_row<SPLIT_ROWS, true, false>(std::make_index_sequence<std::size(SPLIT_ROWS)>{}, t.channels, nt, conv_heads, d, grid, stream);
-    else return launch_row<PLAIN_ROWS, false, BF>(std::make_index_sequence<std::size(PLAIN_ROWS)>{}, t.channels, nt, conv_heads, d, grid, stream);
+    if constexpr (SPLIT) return launch_row<SPLIT_ROWS, true, false>(std::make_index_sequence<std::size(SPLIT_ROWS)>{}, t.channels, nt, conv_heads, tap, d, grid, stream);
+    else return launch_row<PLAIN_ROWS, false, BF>(std::make_index_sequence<std::size(PLAIN_ROWS)>{}, t.channels, nt, conv_heads, tap, d, grid, stream);
 }
 
 }  // namespace

@@ -125,6 +125,11 @@ extern "C" {
     // the range histogram: binade counts of every stored tower tensor, hist_out u64 [n_sites][KZ_RANGE_BINS]
     fn kz_model_range_histogram(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, hist_out: *mut c_void) -> c_int;
     fn kz_model_range_histogram_fast(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, hist_out: *mut c_void) -> c_int;
+    // tower taps and error profile: what the one-launch tower of (max_batch, dtype) stores at every range site, and its
+    // deviation from exact f32 per site, out KzSiteError [n_sites]
+    fn kz_model_tower_taps_path(model: *const c_void, max_batch: c_int, dtype: c_int, buf: *mut c_char, len: usize) -> c_int;
+    fn kz_model_tower_taps(model: *const c_void, device: c_int, max_batch: c_int, dtype: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, site_first: c_int, n_sites: c_int, out: *mut f32) -> c_int;
+    fn kz_model_error_profile(model: *const c_void, device: c_int, max_batch: c_int, dtype: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, out: *mut c_void) -> c_int;
     fn kz_engine_max_batch(engine: *const c_void) -> c_int;
     fn kz_engine_eval_dense(engine: *mut c_void, input_nchw: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
     fn kz_engine_eval_packed(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
@@ -369,6 +374,37 @@ impl HipModel {
         hist
     }
 
+    /// The kernel a tap call runs: `kz_model_plan(max_batch, dtype)`'s tower without "+heads" (`kz_model_tower_taps_path`; no GPU).
+    pub fn tower_taps_path(&self, max_batch: usize, dtype: i32) -> String {
+        let mut buf = [0 as c_char; 64];
+        check(unsafe { kz_model_tower_taps_path(self.ptr, max_batch as c_int, dtype as c_int, buf.as_mut_ptr(), buf.len()) });
+        unsafe { CStr::from_ptr(buf.as_ptr()) }.to_string_lossy().into_owned()
+    }
+
+    /// What the one-launch tower of an engine of (max_batch, dtype) stores at the range sites `site_first .. site_first + n_sites`
+    /// on these packed boards, as the kernel rounds it (`kz_model_tower_taps`): f32 `[n_sites][batch][C][H][W]` flat.
+    pub fn tower_taps(&self, device: HipDevice, max_batch: usize, dtype: i32, bits: &[u8], bits_stride: usize, scalars_in: &[f32], batch: usize, site_first: usize, n_sites: usize) -> Vec<f32> {
+        assert!(bits.len() >= batch * bits_stride && scalars_in.len() >= batch * self.info.input_scalar_channels.max(0) as usize);
+        let per_site = batch * self.info.tower_channels as usize * self.info.board_h as usize * self.info.board_w as usize;
+        let mut out = vec![0f32; n_sites * per_site];
+        check(unsafe {
+            kz_model_tower_taps(self.ptr, device.0 as c_int, max_batch as c_int, dtype as c_int, bits.as_ptr(), bits_stride, scalars_in.as_ptr(), batch as c_int, site_first as c_int, n_sites as c_int, out.as_mut_ptr())
+        });
+        out
+    }
+
+    /// Per range site, how far that tower's stored tensors are from exact f32 on these boards (`kz_model_error_profile`).
+    pub fn error_profile(&self, device: HipDevice, max_batch: usize, dtype: i32, bits: &[u8], bits_stride: usize, scalars_in: &[f32], batch: usize) -> Vec<KzSiteError> {
+        let mut n = 0;
+        check(unsafe { kz_model_range_sites(self.ptr, &mut n) });
+        assert!(bits.len() >= batch * bits_stride && scalars_in.len() >= batch * self.info.input_scalar_channels.max(0) as usize);
+        let mut out = vec![KzSiteError::default(); n as usize];
+        check(unsafe {
+            kz_model_error_profile(self.ptr, device.0 as c_int, max_batch as c_int, dtype as c_int, bits.as_ptr(), bits_stride, scalars_in.as_ptr(), batch as c_int, out.as_mut_ptr() as *mut c_void)
+        });
+        out
+    }
+
     /// Where `range_profile_fast` runs: "tower_resident_f32" or "conv_igemm_f32" (`kz_model_range_profile_fast_path`; no GPU).
     pub fn range_profile_fast_path(&self) -> String {
         let mut buf = [0 as c_char; 32];
@@ -479,6 +515,18 @@ impl PositionSample {
         }
         snap
     }
+}
+
+/// `kz_site_error` (include/kz_hip.h): one range site of `HipModel::error_profile`, 48 bytes.
+#[repr(C)]
+#[derive(Debug, Default, Copy, Clone, PartialEq)]
+pub struct KzSiteError {
+    pub max_abs_err: f64,
+    pub sum_sq_err: f64,
+    pub sum_sq_ref: f64,
+    pub max_abs_ref: f64,
+    pub count: u64,
+    pub nonfinite: u64,
 }
 
 /// The bins of `HipModel::range_histogram` (include/kz_hip.h): 0 is +-0, 95 inf or NaN, b in 1..=94 the binade E = b - 51
