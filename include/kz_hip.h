@@ -57,6 +57,25 @@ extern "C" {
                            kz_engine_create fails, and kz_model_supports_dtype says 0, for Go 19x19 and any other shape
                            that runs per layer, AttentionTower networks, DenseNetworks and a tower without blocks.
                            Everything outside the tower is the KZ_DTYPE_F32 path */
+#define KZ_DTYPE_INT8 4 /* f16 tensors at every boundary — the f16 engine with the tower's launch exchanged —, the tower's block
+                           convolutions on the i8 matrix cores (v_mfma_i32_16x16x64_i8: the f16 instruction's 16 bytes per
+                           lane, twice its k): int8 activations and weights, exact i32 sums, one power-of-two scale per range
+                           site and per (block convolution, output channel).  Only a CALIBRATED model runs it
+                           (kz_model_quantize_int8 below, which also states the arithmetic to the bit).  The stem and the
+                           residual stream stay f16 (RANGE: the +-65504 limit and the non-finite check of KZ_DTYPE_F16,
+                           unchanged; saturation of a quantised image at +-127 steps is silent by design), bias, ReLU,
+                           residual add and the final BN are f32.  PRECISION: 7 bits and a sign per stored activation where
+                           f16 has 11 (README, "which number is which arithmetic"; kz_engine_set_audit measures it on a
+                           network's own positions).  One launch for the tower ("tower_resident_i8"; no "+heads": the f16
+                           engine's head kernels follow it) at 256 tower channels on <= 64 squares (two 8x8 boards per
+                           workgroup when max_batch gives 128 such workgroups) and 128 channels on <= 96 squares; a
+                           channel count in between runs widened to the next multiple of 64, as above: 193 .. 255 as 256,
+                           65 .. 127 as 128.  64 channels or fewer, 129 .. 192 and more than 256 have no int8 kernel.  kz_engine_create fails, and kz_model_supports_dtype says 0, for
+                           an uncalibrated model, every other shape, AttentionTower networks, DenseNetworks and a tower
+                           without blocks; the message says whether the calibration or the kernel is missing, and to a model
+                           that carries no calibration dtype 4 is, first of all, an unknown dtype.  It reads
+                           none of the environment switches.  kz_model_tower_taps, _taps_path and kz_model_error_profile
+                           refuse it */
 
 #define KZ_POLICY_ATAXX_CONV 0 /* AtaxxConvPolicyHead, python/lib/model/post_act.py:91-112 */
 #define KZ_POLICY_CONV 1       /* ConvPolicyHead,      post_act.py:54-88 */
@@ -354,6 +373,31 @@ int kz_engine_audit_stats(kz_engine *engine, void *out, int reset);
  * (1e-4 relative).  kz_model_range_profile_fast_path writes which of the two it is, "tower_resident_f32" or "conv_igemm_f32"
  * (buf of at least 24 bytes), without touching a GPU; it fails where the profile fails. */
 int kz_model_stream_shift(const kz_model *model, int k, kz_model **out);
+
+/* ---- int8 calibration: what KZ_DTYPE_INT8 needs of a model ----
+ * kz_model_quantize_int8(model, site_max, n_sites, &out) returns a new immutable model, independent of `model` and freed with
+ * kz_model_free, whose f32 tensors and descriptor are the source's bit for bit — every other dtype's engines of it return what
+ * they return on the source — with a calibration beside them: site_max [n_sites] is max |x| of every range site on the caller's
+ * positions (kz_model_range_profile_fast's site_max_out, times any headroom), in the sites' order.  No GPU is touched, and the
+ * calibration lives in memory only: the .kzm container does not change.  The arithmetic of an engine of dtype 4 on the result,
+ * every scale a power of two (exact to apply), the roundings exactly these:
+ *   activation exponent of site s:  e_s = ceil(log2(site_max[s] / 127)); a quantised image holds
+ *     q = clamp(rne(v * 2^-e_s), -127, 127) as int8, rne to nearest even; -128 is never produced
+ *   weight exponent per (block convolution, output channel), on the folded Conv+BN weights:
+ *     f = ceil(log2(max |w[oc,:,:,:]| / 127)), wq = rne(w * 2^-f); an all-zero filter has f = 0
+ *   a block convolution, per output element: acc = the i32 sum of wq * q over 9 taps x C (exact); t = (float)acc (nearest even);
+ *     v = t * 2^(e_in + f_oc) + bias[oc] (one rounding); ReLU
+ *   conv A stores quant(v, e_mid).  Conv B adds the f16 stream x to v in f32, after the ReLU, then stores x = f16(v) and
+ *     quant(v, e_next), both from the same f32 v.  The stem is the f16 engine's and stores f16(v) and quant(v, e_0).  The last
+ *     layer: ReLU, residual add, final BN in f32, f16 rows out — the last range site is not quantised, and its site_max entry
+ *     is accepted and ignored.
+ * Fails, with a message of its own each: a null argument, n_sites != kz_model_range_sites, an entry among the first n_sites - 1
+ * that is not finite or not > 0 (or whose exponent is beyond +-64), an AttentionTower network, a DenseNetwork, a tower without
+ * blocks, a model that is calibrated already.  kz_model_stream_shift refuses a calibrated model: shift first, then calibrate.
+ * kz_model_int8_site_exponents writes e_s of the n_sites - 1 quantised sites; it fails on a model that is not calibrated. */
+int kz_model_quantize_int8(const kz_model *model, const float *site_max, int n_sites, kz_model **out);
+int kz_model_int8_site_exponents(const kz_model *model, int *exp_out /* [n_sites - 1], 32-bit */);
+
 int kz_model_range_sites(const kz_model *model, int *n_sites);
 int kz_model_range_site_name(const kz_model *model, int site, char *buf, size_t len);
 int kz_model_range_profile(const kz_model *model, int device, const uint8_t *bits, size_t bits_stride, const float *scalars_in,

@@ -15,6 +15,7 @@ KZ_DTYPE_F32 = 0
 KZ_DTYPE_F16 = 1
 KZ_DTYPE_F32_SPLIT16 = 2
 KZ_DTYPE_BF16 = 3  # f32 tensors, the tower in bf16 (f32 range at the f16 rate, 8 significant bits)
+KZ_DTYPE_INT8 = 4  # f16 tensors, the tower's block convolutions on the i8 matrix cores: a calibrated model only (Model.quantize_int8)
 KZ_ENGINE_SLOTS = 4
 # per-board status bits (kz_engine_wait_decoded_status / kz_engine_eval_packed_decoded_status)
 KZ_BOARD_OK = 0
@@ -104,6 +105,8 @@ SIGNATURES = {
     "kz_model_supports_dtype": (C.c_int, [C.c_void_p, C.c_int]),
     "kz_model_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "kz_model_stream_shift": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "kz_model_quantize_int8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
+    "kz_model_int8_site_exponents": (C.c_int, [C.c_void_p, C.c_void_p]),
     "kz_model_range_sites": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "kz_model_range_site_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_size_t]),
     "kz_model_range_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
@@ -301,6 +304,22 @@ class Model:
         check(load().kz_model_stream_shift(self._h, int(k), C.byref(out)))
         return Model._adopt(out)
 
+    def quantize_int8(self, site_max) -> "Model":
+        """The same network with an int8 calibration beside it (kz_model_quantize_int8): a new Model, the only kind an engine of
+        KZ_DTYPE_INT8 takes.  site_max: max |x| per range site, in range_sites' order (range_profile_fast's, times any headroom);
+        the last entry is accepted and ignored."""
+        site_max = np.ascontiguousarray(site_max, dtype=np.float32)
+        out = C.c_void_p()
+        check(load().kz_model_quantize_int8(self._h, site_max.ctypes.data, int(site_max.size), C.byref(out)))
+        return Model._adopt(out)
+
+    def int8_site_exponents(self) -> np.ndarray:
+        """e_s = ceil(log2(site_max[s] / 127)) of every quantised range site — all but the last — of a calibrated model
+        (kz_model_int8_site_exponents): int32 [n_sites - 1]."""
+        exp = np.zeros(max(2 * self.info.tower_depth, 1), np.int32)
+        check(load().kz_model_int8_site_exponents(self._h, exp.ctypes.data))
+        return exp[:2 * self.info.tower_depth]
+
     def range_sites(self):
         """The names of the range profile's sites, in order (kz_model_range_sites / kz_model_range_site_name)."""
         n = C.c_int()
@@ -411,6 +430,13 @@ class Model:
             self.close()
         except Exception:
             pass
+
+
+def calibrate_int8(model: Model, device: int, bits: np.ndarray, scalars_in: np.ndarray, headroom: float = 1.0) -> Model:
+    """`model` calibrated for KZ_DTYPE_INT8 on these positions: range_profile_fast, then quantize_int8 with site_max x headroom.
+    headroom 1 fits the profiled positions exactly; positions not yet seen can be larger, and what exceeds +-127 steps saturates."""
+    site_max, _ = model.range_profile_fast(device, bits, scalars_in)
+    return model.quantize_int8(site_max.astype(np.float64) * float(headroom))
 
 
 def auto_stream_shift(model: Model, device: int, bits: np.ndarray, scalars_in: np.ndarray, headroom_bits: int = 2):

@@ -55,9 +55,12 @@ struct DeviceWeights {
     // every tower but the dense network: the final BatchNorm, [round_up(C, 32)]
     float *post_scale = nullptr, *post_shift = nullptr;
     // the one-launch ResTowers.  resident_f32, resident_split16, resident_f16g, resident_bf16g: w32 and bias (and small where
-    // the stream carries the conv heads); resident_f16: w_stem, w_tower and bias; att_idx where it carries the attention heads
+    // the stream carries the conv heads); resident_f16: w_stem, w_tower and bias; att_idx where it carries the attention heads;
+    // resident_i8: w32, bias, mult and qscale
     struct {
-        void *w32 = nullptr;  // one packed weight stream: exact f32, split f16 pairs, plain f16 or bf16
+        void *w32 = nullptr;  // one packed weight stream: exact f32, split f16 pairs, plain f16 or bf16; f16 stem + int8 blocks
+        float *mult = nullptr;    // resident_i8: [1 + 2·depth][C], 2^(e_in + f_oc) per block convolution and output channel
+        float *qscale = nullptr;  // resident_i8: [2·depth], 2^-e_s per quantised range site
         void *w_stem = nullptr, *w_tower = nullptr;
         float *bias = nullptr;  // [1 + 2·depth (+ head rows)][C]
         float *small = nullptr;  // the fused conv heads' small 1x1 convolutions (tower32_pack_small_weights, or in f16)
@@ -296,6 +299,36 @@ struct DeviceWeights {
         }
         st.take(std::move(packed), &res.w32);
     }
+    // resident_i8 (a calibrated model: m.i8_exp): the stem's k-steps as f16 fragments, the block convolutions' as int8 fragments
+    // — 16 B per lane, 64 channels per k-step —, one f32 multiplier table beside the bias table.  The weight exponent of a
+    // (block convolution, output channel) is f = ceil(log2(max |w[oc]| / 127)) on the folded weights, wq = rne(w · 2^-f); an
+    // all-zero filter (a widened channel) gets f = 0.  Every scale is a power of two: exact to apply.
+    void pack_i8(const Model &m, Staged &st) {
+        const int C = m.channels, hw = m.h * m.w, layers = 2 * m.depth;
+        const size_t stem_bytes = kz::tower_split_stem_elems(C, m.c_in, false) * 2, layer_bytes = kz::tower_i8_layer_bytes(C);
+        std::vector<uint8_t> packed(stem_bytes + layer_bytes * layers);
+        kz::tower_split_pack_weights(m.tower[0].w.data(), C, m.c_in, hw, true, false, reinterpret_cast<uint16_t *>(packed.data()));
+        std::vector<float> mult((size_t)(1 + layers) * C, 1.0f), qscale(layers);
+        std::vector<int8_t> wq((size_t)C * C * 9);
+        for (int l = 1; l <= layers; l++) {
+            const std::vector<float> &w = m.tower[l].w;
+            const int e_in = m.i8_exp[l - 1];
+            for (int oc = 0; oc < C; oc++) {
+                const float *row = w.data() + (size_t)oc * C * 9;
+                float top = 0.0f;
+                for (int i = 0; i < C * 9; i++) top = std::max(top, std::fabs(row[i]));
+                const int f = top > 0.0f ? kz::i8_exponent(top) : 0;
+                for (int i = 0; i < C * 9; i++) wq[(size_t)oc * C * 9 + i] = (int8_t)std::nearbyint(std::ldexp((double)row[i], -f));
+                mult[(size_t)l * C + oc] = std::ldexp(1.0f, e_in + f);  // (|e_in| <= I8_EXP_MAX, f32 weights: a normal f32 or, far out, 0 / inf like the weight itself)
+            }
+            kz::tower_i8_pack_weights(wq.data(), C, reinterpret_cast<int8_t *>(packed.data() + stem_bytes + layer_bytes * (l - 1)));
+        }
+        for (int s = 0; s < layers; s++) qscale[s] = std::ldexp(1.0f, -m.i8_exp[s]);
+        put_bias_rows(m, 0, nullptr, st);
+        st.take(std::move(mult), &res.mult);
+        st.take(std::move(qscale), &res.qscale);
+        st.take(std::move(packed), &res.w32);
+    }
     // resident_f32.  (The conv policy head's first 1x1 conv rides at the end of the stream whenever the launch can fuse the
     // heads — weights_spec says so; a launch without heads never reads it)
     void pack_resident_f32(const Model &m, const WeightsSpec &s, Staged &st) {
@@ -434,6 +467,7 @@ struct DeviceWeights {
             case Tower::resident_split16:
             case Tower::resident_f16g:
             case Tower::resident_bf16g: pack_pairs(m, s, st); break;
+            case Tower::resident_i8: pack_i8(m, st); break;
             case Tower::resident_f32: pack_resident_f32(m, s, st); break;
             case Tower::resident_f16: pack_resident_f16(m, s, st); break;
             default:

@@ -194,7 +194,7 @@ KZ_API void kz_engine_destroy(kz_engine *e) {
 }
 
 static bool known_dtype(int dtype) {
-    return dtype == KZ_DTYPE_F32 || dtype == KZ_DTYPE_F16 || dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16;
+    return dtype == KZ_DTYPE_F32 || dtype == KZ_DTYPE_F16 || dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16 || dtype == KZ_DTYPE_INT8;
 }
 
 // kz_engine_create; profile: the range profile's internal engine — exact f32, no environment switch read, whatever plan_path
@@ -231,6 +231,7 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         // KZ_DTYPE_F32_SPLIT16 and bf16 are the f32 engine with one kernel exchanged: everything below sees KZ_DTYPE_F32
         const int dtype_in = dtype;
         if (dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16) dtype = KZ_DTYPE_F32;
+        if (dtype == KZ_DTYPE_INT8) dtype = KZ_DTYPE_F16;  // ... and int8 is the f16 engine with the tower's launch exchanged
         int ndev = 0;
         HIP_TRY(hipGetDeviceCount(&ndev));
         if (device < 0 || device >= ndev)
@@ -401,6 +402,27 @@ KZ_API int kz_model_plan(const kz_model *model, int max_batch, int dtype, kz_pat
 // Stream shift and range profile: the same function with a residual stream 2^-k times as large (kz::stream_shift), and how
 // large the stored tower tensors of a network are on the caller's positions, measured in exact f32
 // ------------------------------------------------------------------------------------------------
+KZ_API int kz_model_quantize_int8(const kz_model *model, const float *site_max, int n_sites, kz_model **out) {
+    return guarded("kz_model_quantize_int8", [&]() -> int {
+        if (!model || !site_max || !out) return fail("kz_model_quantize_int8: null argument");
+        std::string err;
+        Model *m = kz::quantize_int8(*model->m, site_max, n_sites, err);
+        if (!m) return fail("kz_model_quantize_int8: " + err);
+        *out = new kz_model(std::shared_ptr<Model>(m));
+        return 0;
+    });
+}
+
+KZ_API int kz_model_int8_site_exponents(const kz_model *model, int *exp_out) {
+    return guarded("kz_model_int8_site_exponents", [&]() -> int {
+        if (!model || !exp_out) return fail("kz_model_int8_site_exponents: null argument");
+        const Model &m = *model->m;
+        if (m.i8_exp.empty()) return fail("kz_model_int8_site_exponents: this model is not calibrated (kz_model_quantize_int8 makes one that is)");
+        std::copy(m.i8_exp.begin(), m.i8_exp.end(), exp_out);
+        return 0;
+    });
+}
+
 KZ_API int kz_model_stream_shift(const kz_model *model, int k, kz_model **out) {
     return guarded("kz_model_stream_shift", [&]() -> int {
         if (!model || !out) return fail("kz_model_stream_shift: null argument");
@@ -583,6 +605,7 @@ static int tap_plan(const std::string &fn, const kz_model *model, int max_batch,
     n = 2 * m.depth + 1;
     if (max_batch <= 0) return fail(fn + ": max_batch must be positive");
     if (!known_dtype(dtype)) return fail(fn + ": unknown dtype " + std::to_string(dtype));
+    if (dtype == KZ_DTYPE_INT8) return fail(fn + ": the int8 tower (dtype 4) has no tap instance: its stored tensors are int8 images at a scale per site, which the taps' element formats do not hold");
     std::string why;
     if (!plan_path(*effective_model(model, dtype, max_batch), max_batch, dtype, plan, why))
         return fail(fn + ": this model does not run in dtype " + std::to_string(dtype) + ": " + why);
@@ -778,6 +801,7 @@ KZ_API int kz_engine_launch_geometry(const kz_engine *e, int batch, int *workgro
             case Tower::resident_bf16g:
                 per = kz::tower_split_boards_per_workgroup(m.h, m.w, m.channels, e->split16(), p.wide ? batch : 0);
                 break;
+            case Tower::resident_i8: per = kz::tower_i8_boards_per_workgroup(m.h, m.w, m.channels, p.wide ? batch : 0); break;
             case Tower::board_conv_f16:
             case Tower::board_conv_split16: wgs = kz::board_conv_workgroups(batch, m.h, m.w, m.channels); break;
             case Tower::conv_igemm: wgs = kz::conv_workgroups(e->dtype, batch * m.h * m.w, e->cp); break;

@@ -118,7 +118,7 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         tower_out = 0;
         return 0;
     }
-    if (!per_layer(plan)) {  // resident_f32, resident_split16, resident_f16g, resident_bf16g
+    if (!per_layer(plan)) {  // resident_f32, resident_split16, resident_f16g, resident_bf16g, resident_i8
         kz::Tower32Args t{};
         t.x0 = (const float *)x_in; t.ldx0 = cin_p; t.c_in = m.c_in; t.weights = wts->res.w32; t.bias = wts->res.bias;
         t.post_scale = wts->post_scale; t.post_shift = wts->post_shift;
@@ -164,13 +164,14 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
             range_site = 2 * m.depth + 1;
         }
         const bool f16g = plan.tower == Tower::resident_f16g;
-        const char *name = split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : "kz_tower_resident_f32";
+        const char *name = split16() ? "kz_tower_resident_split" : f16g ? "kz_tower_resident_f16g" : bf16() ? "kz_tower_resident_bf16g" : i8() ? "kz_tower_resident_i8" : "kz_tower_resident_f32";
         bool launched = false;  // (the family has a fixed table of instances: a shape outside it launches nothing)
         int nt = 0;
         if (launch(p, name, [&] {
                 if (split16()) launched = kz::launch_tower_split(t, p.stream, &nt);
                 else if (bf16()) launched = kz::launch_tower_bf16(t, p.stream, &nt);  // f32 tensors, like the split launch
                 else if (f16g) launched = kz::launch_tower_pairs(t, p.stream, &nt);  // f16 tensors behind the same pointers
+                else if (i8()) launched = kz::launch_tower_i8(t, wts->res.mult, wts->res.qscale, p.stream, &nt);  // f16 tensors too
                 else launched = kz::launch_tower32(t, p.stream, &nt);
             }))
             return 1;

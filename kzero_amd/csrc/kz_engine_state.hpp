@@ -68,8 +68,9 @@ namespace {
 // for 128 / 256 channels only and the f32 matrix rate makes the zero work expensive).
 std::shared_ptr<Model> effective_model(const kz_model *model, int dtype_in, int max_batch) {
     const Model &m = *model->m;
-    if (dtype_in == KZ_DTYPE_F32 || m.tower_kind != kz::TOWER_RES || m.channels % 64 == 0 || m.channels > 512 || m.depth < 1 || env_on("KZ_FORCE_GENERIC") ||
-        env_on("KZ_KEEP_ACTIVATIONS"))
+    // (the int8 arithmetic reads none of the switches: it has one tower, and that tower wants a multiple of 64 channels)
+    const bool switched = dtype_in != KZ_DTYPE_INT8 && (env_on("KZ_FORCE_GENERIC") || env_on("KZ_KEEP_ACTIVATIONS"));
+    if (dtype_in == KZ_DTYPE_F32 || m.tower_kind != kz::TOWER_RES || m.channels % 64 == 0 || m.channels > 512 || m.depth < 1 || switched)
         return model->m;
     std::shared_ptr<Model> wide;
     {
@@ -161,8 +162,10 @@ struct kz_engine {
     PathPlan plan;  // which kernels run the network (plan_path, then the experiment build's switches)
     bool split16() const { return split_arithmetic(plan); }
     bool bf16() const { return plan.tower == Tower::resident_bf16g; }
-    // the dtype kz_engine_create was given (`dtype` is KZ_DTYPE_F32 for the two f32 engines with an exchanged tower)
-    int public_dtype() const { return bf16() ? KZ_DTYPE_BF16 : split16() ? KZ_DTYPE_F32_SPLIT16 : dtype; }
+    bool i8() const { return plan.tower == Tower::resident_i8; }
+    // the dtype kz_engine_create was given (`dtype` is KZ_DTYPE_F32 for the two f32 engines with an exchanged tower, and
+    // KZ_DTYPE_F16 for the int8 engine: the f16 engine with it exchanged)
+    int public_dtype() const { return bf16() ? KZ_DTYPE_BF16 : split16() ? KZ_DTYPE_F32_SPLIT16 : i8() ? KZ_DTYPE_INT8 : dtype; }
     void *xres = nullptr;  // (experiment build, PathPlan::nb4: the four-board launch's residual scratch)
 
     // activations

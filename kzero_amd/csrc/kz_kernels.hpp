@@ -510,6 +510,18 @@ bool launch_tower_pairs(const Tower32Args &a, hipStream_t stream, int *nt = null
 // `weights` = the split = false stream packed with bf16 = true, Heads::small_w = tower32_pack_small_weights (the tail is exact f32)
 bool launch_tower_bf16(const Tower32Args &a, hipStream_t stream, int *nt = nullptr);
 
+// ---- the one-launch tower on the i8 matrix cores (kz_tower_i8.hip: "tower_resident_i8", dtype 4 on a calibrated model): the
+// plain-f16 launch's tensors — f16 x0 and y behind the float pointers of Tower32Args, or packed boards in — around int8 block
+// convolutions; no heads inside, no tap instance.  `weights` = the stem's k-steps as tower_split_pack_weights packs them
+// (stem, split = false), then tower_i8_pack_weights per block convolution; mult [1 + 2*depth][channels] = 2^(e_in + f_oc) beside
+// the bias table (row 0, the stem's, is not read); qscale [2*depth] = 2^-e_s per quantised range site ----
+bool tower_i8_supported(int h, int w, int channels, int depth, int c_in);  // 128 / 256 tower channels: the table I8_ROWS
+bool tower_i8_wide_supported(int h, int w, int channels, int max_batch);   // 256 channels, 8x8: two boards per workgroup
+int tower_i8_boards_per_workgroup(int h, int w, int channels, int wide_batch = 0);
+size_t tower_i8_layer_bytes(int channels);
+void tower_i8_pack_weights(const int8_t *wq /* [C][C][9], quantised OIHW */, int channels, int8_t *dst);
+bool launch_tower_i8(const Tower32Args &a, const float *mult, const float *qscale, hipStream_t stream, int *nt = nullptr);
+
 // ---- 1x1 convolution in the same split arithmetic (the head convolutions behind the split tower), f32 in and out:
 // y[r][0..cout_p) = [relu](bias + W x[row(r)]), row(r) = (r / group) * src_group + src_off + r % group ----
 struct Conv1x1SplitArgs {

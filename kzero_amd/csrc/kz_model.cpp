@@ -641,6 +641,10 @@ Model *stream_shift(const Model &m, int k, std::string &err) {
         err = "a tower without blocks has no residual stream to shift";
         return nullptr;
     }
+    if (!m.i8_exp.empty()) {
+        err = "this model carries an int8 calibration, which was measured on the unshifted stream: shift first, then calibrate";
+        return nullptr;
+    }
     if (k < -STREAM_SHIFT_MAX || k > STREAM_SHIFT_MAX) {
         err = "k = " + std::to_string(k) + " out of range: the shift is 2^-k with k in [-" + std::to_string(STREAM_SHIFT_MAX) + ", " +
               std::to_string(STREAM_SHIFT_MAX) + "]";
@@ -655,6 +659,55 @@ Model *stream_shift(const Model &m, int k, std::string &err) {
               "range (no value is rounded silently: choose a smaller |k|)";
         return nullptr;
     }
+    return o.release();
+}
+
+// ---- the same network with an int8 calibration ----
+int i8_exponent(float max_abs) {
+    // the smallest e with 127 * 2^e >= max_abs, in exact arithmetic (both sides are doubles without rounding)
+    const double m = max_abs;
+    int e = std::ilogb(m) - 7;  // 127 * 2^e < 2^(e + 7) <= m
+    while (std::ldexp(127.0, e) < m) e++;
+    return e;
+}
+
+Model *quantize_int8(const Model &m, const float *site_max, int n_sites, std::string &err) {
+    if (m.tower_kind == TOWER_ATTENTION) {
+        err = "an AttentionTower network has no int8 kernel: its LayerNorms re-normalise every token, there is no stream of range sites to calibrate";
+        return nullptr;
+    }
+    if (m.tower_kind == TOWER_DENSE_NET) {
+        err = "a DenseNetwork has no residual tower to calibrate";
+        return nullptr;
+    }
+    if (m.depth < 1 || m.tower.size() != (size_t)(2 * m.depth + 1)) {
+        err = "a tower without blocks has no block convolution to quantise";
+        return nullptr;
+    }
+    if (!m.i8_exp.empty()) {
+        err = "this model is calibrated already: calibrate the model it was made from";
+        return nullptr;
+    }
+    if (n_sites != 2 * m.depth + 1) {
+        err = "n_sites = " + std::to_string(n_sites) + ", but this model has " + std::to_string(2 * m.depth + 1) + " range sites (kz_model_range_sites)";
+        return nullptr;
+    }
+    std::vector<int32_t> e(n_sites - 1);
+    for (int s = 0; s < n_sites - 1; s++) {
+        if (!std::isfinite(site_max[s]) || !(site_max[s] > 0.0f)) {
+            err = "site_max[" + std::to_string(s) + "] is not a finite number above zero: a site's maximum on the calibration positions "
+                  "(kz_model_range_profile_fast), times any headroom";
+            return nullptr;
+        }
+        e[s] = i8_exponent(site_max[s]);
+        if (e[s] < -I8_EXP_MAX || e[s] > I8_EXP_MAX) {
+            err = "site_max[" + std::to_string(s) + "] asks for a step of 2^" + std::to_string(e[s]) + ": beyond 2^+-" + std::to_string(I8_EXP_MAX) +
+                  ", where the f16 residual stream beside the int8 images has nothing to hold";
+            return nullptr;
+        }
+    }
+    std::unique_ptr<Model> o(new Model(m));
+    o->i8_exp = std::move(e);
     return o.release();
 }
 

@@ -92,6 +92,10 @@ struct Model {
 
     int64_t param_count = 0;
     double flops_per_eval = 0;
+
+    // int8 calibration (quantize_int8; in memory only, never in a .kzm): the activation exponent e_s of every range site but
+    // the last, 2 * depth of them.  Empty: not calibrated.  Everything else of a calibrated model is its source's.
+    std::vector<int32_t> i8_exp;
 };
 
 // Returns nullptr and sets `err` on failure.
@@ -111,6 +115,15 @@ Model *pad_channels(const Model &m, int cpad);
 // a value out of range.
 constexpr int STREAM_SHIFT_MAX = 24;
 Model *stream_shift(const Model &m, int k, std::string &err);
+
+// The same network with an int8 calibration beside it (include/kz_hip.h, "KZ_DTYPE_INT8"): e_s = ceil(log2(site_max[s] / 127)),
+// the smallest power-of-two step at which +-127 steps hold site s's maximum, for every range site but the last (whose entry is
+// accepted and ignored: that site is not quantised).  Every tensor and the descriptor are the source's, bit for bit.  Returns
+// nullptr and sets `err` for an AttentionTower network, a DenseNetwork, a tower without blocks, n_sites != 2 * depth + 1, an
+// entry that is not finite or not > 0 (or whose exponent is beyond +-I8_EXP_MAX) and a model that is calibrated already.
+constexpr int I8_EXP_MAX = 64;
+int i8_exponent(float max_abs);  // ceil(log2(max_abs / 127)), exact; max_abs finite and > 0
+Model *quantize_int8(const Model &m, const float *site_max, int n_sites, std::string &err);
 
 // ONNX as exported by the trainer (python/lib/save_onnx.py:60-122), kz_onnx.cpp.  n_scalar = how many of the input
 // planes are broadcast scalars (InputMapper::input_scalar_count, rust/kz-core/src/mapping/mod.rs:21) — the graph does

@@ -20,12 +20,14 @@
 //                      else                                       -> refused (kz_model_supports_dtype says 0)
 //   dtype bf16 (3):    a shape of kz_tower_f16g.hip               -> tower_resident_bf16g [+heads: conv heads at 128 / 256]
 //                      else                                       -> refused
+//   dtype int8 (4):    a calibrated model (kz_model_quantize_int8) of a shape of kz_tower_i8.hip -> tower_resident_i8
+//                      else                                       -> refused (the message says which of the two is missing)
 // ------------------------------------------------------------------------------------------------
 //   AttentionTower (attention.py) instead of the ResTower:
 //     8x8, 8 heads of d_k = d_v = 16, d_model 128 / 256: dtype f16 -> attention_tower_f16, f32 -> attention_tower_f32 (the same
 //                                                       launch on v_mfma_f32_16x16x4_f32; d_ff <= 256)
 //     any other shape (f32, or f16 rows around f32 arithmetic)   -> attention_tower_f32_valu (one launch, vector ALUs)
-//     f32split16, bf16                                           -> refused
+//     f32split16, bf16, int8                                     -> refused
 //   DenseNetwork (simple.py: no tower, no heads), f32 / f16         -> dense_network_f32 (one launch, f32 arithmetic)
 
 // the kernel family that runs the tower (path_name: the name kz_model_plan / kz_engine_tower_path report)
@@ -38,6 +40,7 @@ enum class Tower {
     resident_split16,    // kz_tower_split.hip: split arithmetic, one launch
     resident_f16g,       // kz_tower_f16g.hip: the split kernel without its lo halves — plain f16, generic shapes
     resident_bf16g,      // kz_tower_bf16g.hip: that plain kernel on bf16 elements, f32 tensors around it
+    resident_i8,         // kz_tower_i8.hip: int8 block convolutions beside an f16 residual stream, f16 tensors around it
     board_conv_f16,      // kz_board_conv.hip: one launch per layer, whole boards as LDS tiles
     board_conv_split16,  // the same per layer in split arithmetic (boards the one-launch split tower cannot hold)
     conv_igemm,          // kz_kernels.hip: one implicit GEMM per layer
@@ -46,7 +49,7 @@ enum class Tower {
 struct PathPlan {
     Tower tower = Tower::conv_igemm;
     bool heads = false;      // the tower launch runs the heads too ("+heads"), and can end in decode_output
-    bool wide = false;       // resident_f16g with more boards per workgroup (kz::tower_split_wide_supported)
+    bool wide = false;       // resident_f16g with more boards per workgroup (kz::tower_split_wide_supported); resident_i8: tower_i8_wide_supported
     bool att_heads = false;  // heads in launches of their own: ScalarHead + AttentionPolicyHead as one (kz_att_heads.hip)
     bool keep = false;       // KZ_KEEP_ACTIVATIONS: the per-layer path keeps every layer's output
     int tower_nb = 2;        // KZ_TOWER_NB: boards per workgroup of the resident_f16 launch at up to 32 input planes (1 or 2)
@@ -112,6 +115,7 @@ const char *path_name(const PathPlan &p, int dtype) {
         case Tower::resident_split16: return p.heads ? "tower_resident_split16+heads" : "tower_resident_split16";
         case Tower::resident_f16g: return p.heads ? "tower_resident_f16g+heads" : "tower_resident_f16g";
         case Tower::resident_bf16g: return p.heads ? "tower_resident_bf16g+heads" : "tower_resident_bf16g";
+        case Tower::resident_i8: return "tower_resident_i8";
         case Tower::board_conv_f16: return "board_conv_f16";
         case Tower::board_conv_split16: return "board_conv_split16";
         case Tower::conv_igemm: return f16 ? "conv_igemm_f16" : "conv_igemm_f32";
@@ -160,15 +164,23 @@ int head_launches(const Model &m, int dtype, const PathPlan &p, int cp) {
     return n;
 }
 
-// dtype_in: KZ_DTYPE_F32 / KZ_DTYPE_F16 / KZ_DTYPE_F32_SPLIT16 / KZ_DTYPE_BF16.  false + why: kz_engine_create refuses.
-// (The messages say "bf16" or "dtype 3": the library's strings name no KZ_ identifier but the documented ones.)
+// dtype_in: KZ_DTYPE_F32 / KZ_DTYPE_F16 / KZ_DTYPE_F32_SPLIT16 / KZ_DTYPE_BF16 / int8.  false + why: kz_engine_create refuses.
+// (The messages say "bf16" or "dtype 3", "int8" or "dtype 4": the library's strings name no KZ_ identifier but the documented ones.)
 bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::string &why) {
-    const bool split16 = dtype_in == KZ_DTYPE_F32_SPLIT16, bf16 = dtype_in == KZ_DTYPE_BF16;
-    const int dtype = split16 || bf16 ? KZ_DTYPE_F32 : dtype_in;  // both are the f32 engine with the tower's launch exchanged
+    const bool split16 = dtype_in == KZ_DTYPE_F32_SPLIT16, bf16 = dtype_in == KZ_DTYPE_BF16, i8 = dtype_in == KZ_DTYPE_INT8;
+    // split16 and bf16 are the f32 engine with the tower's launch exchanged, int8 is the f16 engine with it exchanged
+    const int dtype = split16 || bf16 ? KZ_DTYPE_F32 : i8 ? KZ_DTYPE_F16 : dtype_in;
     const int cp = round_up(m.channels, 32);
     const bool force = env_on("KZ_FORCE_GENERIC"), nofuse = env_on("KZ_NO_FUSED_HEADS");
     p = PathPlan();
+    // dtype 4 exists for a calibrated model only: to a model as loaded it is what it was before there was an int8 arithmetic, an
+    // unknown dtype — said first, then which of the two, calibration or kernel, is missing
+    const std::string i8_pre = i8 && m.i8_exp.empty() ? "unknown dtype 4 for a model that carries no int8 calibration (kz_model_quantize_int8 makes one that does): " : "";
     if (m.tower_kind == kz::TOWER_DENSE_NET) {  // DenseNetwork (simple.py): the whole network is one launch behind the encode
+        if (i8) {
+            why = i8_pre + "the int8 arithmetic (dtype 4) has no DenseNetwork kernel: a network without a tower runs in f32 arithmetic (dtype f32, or f16 rows around it)";
+            return false;
+        }
         if (bf16) {
             why = "the bf16 arithmetic (dtype 3) has no DenseNetwork kernel: a network without a tower runs in f32 arithmetic (dtype f32, or f16 rows around it)";
             return false;
@@ -186,6 +198,10 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
         return true;
     }
     if (m.tower_kind == kz::TOWER_ATTENTION) {
+        if (i8) {
+            why = i8_pre + "the int8 arithmetic (dtype 4) has no attention-tower kernel: an AttentionTower network runs in exact f32 or in f16";
+            return false;
+        }
         if (bf16) {
             why = "the bf16 arithmetic (dtype 3) has no attention-tower kernel: an AttentionTower network runs in exact f32 or in f16";
             return false;
@@ -204,6 +220,27 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
                                                       dtype == KZ_DTYPE_F32)
                       ? Tower::att_mfma
                       : Tower::att_valu;
+    } else if (i8) {
+        // the one-launch int8 tower or nothing; of the switches it reads none (it has one tower), and the heads behind it are
+        // the f16 engine's
+        if (m.depth < 1) {
+            why = i8_pre + "the int8 arithmetic (dtype 4) needs a tower with at least one residual block: only the block convolutions are quantised";
+            return false;
+        }
+        if (!kz::tower_i8_supported(m.h, m.w, m.channels, m.depth, m.c_in)) {
+            why = i8_pre + "the int8 arithmetic (dtype 4) has no kernel for this shape (" + std::string(m.i8_exp.empty() ? "and the model is not calibrated either" : "the model is calibrated") +
+                  "): the one-launch int8 tower takes 256 tower channels (193 to 255 run widened to 256) on a board of at most 64 "
+                  "squares with at most 128 input planes, and 128 (65 to 127 widened) on at most 96 squares with at most 64 input "
+                  "planes; 64 channels or fewer, 129 to 192 and more than 256 have no int8 kernel";
+            return false;
+        }
+        if (m.i8_exp.size() != (size_t)(2 * m.depth)) {
+            why = i8_pre + "the int8 arithmetic (dtype 4) needs a calibrated model (the shape has a kernel, the calibration is missing): make one with "
+                  "kz_model_quantize_int8 from the site maxima of kz_model_range_profile_fast";
+            return false;
+        }
+        p.tower = Tower::resident_i8;
+        p.wide = kz::tower_i8_wide_supported(m.h, m.w, m.channels, max_batch);
     } else if (!force && kz::tower_resident_supported(dtype, m.h, m.w, m.channels, m.depth, m.c_in)) {  // (f16 only)
         p.tower = Tower::resident_f16;
         if (const char *nb = getenv("KZ_TOWER_NB"); nb && atoi(nb) == 1) p.tower_nb = 1;

@@ -1,0 +1,488 @@
+// kz_tower_i8.hip — the one-launch ResTower on the i8 matrix cores: "tower_resident_i8" (dtype 4, a calibrated model).
+//
+// The organisation of the plain-f16 launch (kz_tower_pairs.hpp with SPLIT = false): 256 threads, each wave a quarter of the
+// output channels; the residual stream and the mid activation live in LDS for the whole tower; the weights stream from L2
+// straight into MFMA A-fragment registers through a ring that runs on across layer boundaries; im2col is LDS addressing, a
+// tap outside the board reads an all-zero row; the board encode is fused.  What differs is the operand width of the block
+// convolutions: v_mfma_i32_16x16x64_i8 takes the same 16 bytes per lane as the f16 instruction and multiplies 64 values of
+// k with them, so a k-step is 64 input channels (G = C / 64 k-steps per tap) and the sums are exact integers.
+//
+// The arithmetic (include/kz_hip.h, "KZ_DTYPE_INT8"; every scale a power of two, so applying one is exact in f32):
+//   quant(v, e) = clamp(rne(v * 2^-e), -127, 127) as int8 (v_rndne_f32; -128 is never produced)
+//   a block convolution, per output element: acc = the i32 sum of wq * q over 9 taps x C (exact); t = (float)acc;
+//     v = t * 2^(e_in + f_oc) + bias[oc] (the product is exact: one rounding); ReLU
+//   conv A stores Y8 = quant(v, e_mid).  Conv B adds (float)X to v in f32, after the ReLU, and stores X = f16(v) and
+//     X8 = quant(v, e_next), both from the same f32 v.  The last layer: ReLU, residual, final BN in f32, f16 rows out.
+//   the stem stays in f16 (its inputs are bits and a few scalars; nine k-steps): X = f16(v), X8 = quant(v, e_0)
+// LDS holds X as an f16 image (rows of 2 C + 16 bytes; only its own lane's slot is ever read back, by the residual add), and
+// the two int8 images X8 and Y8, which the convolutions read.
+//
+// Bank conflicts of the int8 fragment reads (the rule of Geo's comment in kz_tower_pairs.hpp, re-derived for 1-byte elements).
+// A ds_read_b128 is served in four groups of sixteen lanes, and a group mixes eight rows of lane group kq = 0 (or 2) with the
+// OTHER eight rows of kq = 1 (or 3): its sixteen 16-byte pieces fall on sixteen different slots of the 256-byte bank row only
+// if the pieces of kq and kq + 1 of the same row are a multiple of 256 B apart and rows advance by an odd number of slots.  An
+// int8 row is C <= 256 bytes, so inside ONE row no two pieces are 256 B apart, at any C: an int8 image is always TWO planes —
+// channels [0, C/2) and [C/2, C) of every row, rows of C/2 + 16 bytes (9 or 5 slots), the planes a multiple of 256 B apart —
+// and lane group kq reads plane kq & 1 at (kq >> 1) * C/4 bytes.  Byte j of lane group kq in k-step ch is channel
+// {0, C/2, C/4, 3C/4}[kq] + 16 ch + j: the f16 family's assignment with 16-byte pieces of 16 channels (tower_i8_pack_weights
+// packs the weights to match; the k order of a sum is free as long as both operands agree).
+#include <iterator>
+#include <utility>
+
+#include "kz_kernels.hpp"
+#include "kz_launch.hpp"
+
+namespace kz {
+
+typedef _Float16 h16;
+typedef h16 h16x8 __attribute__((ext_vector_type(8)));
+typedef h16 h16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+namespace {
+
+#include "kz_encode_dev.hpp"  // encoded_plane: the board encode's one statement
+
+// ---- which instance a shape takes: tiles of 16 pixel rows per workgroup = floor(16 NT / hw) whole boards packed densely ----
+struct I8Row {
+    int c, nt;
+};
+// 256 channels: one 8x8 board (or as many smaller ones as 64 rows hold), two; 128 channels: chess, one Go 9x9 board, two Ataxx
+// 7x7 boards (which straddle tile boundaries)
+constexpr I8Row I8_ROWS[] = {{256, 4}, {256, 8}, {128, 4}, {128, 6}, {128, 7}};
+
+constexpr int i8_tiles_for(int hw, int channels) {
+    if (channels == 256) return hw <= 64 ? 4 : 0;
+    if (channels == 128) return hw * 2 <= 112 ? 7 : hw <= 64 ? 4 : hw <= 96 ? 6 : 0;
+    return 0;
+}
+// two 8x8 boards per workgroup at 256 channels (the f16 chess launch's footprint: 32 + 16 + 16 KB per board) when the batch
+// still gives 128 such workgroups — the form of split_wide_tiles_for (kz_tower_pairs_shapes.hpp)
+constexpr int i8_wide_tiles_for(int hw, int channels, int batch) {
+    return channels == 256 && hw == 64 && (batch + 1) / 2 >= 128 ? 8 : 0;
+}
+constexpr int i8_tiles(int hw, int channels, int wide_batch) {
+    const int nt = wide_batch ? i8_wide_tiles_for(hw, channels, wide_batch) : 0;
+    return nt ? nt : i8_tiles_for(hw, channels);
+}
+constexpr bool i8_has_row(int channels, int nt) {
+    for (const I8Row &r : I8_ROWS)
+        if (r.c == channels && r.nt == nt) return true;
+    return false;
+}
+constexpr bool i8_rules_have_rows() {
+    for (int c = 64; c <= 512; c += 64)
+        for (int hw = 1; hw <= 512; hw++)
+            for (int batch : {0, 1, 255, 256, 1 << 20}) {
+                const int nt = i8_tiles(hw, c, batch);
+                if (nt && !i8_has_row(c, nt)) return false;
+            }
+    return true;
+}
+static_assert(i8_rules_have_rows(), "i8_tiles_for / i8_wide_tiles_for return a tile count that has no instance");
+
+constexpr int SG_MFMA = 0x8, SG_VMEM_READ = 0x20, SG_DS_READ = 0x100;
+
+template <int C, int NT>
+struct GeoI8 {
+    static constexpr int ROWS = NT * 16;
+    static constexpr int OT = C / 64;  // 16-channel output tiles per wave
+    static constexpr int G = C / 64;   // k-steps per tap: 64 channels each
+    static constexpr int XRS = C * 2 + 16;  // the f16 stream image: bytes per pixel row
+    static constexpr int XIMG = ROWS * XRS;
+    static constexpr int RS = C / 2 + 16;   // a plane's row of an int8 image: an odd number of 16-byte slots
+    static_assert((RS / 16) % 2 == 1, "rows advance by an odd number of slots");
+    static constexpr int IMG = ROWS * RS;   // (a multiple of 256: every image of a plane starts on a bank row)
+    // a plane = [X8][Y8][16 all-zero rows]; the planes a multiple of 256 B apart, behind the f16 image
+    static constexpr int X8 = 0, Y8 = IMG, Z8 = 2 * IMG;
+    static constexpr int PLANE = (2 * IMG + 16 * RS + 255) / 256 * 256;
+    static constexpr int Q_OFF = (XIMG + 255) / 256 * 256;
+    static constexpr int LDS_BYTES = Q_OFF + 2 * PLANE;
+    static constexpr int STEP = 4 * OT * 64;  // uint4 per k-step: [wave 4][ot][lane 64], the stem's f16 k-steps and the int8 ones alike
+    // the ring, as in Geo: at 128 channels a k-step is 8-14 MFMAs and the ring as deep as the registers allow — the nine taps
+    // unrolled, nine stages —; at 256 four stages, one per k-step of a tap
+    static constexpr int PF = G == 2 ? 9 : 4;
+    static constexpr int U = G == 2 ? 9 : 1;
+    static_assert((U * G) % PF == 0 && (9 * G) % PF == 0, "ring stage of a k-step must be a compile-time constant");
+    static_assert(C % 64 == 0 && LDS_BYTES <= 160 * 1024, "LDS budget");
+    // byte offset within a plane's row pair of channel c: plane (c >= C/2), then the channel inside it
+    __device__ static constexpr int chan_off(int c) { return c >= C / 2 ? PLANE + c - C / 2 : c; }
+};
+
+struct I8Dev {
+    const h16 *x0;       // encoded input [batch*hw][ldx0] f16 (in.bits == nullptr)
+    const uint4 *w;      // 9 * stem_chunks stem k-steps of f16 fragments, then 2*depth*9*C/64 k-steps of int8 fragments
+    const float *bias;   // [1 + 2*depth][C]
+    const float *mult;   // [1 + 2*depth][C]: 2^(e_in + f_oc) of layer l's output channels (row 0, the stem's, is not read)
+    const float *qscale; // [2*depth]: 2^-e_s of site s (the stem's output, then every layer's but the last)
+    const float *post_scale, *post_shift;
+    h16 *y;              // tower output [batch*hw][ldy] f16
+    int ldx0, ldy, batch, depth, h, w_, hw, nb;
+    int stem_chunks;
+    unsigned inv_w, inv_hw;  // ceil(65536 / w), ceil(65536 / hw): exact quotients for values < 512
+    PackedBoards in;
+};
+
+// clamp(rne(v * qs), -127, 127) of four values as the four bytes of a word, the first channel lowest
+__device__ __forceinline__ int quant4(f32x4 v, float qs) {
+    int r = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float q = fminf(fmaxf(__builtin_rintf(v[j] * qs), -127.0f), 127.0f);
+        r |= ((int)q & 0xff) << (8 * j);
+    }
+    return r;
+}
+
+template <int C, int NT>
+__global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
+    using L = GeoI8<C, NT>;
+    constexpr int PF = L::PF, RS = L::RS, XRS = L::XRS, OT = L::OT, G = L::G;
+    constexpr int X8 = L::Q_OFF + L::X8, Y8 = L::Q_OFF + L::Y8, Z8 = L::Q_OFF + L::Z8;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int fr = lane & 15, kq = lane >> 4;
+    const int board0 = blockIdx.x * a.nb;
+    const int boards = min(a.nb, a.batch - board0);
+    const int rows_valid = boards * a.hw;
+    const int layers = 2 * a.depth;
+    const int total_ksteps = layers * 9 * G;  // of the ring: the stem's k-steps in front of them are read directly
+
+    // ---- weight stream: prime PF stages (stage s = k-step g % PF) ----
+    const uint4 *wp_stem = a.w + wave * OT * 64 + lane;
+    const int sc = a.stem_chunks;
+    const uint4 *wp = wp_stem + (size_t)9 * sc * L::STEP;
+    auto wload = [&](int gk, int ot) __attribute__((always_inline)) { return wp[(size_t)gk * L::STEP + ot * 64]; };
+    uint4 wreg[PF][OT];
+#pragma unroll
+    for (int s = 0; s < PF; s++)
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++) wreg[s][ot] = wload(s < total_ksteps ? s : total_ksteps - 1, ot);
+    int g = 0;
+    auto ring_take = [&](int stage, i32x4 (&af)[OT]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++) af[ot] = __builtin_bit_cast(i32x4, wreg[stage][ot]);
+        const int gn = g + PF < total_ksteps ? g + PF : total_ksteps - 1;
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++) wreg[stage][ot] = wload(gn, ot);
+    };
+
+    // ---- zero rows (both planes) and the stem input, staged as f16 in the Y8 image, which nothing else touches before the
+    // first block's epilogue: rows of 64 B per chunk of 32 input planes, chunk k in plane k & 1 at (k >> 1) * 64 of a row of
+    // 64 ceil(sc / 2) bytes (tower_i8_supported: such a row is no longer than a plane's) ----
+    const int srow = 64 * ((sc + 1) >> 1), spieces = 8 * sc;
+    auto stem_at = [&](int row, int chunk) __attribute__((always_inline)) {
+        return Y8 + (chunk & 1) * L::PLANE + row * srow + (chunk >> 1) * 64;
+    };
+    for (int id = tid; id < 16 * RS / 16; id += 256) {
+        *reinterpret_cast<uint4 *>(lds + Z8 + id * 16) = make_uint4(0, 0, 0, 0);
+        *reinterpret_cast<uint4 *>(lds + Z8 + L::PLANE + id * 16) = make_uint4(0, 0, 0, 0);
+    }
+    for (int id = tid; id < L::ROWS * spieces; id += 256) {  // (row, 4-channel piece)
+        const int row = id / spieces, c4 = id - row * spieces;
+        h16x4 v = h16x4{};
+        if (a.in.bits) {  // 4 channels of one square (kz_encode_dev.hpp)
+            if (row < rows_valid) {
+                const int b = (int)(((unsigned)row * a.inv_hw) >> 16), q = row - b * a.hw;
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] = (h16)encoded_plane(a.in, board0 + b, c4 * 4 + j, q, a.hw);
+            }
+        } else if (row < rows_valid && c4 * 4 < a.ldx0) {
+            v = *reinterpret_cast<const h16x4 *>(a.x0 + ((size_t)board0 * a.hw + row) * a.ldx0 + c4 * 4);
+        }
+        *reinterpret_cast<h16x4 *>(lds + stem_at(row, c4 >> 3) + (c4 & 7) * 8) = v;
+    }
+
+    // Validity of (tile row, tap) as bitmasks: bit nt of okmask[tap] says that for this lane's row of tile nt the tap
+    // lands on the same board
+    unsigned okmask[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int nt = 0; nt < NT; nt++) {
+        const int r = nt * 16 + fr;
+        const int b = (int)(((unsigned)r * a.inv_hw) >> 16), q = r - b * a.hw;
+        const unsigned valid = r < rows_valid;
+        const int yy = (int)(((unsigned)q * a.inv_w) >> 16), xx = q - yy * a.w_;
+        const unsigned ym[3] = {(unsigned)(yy >= 1), 1u, (unsigned)(yy <= a.h - 2)};
+        const unsigned xm[3] = {(unsigned)(xx >= 1), 1u, (unsigned)(xx <= a.w_ - 2)};
+#pragma unroll
+        for (int tap = 0; tap < 9; tap++) okmask[tap] |= (valid & ym[tap / 3] & xm[tap % 3]) << nt;
+    }
+    __syncthreads();
+    auto ok_of = [&](int tap) __attribute__((always_inline)) {
+        return tap == 0   ? okmask[0] : tap == 1 ? okmask[1] : tap == 2 ? okmask[2] : tap == 3 ? okmask[3]
+               : tap == 4 ? okmask[4] : tap == 5 ? okmask[5] : tap == 6 ? okmask[6] : tap == 7 ? okmask[7] : okmask[8];
+    };
+
+    // per-channel tables of a layer — bias and 2^(e_in + f_oc) of this lane's channels — are fetched a layer ahead: a load that
+    // is consumed right away would make the compiler wait for vmcnt(0) and drain the weight ring once per layer
+    f32x4 bias_cur[OT], mult_cur[OT], bias_next[OT], mult_next[OT];
+    auto fetch_tables = [&](int row) __attribute__((always_inline)) {
+        const int l = row <= layers ? row : layers;
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++) {
+            bias_next[ot] = *reinterpret_cast<const f32x4 *>(a.bias + l * C + (wave * OT + ot) * 16 + kq * 4);
+            mult_next[ot] = *reinterpret_cast<const f32x4 *>(a.mult + l * C + (wave * OT + ot) * 16 + kq * 4);
+        }
+    };
+    auto take_tables = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++) {
+            bias_cur[ot] = bias_next[ot];
+            mult_cur[ot] = mult_next[ot];
+        }
+    };
+
+    // this lane's four channels of output tile ot, pixel row of tile nt: byte offsets within the f16 image and an int8 image
+    const int oc0 = wave * OT * 16 + kq * 4;
+    auto x_off = [&](int ot, int nt) __attribute__((always_inline)) { return (nt * 16 + fr) * XRS + (oc0 + ot * 16) * 2; };
+    auto q_off = [&](int ot, int nt) __attribute__((always_inline)) { return (nt * 16 + fr) * RS + L::chan_off(oc0 + ot * 16); };
+
+    // ---- stem in f16, exactly as the plain-f16 launch: 9 sc k-steps over the 32 sc (padded) input channels; conv + bias, no
+    // activation (post_act.py:205).  Its epilogue writes X and X8 = quant(v, e_0) ----
+    {
+        f32x4 sacc[OT][NT];
+        fetch_tables(0);
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++)
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) sacc[ot][nt] = bias_next[ot];
+        fetch_tables(1);
+#pragma nounroll
+        for (int ks = 0; ks < 9 * sc; ks++) {
+            const int tap = sc == 1 ? ks : ks / sc, chunk = ks - tap * sc;
+            const int shift = (tap / 3 - 1) * a.w_ + (tap % 3 - 1);
+            const unsigned ok = ok_of(tap);
+            h16x8 ah[OT], bh[NT];
+#pragma unroll
+            for (int ot = 0; ot < OT; ot++) {
+                const uint4 th = wp_stem[(size_t)ks * L::STEP + ot * 64];
+                ah[ot] = *reinterpret_cast<const h16x8 *>(&th);
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) {
+                const int off = stem_at(nt * 16 + fr + shift, chunk) + kq * 16;  // stem: natural k (channel = 32 chunk + 8 kq + j)
+                const bool valid = (ok >> nt) & 1;
+                bh[nt] = valid ? *reinterpret_cast<const h16x8 *>(lds + off) : h16x8{};
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++)
+#pragma unroll
+                for (int ot = 0; ot < OT; ot++)
+                    sacc[ot][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[ot], bh[nt], sacc[ot][nt], 0, 0, 0);
+        }
+        const float qs = a.qscale[0];
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++)
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) {
+                const f32x4 v = sacc[ot][nt];
+                *reinterpret_cast<h16x4 *>(lds + x_off(ot, nt)) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                *reinterpret_cast<int *>(lds + X8 + q_off(ot, nt)) = quant4(v, qs);
+            }
+    }
+    __syncthreads();
+
+    // ---- convolution passes over the int8 images ----
+    const int kq_off = L::PLANE * (kq & 1) + (C / 4) * (kq >> 1);
+    const int frag_base = fr * RS + kq_off;
+    // T[nt] = LDS address of this lane's fragment row (pixel shifted by the tap) or of a zero row with the same slot
+    auto tap_rows = [&](int tap, int src, int (&T)[NT]) __attribute__((always_inline)) {
+        const int shift = (tap / 3 - 1) * a.w_ + (tap % 3 - 1);
+        const unsigned ok = ok_of(tap);
+        const int shifted = src + frag_base + shift * RS;
+        const int zrow = Z8 + ((fr + shift) & 15) * RS + kq_off;
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++) T[nt] = ((ok >> nt) & 1) ? shifted + nt * 16 * RS : zrow;
+    };
+    i32x4 acc[OT][NT];
+    auto conv_3x3 = [&](int src) __attribute__((always_inline)) {
+        int T[NT], Tn[NT];
+        i32x4 bf[2][NT];
+        tap_rows(0, src, T);
+        auto rd = [&](int t, int extra) __attribute__((always_inline)) { return *reinterpret_cast<const i32x4 *>(lds + t + extra); };
+#pragma unroll
+        for (int nt = 0; nt < NT; nt++) bf[0][nt] = rd(T[nt], 0);
+#pragma nounroll
+        for (int tb = 0; tb < 9; tb += L::U)
+#pragma unroll
+        for (int tu = 0; tu < L::U; tu++) {
+            const int tap = tb + tu;
+            tap_rows(tap + 1 < 9 ? tap + 1 : tap, src, Tn);
+#pragma unroll
+            for (int ch = 0; ch < G; ch++) {
+                const int stage = (tu * G + ch) % PF, cur = (tu * G + ch) & 1, nxt = cur ^ 1;
+#pragma unroll
+                for (int nt = 0; nt < NT; nt++) bf[nxt][nt] = ch < G - 1 ? rd(T[nt], (ch + 1) * 16) : rd(Tn[nt], 0);
+                i32x4 af[OT];
+                ring_take(stage, af);
+#pragma unroll
+                for (int nt = 0; nt < NT; nt++)
+#pragma unroll
+                    for (int ot = 0; ot < OT; ot++)
+                        acc[ot][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[ot], bf[cur][nt], acc[ot][nt], 0, 0, 0);
+                // every memory instruction in the shadow of an MFMA: the ring refills, the fragment reads, then the
+                // remaining MFMAs back to back
+                constexpr int NMF = OT * NT, NVM = OT, NDS = NT;
+                constexpr int PAIRED = NVM + NDS < NMF ? NVM + NDS : NMF;
+#pragma unroll
+                for (int i = 0; i < NVM; i++) {
+                    if (i < PAIRED) __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(SG_VMEM_READ, 1, 0);
+                }
+#pragma unroll
+                for (int i = 0; i < NDS; i++) {
+                    if (NVM + i < PAIRED) __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
+                }
+                if constexpr (NMF > PAIRED) __builtin_amdgcn_sched_group_barrier(SG_MFMA, NMF - PAIRED, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                g++;
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) T[nt] = Tn[nt];
+        }
+    };
+    static_assert(G % 2 == 0, "the double buffer's parity is a tap's own: an even number of k-steps per tap");
+
+    // ---- the 2*depth 3x3 convolutions ----
+    for (int layer = 1; layer <= layers; layer++) {
+        const bool is_b = (layer & 1) == 0;  // conv A: X8 -> Y8; conv B: Y8 -> X, X8 (+ residual)
+        take_tables();
+        fetch_tables(layer + 1);
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++)
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) acc[ot][nt] = i32x4{0, 0, 0, 0};
+        conv_3x3(is_b ? Y8 : X8);
+        const float qs = a.qscale[layer < layers ? layer : layers - 1];  // (the last layer's output is not quantised)
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++) {
+            f32x4 ps = f32x4{1.f, 1.f, 1.f, 1.f}, pt = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (layer == layers) {
+                ps = *reinterpret_cast<const f32x4 *>(a.post_scale + oc0 + ot * 16);
+                pt = *reinterpret_cast<const f32x4 *>(a.post_shift + oc0 + ot * 16);
+            }
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) {
+                f32x4 v;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    v[j] = (float)acc[ot][nt][j] * mult_cur[ot][j] + bias_cur[ot][j];
+                    v[j] = v[j] > 0.0f ? v[j] : 0.0f;
+                }
+                if (!is_b) {
+                    *reinterpret_cast<int *>(lds + Y8 + q_off(ot, nt)) = quant4(v, qs);
+                    continue;
+                }
+                const h16x4 rx = *reinterpret_cast<const h16x4 *>(lds + x_off(ot, nt));
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] += (float)rx[j];  // added in f32, AFTER the ReLU (post_act.py:227-228)
+                if (layer != layers) {
+                    *reinterpret_cast<h16x4 *>(lds + x_off(ot, nt)) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                    *reinterpret_cast<int *>(lds + X8 + q_off(ot, nt)) = quant4(v, qs);
+                } else {
+                    // last layer: the final BN in f32 -> f16 rows of the tower output in global memory
+                    v = v * ps + pt;
+                    const int r = nt * 16 + fr;
+                    if (r < rows_valid)
+                        *reinterpret_cast<h16x4 *>(a.y + ((size_t)board0 * a.hw + r) * a.ldy + oc0 + ot * 16) =
+                            h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <int C, int NT>
+void launch(const I8Dev &d, int grid, hipStream_t stream) {
+    constexpr int LDS = GeoI8<C, NT>::LDS_BYTES;
+    allow_dynamic_lds<kz_tower_resident_i8<C, NT>>(LDS);
+    kz_tower_resident_i8<C, NT><<<grid, 256, LDS, stream>>>(d);
+}
+
+template <size_t... I>
+bool launch_row(std::index_sequence<I...>, int channels, int nt, const I8Dev &d, int grid, hipStream_t stream) {
+    return (... || [&] {
+        constexpr I8Row R = I8_ROWS[I];
+        if (R.c != channels || R.nt != nt) return false;
+        launch<R.c, R.nt>(d, grid, stream);
+        return true;
+    }());
+}
+
+}  // namespace
+
+// (the stem's input planes, in chunks of 32, are staged as f16 rows in the Y8 image: 64 B per pair of chunks and row must fit a
+// plane's row of C / 2 + 16 B)
+bool tower_i8_supported(int h, int w, int channels, int depth, int c_in) {
+    const int sc = (c_in + 31) / 32;
+    return depth >= 1 && c_in >= 1 && 64 * ((sc + 1) / 2) <= channels / 2 + 16 && h >= 2 && w >= 2 && w <= 32 &&
+           i8_tiles_for(h * w, channels) != 0;
+}
+
+bool tower_i8_wide_supported(int h, int w, int channels, int max_batch) {
+    return i8_tiles_for(h * w, channels) != 0 && i8_wide_tiles_for(h * w, channels, max_batch) != 0;
+}
+
+int tower_i8_boards_per_workgroup(int h, int w, int channels, int wide_batch) {
+    const int nt = i8_tiles(h * w, channels, wide_batch);
+    return nt ? nt * 16 / (h * w) : 0;
+}
+
+size_t tower_i8_layer_bytes(int channels) { return (size_t)9 * channels * channels; }
+
+// [C out][C in][9] int8 (OIHW, quantised) -> the 9 * C/64 k-steps of a block convolution, [tap][chunk] of
+// [wave 4][ot C/64][lane 64][16] int8: byte j of lane (fr, kq) of (wave, ot) is
+// wq[oc = 16*(wave*C/64 + ot) + fr][channel = {0, C/2, C/4, 3C/4}[kq] + 16*chunk + j][tap] — the A fragment of
+// v_mfma_i32_16x16x64_i8 with the k order of the kernel's LDS reads
+void tower_i8_pack_weights(const int8_t *wq, int channels, int8_t *dst) {
+    const int C = channels, ot_n = C / 64, g_n = C / 64;
+    const int kq_base[4] = {0, C / 2, C / 4, 3 * C / 4};
+    for (int tap = 0; tap < 9; tap++)
+        for (int chunk = 0; chunk < g_n; chunk++) {
+            int8_t *step = dst + ((size_t)tap * g_n + chunk) * C * 64;
+            for (int wave = 0; wave < 4; wave++)
+                for (int ot = 0; ot < ot_n; ot++)
+                    for (int lane = 0; lane < 64; lane++)
+                        for (int j = 0; j < 16; j++) {
+                            const int oc = 16 * (wave * ot_n + ot) + (lane & 15);
+                            const int ch = kq_base[lane >> 4] + 16 * chunk + j;
+                            step[(((size_t)wave * ot_n + ot) * 64 + lane) * 16 + j] = wq[((size_t)oc * C + ch) * 9 + tap];
+                        }
+        }
+}
+
+bool launch_tower_i8(const Tower32Args &t, const float *mult, const float *qscale, hipStream_t stream, int *nt_out) {
+    I8Dev d{};
+    d.in = t.in;
+    d.x0 = reinterpret_cast<const h16 *>(t.x0);  // (f16 tensors behind the float pointers, as for launch_tower_pairs)
+    d.ldx0 = t.ldx0;
+    d.w = static_cast<const uint4 *>(t.weights);
+    d.bias = t.bias;
+    d.mult = mult;
+    d.qscale = qscale;
+    d.post_scale = t.post_scale;
+    d.post_shift = t.post_shift;
+    d.y = reinterpret_cast<h16 *>(t.y);
+    d.ldy = t.ldy;
+    d.batch = t.batch;
+    d.depth = t.depth;
+    d.h = t.h;
+    d.w_ = t.w;
+    d.hw = t.h * t.w;
+    d.stem_chunks = (t.c_in + 31) / 32;
+    const int nt = i8_tiles(d.hw, t.channels, t.wide ? t.batch : 0);
+    if (nt_out) *nt_out = nt;
+    if (!nt) return false;
+    d.nb = nt * 16 / d.hw;
+    d.inv_w = (65536u + (unsigned)t.w - 1) / (unsigned)t.w;
+    d.inv_hw = (65536u + (unsigned)d.hw - 1) / (unsigned)d.hw;
+    const int grid = (t.batch + d.nb - 1) / d.nb;
+    return launch_row(std::make_index_sequence<std::size(I8_ROWS)>{}, t.channels, nt, d, grid, stream);
+}
+
+}  // namespace kz

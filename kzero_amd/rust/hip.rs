@@ -89,6 +89,8 @@ pub const KZ_DTYPE_F16: c_int = 1;
 /// f32 tensors and the same <= 1e-4 parity as KZ_DTYPE_F32, the tower's products as three f16 MFMAs on (hi, lo) pairs
 pub const KZ_DTYPE_F32_SPLIT16: c_int = 2;
 pub const KZ_DTYPE_BF16: i32 = 3;
+/// f16 tensors, the tower's block convolutions on the i8 matrix cores: a calibrated model only (`kz_model_quantize_int8`)
+pub const KZ_DTYPE_INT8: i32 = 4;
 pub const KZ_ENGINE_SLOTS: usize = 4;
 /// Per-board status bits of `kz_engine_wait_decoded_status` / `kz_engine_eval_packed_decoded_status` (include/kz_hip.h)
 pub const KZ_BOARD_OK: u8 = 0;
@@ -116,6 +118,10 @@ extern "C" {
     fn kz_model_plan(model: *const c_void, max_batch: c_int, dtype: c_int, out: *mut KzPathPlan) -> c_int;
     // stream shift (a new model: the same function, the residual stream 2^-k times as large) and the exact-f32 range profile
     fn kz_model_stream_shift(model: *const c_void, k: c_int, out: *mut *mut c_void) -> c_int;
+    // int8 calibration (a new model: the same tensors with an exponent per range site beside them; the only kind dtype 4 takes).
+    // No KZ_HIP_DTYPE=int8 yet: the shim has no calibration policy of its own.
+    fn kz_model_quantize_int8(model: *const c_void, site_max: *const f32, n_sites: c_int, out: *mut *mut c_void) -> c_int;
+    fn kz_model_int8_site_exponents(model: *const c_void, exp_out: *mut c_int) -> c_int;
     fn kz_model_range_sites(model: *const c_void, n_sites: *mut c_int) -> c_int;
     fn kz_model_range_site_name(model: *const c_void, site: c_int, buf: *mut c_char, len: usize) -> c_int;
     fn kz_model_range_profile(model: *const c_void, device: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, site_max_out: *mut f32, board_max_out: *mut f32) -> c_int;
