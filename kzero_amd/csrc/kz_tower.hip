@@ -30,7 +30,7 @@
 
 #include "kz_kernels.hpp"
 #include "kz_launch.hpp"
-
+#include "kz_tower_boundary.hpp"  // relu_f16_bits: conv A's ReLU on the packed f16 bits
 namespace kz {
 
 typedef _Float16 h16;
@@ -501,8 +501,8 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
             for (int mt = 0; mt < MT; mt++) T[mt] = Tn[mt];
         }
     };
-    constexpr std::integral_constant<int, 3> THREE_ROWS{};
-    constexpr std::integral_constant<int, 1> ONE_ROW{};
+    constexpr std::integral_constant<int, 3> THREE_ROWS{}; constexpr std::integral_constant<int, 1> ONE_ROW{};
+#include "kz_tower_boundary_body.hpp"  // LEAN, conv_3x3_lean, epilogue_lean: the line-tile layer with a short boundary
     // all nine taps
     auto conv_3x3 = [&](int src_off) __attribute__((always_inline)) {
         if constexpr (L::LINE_TILES && !PREV) conv_3x3_lines(src_off);
@@ -514,8 +514,8 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
     // ---- the 2*depth 3x3 convolutions ----
     for (int layer = 1; layer <= layers; layer++) {
         const bool is_b = (layer & 1) == 0;  // conv A: X -> Y; conv B: Y -> X (+ residual)
-        init_acc();
-        fetch_bias(layer + 1);
+        // (LEAN: the first MFMA into an accumulator adds the bias, and the coming bias is fetched behind the first super-step)
+        if constexpr (!LEAN) { init_acc(); fetch_bias(layer + 1); }
         if (layer == layers) {
 #pragma unroll
             for (int nt = 0; nt < 4; nt++) {
@@ -524,10 +524,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident(TowerDev a) {
                 post_t[nt] = *reinterpret_cast<const f32x4 *>(a.post_shift + oc);
             }
         }
-        conv_3x3(is_b ? L::Y_OFF : L::X_OFF);
-        if (!is_b) epilogue(L::Y_OFF, YES, NO, NO, layer);
-        else if (layer != layers) epilogue(L::X_OFF, YES, YES, NO, layer);
-        else epilogue(L::X_OFF, YES, YES, YES, layer);
+        if constexpr (LEAN) conv_3x3_lean(is_b ? L::Y_OFF : L::X_OFF, is_b ? L::X_OFF : L::Y_OFF, layer + 1); else conv_3x3(is_b ? L::Y_OFF : L::X_OFF);
+        if constexpr (LEAN) { if (!is_b) epilogue_lean(L::Y_OFF, NO, NO); else if (layer != layers) epilogue_lean(L::X_OFF, YES, NO); else epilogue_lean(L::X_OFF, YES, YES); }
+        else if (!is_b) epilogue(L::Y_OFF, YES, NO, NO, layer);
+        else if (layer != layers) epilogue(L::X_OFF, YES, YES, NO, layer); else epilogue(L::X_OFF, YES, YES, YES, layer);
         __syncthreads();
     }
 
