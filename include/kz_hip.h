@@ -76,6 +76,21 @@ extern "C" {
                            that carries no calibration dtype 4 is, first of all, an unknown dtype.  It reads
                            none of the environment switches.  kz_model_tower_taps, _taps_path and kz_model_error_profile
                            refuse it */
+#define KZ_DTYPE_INT8_HEADS 5 /* KZ_DTYPE_INT8's tower, bit for bit, with the heads inside its launch where the launch can carry
+                                 them: ScalarHead, ConvPolicyHead or AtaxxConvPolicyHead and decode_output run behind the last
+                                 block in f16, on the f16 values the tower holds — the plain-f16 launch's tail
+                                 ("tower_resident_f16g+heads"), so the heads' bits are that tail's, not those of the separate
+                                 head kernels behind dtype 4.  "tower_resident_i8+heads": ONE launch per batch, zero-copy slots
+                                 on two streams like every "+heads" plan.  That is 128 tower channels (65 .. 127 widened) on
+                                 <= 96 squares and 256 (193 .. 255 widened) on <= 64, a conv policy head with <= 32 planes, a
+                                 scalar head of <= 32 channels (one less with extra moves) and <= 256 hidden units, at most
+                                 four boards per workgroup, the tail's floats within 16 KB of LDS; always ONE 8x8 board per
+                                 workgroup at 256 channels (no two-board tiles with the heads inside).  Everywhere else —
+                                 attention or dense policy heads, more boards per workgroup — dtype 5 is EXACTLY dtype 4's
+                                 plan: same path name, same launches, same bits; a caller can always pass 5.
+                                 kz_model_supports_dtype(m, 5) == kz_model_supports_dtype(m, 4) for every model; the refusals
+                                 are dtype 4's with "dtype 5" in them (an uncalibrated model: first of all an unknown dtype 5);
+                                 it reads none of the environment switches; the taps and the error profile refuse it */
 
 #define KZ_POLICY_ATAXX_CONV 0 /* AtaxxConvPolicyHead, python/lib/model/post_act.py:91-112 */
 #define KZ_POLICY_CONV 1       /* ConvPolicyHead,      post_act.py:54-88 */
@@ -527,7 +542,9 @@ int kz_engine_kernel_time(kz_engine *engine, const char *prefix, double *total_m
  * channels and the conv-policy networks at 128 / 256 channels: encode, tower, scalar head and policy head in one launch),
  * "tower_resident_split16" (the other shapes of
  * KZ_DTYPE_F32_SPLIT16: tower launch + f32 head kernels), "tower_resident_bf16g+heads" / "tower_resident_bf16g"
- * (KZ_DTYPE_BF16: conv policy heads at 128 / 256 channels inside; else tower launch + f32 head kernels).  One launch per layer:
+ * (KZ_DTYPE_BF16: conv policy heads at 128 / 256 channels inside; else tower launch + f32 head kernels), "tower_resident_i8"
+ * (KZ_DTYPE_INT8, and KZ_DTYPE_INT8_HEADS elsewhere: tower launch + f16 head kernels) / "tower_resident_i8+heads"
+ * (KZ_DTYPE_INT8_HEADS: conv policy heads, scalar head and decode inside).  One launch per layer:
  * "board_conv_f16" (whole boards as LDS tiles, Go-size boards), "board_conv_split16" (the same per-layer kernel in split
  * arithmetic: KZ_DTYPE_F32_SPLIT16 on boards the one-launch split tower cannot hold), "conv_igemm_f16", "conv_igemm_f32".
  * Networks whose tower is the reference's AttentionTower (python/lib/model/attention.py:8-45) instead of the ResTower — one

@@ -56,7 +56,7 @@ struct DeviceWeights {
     float *post_scale = nullptr, *post_shift = nullptr;
     // the one-launch ResTowers.  resident_f32, resident_split16, resident_f16g, resident_bf16g: w32 and bias (and small where
     // the stream carries the conv heads); resident_f16: w_stem, w_tower and bias; att_idx where it carries the attention heads;
-    // resident_i8: w32, bias, mult and qscale
+    // resident_i8: w32, bias, mult and qscale (and small, in f16, where the stream carries the conv heads)
     struct {
         void *w32 = nullptr;  // one packed weight stream: exact f32, split f16 pairs, plain f16 or bf16; f16 stem + int8 blocks
         float *mult = nullptr;    // resident_i8: [1 + 2·depth][C], 2^(e_in + f_oc) per block convolution and output channel
@@ -303,10 +303,15 @@ struct DeviceWeights {
     // — 16 B per lane, 64 channels per k-step —, one f32 multiplier table beside the bias table.  The weight exponent of a
     // (block convolution, output channel) is f = ceil(log2(max |w[oc]| / 127)) on the folded weights, wq = rne(w · 2^-f); an
     // all-zero filter (a widened channel) gets f = 0.  Every scale is a power of two: exact to apply.
-    void pack_i8(const Model &m, Staged &st) {
+    // With the conv heads in the stream ("tower_resident_i8+heads"): the policy head's hidden layer as one more pass of C/32 f16
+    // k-steps behind the tower's (a k-step is C * 64 bytes in either element), its bias as one more bias row, and the plain-f16
+    // launch's small convolutions beside the stream; without them the stream is byte for byte what it was.
+    void pack_i8(const Model &m, const WeightsSpec &s, Staged &st) {
         const int C = m.channels, hw = m.h * m.w, layers = 2 * m.depth;
+        const bool conv_heads = s.heads == StreamHeads::conv;
         const size_t stem_bytes = kz::tower_split_stem_elems(C, m.c_in, false) * 2, layer_bytes = kz::tower_i8_layer_bytes(C);
-        std::vector<uint8_t> packed(stem_bytes + layer_bytes * layers);
+        const size_t tower_bytes = stem_bytes + layer_bytes * layers;
+        std::vector<uint8_t> packed(tower_bytes + (conv_heads ? kz::tower_split_conv_heads_weight_elems(C, false) * 2 : 0));
         kz::tower_split_pack_weights(m.tower[0].w.data(), C, m.c_in, hw, true, false, reinterpret_cast<uint16_t *>(packed.data()));
         std::vector<float> mult((size_t)(1 + layers) * C, 1.0f), qscale(layers);
         std::vector<int8_t> wq((size_t)C * C * 9);
@@ -324,7 +329,14 @@ struct DeviceWeights {
             kz::tower_i8_pack_weights(wq.data(), C, reinterpret_cast<int8_t *>(packed.data() + stem_bytes + layer_bytes * (l - 1)));
         }
         for (int s = 0; s < layers; s++) qscale[s] = std::ldexp(1.0f, -m.i8_exp[s]);
-        put_bias_rows(m, 0, nullptr, st);
+        put_bias_rows(m, conv_heads ? 1 : 0, conv_heads ? &m.p_conv0 : nullptr, st);
+        if (conv_heads) {
+            kz::tower_split_pack_conv_heads(m.p_conv0.w.data(), C, false, reinterpret_cast<uint16_t *>(packed.data() + tower_bytes));
+            std::vector<uint16_t> small(kz::tower_split_small_weight16_elems(C));
+            kz::tower_split_pack_small_weights16(m.sh_conv.w.data(), m.sh_conv.cout, m.policy_extra_moves ? m.p_extra_conv.w.data() : nullptr,
+                                                 m.p_conv1.w.data(), m.policy_conv_channels, C, small.data());
+            st.take(std::move(small), &res.small);
+        }
         st.take(std::move(mult), &res.mult);
         st.take(std::move(qscale), &res.qscale);
         st.take(std::move(packed), &res.w32);
@@ -467,7 +479,7 @@ struct DeviceWeights {
             case Tower::resident_split16:
             case Tower::resident_f16g:
             case Tower::resident_bf16g: pack_pairs(m, s, st); break;
-            case Tower::resident_i8: pack_i8(m, st); break;
+            case Tower::resident_i8: pack_i8(m, s, st); break;
             case Tower::resident_f32: pack_resident_f32(m, s, st); break;
             case Tower::resident_f16: pack_resident_f16(m, s, st); break;
             default:

@@ -194,7 +194,7 @@ KZ_API void kz_engine_destroy(kz_engine *e) {
 }
 
 static bool known_dtype(int dtype) {
-    return dtype == KZ_DTYPE_F32 || dtype == KZ_DTYPE_F16 || dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16 || dtype == KZ_DTYPE_INT8;
+    return dtype == KZ_DTYPE_F32 || dtype == KZ_DTYPE_F16 || dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16 || int8_dtype(dtype);
 }
 
 // kz_engine_create; profile: the range profile's internal engine — exact f32, no environment switch read, whatever plan_path
@@ -231,7 +231,7 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         // KZ_DTYPE_F32_SPLIT16 and bf16 are the f32 engine with one kernel exchanged: everything below sees KZ_DTYPE_F32
         const int dtype_in = dtype;
         if (dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16) dtype = KZ_DTYPE_F32;
-        if (dtype == KZ_DTYPE_INT8) dtype = KZ_DTYPE_F16;  // ... and int8 is the f16 engine with the tower's launch exchanged
+        if (int8_dtype(dtype)) dtype = KZ_DTYPE_F16;  // ... and int8 (4, 5) is the f16 engine with the tower's launch exchanged
         int ndev = 0;
         HIP_TRY(hipGetDeviceCount(&ndev));
         if (device < 0 || device >= ndev)
@@ -246,6 +246,7 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
         const Model &m = *e->model;
         e->device = device;
         e->dtype = dtype;
+        e->created_dtype = dtype_in;
         e->max_batch = max_batch;
         e->esz = dtype == KZ_DTYPE_F32 ? 4 : 2;
         e->cin_p = round_up(m.c_in, 32);
@@ -605,7 +606,7 @@ static int tap_plan(const std::string &fn, const kz_model *model, int max_batch,
     n = 2 * m.depth + 1;
     if (max_batch <= 0) return fail(fn + ": max_batch must be positive");
     if (!known_dtype(dtype)) return fail(fn + ": unknown dtype " + std::to_string(dtype));
-    if (dtype == KZ_DTYPE_INT8) return fail(fn + ": the int8 tower (dtype 4) has no tap instance: its stored tensors are int8 images at a scale per site, which the taps' element formats do not hold");
+    if (int8_dtype(dtype)) return fail(fn + ": the int8 tower (dtype " + std::to_string(dtype) + ") has no tap instance: its stored tensors are int8 images at a scale per site, which the taps' element formats do not hold");
     std::string why;
     if (!plan_path(*effective_model(model, dtype, max_batch), max_batch, dtype, plan, why))
         return fail(fn + ": this model does not run in dtype " + std::to_string(dtype) + ": " + why);

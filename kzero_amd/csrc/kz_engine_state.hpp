@@ -69,7 +69,7 @@ namespace {
 std::shared_ptr<Model> effective_model(const kz_model *model, int dtype_in, int max_batch) {
     const Model &m = *model->m;
     // (the int8 arithmetic reads none of the switches: it has one tower, and that tower wants a multiple of 64 channels)
-    const bool switched = dtype_in != KZ_DTYPE_INT8 && (env_on("KZ_FORCE_GENERIC") || env_on("KZ_KEEP_ACTIVATIONS"));
+    const bool switched = !int8_dtype(dtype_in) && (env_on("KZ_FORCE_GENERIC") || env_on("KZ_KEEP_ACTIVATIONS"));
     if (dtype_in == KZ_DTYPE_F32 || m.tower_kind != kz::TOWER_RES || m.channels % 64 == 0 || m.channels > 512 || m.depth < 1 || switched)
         return model->m;
     std::shared_ptr<Model> wide;
@@ -164,8 +164,10 @@ struct kz_engine {
     bool bf16() const { return plan.tower == Tower::resident_bf16g; }
     bool i8() const { return plan.tower == Tower::resident_i8; }
     // the dtype kz_engine_create was given (`dtype` is KZ_DTYPE_F32 for the two f32 engines with an exchanged tower, and
-    // KZ_DTYPE_F16 for the int8 engine: the f16 engine with it exchanged)
-    int public_dtype() const { return bf16() ? KZ_DTYPE_BF16 : split16() ? KZ_DTYPE_F32_SPLIT16 : i8() ? KZ_DTYPE_INT8 : dtype; }
+    // KZ_DTYPE_F16 for the int8 engines, 4 and 5: the f16 engine with it exchanged — which of the two the plan does not say
+    // where 5 plans as 4 does, so the engine keeps the value it was created with)
+    int created_dtype = 0;
+    int public_dtype() const { return bf16() ? KZ_DTYPE_BF16 : split16() ? KZ_DTYPE_F32_SPLIT16 : i8() ? created_dtype : dtype; }
     void *xres = nullptr;  // (experiment build, PathPlan::nb4: the four-board launch's residual scratch)
 
     // activations

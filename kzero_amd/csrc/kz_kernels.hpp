@@ -512,11 +512,16 @@ bool launch_tower_bf16(const Tower32Args &a, hipStream_t stream, int *nt = nullp
 
 // ---- the one-launch tower on the i8 matrix cores (kz_tower_i8.hip: "tower_resident_i8", dtype 4 on a calibrated model): the
 // plain-f16 launch's tensors — f16 x0 and y behind the float pointers of Tower32Args, or packed boards in — around int8 block
-// convolutions; no heads inside, no tap instance.  `weights` = the stem's k-steps as tower_split_pack_weights packs them
+// convolutions; no tap instance.  `weights` = the stem's k-steps as tower_split_pack_weights packs them
 // (stem, split = false), then tower_i8_pack_weights per block convolution; mult [1 + 2*depth][channels] = 2^(e_in + f_oc) beside
-// the bias table (row 0, the stem's, is not read); qscale [2*depth] = 2^-e_s per quantised range site ----
+// the bias table (row 0, the stem's, is not read); qscale [2*depth] = 2^-e_s per quantised range site.
+// With Tower32Args::Heads of kind conv ("tower_resident_i8+heads", dtype 5 where tower_i8_conv_heads_supported holds) the conv
+// policy heads, the scalar head and decode_output run inside, in f16 as in launch_tower_pairs: `weights` then ends in
+// tower_split_pack_conv_heads (split = false) — C/32 f16 k-steps of the same size as an int8 one —, `bias` has one more row
+// (the policy head's hidden layer's), and Heads::small_w = tower_split_pack_small_weights16; `wide` must be false ----
 bool tower_i8_supported(int h, int w, int channels, int depth, int c_in);  // 128 / 256 tower channels: the table I8_ROWS
 bool tower_i8_wide_supported(int h, int w, int channels, int max_batch);   // 256 channels, 8x8: two boards per workgroup
+bool tower_i8_conv_heads_supported(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs);  // narrow tiles only
 int tower_i8_boards_per_workgroup(int h, int w, int channels, int wide_batch = 0);
 size_t tower_i8_layer_bytes(int channels);
 void tower_i8_pack_weights(const int8_t *wq /* [C][C][9], quantised OIHW */, int channels, int8_t *dst);

@@ -22,6 +22,9 @@
 //                      else                                       -> refused
 //   dtype int8 (4):    a calibrated model (kz_model_quantize_int8) of a shape of kz_tower_i8.hip -> tower_resident_i8
 //                      else                                       -> refused (the message says which of the two is missing)
+//   dtype int8 + heads (5): dtype 4's tower; a conv policy head and a scalar head the tail takes on the narrow tiles
+//                      (kz::tower_i8_conv_heads_supported: at most four boards per workgroup) -> tower_resident_i8+heads, one
+//                      launch and never the wide tiles; else                       -> exactly dtype 4's plan
 // ------------------------------------------------------------------------------------------------
 //   AttentionTower (attention.py) instead of the ResTower:
 //     8x8, 8 heads of d_k = d_v = 16, d_model 128 / 256: dtype f16 -> attention_tower_f16, f32 -> attention_tower_f32 (the same
@@ -49,7 +52,7 @@ enum class Tower {
 struct PathPlan {
     Tower tower = Tower::conv_igemm;
     bool heads = false;      // the tower launch runs the heads too ("+heads"), and can end in decode_output
-    bool wide = false;       // resident_f16g with more boards per workgroup (kz::tower_split_wide_supported); resident_i8: tower_i8_wide_supported
+    bool wide = false;       // resident_f16g with more boards per workgroup (kz::tower_split_wide_supported); resident_i8: tower_i8_wide_supported, never with the heads inside
     bool att_heads = false;  // heads in launches of their own: ScalarHead + AttentionPolicyHead as one (kz_att_heads.hip)
     bool keep = false;       // KZ_KEEP_ACTIVATIONS: the per-layer path keeps every layer's output
     int tower_nb = 2;        // KZ_TOWER_NB: boards per workgroup of the resident_f16 launch at up to 32 input planes (1 or 2)
@@ -115,7 +118,7 @@ const char *path_name(const PathPlan &p, int dtype) {
         case Tower::resident_split16: return p.heads ? "tower_resident_split16+heads" : "tower_resident_split16";
         case Tower::resident_f16g: return p.heads ? "tower_resident_f16g+heads" : "tower_resident_f16g";
         case Tower::resident_bf16g: return p.heads ? "tower_resident_bf16g+heads" : "tower_resident_bf16g";
-        case Tower::resident_i8: return "tower_resident_i8";
+        case Tower::resident_i8: return p.heads ? "tower_resident_i8+heads" : "tower_resident_i8";
         case Tower::board_conv_f16: return "board_conv_f16";
         case Tower::board_conv_split16: return "board_conv_split16";
         case Tower::conv_igemm: return f16 ? "conv_igemm_f16" : "conv_igemm_f32";
@@ -164,21 +167,25 @@ int head_launches(const Model &m, int dtype, const PathPlan &p, int cp) {
     return n;
 }
 
-// dtype_in: KZ_DTYPE_F32 / KZ_DTYPE_F16 / KZ_DTYPE_F32_SPLIT16 / KZ_DTYPE_BF16 / int8.  false + why: kz_engine_create refuses.
-// (The messages say "bf16" or "dtype 3", "int8" or "dtype 4": the library's strings name no KZ_ identifier but the documented ones.)
+// the two int8 dtypes: one tower; 5 with the conv heads inside its launch where the launch can carry them
+bool int8_dtype(int dtype) { return dtype == KZ_DTYPE_INT8 || dtype == KZ_DTYPE_INT8_HEADS; }
+
+// dtype_in: KZ_DTYPE_F32 / KZ_DTYPE_F16 / KZ_DTYPE_F32_SPLIT16 / KZ_DTYPE_BF16 / int8 (4, 5).  false + why: kz_engine_create refuses.
+// (The messages say "bf16" or "dtype 3", "int8" or "dtype 4" / "dtype 5": the library's strings name no KZ_ identifier but the documented ones.)
 bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::string &why) {
-    const bool split16 = dtype_in == KZ_DTYPE_F32_SPLIT16, bf16 = dtype_in == KZ_DTYPE_BF16, i8 = dtype_in == KZ_DTYPE_INT8;
+    const bool split16 = dtype_in == KZ_DTYPE_F32_SPLIT16, bf16 = dtype_in == KZ_DTYPE_BF16, i8 = int8_dtype(dtype_in);
+    const std::string i8_name = "(dtype " + std::to_string(dtype_in) + ")";  // in the int8 messages: the value the caller gave
     // split16 and bf16 are the f32 engine with the tower's launch exchanged, int8 is the f16 engine with it exchanged
     const int dtype = split16 || bf16 ? KZ_DTYPE_F32 : i8 ? KZ_DTYPE_F16 : dtype_in;
     const int cp = round_up(m.channels, 32);
     const bool force = env_on("KZ_FORCE_GENERIC"), nofuse = env_on("KZ_NO_FUSED_HEADS");
     p = PathPlan();
-    // dtype 4 exists for a calibrated model only: to a model as loaded it is what it was before there was an int8 arithmetic, an
-    // unknown dtype — said first, then which of the two, calibration or kernel, is missing
-    const std::string i8_pre = i8 && m.i8_exp.empty() ? "unknown dtype 4 for a model that carries no int8 calibration (kz_model_quantize_int8 makes one that does): " : "";
+    // dtype 4 (and 5) exists for a calibrated model only: to a model as loaded it is what it was before there was an int8
+    // arithmetic, an unknown dtype — said first, then which of the two, calibration or kernel, is missing
+    const std::string i8_pre = i8 && m.i8_exp.empty() ? "unknown dtype " + std::to_string(dtype_in) + " for a model that carries no int8 calibration (kz_model_quantize_int8 makes one that does): " : "";
     if (m.tower_kind == kz::TOWER_DENSE_NET) {  // DenseNetwork (simple.py): the whole network is one launch behind the encode
         if (i8) {
-            why = i8_pre + "the int8 arithmetic (dtype 4) has no DenseNetwork kernel: a network without a tower runs in f32 arithmetic (dtype f32, or f16 rows around it)";
+            why = i8_pre + "the int8 arithmetic " + i8_name + " has no DenseNetwork kernel: a network without a tower runs in f32 arithmetic (dtype f32, or f16 rows around it)";
             return false;
         }
         if (bf16) {
@@ -199,7 +206,7 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
     }
     if (m.tower_kind == kz::TOWER_ATTENTION) {
         if (i8) {
-            why = i8_pre + "the int8 arithmetic (dtype 4) has no attention-tower kernel: an AttentionTower network runs in exact f32 or in f16";
+            why = i8_pre + "the int8 arithmetic " + i8_name + " has no attention-tower kernel: an AttentionTower network runs in exact f32 or in f16";
             return false;
         }
         if (bf16) {
@@ -222,25 +229,32 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
                       : Tower::att_valu;
     } else if (i8) {
         // the one-launch int8 tower or nothing; of the switches it reads none (it has one tower), and the heads behind it are
-        // the f16 engine's
+        // the f16 engine's — or, dtype 5, inside the launch where its tail takes them
         if (m.depth < 1) {
-            why = i8_pre + "the int8 arithmetic (dtype 4) needs a tower with at least one residual block: only the block convolutions are quantised";
+            why = i8_pre + "the int8 arithmetic " + i8_name + " needs a tower with at least one residual block: only the block convolutions are quantised";
             return false;
         }
         if (!kz::tower_i8_supported(m.h, m.w, m.channels, m.depth, m.c_in)) {
-            why = i8_pre + "the int8 arithmetic (dtype 4) has no kernel for this shape (" + std::string(m.i8_exp.empty() ? "and the model is not calibrated either" : "the model is calibrated") +
+            why = i8_pre + "the int8 arithmetic " + i8_name + " has no kernel for this shape (" + std::string(m.i8_exp.empty() ? "and the model is not calibrated either" : "the model is calibrated") +
                   "): the one-launch int8 tower takes 256 tower channels (193 to 255 run widened to 256) on a board of at most 64 "
                   "squares with at most 128 input planes, and 128 (65 to 127 widened) on at most 96 squares with at most 64 input "
                   "planes; 64 channels or fewer, 129 to 192 and more than 256 have no int8 kernel";
             return false;
         }
         if (m.i8_exp.size() != (size_t)(2 * m.depth)) {
-            why = i8_pre + "the int8 arithmetic (dtype 4) needs a calibrated model (the shape has a kernel, the calibration is missing): make one with "
+            why = i8_pre + "the int8 arithmetic " + i8_name + " needs a calibrated model (the shape has a kernel, the calibration is missing): make one with "
                   "kz_model_quantize_int8 from the site maxima of kz_model_range_profile_fast";
             return false;
         }
         p.tower = Tower::resident_i8;
         p.wide = kz::tower_i8_wide_supported(m.h, m.w, m.channels, max_batch);
+        // one launch per batch — zero-copy slots, the decode inside — is worth more than the two-board tiles (the precedent of
+        // resident_f16g below): with the heads inside the plan is never wide
+        if (dtype_in == KZ_DTYPE_INT8_HEADS && kz::tower_i8_conv_heads_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels,
+                                                                                 m.h, m.w, m.channels, m.sh_conv.cout, m.sh_fc0.out)) {
+            p.wide = false;
+            p.heads = true;
+        }
     } else if (!force && kz::tower_resident_supported(dtype, m.h, m.w, m.channels, m.depth, m.c_in)) {  // (f16 only)
         p.tower = Tower::resident_f16;
         if (const char *nb = getenv("KZ_TOWER_NB"); nb && atoi(nb) == 1) p.tower_nb = 1;

@@ -1,4 +1,6 @@
-// kz_tower_i8.hip — the one-launch ResTower on the i8 matrix cores: "tower_resident_i8" (dtype 4, a calibrated model).
+// kz_tower_i8.hip — the one-launch ResTower on the i8 matrix cores: "tower_resident_i8" (dtype 4 and 5, a calibrated model),
+// and with the conv policy heads, the scalar head and decode_output behind it in the same launch "tower_resident_i8+heads"
+// (dtype 5 where tower_i8_conv_heads_supported holds; the HEADS = 2 instances, described in front of the kernel).
 //
 // The organisation of the plain-f16 launch (kz_tower_pairs.hpp with SPLIT = false): 256 threads, each wave a quarter of the
 // output channels; the residual stream and the mid activation live in LDS for the whole tower; the weights stream from L2
@@ -42,15 +44,19 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
+#include "kz_decode_dev.hpp"  // DecodeDev, decode_board_wave: decode_output as the last step of a launch with the heads inside
+#include "kz_conv_heads.hpp"  // conv_heads_tail: the conv policy heads and the scalar head behind two images in LDS
 #include "kz_encode_dev.hpp"  // encoded_plane: the board encode's one statement
 
 // ---- which instance a shape takes: tiles of 16 pixel rows per workgroup = floor(16 NT / hw) whole boards packed densely ----
 struct I8Row {
     int c, nt;
+    bool conv_heads;  // compiled with the conv heads' tail (HEADS = 2) too
 };
 // 256 channels: one 8x8 board (or as many smaller ones as 64 rows hold), two; 128 channels: chess, one Go 9x9 board, two Ataxx
 // 7x7 boards (which straddle tile boundaries)
-constexpr I8Row I8_ROWS[] = {{256, 4}, {256, 8}, {128, 4}, {128, 6}, {128, 7}};
+// (the heads ride on the narrow tiles only: the wide ones hold two boards of a shape whose one-board launch has them already)
+constexpr I8Row I8_ROWS[] = {{256, 4, true}, {256, 8, false}, {128, 4, true}, {128, 6, true}, {128, 7, true}};
 
 constexpr int i8_tiles_for(int hw, int channels) {
     if (channels == 256) return hw <= 64 ? 4 : 0;
@@ -66,9 +72,9 @@ constexpr int i8_tiles(int hw, int channels, int wide_batch) {
     const int nt = wide_batch ? i8_wide_tiles_for(hw, channels, wide_batch) : 0;
     return nt ? nt : i8_tiles_for(hw, channels);
 }
-constexpr bool i8_has_row(int channels, int nt) {
+constexpr bool i8_has_row(int channels, int nt, bool conv_heads = false) {
     for (const I8Row &r : I8_ROWS)
-        if (r.c == channels && r.nt == nt) return true;
+        if (r.c == channels && r.nt == nt && (r.conv_heads || !conv_heads)) return true;
     return false;
 }
 constexpr bool i8_rules_have_rows() {
@@ -83,6 +89,18 @@ constexpr bool i8_rules_have_rows() {
 static_assert(i8_rules_have_rows(), "i8_tiles_for / i8_wide_tiles_for return a tile count that has no instance");
 
 constexpr int SG_MFMA = 0x8, SG_VMEM_READ = 0x20, SG_DS_READ = 0x100;
+
+// LDS bytes of the launch's own images (GeoI8<C, NT>::LDS_BYTES restated for the host: launch() asserts the two agree) and what
+// the conv heads' tail gets as scratch behind them: the plain-f16 launch's 16 KB, or what is left of a CU's 160 KB
+constexpr int i8_own_lds_bytes(int channels, int nt) {
+    const int rows = nt * 16, rs = channels / 2 + 16;
+    const int q_off = (rows * (channels * 2 + 16) + 255) / 256 * 256, plane = (2 * rows * rs + 16 * rs + 255) / 256 * 256;
+    return q_off + 2 * plane;
+}
+constexpr int i8_tail_scratch_bytes(int channels, int nt) {
+    const int room = 160 * 1024 - i8_own_lds_bytes(channels, nt);
+    return room < (int)F16_TAIL_SCRATCH_BYTES ? room : (int)F16_TAIL_SCRATCH_BYTES;
+}
 
 template <int C, int NT>
 struct GeoI8 {
@@ -122,6 +140,15 @@ struct I8Dev {
     int stem_chunks;
     unsigned inv_w, inv_hw;  // ceil(65536 / w), ceil(65536 / hw): exact quotients for values < 512
     PackedBoards in;
+    // HEADS == 2 (conv policy heads and the scalar head inside the launch): the policy head's Conv1x1 C->C + ReLU is one more
+    // pass of C/32 f16 k-steps behind the tower's in `w`, its bias one more row of `bias`; then kz_conv_heads.hpp's members
+    int hc, hs, pc, policy_len, zero_tail, extra;
+    const float *sh_b0, *sh_w1t, *sh_b1, *sh_w2, *sh_b2, *p_b1, *pe_bc, *pe_wl, *pe_bl;
+    const uint4 *small_w16;  // the two small convolutions as f16 fragments (tower_split_pack_small_weights16)
+    float *scalars, *policy;
+    int *nonfinite_flag;
+    int epoch;
+    DecodeDev dec;  // dec.move_offsets set: decode_output inside the launch
 };
 
 // clamp(rne(v * qs), -127, 127) of four values as the four bytes of a word, the first channel lowest
@@ -135,8 +162,23 @@ __device__ __forceinline__ int quant4(f32x4 v, float qs) {
     return r;
 }
 
-template <int C, int NT>
+// HEADS: 0 = the tower alone, its output as f16 rows in global memory; 2 = + the conv policy heads (ConvPolicyHead,
+// AtaxxConvPolicyHead), the scalar head and decode_output, as in the plain-f16 launch (kz_tower_pairs.hpp, HEADS == 2 without
+// SPLIT), on values the tower holds as f16 already:
+//   the last layer writes its f16 output in place into X (this lane's own slot) instead of to global memory;
+//   the policy head's hidden layer, Conv1x1 C->C + ReLU, is one more pass of the weight ring — C/32 k-steps of
+//     v_mfma_f32_16x16x32_f16 over X, the accumulators started from its bias row — into YH, an f16 image in X's layout at Q_OFF:
+//     the int8 images are dead behind the layer loop's last barrier;
+//   X is ONE plane in natural channel order (rows of 2 C + 16 bytes), so lane group kq's 16-byte piece of k-step ch — channels
+//     8 ch + {0, C/2, C/4, 3C/4}[kq] + j, the packers' assignment — is at byte 2 * {0, C/2, C/4, 3C/4}[kq] + 16 ch of the row.  At
+//     256 channels kq and kq + 1 are 256 B apart: the chess launch's conflict-free pattern.  At 128 channels they are 128 B
+//     apart and two lane groups share banks (two-way conflicts): 4 NT + 8 ceil(NT / 4) such fragment reads per wave and launch
+//     beside the tower's 36 depth NT conflict-free ones, accepted;
+//   the two small convolutions are f16 MFMAs on X and YH (row tiles over the waves), the tail kz_conv_heads.hpp with its
+//     scratch behind the launch's own LDS and X as the decode's staging.
+template <int C, int NT, int HEADS = 0>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
+    static_assert(HEADS == 0 || HEADS == 2, "0: the tower alone; 2: conv heads and decode inside");
     using L = GeoI8<C, NT>;
     constexpr int PF = L::PF, RS = L::RS, XRS = L::XRS, OT = L::OT, G = L::G;
     constexpr int X8 = L::Q_OFF + L::X8, Y8 = L::Q_OFF + L::Y8, Z8 = L::Q_OFF + L::Z8;
@@ -149,7 +191,8 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
     const int boards = min(a.nb, a.batch - board0);
     const int rows_valid = boards * a.hw;
     const int layers = 2 * a.depth;
-    const int total_ksteps = layers * 9 * G;  // of the ring: the stem's k-steps in front of them are read directly
+    // of the ring: the stem's k-steps in front of them are read directly; the head pass follows the tower's
+    const int total_ksteps = layers * 9 * G + (HEADS == 2 ? C / 32 : 0);
 
     // ---- weight stream: prime PF stages (stage s = k-step g % PF) ----
     const uint4 *wp_stem = a.w + wave * OT * 64 + lane;
@@ -221,9 +264,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
     f32x4 bias_cur[OT], mult_cur[OT], bias_next[OT], mult_next[OT];
     auto fetch_tables = [&](int row) __attribute__((always_inline)) {
         const int l = row <= layers ? row : layers;
+        const int lb = HEADS == 2 && row == layers + 1 ? row : l;  // (the head pass's bias row; `mult` has none for it)
 #pragma unroll
         for (int ot = 0; ot < OT; ot++) {
-            bias_next[ot] = *reinterpret_cast<const f32x4 *>(a.bias + l * C + (wave * OT + ot) * 16 + kq * 4);
+            bias_next[ot] = *reinterpret_cast<const f32x4 *>(a.bias + lb * C + (wave * OT + ot) * 16 + kq * 4);
             mult_next[ot] = *reinterpret_cast<const f32x4 *>(a.mult + l * C + (wave * OT + ot) * 16 + kq * 4);
         }
     };
@@ -386,6 +430,10 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
                 } else {
                     // last layer: the final BN in f32 -> f16 rows of the tower output in global memory
                     v = v * ps + pt;
+                    if constexpr (HEADS != 0) {  // the heads read the tower output from X (in place: this lane owns the slot)
+                        *reinterpret_cast<h16x4 *>(lds + x_off(ot, nt)) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                        continue;
+                    }
                     const int r = nt * 16 + fr;
                     if (r < rows_valid)
                         *reinterpret_cast<h16x4 *>(a.y + ((size_t)board0 * a.hw + r) * a.ldy + oc0 + ot * 16) =
@@ -395,22 +443,102 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
         }
         __syncthreads();
     }
+
+    if constexpr (HEADS == 2) {
+        // ---- conv policy heads (post_act.py:75-110) and scalar head (post_act.py:8-31) ----
+        constexpr int GH = C / 32, YH = L::Q_OFF;
+        static_assert(L::ROWS * XRS <= 2 * L::PLANE, "the hidden image fits the dead int8 region");
+        static_assert((9 * G) % PF == 0, "the head pass starts at ring stage 0");
+        const int kx_off = 2 * ((C / 2) * (kq & 1) + (C / 4) * (kq >> 1));
+        // The policy head's hidden layer, Conv1x1 C->C + ReLU: one more pass of the weight ring over X into YH
+        take_tables();
+        f32x4 hacc[OT][NT];
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++)
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) hacc[ot][nt] = bias_cur[ot];
+#pragma unroll
+        for (int ch = 0; ch < GH; ch++) {
+            h16x8 bh[NT];
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) bh[nt] = *reinterpret_cast<const h16x8 *>(lds + (nt * 16 + fr) * XRS + kx_off + ch * 16);
+            i32x4 af[OT];
+            ring_take(ch % PF, af);
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++)
+#pragma unroll
+                for (int ot = 0; ot < OT; ot++)
+                    hacc[ot][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, af[ot]), bh[nt], hacc[ot][nt], 0, 0, 0);
+            g++;
+        }
+#pragma unroll
+        for (int ot = 0; ot < OT; ot++)
+#pragma unroll
+            for (int nt = 0; nt < NT; nt++) {
+                f32x4 v = hacc[ot][nt];
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] = v[j] > 0.0f ? v[j] : 0.0f;
+                *reinterpret_cast<h16x4 *>(lds + YH + x_off(ot, nt)) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+            }
+        __syncthreads();
+        // The two small convolutions as f16 MFMAs straight on the two f16 images, row tiles split over the waves (the plain-f16
+        // launch's provider on one-plane images); the tail's scratch is BEHIND the launch's own LDS (the launcher asks for it)
+        constexpr int TW = (NT + 3) / 4;
+        auto small_conv = [&](int which, auto emit) {
+            const int img = which ? YH : 0;
+            const uint4 *wfrag = a.small_w16 + which * (GH * 2 * 64);  // [GH][2][64]
+            f32x4 sa[2][TW];
+            int base[TW];
+#pragma unroll
+            for (int t = 0; t < TW; t++) {
+                sa[0][t] = sa[1][t] = f32x4{0, 0, 0, 0};
+                const int row = (wave + 4 * t) * 16 + fr;
+                base[t] = img + (row < L::ROWS ? row : L::ROWS - 1) * XRS + kx_off;
+            }
+#pragma unroll
+            for (int gs = 0; gs < GH; gs++) {
+                const uint4 w0 = wfrag[(gs * 2 + 0) * 64 + lane], w1 = wfrag[(gs * 2 + 1) * 64 + lane];
+                const h16x8 a0 = __builtin_bit_cast(h16x8, w0), a1 = __builtin_bit_cast(h16x8, w1);
+#pragma unroll
+                for (int t = 0; t < TW; t++) {
+                    const h16x8 b = *reinterpret_cast<const h16x8 *>(lds + base[t] + gs * 16);
+                    sa[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, b, sa[0][t], 0, 0, 0);
+                    sa[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, b, sa[1][t], 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < TW; t++) {
+                const int row = (wave + 4 * t) * 16 + fr;
+                if (wave + 4 * t < NT && row < rows_valid) {
+#pragma unroll
+                    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+                        for (int q = 0; q < 4; q++) emit(mt, q, row, sa[mt][t][q]);
+                }
+            }
+        };
+        conv_heads_tail<C, NT>(a, lds, L::LDS_BYTES, board0, boards, rows_valid, small_conv, 0, L::XIMG);
+    }
 }
 
-template <int C, int NT>
+template <int C, int NT, int HEADS = 0>
 void launch(const I8Dev &d, int grid, hipStream_t stream) {
-    constexpr int LDS = GeoI8<C, NT>::LDS_BYTES;
-    allow_dynamic_lds<kz_tower_resident_i8<C, NT>>(LDS);
-    kz_tower_resident_i8<C, NT><<<grid, 256, LDS, stream>>>(d);
+    static_assert(GeoI8<C, NT>::LDS_BYTES == i8_own_lds_bytes(C, NT), "the host's restatement of the LDS geometry");
+    constexpr int LDS = GeoI8<C, NT>::LDS_BYTES + (HEADS == 2 ? i8_tail_scratch_bytes(C, NT) : 0);
+    static_assert(LDS <= 160 * 1024, "LDS budget");
+    allow_dynamic_lds<kz_tower_resident_i8<C, NT, HEADS>>(LDS);
+    kz_tower_resident_i8<C, NT, HEADS><<<grid, 256, LDS, stream>>>(d);
 }
 
+// The instance of (channels, nt) among I8_ROWS, with the conv heads' tail if asked for: no such row = no launch (false)
 template <size_t... I>
-bool launch_row(std::index_sequence<I...>, int channels, int nt, const I8Dev &d, int grid, hipStream_t stream) {
+bool launch_row(std::index_sequence<I...>, int channels, int nt, bool conv_heads, const I8Dev &d, int grid, hipStream_t stream) {
     return (... || [&] {
         constexpr I8Row R = I8_ROWS[I];
         if (R.c != channels || R.nt != nt) return false;
-        launch<R.c, R.nt>(d, grid, stream);
-        return true;
+        if (!conv_heads) launch<R.c, R.nt>(d, grid, stream);
+        else if constexpr (R.conv_heads) launch<R.c, R.nt, 2>(d, grid, stream);
+        return !conv_heads || R.conv_heads;
     }());
 }
 
@@ -431,6 +559,13 @@ bool tower_i8_wide_supported(int h, int w, int channels, int max_batch) {
 int tower_i8_boards_per_workgroup(int h, int w, int channels, int wide_batch) {
     const int nt = i8_tiles(h * w, channels, wide_batch);
     return nt ? nt * 16 / (h * w) : 0;
+}
+
+// kz_conv_heads.hpp behind the narrow tiles (never the wide ones: one launch per batch before two boards per workgroup)
+bool tower_i8_conv_heads_supported(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs) {
+    const int nt = i8_tiles_for(h * w, channels);
+    if (!nt || !i8_has_row(channels, nt, true)) return false;
+    return conv_heads_fit(nt, policy_kind, extra_moves, pc, h, w, channels, hc, hs, (size_t)i8_tail_scratch_bytes(channels, nt));
 }
 
 size_t tower_i8_layer_bytes(int channels) { return (size_t)9 * channels * channels; }
@@ -482,7 +617,19 @@ bool launch_tower_i8(const Tower32Args &t, const float *mult, const float *qscal
     d.inv_w = (65536u + (unsigned)t.w - 1) / (unsigned)t.w;
     d.inv_hw = (65536u + (unsigned)d.hw - 1) / (unsigned)d.hw;
     const int grid = (t.batch + d.nb - 1) / d.nb;
-    return launch_row(std::make_index_sequence<std::size(I8_ROWS)>{}, t.channels, nt, d, grid, stream);
+    const Tower32Args::Heads &hd = t.heads;
+    if (hd.kind == Tower32Args::Heads::Kind::attention) return false;  // (no attention heads in this launch)
+    const bool conv_heads = hd.kind == Tower32Args::Heads::Kind::conv;  // "...+heads" (the engine asked tower_i8_conv_heads_supported)
+    if (conv_heads) {
+        d.hc = hd.hc; d.hs = hd.hs; d.pc = hd.pc; d.policy_len = hd.policy_len; d.zero_tail = hd.zero_tail; d.extra = hd.extra;
+        d.sh_b0 = hd.sh_b0; d.sh_w1t = hd.sh_w1t; d.sh_b1 = hd.sh_b1; d.sh_w2 = hd.sh_w2; d.sh_b2 = hd.sh_b2;
+        d.p_b1 = hd.p_b1; d.pe_bc = hd.pe_bc; d.pe_wl = hd.pe_wl; d.pe_bl = hd.pe_bl;
+        d.small_w16 = reinterpret_cast<const uint4 *>(hd.small_w);
+        d.scalars = hd.scalars; d.policy = hd.policy;
+        d.nonfinite_flag = hd.nonfinite_flag; d.epoch = hd.epoch;
+        d.dec = decode_dev(hd.decode, true, hd.policy_len);
+    }
+    return launch_row(std::make_index_sequence<std::size(I8_ROWS)>{}, t.channels, nt, conv_heads, d, grid, stream);
 }
 
 }  // namespace kz

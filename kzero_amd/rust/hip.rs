@@ -91,6 +91,9 @@ pub const KZ_DTYPE_F32_SPLIT16: c_int = 2;
 pub const KZ_DTYPE_BF16: i32 = 3;
 /// f16 tensors, the tower's block convolutions on the i8 matrix cores: a calibrated model only (`kz_model_quantize_int8`)
 pub const KZ_DTYPE_INT8: i32 = 4;
+/// dtype 4's tower with the conv policy heads, the scalar head and the decode inside its launch where it can carry them
+/// ("tower_resident_i8+heads"); everywhere else exactly dtype 4's plan
+pub const KZ_DTYPE_INT8_HEADS: i32 = 5;
 pub const KZ_ENGINE_SLOTS: usize = 4;
 /// Per-board status bits of `kz_engine_wait_decoded_status` / `kz_engine_eval_packed_decoded_status` (include/kz_hip.h)
 pub const KZ_BOARD_OK: u8 = 0;

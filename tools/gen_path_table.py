@@ -21,12 +21,17 @@ tests/golden/path_table_int8.json (--int8) is that column for the int8 arithmeti
 as loaded is told, always "refused" — and "no calibration" where kz_model_quantize_int8 itself refuses the network;
 tests/test_int8_api.py recomputes it.
 
+tests/golden/path_table_int8_heads.json (--int8-heads) is the same table, cases and batches for KZ_DTYPE_INT8_HEADS (dtype 5):
+"tower_resident_i8+heads 1" where the int8 launch carries the conv heads, dtype 4's entry everywhere else;
+tests/test_int8_heads_api.py recomputes both.
+
 tests/test_path_table.py recomputes both from the built library and fails on any difference: a change of a support
 predicate has to come with a regenerated table (python tools/gen_path_table.py) and shows up in the diff.
 
     python tools/gen_path_table.py            # rewrite the JSON
     python tools/gen_path_table.py --bf16     # rewrite tests/golden/path_table_bf16.json
     python tools/gen_path_table.py --int8     # rewrite tests/golden/path_table_int8.json
+    python tools/gen_path_table.py --int8-heads  # rewrite tests/golden/path_table_int8_heads.json
     python tools/gen_path_table.py --md       # print the DESIGN table (with measured rates from a sweep record, if given:
                                               #   --rates profiles/r4/shape_sweep.json)
 """
@@ -44,6 +49,7 @@ from tests import sweep_cases  # noqa: E402
 OUT = os.path.join(REPO, "tests", "golden", "path_table.json")
 OUT_BF16 = os.path.join(REPO, "tests", "golden", "path_table_bf16.json")
 OUT_INT8 = os.path.join(REPO, "tests", "golden", "path_table_int8.json")
+OUT_INT8_HEADS = os.path.join(REPO, "tests", "golden", "path_table_int8_heads.json")
 MAX_BATCH = 256
 DTYPES = {"f32": capi.KZ_DTYPE_F32, "f16": capi.KZ_DTYPE_F16, "f32split16": capi.KZ_DTYPE_F32_SPLIT16}
 SWITCH_BATCHES = (1, 8, 256, 2048)
@@ -129,13 +135,13 @@ def build_bf16():
     return {"max_batch": list(SWITCH_BATCHES), "cases": cases}
 
 
-def build_int8():
+def build_int8(dtype=capi.KZ_DTYPE_INT8):
     """The int8 column: every sweep case, calibrated, x max_batch (SWITCH_BATCHES) -> "path launches", or "refused"; "no
     calibration" where the network cannot be calibrated at all."""
     cases, uncalibrated = {}, {}
     for case in sweep_cases.CASES:
         model = capi.Model(blob=synth.random_model(case.game, case.depth, case.channels, case.head, seed=11, **case.kw))
-        assert not model.supports_dtype(capi.KZ_DTYPE_INT8), case.id
+        assert not model.supports_dtype(dtype), case.id
         uncalibrated[case.id] = "refused"
         try:
             quant = model.quantize_int8([1.0] * len(model.range_sites()))
@@ -145,12 +151,17 @@ def build_int8():
         row = []
         for mb in SWITCH_BATCHES:
             try:
-                row.append("%s %d" % quant.plan(mb, capi.KZ_DTYPE_INT8))
+                row.append("%s %d" % quant.plan(mb, dtype))
             except capi.KzError:
                 row.append("refused")
-        assert (row[0] != "refused") == quant.supports_dtype(capi.KZ_DTYPE_INT8), case.id
+        assert (row[0] != "refused") == quant.supports_dtype(dtype), case.id
         cases[case.id] = row
     return {"max_batch": list(SWITCH_BATCHES), "cases": cases, "uncalibrated": uncalibrated}
+
+
+def build_int8_heads():
+    """The same column for dtype 5 (KZ_DTYPE_INT8_HEADS): the cases and batches of build_int8."""
+    return build_int8(capi.KZ_DTYPE_INT8_HEADS)
 
 
 def markdown(table, rates, games=None):
@@ -180,8 +191,12 @@ if __name__ == "__main__":
     ap.add_argument("--games", default=None, help="comma-separated subset of the lattice's games for --md")
     ap.add_argument("--bf16", action="store_true", help="write the bf16 column (tests/golden/path_table_bf16.json)")
     ap.add_argument("--int8", action="store_true", help="write the int8 column (tests/golden/path_table_int8.json)")
+    ap.add_argument("--int8-heads", action="store_true", help="write the dtype-5 column (tests/golden/path_table_int8_heads.json)")
     args = ap.parse_args()
-    if args.int8:
+    if args.int8_heads:
+        json.dump(build_int8_heads(), open(OUT_INT8_HEADS, "w"), indent=1, sort_keys=True)
+        print("wrote", OUT_INT8_HEADS)
+    elif args.int8:
         json.dump(build_int8(), open(OUT_INT8, "w"), indent=1, sort_keys=True)
         print("wrote", OUT_INT8)
     elif args.bf16:

@@ -12,6 +12,13 @@ decode; the f16 plan of a network whose heads fit its launch is ONE launch.  So 
             network whose f16 plan has the heads inside, a third engine — f16 with KZ_NO_FUSED_HEADS=1: the same tower kernel,
             the heads behind it like behind the int8 tower — gives the f16 tower alone: `tower_i8_over_f16` compares like with like.
 
+--heads adds a third engine, KZ_DTYPE_INT8_HEADS (dtype 5: the same int8 tower with the conv policy heads, the scalar head and
+the decode inside its launch where it can carry them — one launch per batch like the f16 plan), to the same interleaved regions,
+and the decoded and resident ratios of dtype 5 over dtype 4 and over f16: the ratio of the medians, and the smallest and largest
+ratio of a region of the one to the region of the other that ran beside it (`*_regions_min_max`: the regions' spread).  Dtype 4's
+kernels are untouched by dtype 5, so "5 over 4" in one process is the comparison with the library before dtype 5.  On a network
+whose heads the int8 launch cannot carry (chess) dtype 5 is dtype 4's plan and the ratio is 1 within that spread.
+
 Networks and batches: README's rows — chess 20x256 at 256, Ataxx 7x7 8x128 at 256, Go 9x9 16x128 at 2048.  The model is
 calibrated on a disjoint board sample (capi.calibrate_int8, headroom 2); the rate does not depend on the calibration.
 
@@ -21,6 +28,7 @@ post-softmax max |delta p| over the whole policy, with the f16 engine's figures 
 random-init: the error of a trained network is the caller's to measure with kz_engine_set_audit.  Prints one JSON object.
 
     python tools/int8_rate.py [--regions 7] [--seconds 0.5] [--nets chess,ataxx,go9] [--contract] [--out profiles/int8_rate.json]
+    python tools/int8_rate.py --heads     # the three engines; writes profiles/int8_heads_rate.json unless --out says otherwise
 """
 import argparse
 import json
@@ -38,6 +46,7 @@ from bf16_rate import Loop  # noqa: E402  (one engine's four-slot loop of the de
 
 NETS = {"chess": ("chess", 20, 256, "attention", 256), "ataxx": ("ataxx-7", 8, 128, "ataxx_conv", 256),
         "go9": ("go-9", 16, 128, "conv", 2048)}
+OUT_HEADS = os.path.join(REPO, "profiles", "int8_heads_rate.json")
 KERNEL = {"tower_resident_i8": "kz_tower_resident_i8", "tower_resident_f16": "kz_tower_resident_f16",
           "tower_resident_f16g": "kz_tower_resident_f16g"}
 CALIBRATION_BOARDS, CALIBRATION_SEED, HEADROOM = 64, 7, 2.0
@@ -88,7 +97,7 @@ def interleaved(loops, batch, regions, seconds):
     for _ in range(regions):  # interleaved: every engine sees the same minutes of the chip
         for name, loop in loops.items():
             elapsed[name].append(benchlib.run_timed(loop.step, loop.sync, steps[name], 4))
-    out = {}
+    out = {"_elapsed": elapsed, "_steps": steps}
     for name in loops:
         med = benchlib.median_region(elapsed[name])
         out[name] = {"steps_per_region": steps[name], "evals_per_s_median": round(steps[name] * batch / med),
@@ -107,16 +116,26 @@ def tower_time(eng, res, launches=40):
     return 1e3 * total / max(n, 1), n
 
 
-def rates(key, regions, seconds):
+def ratio(result, a, b):
+    """evals/s of engine a over engine b: the ratio of the medians, and the smallest and largest ratio over the regions (region i
+    of a ran next to region i of b)."""
+    per_region = [(result["_steps"][a] / ta) / (result["_steps"][b] / tb) for ta, tb in zip(result["_elapsed"][a], result["_elapsed"][b])]
+    return round(result[a]["evals_per_s_median"] / result[b]["evals_per_s_median"], 3), [round(min(per_region), 3), round(max(per_region), 3)]
+
+
+def rates(key, regions, seconds, heads=False):
     game, depth, channels, head, batch = NETS[key]
     model = calibrated(game, depth, channels, head)
     rng = np.random.default_rng(1)
     bits, scalars = synth.random_boards(game, batch, seed=2)
     moves = [rng.permutation(model.info.policy_len)[:int(n)].astype(np.int32) for n in rng.integers(1, 61, size=batch)]
     out = {"network": f"{game} {depth}x{channels}", "batch": batch, "regions": regions}
-    engines = {name: [capi.Engine(model, 0, batch, dtype) for _ in range(2)] for name, dtype in (("int8", capi.KZ_DTYPE_INT8), ("f16", capi.KZ_DTYPE_F16))}
+    dtypes = {"int8": capi.KZ_DTYPE_INT8, "f16": capi.KZ_DTYPE_F16}
+    if heads:
+        dtypes["int8_heads"] = capi.KZ_DTYPE_INT8_HEADS
+    engines = {name: [capi.Engine(model, 0, batch, dtype) for _ in range(2)] for name, dtype in dtypes.items()}
     out["tower_path"] = {name: e[0].tower_path for name, e in engines.items()}
-    out["launches_per_batch"] = {"int8": model.plan(batch, capi.KZ_DTYPE_INT8)[1], "f16": model.plan(batch, capi.KZ_DTYPE_F16)[1]}
+    out["launches_per_batch"] = {name: model.plan(batch, dtype)[1] for name, dtype in dtypes.items()}
     decoded = {}
     for name, e in engines.items():
         offsets, idx = e[0]._csr(moves)
@@ -125,9 +144,15 @@ def rates(key, regions, seconds):
     resident = {name: Resident(e, bits, scalars, batch, model.info.policy_len) for name, e in engines.items()}
     out["resident"] = interleaved(resident, batch, regions, seconds)
     for boundary in ("decoded", "resident"):
-        out[boundary]["int8_over_f16"] = round(out[boundary]["int8"]["evals_per_s_median"] / out[boundary]["f16"]["evals_per_s_median"], 3)
+        out[boundary]["int8_over_f16"] = ratio(out[boundary], "int8", "f16")[0]
+        if heads:
+            for a, b in (("int8_heads", "int8"), ("int8_heads", "f16")):
+                out[boundary][f"{a}_over_{b}"], out[boundary][f"{a}_over_{b}_regions_min_max"] = ratio(out[boundary], a, b)
+        del out[boundary]["_elapsed"], out[boundary]["_steps"]
     tower = {}
     for name, e in engines.items():
+        if name == "int8_heads":  # (dtype 4's tower, bit for bit: nothing of its own to time)
+            continue
         eng = e[0]
         if eng.tower_path.endswith("+heads"):
             eng = f16_heads_outside(model, batch)
@@ -171,10 +196,13 @@ def main():
     ap.add_argument("--seconds", type=float, default=0.5, help="length of a timed region")
     ap.add_argument("--nets", default="chess,ataxx,go9")
     ap.add_argument("--contract", action="store_true")
+    ap.add_argument("--heads", action="store_true", help="a third engine, dtype 5, and its ratios over dtype 4 and f16")
     ap.add_argument("--out")
     args = ap.parse_args()
     assert capi.device_count() >= 1, "needs a GPU"
-    out = {"tool": "int8_rate", "rates": [rates(k, args.regions, args.seconds) for k in args.nets.split(",") if k]}
+    if args.heads and not args.out:
+        args.out = OUT_HEADS
+    out = {"tool": "int8_rate", "rates": [rates(k, args.regions, args.seconds, args.heads) for k in args.nets.split(",") if k]}
     if args.contract:
         out["contract"] = contract()
     text = json.dumps(out, indent=1)
