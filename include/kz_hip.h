@@ -68,7 +68,10 @@ extern "C" {
                            f16 has 11 (README, "which number is which arithmetic"; kz_engine_set_audit measures it on a
                            network's own positions).  One launch for the tower ("tower_resident_i8"; no "+heads": the f16
                            engine's head kernels follow it) at 256 tower channels on <= 64 squares (two 8x8 boards per
-                           workgroup when max_batch gives 128 such workgroups) and 128 channels on <= 96 squares; a
+                           workgroup when max_batch gives 128 such workgroups) and 128 channels on <= 96 squares (there
+                           wide tiles chosen per launch from its batch: two 8x8 / two 9x9 / four 7x7 / eight 5x5 boards per
+                           workgroup in a batch of 256 such workgroups, else the narrow tiles — measured thresholds,
+                           DESIGN.md 6.2.3; the bits do not depend on it; kz_model_launch_geometry says which); a
                            channel count in between runs widened to the next multiple of 64, as above: 193 .. 255 as 256,
                            65 .. 127 as 128.  64 channels or fewer, 129 .. 192 and more than 256 have no int8 kernel.  kz_engine_create fails, and kz_model_supports_dtype says 0, for
                            an uncalibrated model, every other shape, AttentionTower networks, DenseNetworks and a tower
@@ -84,8 +87,15 @@ extern "C" {
                                  on two streams like every "+heads" plan.  That is 128 tower channels (65 .. 127 widened) on
                                  <= 96 squares and 256 (193 .. 255 widened) on <= 64, a conv policy head with <= 32 planes, a
                                  scalar head of <= 32 channels (one less with extra moves) and <= 256 hidden units, at most
-                                 four boards per workgroup, the tail's floats within 16 KB of LDS; always ONE 8x8 board per
-                                 workgroup at 256 channels (no two-board tiles with the heads inside).  Everywhere else —
+                                 four boards per workgroup on the narrow tiles, the tail's floats within 16 KB of LDS.  Where
+                                 the narrow tiles carry the heads, the launch also takes wide tiles at 128 channels, per
+                                 launch from its batch: dtype 4's levels from 128 such workgroups, and sixteen tiles — three 9x9
+                                 or four 8x8 boards, a level that exists with the heads inside only — from 342, up to the widest
+                                 level whose tail still fits (at most four boards; at sixteen tiles 9,728 B are left for the
+                                 tail: three Go 9x9 boards with the default scalar head fit, four 8x8 boards stay at two per
+                                 workgroup, 5x5 boards at the narrow tiles' four);
+                                 always ONE 8x8 board per workgroup at 256 channels.  kz_model_launch_geometry says which.
+                                 Everywhere else —
                                  attention or dense policy heads, more boards per workgroup — dtype 5 is EXACTLY dtype 4's
                                  plan: same path name, same launches, same bits; a caller can always pass 5.
                                  kz_model_supports_dtype(m, 5) == kz_model_supports_dtype(m, 4) for every model; the refusals
@@ -556,6 +566,9 @@ const char *kz_engine_tower_path(const kz_engine *engine);
 /* How the dominant launch of that path covers the chip for a batch of `batch` boards: workgroups per launch and boards
  * per workgroup (per-layer paths: boards_per_workgroup = 0 when a workgroup holds a tile, not whole boards). */
 int kz_engine_launch_geometry(const kz_engine *engine, int batch, int *workgroups, int *boards_per_workgroup);
+/* The same answer without an engine: what an engine of (max_batch, dtype) on this model reports for `batch` (0 <= batch <=
+ * max_batch).  Host logic like kz_model_plan — no GPU is touched — with kz_model_plan's refusals under this function's name. */
+int kz_model_launch_geometry(const kz_model *model, int max_batch, int dtype, int batch, int *workgroups, int *boards_per_workgroup);
 
 /* ---- debugging / parity: copy an intermediate activation of the last evaluation to the host as f32 NCHW.
  * name: "tower.<i>" as in python/lib/model/post_act.py's nn.Sequential indices (0 = stem, 1..d = blocks,

@@ -105,6 +105,7 @@ SIGNATURES = {
     "kz_engine_destroy": (None, [C.c_void_p]),
     "kz_model_supports_dtype": (C.c_int, [C.c_void_p, C.c_int]),
     "kz_model_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "kz_model_launch_geometry": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "kz_model_stream_shift": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "kz_model_quantize_int8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "kz_model_int8_site_exponents": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -287,6 +288,12 @@ class Model:
         out = PathPlan()
         check(load().kz_model_plan(self._h, max_batch, dtype, C.byref(out)))
         return out.tower_path.decode(), out.launches_per_batch
+
+    def launch_geometry(self, max_batch: int, dtype: int, batch: int):
+        """(workgroups, boards per workgroup) an engine of (max_batch, dtype) reports for `batch` — host logic, no GPU needed."""
+        wgs, per = C.c_int(0), C.c_int(0)
+        check(load().kz_model_launch_geometry(self._h, max_batch, dtype, batch, C.byref(wgs), C.byref(per)))
+        return wgs.value, per.value
 
     def supports_dtype(self, dtype: int) -> bool:
         return load().kz_model_supports_dtype(self._h, dtype) == 1

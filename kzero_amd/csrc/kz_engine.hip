@@ -58,6 +58,37 @@ static void experiment_switches(const Model &m, int dtype, int cin_p, PathPlan &
 #endif
 }
 
+// Workgroups and boards per workgroup of the tower launch of `batch` boards under a plan — pure host logic over the kernels'
+// own rules, so what kz_engine_launch_geometry and kz_model_launch_geometry report is what the launchers launch.  m: the
+// network the kernels run (effective_model), dtype: the engine's arithmetic (f32 or f16) behind the dtype it was asked for.
+static void launch_geometry_of(const Model &m, const PathPlan &p, int dtype, int batch, int *workgroups, int *boards_per_workgroup) {
+    const int cin_p = round_up(m.c_in, 32), cp = round_up(m.channels, 32);
+    int per = 0, wgs = 0;
+    switch (p.tower) {
+        case Tower::dense_net:
+        case Tower::att_valu: per = 1; break;  // a workgroup is a board
+        case Tower::att_mfma: per = kz::att_tower16_boards_per_workgroup(m.channels, m.att_dff, batch, dtype == KZ_DTYPE_F32); break;
+        case Tower::resident_f16: per = cin_p > 32 ? 2 : p.tower_nb; break;
+        case Tower::resident_f32: per = kz::tower32_boards_per_workgroup(m.h, m.w, m.channels); break;
+        case Tower::resident_split16:
+        case Tower::resident_f16g:  // (per launch: the widest level this batch fills the chip with)
+        case Tower::resident_bf16g:
+            per = kz::tower_split_boards_per_workgroup(m.h, m.w, m.channels, split_arithmetic(p), p.wide ? batch : 0);
+            break;
+        case Tower::resident_i8: per = kz::tower_i8_boards_per_workgroup(m.h, m.w, m.channels, p.wide ? batch : 0, p.wide_cap); break;
+        case Tower::board_conv_f16:
+        case Tower::board_conv_split16: wgs = kz::board_conv_workgroups(batch, m.h, m.w, m.channels); break;
+        case Tower::conv_igemm: wgs = kz::conv_workgroups(dtype, batch * m.h * m.w, cp); break;
+    }
+#ifdef KZ_EXPERIMENTS
+    if (p.nb4) per = 4;
+    if (p.t32_dense3) per = 3;
+    if (p.conv2) wgs = kz::board_conv2_workgroups(batch, m.channels);
+#endif
+    if (per) wgs = (batch + per - 1) / per;
+    *workgroups = wgs;
+    *boards_per_workgroup = per;
+}
 
 // ------------------------------------------------------------------------------------------------
 // C ABI
@@ -395,6 +426,24 @@ KZ_API int kz_model_plan(const kz_model *model, int max_batch, int dtype, kz_pat
         memset(out, 0, sizeof *out);
         snprintf(out->tower_path, sizeof out->tower_path, "%s", path_name(plan, dtype));
         out->launches_per_batch = plan.launches;
+        return 0;
+    });
+}
+
+KZ_API int kz_model_launch_geometry(const kz_model *model, int max_batch, int dtype, int batch, int *workgroups, int *boards_per_workgroup) {
+    return guarded("kz_model_launch_geometry", [&]() -> int {
+        if (!model || !workgroups || !boards_per_workgroup) return fail("kz_model_launch_geometry: null argument");
+        if (max_batch <= 0) return fail("kz_model_launch_geometry: max_batch must be positive");
+        if (!known_dtype(dtype)) return fail("kz_model_launch_geometry: unknown dtype");
+        if (batch < 0 || batch > max_batch) return fail("kz_model_launch_geometry: batch out of range");
+        const std::shared_ptr<Model> m = effective_model(model, dtype, max_batch);
+        PathPlan plan;
+        std::string why;
+        if (!plan_path(*m, max_batch, dtype, plan, why)) return fail("kz_model_launch_geometry: " + why);
+        // (what kz_engine_create makes of the dtype: split16 and bf16 are the f32 engine, int8 the f16 engine)
+        const int engine_dtype = dtype == KZ_DTYPE_F32_SPLIT16 || dtype == KZ_DTYPE_BF16 ? KZ_DTYPE_F32 : int8_dtype(dtype) ? KZ_DTYPE_F16 : dtype;
+        experiment_switches(*m, engine_dtype, round_up(m->c_in, 32), plan);
+        launch_geometry_of(*m, plan, engine_dtype, batch, workgroups, boards_per_workgroup);
         return 0;
     });
 }
@@ -788,33 +837,7 @@ KZ_API int kz_engine_launch_geometry(const kz_engine *e, int batch, int *workgro
     return guarded("kz_engine_launch_geometry", [&]() -> int {
         if (!e || !workgroups || !boards_per_workgroup) return fail("kz_engine_launch_geometry: null argument");
         if ((batch < 0 || batch > e->max_batch ? fail("kz_engine_launch_geometry: batch out of range") : 0)) return 1;
-        const Model &m = *e->model;
-        const PathPlan &p = e->plan;
-        int per = 0, wgs = 0;
-        switch (p.tower) {
-            case Tower::dense_net:
-            case Tower::att_valu: per = 1; break;  // a workgroup is a board
-            case Tower::att_mfma: per = kz::att_tower16_boards_per_workgroup(m.channels, m.att_dff, batch, e->dtype == KZ_DTYPE_F32); break;
-            case Tower::resident_f16: per = e->cin_p > 32 ? 2 : p.tower_nb; break;
-            case Tower::resident_f32: per = kz::tower32_boards_per_workgroup(m.h, m.w, m.channels); break;
-            case Tower::resident_split16:
-            case Tower::resident_f16g:  // (per launch: the widest level this batch fills the chip with)
-            case Tower::resident_bf16g:
-                per = kz::tower_split_boards_per_workgroup(m.h, m.w, m.channels, e->split16(), p.wide ? batch : 0);
-                break;
-            case Tower::resident_i8: per = kz::tower_i8_boards_per_workgroup(m.h, m.w, m.channels, p.wide ? batch : 0); break;
-            case Tower::board_conv_f16:
-            case Tower::board_conv_split16: wgs = kz::board_conv_workgroups(batch, m.h, m.w, m.channels); break;
-            case Tower::conv_igemm: wgs = kz::conv_workgroups(e->dtype, batch * m.h * m.w, e->cp); break;
-        }
-    #ifdef KZ_EXPERIMENTS
-        if (p.nb4) per = 4;
-        if (p.t32_dense3) per = 3;
-        if (p.conv2) wgs = kz::board_conv2_workgroups(batch, m.channels);
-    #endif
-        if (per) wgs = (batch + per - 1) / per;
-        *workgroups = wgs;
-        *boards_per_workgroup = per;
+        launch_geometry_of(*e->model, e->plan, e->dtype, batch, workgroups, boards_per_workgroup);
         return 0;
     });
 }

@@ -152,6 +152,7 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         t.dense3 = plan.t32_dense3;
 #endif
         t.wide = plan.wide;
+        t.wide_cap = plan.wide_cap;
         if (range_out) {  // the range profile's engine (resident_f32, no heads): the maxima instead of the tower output
             t.profile = true;
             if (range_hist) t.hist = (unsigned long long *)range_out;  // (the counts instead of the maxima)

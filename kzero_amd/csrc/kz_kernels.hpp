@@ -412,6 +412,8 @@ struct Tower32Args {
     PackedBoards in;
     bool wide = false;    // launch_tower_pairs: twice the boards per workgroup (tower_split_wide_supported) — the engine's
                           // choice at max_batch; a launch whose own batch is too small for it takes the narrow tiles
+    int wide_cap = 0;     // launch_tower_i8 with `wide` and the heads inside: no wide level of more than this many tiles — the
+                          // plan's, so that the launch takes no level whose tail does not fit (0: the tower alone)
     bool dense3 = false;  // launch_tower32, experiment build: three 7x7 boards per workgroup (tower32_dense3_supported)
     bool profile = false; // launch_tower32: the range profile's instance — no heads, no tower output; `y` takes max |x| per
                           // (site, board), [1 + 2*depth][ldy] with ldy counted in boards (>= batch)
@@ -518,11 +520,17 @@ bool launch_tower_bf16(const Tower32Args &a, hipStream_t stream, int *nt = nullp
 // With Tower32Args::Heads of kind conv ("tower_resident_i8+heads", dtype 5 where tower_i8_conv_heads_supported holds) the conv
 // policy heads, the scalar head and decode_output run inside, in f16 as in launch_tower_pairs: `weights` then ends in
 // tower_split_pack_conv_heads (split = false) — C/32 f16 k-steps of the same size as an int8 one —, `bias` has one more row
-// (the policy head's hidden layer's), and Heads::small_w = tower_split_pack_small_weights16; `wide` must be false ----
+// (the policy head's hidden layer's), and Heads::small_w = tower_split_pack_small_weights16.  Tower32Args::wide: the widest
+// wide level this launch's batch fills (128 channels: the plain-f16 family's levels; 256: two 8x8 boards, tower alone), no wider
+// than Tower32Args::wide_cap ----
 bool tower_i8_supported(int h, int w, int channels, int depth, int c_in);  // 128 / 256 tower channels: the table I8_ROWS
-bool tower_i8_wide_supported(int h, int w, int channels, int max_batch);   // 256 channels, 8x8: two boards per workgroup
-bool tower_i8_conv_heads_supported(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs);  // narrow tiles only
-int tower_i8_boards_per_workgroup(int h, int w, int channels, int wide_batch = 0);
+// heads_cap (here and below): 0 = the tower alone; else the heads are inside the launch and no wide level of more than this
+// many tiles of 16 rows is taken (sixteen tiles exist with the heads inside only)
+bool tower_i8_wide_supported(int h, int w, int channels, int max_batch, int heads_cap = 0);
+bool tower_i8_conv_heads_supported(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs);  // on the narrow tiles
+// the widest wide level (its tile count) whose tail takes these heads: the heads_cap of a plan with the heads inside; 0: none
+int tower_i8_conv_heads_wide_cap(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs);
+int tower_i8_boards_per_workgroup(int h, int w, int channels, int wide_batch = 0, int heads_cap = 0);
 size_t tower_i8_layer_bytes(int channels);
 void tower_i8_pack_weights(const int8_t *wq /* [C][C][9], quantised OIHW */, int channels, int8_t *dst);
 bool launch_tower_i8(const Tower32Args &a, const float *mult, const float *qscale, hipStream_t stream, int *nt = nullptr);

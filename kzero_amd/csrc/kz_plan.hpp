@@ -23,8 +23,9 @@
 //   dtype int8 (4):    a calibrated model (kz_model_quantize_int8) of a shape of kz_tower_i8.hip -> tower_resident_i8
 //                      else                                       -> refused (the message says which of the two is missing)
 //   dtype int8 + heads (5): dtype 4's tower; a conv policy head and a scalar head the tail takes on the narrow tiles
-//                      (kz::tower_i8_conv_heads_supported: at most four boards per workgroup) -> tower_resident_i8+heads, one
-//                      launch and never the wide tiles; else                       -> exactly dtype 4's plan
+//                      (kz::tower_i8_conv_heads_supported) -> tower_resident_i8+heads, one launch; else -> exactly dtype 4's plan
+//                      Either takes the wide tiles (more boards per workgroup, chosen per launch from its batch) where
+//                      max_batch fills a wide level; with the heads inside no level wider than the tail fits (wide_cap)
 // ------------------------------------------------------------------------------------------------
 //   AttentionTower (attention.py) instead of the ResTower:
 //     8x8, 8 heads of d_k = d_v = 16, d_model 128 / 256: dtype f16 -> attention_tower_f16, f32 -> attention_tower_f32 (the same
@@ -52,7 +53,8 @@ enum class Tower {
 struct PathPlan {
     Tower tower = Tower::conv_igemm;
     bool heads = false;      // the tower launch runs the heads too ("+heads"), and can end in decode_output
-    bool wide = false;       // resident_f16g with more boards per workgroup (kz::tower_split_wide_supported); resident_i8: tower_i8_wide_supported, never with the heads inside
+    bool wide = false;       // resident_f16g with more boards per workgroup (kz::tower_split_wide_supported); resident_i8: tower_i8_wide_supported
+    int wide_cap = 0;        // resident_i8, wide with the heads inside: the widest wide level whose tail fits, in tiles (0: the tower alone)
     bool att_heads = false;  // heads in launches of their own: ScalarHead + AttentionPolicyHead as one (kz_att_heads.hip)
     bool keep = false;       // KZ_KEEP_ACTIVATIONS: the per-layer path keeps every layer's output
     int tower_nb = 2;        // KZ_TOWER_NB: boards per workgroup of the resident_f16 launch at up to 32 input planes (1 or 2)
@@ -248,12 +250,15 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
         }
         p.tower = Tower::resident_i8;
         p.wide = kz::tower_i8_wide_supported(m.h, m.w, m.channels, max_batch);
-        // one launch per batch — zero-copy slots, the decode inside — is worth more than the two-board tiles (the precedent of
-        // resident_f16g below): with the heads inside the plan is never wide
+        // one launch per batch — zero-copy slots, the decode inside — is worth more than wider tiles (the precedent of
+        // resident_f16g below): the narrow tiles decide `heads`, and the plan is then wide only up to the level whose tail fits
         if (dtype_in == KZ_DTYPE_INT8_HEADS && kz::tower_i8_conv_heads_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels,
                                                                                  m.h, m.w, m.channels, m.sh_conv.cout, m.sh_fc0.out)) {
-            p.wide = false;
             p.heads = true;
+            p.wide_cap = kz::tower_i8_conv_heads_wide_cap((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels, m.h, m.w, m.channels,
+                                                          m.sh_conv.cout, m.sh_fc0.out);
+            p.wide = p.wide_cap != 0 && kz::tower_i8_wide_supported(m.h, m.w, m.channels, max_batch, p.wide_cap);
+            if (!p.wide) p.wide_cap = 0;
         }
     } else if (!force && kz::tower_resident_supported(dtype, m.h, m.w, m.channels, m.depth, m.c_in)) {  // (f16 only)
         p.tower = Tower::resident_f16;

@@ -51,42 +51,83 @@ namespace {
 // ---- which instance a shape takes: tiles of 16 pixel rows per workgroup = floor(16 NT / hw) whole boards packed densely ----
 struct I8Row {
     int c, nt;
-    bool conv_heads;  // compiled with the conv heads' tail (HEADS = 2) too
+    bool conv_heads;    // compiled with the conv heads' tail (HEADS = 2)
+    bool plain = true;  // compiled as the tower alone (HEADS = 0)
 };
 // 256 channels: one 8x8 board (or as many smaller ones as 64 rows hold), two; 128 channels: chess, one Go 9x9 board, two Ataxx
-// 7x7 boards (which straddle tile boundaries)
-// (the heads ride on the narrow tiles only: the wide ones hold two boards of a shape whose one-board launch has them already)
-constexpr I8Row I8_ROWS[] = {{256, 4, true}, {256, 8, false}, {128, 4, true}, {128, 6, true}, {128, 7, true}};
+// 7x7 boards (which straddle tile boundaries), and the wide levels of the plain-f16 family (split_wide_tiles_for,
+// kz_tower_pairs_shapes.hpp): two 8x8 boards in 8 tiles, two 9x9 in 11, four 7x7 or eight 5x5 in 13 — and three 9x9 (or four
+// 8x8) in 16 WITH THE HEADS INSIDE only: the tower alone was measured slower in sixteen tiles than in eleven at every batch
+// (DESIGN.md 6.2.3), so that instance does not exist.  (<256, 8> has no tail: its scratch would not fit behind 148 KB.)
+constexpr I8Row I8_ROWS[] = {{256, 4, true}, {256, 8, false}, {128, 4, true},  {128, 6, true},  {128, 7, true},
+                             {128, 8, true}, {128, 11, true}, {128, 13, true}, {128, 16, true, false}};
 
 constexpr int i8_tiles_for(int hw, int channels) {
     if (channels == 256) return hw <= 64 ? 4 : 0;
     if (channels == 128) return hw * 2 <= 112 ? 7 : hw <= 64 ? 4 : hw <= 96 ? 6 : 0;
     return 0;
 }
-// two 8x8 boards per workgroup at 256 channels (the f16 chess launch's footprint: 32 + 16 + 16 KB per board) when the batch
-// still gives 128 such workgroups — the form of split_wide_tiles_for (kz_tower_pairs_shapes.hpp)
-constexpr int i8_wide_tiles_for(int hw, int channels, int batch) {
-    return channels == 256 && hw == 64 && (batch + 1) / 2 >= 128 ? 8 : 0;
+// Workgroups a wide level must fill before it is taken, measured (the smallest measured batch from which the
+// level beat the next narrower one beyond the regions' spread).  The tower alone: 256 at 128 channels — at 128 workgroups, half
+// the CUs, a launch takes 1.7 times as long —, 128 for the two-board instance at 256 channels, as before.  With the heads
+// inside every workgroup pays its encode and decode round trips to host memory once, and fewer, fuller workgroups win earlier:
+// 128, and 342 for sixteen tiles (Go 9x9 at batch 1024).
+constexpr int I8_WIDE_WORKGROUPS_PLAIN_128 = 256, I8_WIDE_WORKGROUPS_PLAIN_256 = 128;
+constexpr int I8_WIDE_WORKGROUPS_HEADS = 128, I8_WIDE_WORKGROUPS_HEADS_16 = 342;
+// More boards per workgroup: the weight stream is read once per workgroup and layer, and a launch with the heads inside pays
+// its host round trips once per workgroup.  256 channels: two 8x8 boards (the f16 chess launch's footprint), the tower alone.
+// 128 channels: the levels of split_wide_tiles_for.  The widest level that `batch` fills with workgroups is taken.
+// heads_cap: 0 = the tower alone; else the launch has the heads inside and takes no level of more than heads_cap tiles (the
+// plan's: the widest level whose tail fits the LDS, tower_i8_conv_heads_wide_cap)
+constexpr int i8_wide_tiles_for(int hw, int channels, int batch, int heads_cap = 0) {
+    int levels[2] = {0, 0};
+    if (channels == 256) levels[0] = hw == 64 && !heads_cap ? 8 : 0;
+    else if (channels == 128) {
+        if (hw == 64 || hw == 81) {
+            levels[0] = heads_cap ? 16 : 0;
+            levels[1] = hw == 64 ? 8 : 11;
+        } else {
+            levels[0] = (hw == 49 || hw == 25) ? 13 : 0;
+        }
+    }
+    for (int nt : levels) {
+        if (!nt || (heads_cap && nt > heads_cap)) continue;
+        const int per = nt * 16 / hw;
+        const int fill = heads_cap ? (nt == 16 ? I8_WIDE_WORKGROUPS_HEADS_16 : I8_WIDE_WORKGROUPS_HEADS)
+                                   : channels == 256 ? I8_WIDE_WORKGROUPS_PLAIN_256 : I8_WIDE_WORKGROUPS_PLAIN_128;
+        if ((batch + per - 1) / per >= fill) return nt;
+    }
+    return 0;
 }
-constexpr int i8_tiles(int hw, int channels, int wide_batch) {
-    const int nt = wide_batch ? i8_wide_tiles_for(hw, channels, wide_batch) : 0;
+constexpr int i8_tiles(int hw, int channels, int wide_batch, int heads_cap = 0) {
+    const int nt = wide_batch ? i8_wide_tiles_for(hw, channels, wide_batch, heads_cap) : 0;
     return nt ? nt : i8_tiles_for(hw, channels);
 }
 constexpr bool i8_has_row(int channels, int nt, bool conv_heads = false) {
     for (const I8Row &r : I8_ROWS)
-        if (r.c == channels && r.nt == nt && (r.conv_heads || !conv_heads)) return true;
+        if (r.c == channels && r.nt == nt && (conv_heads ? r.conv_heads : r.plain)) return true;
     return false;
 }
-constexpr bool i8_rules_have_rows() {
-    for (int c = 64; c <= 512; c += 64)
-        for (int hw = 1; hw <= 512; hw++)
-            for (int batch : {0, 1, 255, 256, 1 << 20}) {
-                const int nt = i8_tiles(hw, c, batch);
-                if (nt && !i8_has_row(c, nt)) return false;
+// every tile count a rule returns has its row, as the tower alone and under every cap with the heads inside — a rule edited
+// past the table does not build.  (One constant per channel count: the whole sweep in one constant expression is past the
+// compiler's step limit.)
+constexpr bool i8_rules_have_rows(int c) {
+    for (int hw = 1; hw <= 512; hw++) {
+        const int narrow = i8_tiles_for(hw, c);
+        if (narrow && !i8_has_row(c, narrow)) return false;
+        for (int batch : {1, 255, 256, 1024, 4096, 1 << 20})
+            for (int cap : {0, 8, 11, 13, 16}) {
+                const int nt = i8_wide_tiles_for(hw, c, batch, cap);
+                if (nt && (!i8_has_row(c, nt, cap != 0) || (cap && nt > cap))) return false;
             }
+    }
     return true;
 }
-static_assert(i8_rules_have_rows(), "i8_tiles_for / i8_wide_tiles_for return a tile count that has no instance");
+template <int C>
+constexpr bool I8_RULES_HAVE_ROWS = i8_rules_have_rows(C);
+static_assert(I8_RULES_HAVE_ROWS<64> && I8_RULES_HAVE_ROWS<128> && I8_RULES_HAVE_ROWS<192> && I8_RULES_HAVE_ROWS<256> &&
+                  I8_RULES_HAVE_ROWS<320> && I8_RULES_HAVE_ROWS<384> && I8_RULES_HAVE_ROWS<448> && I8_RULES_HAVE_ROWS<512>,
+              "i8_tiles_for / i8_wide_tiles_for return a tile count that has no instance");
 
 constexpr int SG_MFMA = 0x8, SG_VMEM_READ = 0x20, SG_DS_READ = 0x100;
 
@@ -119,8 +160,9 @@ struct GeoI8 {
     static constexpr int LDS_BYTES = Q_OFF + 2 * PLANE;
     static constexpr int STEP = 4 * OT * 64;  // uint4 per k-step: [wave 4][ot][lane 64], the stem's f16 k-steps and the int8 ones alike
     // the ring, as in Geo: at 128 channels a k-step is 8-14 MFMAs and the ring as deep as the registers allow — the nine taps
-    // unrolled, nine stages —; at 256 four stages, one per k-step of a tap
-    static constexpr int PF = G == 2 ? 9 : 4;
+    // unrolled, nine stages —; at 256 four stages, one per k-step of a tap.  Sixteen tiles: a k-step is 32 MFMAs of eight passes,
+    // a thousand cycles, and six stages ask for a fragment three L2 round trips ahead; nine would spill
+    static constexpr int PF = G == 2 ? (NT >= 16 ? 6 : 9) : 4;
     static constexpr int U = G == 2 ? 9 : 1;
     static_assert((U * G) % PF == 0 && (9 * G) % PF == 0, "ring stage of a k-step must be a compile-time constant");
     static_assert(C % 64 == 0 && LDS_BYTES <= 160 * 1024, "LDS budget");
@@ -241,6 +283,9 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
 
     // Validity of (tile row, tap) as bitmasks: bit nt of okmask[tap] says that for this lane's row of tile nt the tap
     // lands on the same board
+    // (sixteen tiles: sixteen bits per tap, two taps to a register — taps 2 i and 2 i + 1 in the halves of okmask[i]; a reader
+    // looks at bit nt < 16 of what ok_of returns and at nothing above it)
+    constexpr int OKW = NT >= 16 ? 5 : 9;
     unsigned okmask[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
     for (int nt = 0; nt < NT; nt++) {
@@ -251,12 +296,22 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
         const unsigned ym[3] = {(unsigned)(yy >= 1), 1u, (unsigned)(yy <= a.h - 2)};
         const unsigned xm[3] = {(unsigned)(xx >= 1), 1u, (unsigned)(xx <= a.w_ - 2)};
 #pragma unroll
-        for (int tap = 0; tap < 9; tap++) okmask[tap] |= (valid & ym[tap / 3] & xm[tap % 3]) << nt;
+        for (int tap = 0; tap < 9; tap++) {
+            const unsigned bit = valid & ym[tap / 3] & xm[tap % 3];
+            if constexpr (OKW == 9) okmask[tap] |= bit << nt;
+            else okmask[tap >> 1] |= bit << (nt + 16 * (tap & 1));
+        }
     }
     __syncthreads();
     auto ok_of = [&](int tap) __attribute__((always_inline)) {
-        return tap == 0   ? okmask[0] : tap == 1 ? okmask[1] : tap == 2 ? okmask[2] : tap == 3 ? okmask[3]
-               : tap == 4 ? okmask[4] : tap == 5 ? okmask[5] : tap == 6 ? okmask[6] : tap == 7 ? okmask[7] : okmask[8];
+        if constexpr (OKW == 9) {
+            return tap == 0   ? okmask[0] : tap == 1 ? okmask[1] : tap == 2 ? okmask[2] : tap == 3 ? okmask[3]
+                   : tap == 4 ? okmask[4] : tap == 5 ? okmask[5] : tap == 6 ? okmask[6] : tap == 7 ? okmask[7] : okmask[8];
+        } else {
+            const int i = tap >> 1;
+            const unsigned pair = i == 0 ? okmask[0] : i == 1 ? okmask[1] : i == 2 ? okmask[2] : i == 3 ? okmask[3] : okmask[4];
+            return pair >> (16 * (tap & 1));
+        }
     };
 
     // per-channel tables of a layer — bias and 2^(e_in + f_oc) of this lane's channels — are fetched a layer ahead: a load that
@@ -271,6 +326,13 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
             mult_next[ot] = *reinterpret_cast<const f32x4 *>(a.mult + l * C + (wave * OT + ot) * 16 + kq * 4);
         }
     };
+    // (sixteen tiles with the heads inside: ONE set — a layer's tables are fetched at the top of its own convolution, eighteen unrolled k-steps of
+    // straight-line code in front of the epilogue that reads them, so the wait for them counts the ring's loads behind them and
+    // drains nothing; sixteen registers the allocator needs there)
+    constexpr bool ONE_TABLE = NT >= 16;
+    static_assert(NT < 16 || HEADS == 2, "sixteen tiles exist with the heads inside only");
+    auto &bias_use = *(ONE_TABLE ? &bias_next : &bias_cur);
+    auto &mult_use = *(ONE_TABLE ? &mult_next : &mult_cur);
     auto take_tables = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int ot = 0; ot < OT; ot++) {
@@ -293,7 +355,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
         for (int ot = 0; ot < OT; ot++)
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) sacc[ot][nt] = bias_next[ot];
-        fetch_tables(1);
+        if constexpr (!ONE_TABLE) fetch_tables(1);
 #pragma nounroll
         for (int ks = 0; ks < 9 * sc; ks++) {
             const int tap = sc == 1 ? ks : ks / sc, chunk = ks - tap * sc;
@@ -342,7 +404,76 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
         for (int nt = 0; nt < NT; nt++) T[nt] = ((ok >> nt) & 1) ? shifted + nt * 16 * RS : zrow;
     };
     i32x4 acc[OT][NT];
+    // Sixteen tiles: the accumulators (128 registers), a double buffer of fragments (128), the ring (72) and two sets of row
+    // addresses (32) leave the register file no room and the allocator spills.  There the fragments live in THREE half
+    // buffers: k-step s holds its tiles in halves 2 s and 2 s + 1 (mod 3), the next step's first half is read into the free
+    // one under the first half's MFMAs and its second half into the half those have consumed; and one set of row addresses
+    // serves — the next tap's replace this tap's in its last k-step, behind their last use.  Same reads, same MFMAs in the
+    // same order per accumulator: the sums are the same integers.
+    constexpr bool HALVES = NT >= 16;
     auto conv_3x3 = [&](int src) __attribute__((always_inline)) {
+      if constexpr (HALVES) {
+        constexpr int H = NT / 2;
+        static_assert(NT % 2 == 0 && (L::U * G) % 3 == 0 && L::U == 9, "the half buffers' roles repeat with the unrolled body, which is a whole convolution");
+        int T[NT];
+        i32x4 hb[3][H];
+        tap_rows(0, src, T);
+        auto rd = [&](int t, int extra) __attribute__((always_inline)) { return *reinterpret_cast<const i32x4 *>(lds + t + extra); };
+#pragma unroll
+        for (int nt = 0; nt < H; nt++) {
+            hb[0][nt] = rd(T[nt], 0);
+            hb[1][nt] = rd(T[H + nt], 0);
+        }
+#pragma unroll
+        for (int tap = 0; tap < 9; tap++) {
+#pragma unroll
+            for (int ch = 0; ch < G; ch++) {
+                const int s = tap * G + ch, stage = s % PF;
+                const int b0 = (2 * s) % 3, b1 = (2 * s + 1) % 3, b2 = (2 * s + 2) % 3;
+                if (ch == G - 1) tap_rows(tap + 1 < 9 ? tap + 1 : tap, src, T);
+                const int extra = ch < G - 1 ? (ch + 1) * 16 : 0;
+#pragma unroll
+                for (int nt = 0; nt < H; nt++) hb[b2][nt] = rd(T[nt], extra);
+                i32x4 af[OT];
+                ring_take(stage, af);
+#pragma unroll
+                for (int nt = 0; nt < H; nt++)
+#pragma unroll
+                    for (int ot = 0; ot < OT; ot++)
+                        acc[ot][nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[ot], hb[b0][nt], acc[ot][nt], 0, 0, 0);
+#pragma unroll
+                for (int nt = 0; nt < H; nt++) hb[b0][nt] = rd(T[H + nt], extra);
+#pragma unroll
+                for (int nt = 0; nt < H; nt++)
+#pragma unroll
+                    for (int ot = 0; ot < OT; ot++)
+                        acc[ot][H + nt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af[ot], hb[b1][nt], acc[ot][H + nt], 0, 0, 0);
+                // the ring refills and the first half's reads each behind an MFMA of the first half; the second half's reads
+                // behind the MFMAs that free their registers; then the remaining MFMAs back to back
+                constexpr int HMF = OT * H;
+                static_assert(OT + H <= HMF, "a half's MFMAs cover the ring refills and a half's reads");
+#pragma unroll
+                for (int i = 0; i < OT; i++) {
+                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(SG_VMEM_READ, 1, 0);
+                }
+#pragma unroll
+                for (int i = 0; i < H; i++) {
+                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(SG_MFMA, HMF - OT - H, 0);
+#pragma unroll
+                for (int i = 0; i < H; i++) {
+                    __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(SG_MFMA, HMF - H, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                g++;
+            }
+        }
+      } else {
         int T[NT], Tn[NT];
         i32x4 bf[2][NT];
         tap_rows(0, src, T);
@@ -388,14 +519,19 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
 #pragma unroll
             for (int nt = 0; nt < NT; nt++) T[nt] = Tn[nt];
         }
+      }
     };
     static_assert(G % 2 == 0, "the double buffer's parity is a tap's own: an even number of k-steps per tap");
 
     // ---- the 2*depth 3x3 convolutions ----
     for (int layer = 1; layer <= layers; layer++) {
         const bool is_b = (layer & 1) == 0;  // conv A: X8 -> Y8; conv B: Y8 -> X, X8 (+ residual)
-        take_tables();
-        fetch_tables(layer + 1);
+        if constexpr (ONE_TABLE) {
+            fetch_tables(layer);
+        } else {
+            take_tables();
+            fetch_tables(layer + 1);
+        }
 #pragma unroll
         for (int ot = 0; ot < OT; ot++)
 #pragma unroll
@@ -414,7 +550,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
                 f32x4 v;
 #pragma unroll
                 for (int j = 0; j < 4; j++) {
-                    v[j] = (float)acc[ot][nt][j] * mult_cur[ot][j] + bias_cur[ot][j];
+                    v[j] = (float)acc[ot][nt][j] * mult_use[ot][j] + bias_use[ot][j];
                     v[j] = v[j] > 0.0f ? v[j] : 0.0f;
                 }
                 if (!is_b) {
@@ -451,12 +587,13 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
         static_assert((9 * G) % PF == 0, "the head pass starts at ring stage 0");
         const int kx_off = 2 * ((C / 2) * (kq & 1) + (C / 4) * (kq >> 1));
         // The policy head's hidden layer, Conv1x1 C->C + ReLU: one more pass of the weight ring over X into YH
-        take_tables();
+        if constexpr (ONE_TABLE) fetch_tables(layers + 1);  // (read at once: the one drain of the ring per launch)
+        else take_tables();
         f32x4 hacc[OT][NT];
 #pragma unroll
         for (int ot = 0; ot < OT; ot++)
 #pragma unroll
-            for (int nt = 0; nt < NT; nt++) hacc[ot][nt] = bias_cur[ot];
+            for (int nt = 0; nt < NT; nt++) hacc[ot][nt] = bias_use[ot];
 #pragma unroll
         for (int ch = 0; ch < GH; ch++) {
             h16x8 bh[NT];
@@ -536,9 +673,12 @@ bool launch_row(std::index_sequence<I...>, int channels, int nt, bool conv_heads
     return (... || [&] {
         constexpr I8Row R = I8_ROWS[I];
         if (R.c != channels || R.nt != nt) return false;
-        if (!conv_heads) launch<R.c, R.nt>(d, grid, stream);
-        else if constexpr (R.conv_heads) launch<R.c, R.nt, 2>(d, grid, stream);
-        return !conv_heads || R.conv_heads;
+        if (!conv_heads) {
+            if constexpr (R.plain) launch<R.c, R.nt>(d, grid, stream);
+            return R.plain;
+        }
+        if constexpr (R.conv_heads) launch<R.c, R.nt, 2>(d, grid, stream);
+        return R.conv_heads;
     }());
 }
 
@@ -552,20 +692,36 @@ bool tower_i8_supported(int h, int w, int channels, int depth, int c_in) {
            i8_tiles_for(h * w, channels) != 0;
 }
 
-bool tower_i8_wide_supported(int h, int w, int channels, int max_batch) {
-    return i8_tiles_for(h * w, channels) != 0 && i8_wide_tiles_for(h * w, channels, max_batch) != 0;
+bool tower_i8_wide_supported(int h, int w, int channels, int max_batch, int heads_cap) {
+    return i8_tiles_for(h * w, channels) != 0 && i8_wide_tiles_for(h * w, channels, max_batch, heads_cap) != 0;
 }
 
-int tower_i8_boards_per_workgroup(int h, int w, int channels, int wide_batch) {
-    const int nt = i8_tiles(h * w, channels, wide_batch);
+int tower_i8_boards_per_workgroup(int h, int w, int channels, int wide_batch, int heads_cap) {
+    const int nt = i8_tiles(h * w, channels, wide_batch, heads_cap);
     return nt ? nt * 16 / (h * w) : 0;
 }
 
-// kz_conv_heads.hpp behind the narrow tiles (never the wide ones: one launch per batch before two boards per workgroup)
-bool tower_i8_conv_heads_supported(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs) {
-    const int nt = i8_tiles_for(h * w, channels);
+namespace {
+bool i8_tail_fits(int nt, int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs) {
     if (!nt || !i8_has_row(channels, nt, true)) return false;
     return conv_heads_fit(nt, policy_kind, extra_moves, pc, h, w, channels, hc, hs, (size_t)i8_tail_scratch_bytes(channels, nt));
+}
+}  // namespace
+
+// kz_conv_heads.hpp behind the narrow tiles: what decides whether the launch carries the heads at all
+bool tower_i8_conv_heads_supported(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs) {
+    return i8_tail_fits(i8_tiles_for(h * w, channels), policy_kind, extra_moves, pc, h, w, channels, hc, hs);
+}
+
+// ... and behind the wide ones: the tile count of the widest wide level of this shape whose tail fits (at most four boards, its
+// floats within the scratch left behind that level's own LDS), 0 if none does.  A level is asked at a batch that selects it.
+int tower_i8_conv_heads_wide_cap(int policy_kind, int extra_moves, int pc, int h, int w, int channels, int hc, int hs) {
+    for (int cap = 16; cap >= 8; cap--) {
+        const int nt = i8_wide_tiles_for(h * w, channels, 1 << 20, cap);
+        if (nt != cap) continue;  // (no level of exactly `cap` tiles)
+        if (i8_tail_fits(nt, policy_kind, extra_moves, pc, h, w, channels, hc, hs)) return nt;
+    }
+    return 0;
 }
 
 size_t tower_i8_layer_bytes(int channels) { return (size_t)9 * channels * channels; }
@@ -610,7 +766,7 @@ bool launch_tower_i8(const Tower32Args &t, const float *mult, const float *qscal
     d.w_ = t.w;
     d.hw = t.h * t.w;
     d.stem_chunks = (t.c_in + 31) / 32;
-    const int nt = i8_tiles(d.hw, t.channels, t.wide ? t.batch : 0);
+    const int nt = i8_tiles(d.hw, t.channels, t.wide ? t.batch : 0, t.wide_cap);  // (wide_cap != 0: the heads are inside)
     if (nt_out) *nt_out = nt;
     if (!nt) return false;
     d.nb = nt * 16 / d.hw;

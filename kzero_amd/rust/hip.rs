@@ -119,6 +119,7 @@ extern "C" {
     fn kz_engine_destroy(engine: *mut c_void);
     fn kz_model_supports_dtype(model: *const c_void, dtype: c_int) -> c_int;
     fn kz_model_plan(model: *const c_void, max_batch: c_int, dtype: c_int, out: *mut KzPathPlan) -> c_int;
+    fn kz_model_launch_geometry(model: *const c_void, max_batch: c_int, dtype: c_int, batch: c_int, workgroups: *mut c_int, boards_per_workgroup: *mut c_int) -> c_int;
     // stream shift (a new model: the same function, the residual stream 2^-k times as large) and the exact-f32 range profile
     fn kz_model_stream_shift(model: *const c_void, k: c_int, out: *mut *mut c_void) -> c_int;
     // int8 calibration (a new model: the same tensors with an exponent per range site beside them; the only kind dtype 4 takes).
@@ -381,6 +382,13 @@ impl HipModel {
             }
         });
         hist
+    }
+
+    /// (workgroups, boards per workgroup) an engine of (max_batch, dtype) reports for `batch` (`kz_model_launch_geometry`; no GPU).
+    pub fn launch_geometry(&self, max_batch: usize, dtype: i32, batch: usize) -> (usize, usize) {
+        let (mut wgs, mut per) = (0, 0);
+        check(unsafe { kz_model_launch_geometry(self.ptr, max_batch as c_int, dtype as c_int, batch as c_int, &mut wgs, &mut per) });
+        (wgs as usize, per as usize)
     }
 
     /// The kernel a tap call runs: `kz_model_plan(max_batch, dtype)`'s tower without "+heads" (`kz_model_tower_taps_path`; no GPU).

@@ -19,8 +19,15 @@ ratio of a region of the one to the region of the other that ran beside it (`*_r
 kernels are untouched by dtype 5, so "5 over 4" in one process is the comparison with the library before dtype 5.  On a network
 whose heads the int8 launch cannot carry (chess) dtype 5 is dtype 4's plan and the ratio is 1 within that spread.
 
-Networks and batches: README's rows — chess 20x256 at 256, Ataxx 7x7 8x128 at 256, Go 9x9 16x128 at 2048.  The model is
+Networks and batches: README's rows — chess 20x256 at 256, Ataxx 7x7 8x128 at 256, Go 9x9 16x128 at 2048 —, and chess128
+(chess 20x128, attention head: the tower alone in either int8 dtype).  --batches 512,1024,... runs every network of --nets at
+each of these batches instead of its own (the wide tiles are chosen per launch from its batch: DESIGN.md 6.2.3); every row
+records the launch geometry of each engine at its batch.  The model is
 calibrated on a disjoint board sample (capi.calibrate_int8, headroom 2); the rate does not depend on the calibration.
+
+Against another build of the library (the parent commit's, built in a worktree of its own): run this tool in a second process
+with KZ_LIB_PATH pointing at that build, alternating the two processes; the f16 engine's rate, whose kernels are the same in
+both, is the drift check between them.
 
 --contract adds what the int8 arithmetic costs in precision on chess 20x256 at batch 256 against the CPU oracle
 (tests/oracle_lib.py), calibrated on a disjoint sample: max |delta| / scale and rms / scale per board and output tensor, and the
@@ -45,7 +52,7 @@ from kzero_amd import benchlib, capi, synth  # noqa: E402
 from bf16_rate import Loop  # noqa: E402  (one engine's four-slot loop of the decoded entries)
 
 NETS = {"chess": ("chess", 20, 256, "attention", 256), "ataxx": ("ataxx-7", 8, 128, "ataxx_conv", 256),
-        "go9": ("go-9", 16, 128, "conv", 2048)}
+        "go9": ("go-9", 16, 128, "conv", 2048), "chess128": ("chess", 20, 128, "attention", 256)}
 OUT_HEADS = os.path.join(REPO, "profiles", "int8_heads_rate.json")
 KERNEL = {"tower_resident_i8": "kz_tower_resident_i8", "tower_resident_f16": "kz_tower_resident_f16",
           "tower_resident_f16g": "kz_tower_resident_f16g"}
@@ -123,8 +130,9 @@ def ratio(result, a, b):
     return round(result[a]["evals_per_s_median"] / result[b]["evals_per_s_median"], 3), [round(min(per_region), 3), round(max(per_region), 3)]
 
 
-def rates(key, regions, seconds, heads=False):
-    game, depth, channels, head, batch = NETS[key]
+def rates(key, regions, seconds, heads=False, batch=None):
+    game, depth, channels, head, own_batch = NETS[key]
+    batch = batch or own_batch
     model = calibrated(game, depth, channels, head)
     rng = np.random.default_rng(1)
     bits, scalars = synth.random_boards(game, batch, seed=2)
@@ -136,6 +144,7 @@ def rates(key, regions, seconds, heads=False):
     engines = {name: [capi.Engine(model, 0, batch, dtype) for _ in range(2)] for name, dtype in dtypes.items()}
     out["tower_path"] = {name: e[0].tower_path for name, e in engines.items()}
     out["launches_per_batch"] = {name: model.plan(batch, dtype)[1] for name, dtype in dtypes.items()}
+    out["launch_geometry"] = {name: list(e[0].launch_geometry(batch)) for name, e in engines.items()}  # [workgroups, boards per workgroup]
     decoded = {}
     for name, e in engines.items():
         offsets, idx = e[0]._csr(moves)
@@ -195,6 +204,7 @@ def main():
     ap.add_argument("--regions", type=int, default=7)
     ap.add_argument("--seconds", type=float, default=0.5, help="length of a timed region")
     ap.add_argument("--nets", default="chess,ataxx,go9")
+    ap.add_argument("--batches", help="comma-separated batch sizes: every network at each of them instead of its own")
     ap.add_argument("--contract", action="store_true")
     ap.add_argument("--heads", action="store_true", help="a third engine, dtype 5, and its ratios over dtype 4 and f16")
     ap.add_argument("--out")
@@ -202,7 +212,9 @@ def main():
     assert capi.device_count() >= 1, "needs a GPU"
     if args.heads and not args.out:
         args.out = OUT_HEADS
-    out = {"tool": "int8_rate", "rates": [rates(k, args.regions, args.seconds, args.heads) for k in args.nets.split(",") if k]}
+    batches = [int(b) for b in args.batches.split(",") if b] if args.batches else [None]
+    out = {"tool": "int8_rate", "library": os.path.relpath(capi.LIB_PATH, REPO),
+           "rates": [rates(k, args.regions, args.seconds, args.heads, b) for k in args.nets.split(",") if k for b in batches]}
     if args.contract:
         out["contract"] = contract()
     text = json.dumps(out, indent=1)
