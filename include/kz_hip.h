@@ -101,6 +101,30 @@ extern "C" {
                                  kz_model_supports_dtype(m, 5) == kz_model_supports_dtype(m, 4) for every model; the refusals
                                  are dtype 4's with "dtype 5" in them (an uncalibrated model: first of all an unknown dtype 5);
                                  it reads none of the environment switches; the taps and the error profile refuse it */
+/* (6 and 7 are not dtypes: they stay unknown, like every other value not defined here.) */
+#define KZ_DTYPE_INT8_ANY 8 /* KZ_DTYPE_INT8_HEADS with a per-layer int8 kernel behind it.  On a calibrated ResTower model it is
+                               EXACTLY dtype 5's plan wherever dtype 5 has one: same path name, same launches, same bits.  Where
+                               dtype 5 refuses the shape — Go 19x19 and 13x13, Go 9x9 at 256 channels, a tower above 256
+                               channels, of 64 or fewer, of 129 .. 192 — it is "board_conv_i8": one launch per layer
+                               (kz_board_conv_i8, the board-tile kernel of "board_conv_f16" on v_mfma_i32_16x16x64_i8), the
+                               arithmetic of "int8 calibration" below to the bit, which is stated per convolution and does not
+                               depend on the geometry.  The stem is the f16 board-tile stem with two stores from one f32 v:
+                               f16(v) for the residual stream and quant(v, e_0).  That plan takes a tower with at least one
+                               block on a board of 2 .. 32 squares a side that fits a workgroup of the board-tile kernels (24
+                               tiles of 16 squares, the halo image within its LDS) and at most 512 channels after widening; it
+                               has NO minimum of workgroups (the alternative is a refusal, not another kernel).  CHANNELS: the
+                               int8 images hold the tower widened to the next multiple of 128, a chunk of the kernel, by
+                               all-zero filters (f = 0, bias 0; every widened channel of every image is 0, same outputs): 64
+                               or fewer run as 128, 129 .. 256 as 256, up to 512; the f16 stream keeps the f16 engine's rows.
+                               The tensors around the tower are f16, as for dtype 4: the f16 engine's encode, head kernels
+                               and decode run around it (no "+heads"), and symmetries, per-board status, range fallback, audit
+                               and every entry point work as for dtype 4.  Refusals are dtype 4's with "dtype 8" in them (an
+                               uncalibrated model: first of all an unknown dtype 8); it reads none of the environment
+                               switches; the taps and the error profile refuse it.  kz_model_launch_geometry reports the
+                               per-layer plan's workgroups (64 output channels of the widened tower per workgroup).  SPEED, measured against the
+                               f16 engine of the same build in the same process (README, "which number is which arithmetic";
+                               profiles/int8_board_rate.json): Go 19x19 40x256 at batch 512 1.51 of f16 through the decoded
+                               entries, Go 9x9 16x256 at 2048 1.37 — at 7 bits and a sign per stored activation */
 
 #define KZ_POLICY_ATAXX_CONV 0 /* AtaxxConvPolicyHead, python/lib/model/post_act.py:91-112 */
 #define KZ_POLICY_CONV 1       /* ConvPolicyHead,      post_act.py:54-88 */

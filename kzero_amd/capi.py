@@ -16,6 +16,7 @@ KZ_DTYPE_F16 = 1
 KZ_DTYPE_F32_SPLIT16 = 2
 KZ_DTYPE_BF16 = 3  # f32 tensors, the tower in bf16 (f32 range at the f16 rate, 8 significant bits)
 KZ_DTYPE_INT8 = 4  # f16 tensors, the tower's block convolutions on the i8 matrix cores: a calibrated model only (Model.quantize_int8)
+KZ_DTYPE_INT8_ANY = 8  # dtype 5's plan wherever it has one; elsewhere (Go 19x19, 13x13, 9x9 at 256, other widths up to 512) "board_conv_i8", one int8 launch per layer; 6 and 7 stay unknown
 KZ_DTYPE_INT8_HEADS = 5  # dtype 4's tower with the conv policy heads, the scalar head and the decode inside its launch where it can carry them; elsewhere dtype 4's plan
 KZ_ENGINE_SLOTS = 4
 # per-board status bits (kz_engine_wait_decoded_status / kz_engine_eval_packed_decoded_status)

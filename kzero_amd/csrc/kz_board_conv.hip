@@ -742,6 +742,11 @@ bool board_conv_supported(int dtype, int h, int w, int cin, int cout) {
            geometry(h, w).bpw >= 1;
 }
 
+BoardConvGeometry board_conv_geometry(int h, int w) {
+    const Geometry g = geometry(h, w);
+    return BoardConvGeometry{g.tpb, g.bpw, g.pitch, g.skew16, g.line16, g.board16, g.plane, g.rm_off};
+}
+
 int board_conv_workgroups(int boards, int h, int w, int cout) {
     const int bpw = geometry(h, w).bpw;
     return bpw ? ((boards + bpw - 1) / bpw) * (cout / OCW) : 0;

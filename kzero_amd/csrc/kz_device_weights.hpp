@@ -52,6 +52,17 @@ struct DeviceWeights {
     bool conv2 = false;  // (experiment build, spec.conv2) the board-tile layers go through kz_board_conv2_f16 ...
     int *bc_rowmap = nullptr, bc_n_halo = 0;  // ... with its tile-row map and halo-row list
     unsigned short *bc_halo = nullptr;
+    // board_conv_i8 (kz_board_conv_i8.hip): per convolution the packed stream (the stem's in f16, the block convolutions' in
+    // int8), bias and multiplier 2^(e_in + f_oc) over the widened channels [C8], and 2^-e of the site its int8 image is stored
+    // at; the final BatchNorm over [C8]
+    struct I8Conv {
+        void *w = nullptr;
+        float *bias = nullptr, *mult = nullptr;
+        float qscale = 1.0f;
+    };
+    std::vector<I8Conv> i8conv;
+    float *post8_scale = nullptr, *post8_shift = nullptr;
+    int c8 = 0;
     // every tower but the dense network: the final BatchNorm, [round_up(C, 32)]
     float *post_scale = nullptr, *post_shift = nullptr;
     // the one-launch ResTowers.  resident_f32, resident_split16, resident_f16g, resident_bf16g: w32 and bias (and small where
@@ -341,6 +352,52 @@ struct DeviceWeights {
         st.take(std::move(qscale), &res.qscale);
         st.take(std::move(packed), &res.w32);
     }
+    // board_conv_i8 (a calibrated model), one convolution per call like pack_per_layer: the tower widened to C8 channels by
+    // all-zero filters.  i = 0: the stem for the f16 board-tile instance, its input planes padded to chunks of 64 (the encode
+    // kernel then writes rows of that many channels); i >= 1: wq and f_oc exactly as pack_i8 computes them, the multiplier
+    // table 2^(e_in + f_oc) beside the bias (1 and 0 on a widened channel)
+    void pack_board_i8(const Model &m, size_t i, Staged &st) {
+        const int C = m.channels, C8 = kz::board_conv_i8_channels(C), layers = 2 * m.depth;
+        if (i == 0) {
+            i8conv.resize(m.tower.size());
+            c8 = C8;
+            std::vector<float> ps(C8, 1.0f), pt(C8, 0.0f);
+            std::copy(m.final_scale.begin(), m.final_scale.begin() + C, ps.begin());
+            std::copy(m.final_shift.begin(), m.final_shift.begin() + C, pt.begin());
+            st.take(std::move(ps), &post8_scale);
+            st.take(std::move(pt), &post8_shift);
+        }
+        I8Conv &d = i8conv[i];
+        const Conv &cv = m.tower[i];
+        std::vector<float> bias(C8, 0.0f), mult(C8, 1.0f);
+        std::copy(cv.b.begin(), cv.b.begin() + C, bias.begin());
+        if (i == 0) {
+            const int cin = stem_cin_p = round_up(cv.cin, 64);
+            std::vector<float> w((size_t)C8 * cin * 9, 0.0f);
+            for (int o = 0; o < C; o++)
+                std::copy(cv.w.begin() + (size_t)o * cv.cin * 9, cv.w.begin() + (size_t)(o + 1) * cv.cin * 9, w.begin() + (size_t)o * cin * 9);
+            std::vector<uint16_t> packed(kz::board_conv_weight_elems(cin, C8));
+            kz::board_conv_pack_weights(w.data(), C8, cin, packed.data());
+            st.take(std::move(packed), &d.w);
+        } else {
+            const int e_in = m.i8_exp[i - 1];
+            std::vector<int8_t> wq((size_t)C * C * 9);
+            for (int oc = 0; oc < C; oc++) {
+                const float *row = cv.w.data() + (size_t)oc * C * 9;
+                float top = 0.0f;
+                for (int k = 0; k < C * 9; k++) top = std::max(top, std::fabs(row[k]));
+                const int f = top > 0.0f ? kz::i8_exponent(top) : 0;
+                for (int k = 0; k < C * 9; k++) wq[(size_t)oc * C * 9 + k] = (int8_t)std::nearbyint(std::ldexp((double)row[k], -f));
+                mult[oc] = std::ldexp(1.0f, e_in + f);
+            }
+            std::vector<int8_t> packed(kz::board_conv_i8_weight_bytes(C8, C8));
+            kz::board_conv_i8_pack_weights(wq.data(), C, C, C8, C8, packed.data());
+            st.take(std::move(packed), &d.w);
+        }
+        if ((int)i < layers) d.qscale = std::ldexp(1.0f, -m.i8_exp[i]);  // (the last range site is not quantised)
+        st.take(std::move(bias), &d.bias);
+        st.take(std::move(mult), &d.mult);
+    }
     // resident_f32.  (The conv policy head's first 1x1 conv rides at the end of the stream whenever the launch can fuse the
     // heads — weights_spec says so; a launch without heads never reads it)
     void pack_resident_f32(const Model &m, const WeightsSpec &s, Staged &st) {
@@ -482,6 +539,12 @@ struct DeviceWeights {
             case Tower::resident_i8: pack_i8(m, s, st); break;
             case Tower::resident_f32: pack_resident_f32(m, s, st); break;
             case Tower::resident_f16: pack_resident_f16(m, s, st); break;
+            case Tower::board_conv_i8:
+                for (size_t i = 0; i < m.tower.size(); i++) {
+                    pack_board_i8(m, i, st);
+                    if (upload(st)) return 1;
+                }
+                break;
             default:
                 for (size_t i = 0; i < m.tower.size(); i++) {
                     pack_per_layer(m, s, i, st);

@@ -78,6 +78,7 @@ static void launch_geometry_of(const Model &m, const PathPlan &p, int dtype, int
         case Tower::resident_i8: per = kz::tower_i8_boards_per_workgroup(m.h, m.w, m.channels, p.wide ? batch : 0, p.wide_cap); break;
         case Tower::board_conv_f16:
         case Tower::board_conv_split16: wgs = kz::board_conv_workgroups(batch, m.h, m.w, m.channels); break;
+        case Tower::board_conv_i8: wgs = kz::board_conv_workgroups(batch, m.h, m.w, kz::board_conv_i8_channels(m.channels)); break;
         case Tower::conv_igemm: wgs = kz::conv_workgroups(dtype, batch * m.h * m.w, cp); break;
     }
 #ifdef KZ_EXPERIMENTS
@@ -351,6 +352,10 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
     #endif
         for (int i = 0; i < (per_layer(plan) ? 3 : 1); i++)
             if (e->dmalloc(&e->act[i], rows * e->cp * e->esz)) return 1;
+        if (plan.tower == Tower::board_conv_i8) {  // (within the 2 GiB bound checked above: C8 <= 4 * round_up(channels, 64))
+            for (int i = 0; i < 2; i++)
+                if (e->dmalloc(&e->act8[i], rows * e->wts->c8)) return 1;
+        }
         if (e->dmalloc(&e->head0, h0 * e->esz) || e->dmalloc(&e->head1, h1 * e->esz)) return 1;
 
         const int nb_planes = m.n_bool < 0 ? 0 : m.n_bool, ns_planes = m.n_scalar < 0 ? 0 : m.n_scalar;

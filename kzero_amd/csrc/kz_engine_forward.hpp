@@ -206,6 +206,32 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         tower_out = cur;
         return 0;
     }
+    if (plan.tower == Tower::board_conv_i8) {
+        // the f16 stem storing the stream and X8, then per block conv A: X8 -> Y8 and conv B: Y8 (+ the f16 stream) -> the
+        // stream and X8; the last conv B writes the f16 tower output alone, behind the final BN
+        const int C8 = wts->c8;
+        const auto i8conv = [&](int l, const void *x, const void *res, void *y16, void *y8, bool post) {
+            const DeviceWeights::I8Conv &w = wts->i8conv[l];
+            kz::BoardConvI8Args b{};
+            b.stem = l == 0;
+            b.x = x; b.weights = w.w; b.bias = w.bias; b.mult = w.mult; b.res = res; b.y16 = y16; b.y8 = y8; b.qscale = w.qscale;
+            b.post_scale = post ? wts->post8_scale : nullptr;
+            b.post_shift = post ? wts->post8_shift : nullptr;
+            b.ld16 = cp; b.boards = batch; b.h = m.h; b.w = m.w; b.cin = l == 0 ? cin_p : C8; b.cout = C8; b.relu = l != 0;
+            return launch(p, l == 0 ? "kz_board_conv_i8_stem" : "kz_board_conv_i8", [&] { kz::launch_board_conv_i8(b, p.stream); });
+        };
+        if (i8conv(0, x_in, nullptr, act[0], act8[0], false)) return 1;
+        int cur = 0;
+        for (int i = 1; i <= m.depth; i++) {
+            const int nxt = (cur + 1) % 3;
+            const bool last = i == m.depth;
+            if (i8conv(2 * i - 1, act8[0], nullptr, nullptr, act8[1], false)) return 1;
+            if (i8conv(2 * i, act8[1], act[cur], act[nxt], last ? nullptr : act8[0], last)) return 1;
+            cur = nxt;
+        }
+        tower_out = cur;
+        return 0;
+    }
     // stem: conv + bias, no activation (post_act.py:205)
     range_site = 0;
     if (conv(p, wts->tower[0], x_in, cin_p, act[0], cp, M, 0, nullptr, m.depth == 0, m.h, m.w, hw, hw, 0)) return 1;

@@ -162,7 +162,7 @@ struct kz_engine {
     PathPlan plan;  // which kernels run the network (plan_path, then the experiment build's switches)
     bool split16() const { return split_arithmetic(plan); }
     bool bf16() const { return plan.tower == Tower::resident_bf16g; }
-    bool i8() const { return plan.tower == Tower::resident_i8; }
+    bool i8() const { return plan.tower == Tower::resident_i8 || plan.tower == Tower::board_conv_i8; }
     // the dtype kz_engine_create was given (`dtype` is KZ_DTYPE_F32 for the two f32 engines with an exchanged tower, and
     // KZ_DTYPE_F16 for the int8 engines, 4 and 5: the f16 engine with it exchanged — which of the two the plan does not say
     // where 5 plans as 4 does, so the engine keeps the value it was created with)
@@ -174,6 +174,7 @@ struct kz_engine {
     int cin_p = 0, cp = 0;
     void *x_in = nullptr;
     void *act[3] = {nullptr, nullptr, nullptr};
+    void *act8[2] = {nullptr, nullptr};  // board_conv_i8: the int8 images X8 and Y8 beside the f16 stream, [rows][C8] bytes each
     void *head0 = nullptr, *head1 = nullptr;  // head temporaries
     int tower_out = 0;
 

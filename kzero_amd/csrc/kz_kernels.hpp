@@ -316,6 +316,34 @@ void board_conv_split_pack_weights(const float *oihw, int cout, int cin, uint16_
 void launch_board_conv_split(const BoardConvArgs &a, hipStream_t stream);
 // f32 [rows][c] -> [rows][c / 32][hi 32 | lo 32] f16 (hi = f16(x), lo = f16(x - hi)): the stem's output enters the split layers
 void launch_split_rows(const float *x, void *y, size_t rows, int c, hipStream_t stream);
+// the halo image of the board-tile kernels, for the translation units that share it (kz_board_conv_i8.hip): tiles per board,
+// boards per workgroup (0: the board fits no workgroup), 16-byte slots per line and board, bytes per plane, and where the
+// image (or the f16 output tile, if longer) ends
+struct BoardConvGeometry {
+    int tpb, bpw, pitch, skew16, line16, board16, plane, rm_off;
+};
+BoardConvGeometry board_conv_geometry(int h, int w);
+// ---- the same organisation on the i8 matrix cores (kz_board_conv_i8.hip: "board_conv_i8", KZ_DTYPE_INT8_ANY on a calibrated
+// model the one-launch int8 tower refuses): int8 images [boards*h*w][C8], C8 = board_conv_i8_channels(C) = the next multiple
+// of 128 (all-zero filters), beside the f16 engine's residual stream [boards*h*w][ld16]. ----
+struct BoardConvI8Args {
+    bool stem = false;     // the f16 stem (x: f16 rows of cin channels, a multiple of 64; board_conv_pack_weights) storing f16(v)
+                           // and quant(v); else a block convolution (x: int8 rows of cin = C8 channels)
+    const void *x;
+    const void *weights;   // board_conv_i8_pack_weights layout (the stem: board_conv_pack_weights)
+    const float *bias, *mult;                // [cout]; mult: 2^(e_in + f_oc), block convolutions only
+    const float *post_scale = nullptr, *post_shift = nullptr;  // [cout]: the final BN (the last conv B)
+    const void *res = nullptr;  // optional f16 residual [boards*h*w][ld16], added in f32 after the ReLU
+    void *y16 = nullptr;        // optional f16 rows out [boards*h*w][ld16] (channels >= ld16 are dropped)
+    void *y8 = nullptr;         // optional int8 image out [boards*h*w][cout] = clamp(rne(v * qscale), -127, 127)
+    float qscale = 1.0f;
+    int ld16, boards, h, w, cin, cout, relu;  // cout = C8
+};
+int board_conv_i8_channels(int channels);
+bool board_conv_i8_supported(int h, int w, int channels);
+size_t board_conv_i8_weight_bytes(int cin8, int cout8);
+void board_conv_i8_pack_weights(const int8_t *wq, int cout, int cin, int cout8, int cin8, int8_t *dst);
+void launch_board_conv_i8(const BoardConvI8Args &a, hipStream_t stream);
 // second organisation for boards of 193..384 squares (Go 19x19): two boards per workgroup, one workgroup per CU, staging
 // under the MFMAs (kz_board_conv2.hip).  Same BoardConvArgs, with its own weight packing and tables.
 bool board_conv2_supported(int dtype, int h, int w, int cin, int cout);

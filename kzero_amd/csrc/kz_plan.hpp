@@ -26,6 +26,11 @@
 //                      (kz::tower_i8_conv_heads_supported) -> tower_resident_i8+heads, one launch; else -> exactly dtype 4's plan
 //                      Either takes the wide tiles (more boards per workgroup, chosen per launch from its batch) where
 //                      max_batch fills a wide level; with the heads inside no level wider than the tail fits (wide_cap)
+//   dtype int8, any shape (8): exactly dtype 5's plan wherever dtype 5 has one; else, on a calibrated model with at least one
+//                      block, a board of 2 .. 32 squares a side that fits a workgroup of the board-tile kernels and at most
+//                      512 channels once widened to a multiple of 128 -> board_conv_i8 (one launch per layer, the f16
+//                      engine's encode and heads around it; NO >= 160-workgroup condition: the alternative is a refusal)
+//                      else                                       -> refused
 // ------------------------------------------------------------------------------------------------
 //   AttentionTower (attention.py) instead of the ResTower:
 //     8x8, 8 heads of d_k = d_v = 16, d_model 128 / 256: dtype f16 -> attention_tower_f16, f32 -> attention_tower_f32 (the same
@@ -47,6 +52,7 @@ enum class Tower {
     resident_i8,         // kz_tower_i8.hip: int8 block convolutions beside an f16 residual stream, f16 tensors around it
     board_conv_f16,      // kz_board_conv.hip: one launch per layer, whole boards as LDS tiles
     board_conv_split16,  // the same per layer in split arithmetic (boards the one-launch split tower cannot hold)
+    board_conv_i8,       // kz_board_conv_i8.hip: the same per layer on the i8 matrix cores, int8 images beside the f16 stream
     conv_igemm,          // kz_kernels.hip: one implicit GEMM per layer
 };
 
@@ -102,7 +108,7 @@ WeightsSpec weights_spec(const Model &m, const PathPlan &p) {
 
 // one launch per layer (stem + 2·depth convolutions) through three rotating activation buffers; else one launch, one buffer
 bool per_layer(const PathPlan &p) {
-    return p.tower == Tower::board_conv_f16 || p.tower == Tower::board_conv_split16 || p.tower == Tower::conv_igemm;
+    return p.tower == Tower::board_conv_f16 || p.tower == Tower::board_conv_split16 || p.tower == Tower::board_conv_i8 || p.tower == Tower::conv_igemm;
 }
 
 // the tower launch reads the packed boards itself (no encode launch in front of it)
@@ -123,6 +129,7 @@ const char *path_name(const PathPlan &p, int dtype) {
         case Tower::resident_i8: return p.heads ? "tower_resident_i8+heads" : "tower_resident_i8";
         case Tower::board_conv_f16: return "board_conv_f16";
         case Tower::board_conv_split16: return "board_conv_split16";
+        case Tower::board_conv_i8: return "board_conv_i8";
         case Tower::conv_igemm: return f16 ? "conv_igemm_f16" : "conv_igemm_f32";
     }
     return "";
@@ -169,11 +176,12 @@ int head_launches(const Model &m, int dtype, const PathPlan &p, int cp) {
     return n;
 }
 
-// the two int8 dtypes: one tower; 5 with the conv heads inside its launch where the launch can carry them
-bool int8_dtype(int dtype) { return dtype == KZ_DTYPE_INT8 || dtype == KZ_DTYPE_INT8_HEADS; }
+// the int8 dtypes: one one-launch tower; 5 with the conv heads inside its launch where the launch can carry them; 8 is 5 with
+// the per-layer int8 kernel behind it for the shapes that tower refuses
+bool int8_dtype(int dtype) { return dtype == KZ_DTYPE_INT8 || dtype == KZ_DTYPE_INT8_HEADS || dtype == KZ_DTYPE_INT8_ANY; }
 
 // dtype_in: KZ_DTYPE_F32 / KZ_DTYPE_F16 / KZ_DTYPE_F32_SPLIT16 / KZ_DTYPE_BF16 / int8 (4, 5).  false + why: kz_engine_create refuses.
-// (The messages say "bf16" or "dtype 3", "int8" or "dtype 4" / "dtype 5": the library's strings name no KZ_ identifier but the documented ones.)
+// (The messages say "bf16" or "dtype 3", "int8" or "dtype 4" / "dtype 5" / "dtype 8": the library's strings name no KZ_ identifier but the documented ones.)
 bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::string &why) {
     const bool split16 = dtype_in == KZ_DTYPE_F32_SPLIT16, bf16 = dtype_in == KZ_DTYPE_BF16, i8 = int8_dtype(dtype_in);
     const std::string i8_name = "(dtype " + std::to_string(dtype_in) + ")";  // in the int8 messages: the value the caller gave
@@ -236,7 +244,27 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
             why = i8_pre + "the int8 arithmetic " + i8_name + " needs a tower with at least one residual block: only the block convolutions are quantised";
             return false;
         }
-        if (!kz::tower_i8_supported(m.h, m.w, m.channels, m.depth, m.c_in)) {
+        const bool one_launch = kz::tower_i8_supported(m.h, m.w, m.channels, m.depth, m.c_in);
+        if (!one_launch && dtype_in == KZ_DTYPE_INT8_ANY && !m.i8_exp.empty()) {
+            // dtype 8 behind the one-launch tower: the per-layer int8 kernel, or a refusal (no other kernel, no workgroup floor).
+            // (A model that carries no calibration is told what dtype 4 tells it, below.)
+            if (!kz::board_conv_i8_supported(m.h, m.w, m.channels) || m.tower.empty() || m.tower[0].k != 3) {
+                why = i8_pre + "the int8 arithmetic " + i8_name + " has no kernel for this shape (the model is calibrated): neither the one-launch int8 tower nor the per-layer int8 kernel (board_conv_i8) takes it — per layer a board "
+                      "has 2 to 32 squares a side and fits the 24 tiles of 16 squares and the LDS of a workgroup, and the tower has at "
+                      "most 512 channels once widened to a multiple of 128";
+                return false;
+            }
+            if (m.i8_exp.size() != (size_t)(2 * m.depth)) {
+                why = i8_pre + "the int8 arithmetic " + i8_name + " needs a calibrated model (the shape has a kernel, the calibration is missing): make one with "
+                      "kz_model_quantize_int8 from the site maxima of kz_model_range_profile_fast";
+                return false;
+            }
+            p.tower = Tower::board_conv_i8;
+            p.att_heads = att_heads_one_launch(m, dtype);
+            p.launches = 2 + 2 * m.depth + head_launches(m, dtype, p, cp);  // encode, the stem, the block convolutions, the f16 heads
+            return true;
+        }
+        if (!one_launch) {
             why = i8_pre + "the int8 arithmetic " + i8_name + " has no kernel for this shape (" + std::string(m.i8_exp.empty() ? "and the model is not calibrated either" : "the model is calibrated") +
                   "): the one-launch int8 tower takes 256 tower channels (193 to 255 run widened to 256) on a board of at most 64 "
                   "squares with at most 128 input planes, and 128 (65 to 127 widened) on at most 96 squares with at most 64 input "
@@ -252,7 +280,7 @@ bool plan_path(const Model &m, int max_batch, int dtype_in, PathPlan &p, std::st
         p.wide = kz::tower_i8_wide_supported(m.h, m.w, m.channels, max_batch);
         // one launch per batch — zero-copy slots, the decode inside — is worth more than wider tiles (the precedent of
         // resident_f16g below): the narrow tiles decide `heads`, and the plan is then wide only up to the level whose tail fits
-        if (dtype_in == KZ_DTYPE_INT8_HEADS && kz::tower_i8_conv_heads_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels,
+        if (dtype_in != KZ_DTYPE_INT8 && kz::tower_i8_conv_heads_supported((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels,
                                                                                  m.h, m.w, m.channels, m.sh_conv.cout, m.sh_fc0.out)) {
             p.heads = true;
             p.wide_cap = kz::tower_i8_conv_heads_wide_cap((int)m.policy_kind, m.policy_extra_moves, m.policy_conv_channels, m.h, m.w, m.channels,

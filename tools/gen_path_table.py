@@ -25,6 +25,9 @@ tests/golden/path_table_int8_heads.json (--int8-heads) is the same table, cases 
 "tower_resident_i8+heads 1" where the int8 launch carries the conv heads, dtype 4's entry everywhere else;
 tests/test_int8_heads_api.py recomputes both.
 
+tests/golden/path_table_int8_any.json (--int8-any) is the same table for KZ_DTYPE_INT8_ANY (dtype 8): dtype 5's entry wherever it
+has one, "board_conv_i8 launches" where the per-layer int8 kernel takes over; tests/test_int8_any_api.py recomputes it.
+
 tests/test_path_table.py recomputes both from the built library and fails on any difference: a change of a support
 predicate has to come with a regenerated table (python tools/gen_path_table.py) and shows up in the diff.
 
@@ -32,6 +35,7 @@ predicate has to come with a regenerated table (python tools/gen_path_table.py) 
     python tools/gen_path_table.py --bf16     # rewrite tests/golden/path_table_bf16.json
     python tools/gen_path_table.py --int8     # rewrite tests/golden/path_table_int8.json
     python tools/gen_path_table.py --int8-heads  # rewrite tests/golden/path_table_int8_heads.json
+    python tools/gen_path_table.py --int8-any    # rewrite tests/golden/path_table_int8_any.json
     python tools/gen_path_table.py --md       # print the DESIGN table (with measured rates from a sweep record, if given:
                                               #   --rates profiles/r4/shape_sweep.json)
 """
@@ -50,6 +54,7 @@ OUT = os.path.join(REPO, "tests", "golden", "path_table.json")
 OUT_BF16 = os.path.join(REPO, "tests", "golden", "path_table_bf16.json")
 OUT_INT8 = os.path.join(REPO, "tests", "golden", "path_table_int8.json")
 OUT_INT8_HEADS = os.path.join(REPO, "tests", "golden", "path_table_int8_heads.json")
+OUT_INT8_ANY = os.path.join(REPO, "tests", "golden", "path_table_int8_any.json")
 MAX_BATCH = 256
 DTYPES = {"f32": capi.KZ_DTYPE_F32, "f16": capi.KZ_DTYPE_F16, "f32split16": capi.KZ_DTYPE_F32_SPLIT16}
 SWITCH_BATCHES = (1, 8, 256, 2048)
@@ -164,6 +169,11 @@ def build_int8_heads():
     return build_int8(capi.KZ_DTYPE_INT8_HEADS)
 
 
+def build_int8_any():
+    """The same column for dtype 8 (KZ_DTYPE_INT8_ANY): the cases and batches of build_int8."""
+    return build_int8(capi.KZ_DTYPE_INT8_ANY)
+
+
 def markdown(table, rates, games=None):
     by = {}
     for r in rates:
@@ -192,8 +202,12 @@ if __name__ == "__main__":
     ap.add_argument("--bf16", action="store_true", help="write the bf16 column (tests/golden/path_table_bf16.json)")
     ap.add_argument("--int8", action="store_true", help="write the int8 column (tests/golden/path_table_int8.json)")
     ap.add_argument("--int8-heads", action="store_true", help="write the dtype-5 column (tests/golden/path_table_int8_heads.json)")
+    ap.add_argument("--int8-any", action="store_true", help="write the dtype-8 column (tests/golden/path_table_int8_any.json)")
     args = ap.parse_args()
-    if args.int8_heads:
+    if args.int8_any:
+        json.dump(build_int8_any(), open(OUT_INT8_ANY, "w"), indent=1, sort_keys=True)
+        print("wrote", OUT_INT8_ANY)
+    elif args.int8_heads:
         json.dump(build_int8_heads(), open(OUT_INT8_HEADS, "w"), indent=1, sort_keys=True)
         print("wrote", OUT_INT8_HEADS)
     elif args.int8:
