@@ -63,7 +63,8 @@ extern "C" {
                            site and per (block convolution, output channel).  Only a CALIBRATED model runs it
                            (kz_model_quantize_int8 below, which also states the arithmetic to the bit).  The stem and the
                            residual stream stay f16 (RANGE: the +-65504 limit and the non-finite check of KZ_DTYPE_F16,
-                           unchanged; saturation of a quantised image at +-127 steps is silent by design), bias, ReLU,
+                           unchanged; saturation of a quantised image at +-127 steps is silent by design — counted per
+                           site by kz_model_int8_error_profile), bias, ReLU,
                            residual add and the final BN are f32.  PRECISION: 7 bits and a sign per stored activation where
                            f16 has 11 (README, "which number is which arithmetic"; kz_engine_set_audit measures it on a
                            network's own positions).  One launch for the tower ("tower_resident_i8"; no "+heads": the f16
@@ -78,7 +79,7 @@ extern "C" {
                            without blocks; the message says whether the calibration or the kernel is missing, and to a model
                            that carries no calibration dtype 4 is, first of all, an unknown dtype.  It reads
                            none of the environment switches.  kz_model_tower_taps, _taps_path and kz_model_error_profile
-                           refuse it */
+                           refuse it: kz_model_int8_taps, _taps_path and kz_model_int8_error_profile are its own */
 #define KZ_DTYPE_INT8_HEADS 5 /* KZ_DTYPE_INT8's tower, bit for bit, with the heads inside its launch where the launch can carry
                                  them: ScalarHead, ConvPolicyHead or AtaxxConvPolicyHead and decode_output run behind the last
                                  block in f16, on the f16 values the tower holds — the plain-f16 launch's tail
@@ -527,6 +528,54 @@ int kz_model_tower_taps(const kz_model *model, int device, int max_batch, int dt
                         const float *scalars_in, int batch, int site_first, int n_sites, float *out);
 int kz_model_error_profile(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
                            const float *scalars_in, int batch, void *out);
+
+/* ---- int8 taps and error profile: every stored int8 image, its error and its clamp count ----
+ * The three entries above refuse the int8 dtypes (4, 5, 8): an int8 tower stores int8 images at a scale per site, which their
+ * element formats do not hold.  These three are the int8 towers' own, for a CALIBRATED ResTower model.  The range sites are
+ * kz_model_range_sites': 2 * depth + 1, in kz_model_range_site_name's order.  Site 0 (the stem) and every block output but the
+ * last store an image X8 = quant(v, e_s) and, beside it from the same f32 v, the residual-stream value X = f16(v); a mid site
+ * stores an image Y8 only; the last site stores the f16 tower output behind the final BN and no image (kz_model_quantize_int8
+ * states the arithmetic).  A tap is what the launch DID store: the one-launch tower ("tower_resident_i8") has a tap instance per
+ * geometry of the tower alone — the same arithmetic in the same order and, behind each epilogue store, the same q bytes and f16
+ * values once more to device memory, rows of real boards only —; the per-layer plan ("board_conv_i8") keeps its images in
+ * device memory already, and a tap engine copies every layer's outputs behind that layer's launch.
+ *
+ * kz_model_int8_taps_path(model, max_batch, dtype, buf, len) writes the kernel a tap call runs, "tower_resident_i8" or
+ * "board_conv_i8", never with "+heads", without touching a GPU (buf of at least 32 bytes).  dtype 5 taps what dtype 4 taps: the
+ * tower's bits are dtype 4's, and a tap engine never carries heads, so its wide levels are the tower's own.  dtype 8 taps that
+ * tower wherever dtype 5 has a plan, and the per-layer kernel elsewhere.  The one-launch tower chooses its wide level per launch
+ * from its batch: a tap call runs the level an engine of max_batch runs at `batch` boards (kz_model_launch_geometry(model,
+ * max_batch, 4, batch)), "the batch size whose geometry is tapped".
+ * kz_model_int8_taps is synchronous, in chunks, every device tensor below 2 GiB.  image_out (int8_t elements, typed void like
+ * hist_out): int8 [n_sites][batch][C][h][w] with
+ * C the model's own tower channels (channels the kernels widen the tower by are not returned): the q the epilogue stored; the
+ * last site has no image and returns 0.  stream_out: f32 of the same shape: the f16 value stored beside the image, widened; at
+ * the last site the f16 tower output; a mid site has no stream and returns NaN.  Either pointer may be NULL, not both.  The
+ * image part of the tap buffer is filled with 0x80 before every pass — the contract never produces -128 —, the stream part with
+ * NaN patterns: an element no lane wrote comes back as -128, or NaN.
+ * kz_model_int8_error_profile fills out [kz_model_range_sites] of kz_int8_site_error (typed void like hist_out), reduced on the
+ * device against exact f32 on the same boards — kz_model_error_profile's references: the one-launch f32 tower's own taps where
+ * kz_model_range_profile_fast_path says "tower_resident_f32", the per-layer exact-f32 engine elsewhere.  The six fields of each
+ * kz_site_error are defined as above; an image element of -128 counts in image.nonfinite.  at_clamp counts what the launch
+ * stored at the clamp, an upper bound on what it clamped; ref_beyond counts what an ideal int8 image of the exact network would
+ * clamp (127.5 is the contract's own tie: rne(127.5) = 128).  Both run over real channels of real boards only.
+ * All three fail, each with a message of its own in the function's name, in front of any GPU call: null arguments; a dtype that is
+ * not an int8 dtype; an AttentionTower network; a DenseNetwork; a tower without blocks; a model that is not calibrated; a shape
+ * the dtype refuses (kz_model_plan's reason); a site range outside 0 .. n_sites; batch < 1 or batch > max_batch; a bits_stride
+ * below kz_model_info.bits_bytes. */
+typedef struct kz_int8_site_error {
+    kz_site_error image;  /* a = q * 2^e_s (exact in f32) against r; count 0 at the last site */
+    kz_site_error stream; /* a = the f16 stream value against r; count 0 at a mid site */
+    uint64_t at_clamp;    /* image elements with |q| == 127 */
+    uint64_t ref_beyond;  /* elements whose reference is finite and has |r| * 2^-e_s >= 127.5 */
+    int32_t  exponent;    /* e_s; 0 at the last site */
+    int32_t  reserved;    /* 0 */
+} kz_int8_site_error; /* 120 bytes */
+int kz_model_int8_taps_path(const kz_model *model, int max_batch, int dtype, char *buf, size_t len);
+int kz_model_int8_taps(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
+                       const float *scalars_in, int batch, int site_first, int n_sites, void *image_out, float *stream_out);
+int kz_model_int8_error_profile(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
+                                const float *scalars_in, int batch, void *out);
 
 /* ---- device-resident evaluation (inputs and outputs already in HBM; used by bench.py and the parity tests) ----
  * Pointers are device pointers on the engine's device (kz_device_malloc).  Enqueues on the engine's stream and

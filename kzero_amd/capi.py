@@ -91,6 +91,18 @@ SITE_ERROR_DTYPE = np.dtype([("max_abs_err", np.float64), ("sum_sq_err", np.floa
 assert C.sizeof(SiteError) == SITE_ERROR_DTYPE.itemsize == 48
 
 
+class Int8SiteError(C.Structure):
+    """kz_int8_site_error (include/kz_hip.h): one range site of kz_model_int8_error_profile, 120 bytes."""
+    _fields_ = [("image", SiteError), ("stream", SiteError), ("at_clamp", C.c_uint64), ("ref_beyond", C.c_uint64),
+                ("exponent", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the same record as a numpy dtype (Model.int8_error_profile puts the site's name in front)
+INT8_SITE_ERROR_DTYPE = np.dtype([("image", SITE_ERROR_DTYPE), ("stream", SITE_ERROR_DTYPE), ("at_clamp", np.uint64),
+                                  ("ref_beyond", np.uint64), ("exponent", np.int32), ("reserved", np.int32)])
+assert C.sizeof(Int8SiteError) == INT8_SITE_ERROR_DTYPE.itemsize == 120
+
+
 # name -> (restype, argtypes); every symbol include/kz_hip.h declares
 SIGNATURES = {
     "kz_last_error": (C.c_char_p, []),
@@ -124,6 +136,11 @@ SIGNATURES = {
                                       C.c_int, C.c_void_p]),
     "kz_model_error_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
                                          C.c_void_p]),
+    "kz_model_int8_taps_path": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "kz_model_int8_taps": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_int, C.c_void_p, C.c_void_p]),
+    "kz_model_int8_error_profile": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int,
+                                              C.c_void_p]),
     "kz_engine_max_batch": (C.c_int, [C.c_void_p]),
     "kz_engine_eval_dense": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "kz_engine_eval_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
@@ -414,6 +431,51 @@ class Model:
         out = np.zeros(len(names), np.dtype([("site", "U24")] + SITE_ERROR_DTYPE.descr))
         out["site"] = names
         for f in SITE_ERROR_DTYPE.names:
+            out[f] = raw[f]
+        return out
+
+    def int8_taps_path(self, max_batch: int, dtype: int) -> str:
+        """The kernel an int8 tap call runs, "tower_resident_i8" or "board_conv_i8", never with "+heads"
+        (kz_model_int8_taps_path) — host logic, no GPU needed; fails where the int8 taps fail."""
+        buf = C.create_string_buffer(64)
+        check(load().kz_model_int8_taps_path(self._h, max_batch, dtype, buf, len(buf)))
+        return buf.value.decode()
+
+    def int8_taps(self, device: int, max_batch: int, dtype: int, bits: np.ndarray, scalars_in: np.ndarray, site_first: int = 0,
+                  n_sites: int = None) -> tuple:
+        """What the int8 tower of an engine of (max_batch, dtype) stores at the range sites [site_first, site_first + n_sites)
+        on these boards (kz_model_int8_taps): ({site name: int8 [batch, C, H, W]}, {site name: float32 [batch, C, H, W]}) —
+        the image's q (0 at the last site, which has none; -128 where no lane wrote) and the f16 stream value stored beside it
+        (the tower output at the last site; NaN at a mid site, which has none)."""
+        if n_sites is None:
+            n_sites = len(self.range_sites()) - site_first
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        batch = bits.shape[0]
+        shape = (max(n_sites, 0), batch, self.info.tower_channels, self.info.board_h, self.info.board_w)
+        image, stream = np.zeros(shape, np.int8), np.zeros(shape, np.float32)
+        check(load().kz_model_int8_taps(self._h, device, max_batch, dtype, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                        scalars_in.ctypes.data, batch, site_first, n_sites, image.ctypes.data, stream.ctypes.data))
+        names = self.range_sites()
+        return ({names[site_first + i]: image[i] for i in range(n_sites)}, {names[site_first + i]: stream[i] for i in range(n_sites)})
+
+    def int8_error_profile(self, device: int, max_batch: int, dtype: int, bits: np.ndarray, scalars_in: np.ndarray) -> np.ndarray:
+        """Per range site, how far that int8 tower's stored images (q * 2^e_s) and f16 stream values are from exact f32 on these
+        boards, and how many elements sit at the clamp, reduced on the GPU (kz_model_int8_error_profile): a structured array
+        [n_sites] with the fields site (the name), image and stream (error_profile's six fields each), at_clamp, ref_beyond,
+        exponent, reserved."""
+        try:
+            names = self.range_sites()
+        except KzError:
+            names = [""]  # (a network without range sites: the call below says so in its own name)
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        scalars_in = np.ascontiguousarray(scalars_in, dtype=np.float32)
+        raw = np.zeros(len(names), INT8_SITE_ERROR_DTYPE)
+        check(load().kz_model_int8_error_profile(self._h, device, max_batch, dtype, bits.ctypes.data, bits.shape[1] if bits.ndim == 2 else 0,
+                                                 scalars_in.ctypes.data, bits.shape[0], raw.ctypes.data))
+        out = np.zeros(len(names), np.dtype([("site", "U24")] + INT8_SITE_ERROR_DTYPE.descr))
+        out["site"] = names
+        for f in INT8_SITE_ERROR_DTYPE.names:
             out[f] = raw[f]
         return out
 

@@ -289,7 +289,7 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
             e->plan = PathPlan();  // (Tower::conv_igemm)
             e->plan.keep = true;
             e->plan.launches = 2 + 2 * m.depth;
-        } else if (profile == Profile::taps) {  // (the caller has asked plan_path already: a one-launch ResTower)
+        } else if (profile == Profile::taps) {  // (the caller has asked plan_path already: a one-launch ResTower, or an int8 plan)
             if (!plan_path(m, max_batch, dtype_in, e->plan, why)) return fail("kz_engine_create: " + why);
             e->plan.heads = false;
             e->plan.launches = 1;
@@ -394,6 +394,9 @@ static int create_engine(const kz_model *model, int device, int max_batch, int d
             // every site's tensor for tap_boards boards, all of them together below 2 GiB
             const size_t per_board = (size_t)(2 * m.depth + 1) * hw * m.channels * 4;
             e->tap_boards = (int)std::min<size_t>((size_t)std::min(max_batch, std::max(tap_boards, 1)), std::max<size_t>(((((size_t)1 << 31) - 1) / per_board), 1));
+            // (board_conv_i8: a site's halves hold the engine's own rows, C8 bytes and cp f16 values — kz_engine_state.hpp, tap_copy)
+            if (plan.tower == Tower::board_conv_i8 && (e->wts->c8 > 2 * m.channels || e->cp > m.channels))
+                return fail("kz_engine_create: internal error: the per-layer int8 rows do not fit the tap tensors of this shape");
             if (e->dmalloc((void **)&e->tap_out, per_board * e->tap_boards)) return 1;
         } else if ((profile == Profile::per_layer || profile == Profile::resident) &&
                    e->dmalloc(&e->range_out, (size_t)(2 * m.depth + 1) * max_batch * 4)) {
@@ -699,10 +702,15 @@ static int tap_pass(kz_engine *e, const uint8_t *bits, size_t bits_stride, const
     e->stage_boards(s, bits, bits_stride, scalars_in, nb);
     const Pass p = e->pass_staged(0);
     if (e->copy_boards_in(p, s, nb)) return 1;
-    HIP_TRY(hipMemsetAsync(e->tap_out, 0xff, (size_t)(2 * m.depth + 1) * e->tap_site_bytes(), p.stream));
+    if (e->tap_fill(p)) return 1;  // (an int8 tap engine: 0x80 in the image parts)
     const kz::PackedBoards in = e->packed_boards(s.d_bits, e->bits_bytes(), s.d_sin);
     e->range_site = 0;
-    if (e->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &in)) return 1;
+    if (per_layer(e->plan)) {  // (board_conv_i8: the encode is a launch of its own)
+        if (e->launch(p, "kz_encode_packed", [&] { kz::launch_encode_packed(e->dtype, in, nb, m.h * m.w, e->x_in, e->cin_p, p.stream); })) return 1;
+        if (e->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol)) return 1;
+    } else if (e->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol, &in)) {
+        return 1;
+    }
     if (e->range_site != 2 * m.depth + 1) return fail("internal error: the planned tower has no tap instance");
     HIP_TRY(hipStreamSynchronize(p.stream));
     return 0;
@@ -830,6 +838,157 @@ KZ_API int kz_model_error_profile(const kz_model *model, int device, int max_bat
             }
         }
         HIP_TRY(hipMemcpy(out, dev, (size_t)n * sizeof(kz_site_error), hipMemcpyDeviceToHost));
+        return 0;
+    });
+}
+
+// ------------------------------------------------------------------------------------------------
+// Int8 taps and error profile (include/kz_hip.h): every stored int8 image of the int8 tower an engine of (max_batch, dtype)
+// runs, the f16 stream value stored beside it, and per site the error of both against exact f32 with the clamp counts
+// ------------------------------------------------------------------------------------------------
+
+// What an int8 tap call runs: host logic only.  tap_dtype: the dtype of the tap engine — dtype 5 taps what dtype 4 taps (the
+// tower's bits are dtype 4's, and a tap engine carries no heads: its wide levels are the tower's own), dtype 8 that tower
+// wherever dtype 5 has a plan and the per-layer kernel elsewhere.
+static int int8_tap_plan(const std::string &fn, const kz_model *model, int max_batch, int dtype, PathPlan &plan, int &n, int &tap_dtype) {
+    if (!model) return fail(fn + ": null argument");
+    if (!int8_dtype(dtype)) return fail(fn + ": dtype " + std::to_string(dtype) + " is not an int8 dtype (4, 5 or 8): kz_model_tower_taps and kz_model_error_profile take the others");
+    const Model &m = *model->m;
+    if (m.tower_kind == kz::TOWER_ATTENTION) return fail(fn + ": an AttentionTower network has no range sites to tap, and no int8 arithmetic");
+    if (m.tower_kind == kz::TOWER_DENSE_NET) return fail(fn + ": a DenseNetwork has no tower, and no int8 arithmetic");
+    if (m.depth < 1) return fail(fn + ": a tower without blocks has no quantised image to tap");
+    n = 2 * m.depth + 1;
+    if (max_batch <= 0) return fail(fn + ": max_batch must be positive");
+    if (m.i8_exp.empty())
+        return fail(fn + ": this model is not calibrated (kz_model_quantize_int8 makes one that is): an int8 image of dtype " + std::to_string(dtype) + " has a scale per site");
+    std::string why;
+    if (!plan_path(*effective_model(model, dtype, max_batch), max_batch, dtype, plan, why))
+        return fail(fn + ": this model does not run in dtype " + std::to_string(dtype) + ": " + why);
+    tap_dtype = dtype;
+    if (plan.tower == Tower::resident_i8) {
+        tap_dtype = KZ_DTYPE_INT8;
+        if (!plan_path(*effective_model(model, tap_dtype, max_batch), max_batch, tap_dtype, plan, why)) return fail(fn + ": internal error: " + why);
+    }
+    plan.heads = false;
+    return 0;
+}
+
+KZ_API int kz_model_int8_taps_path(const kz_model *model, int max_batch, int dtype, char *buf, size_t len) {
+    return guarded("kz_model_int8_taps_path", [&]() -> int {
+        const std::string fn = "kz_model_int8_taps_path";
+        PathPlan plan;
+        int n = 0, tap_dtype = 0;
+        if (int8_tap_plan(fn, model, max_batch, dtype, plan, n, tap_dtype)) return 1;
+        const std::string name = path_name(plan, KZ_DTYPE_F16);
+        if (!buf || len < name.size() + 1) return fail(fn + ": buffer of at least " + std::to_string(name.size() + 1) + " bytes needed");
+        memcpy(buf, name.c_str(), name.size() + 1);
+        return 0;
+    });
+}
+
+KZ_API int kz_model_int8_taps(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
+                              const float *scalars_in, int batch, int site_first, int n_sites, void *image_out_, float *stream_out) {
+    return guarded("kz_model_int8_taps", [&]() -> int {
+        const std::string fn = "kz_model_int8_taps";
+        int8_t *image_out = static_cast<int8_t *>(image_out_);
+        if (!model || !bits || (!image_out && !stream_out)) return fail(fn + ": null argument");
+        PathPlan plan;
+        int n = 0, tap_dtype = 0;
+        if (int8_tap_plan(fn, model, max_batch, dtype, plan, n, tap_dtype)) return 1;
+        if (site_first < 0 || n_sites < 1 || site_first > n - n_sites)
+            return fail(fn + ": sites [" + std::to_string(site_first) + ", " + std::to_string((long long)site_first + n_sites) + ") out of range (" +
+                        std::to_string(n) + " sites)");
+        const Model &src = *model->m;
+        if (tap_arguments(fn, src, max_batch, bits, bits_stride, scalars_in, batch)) return 1;
+        EnginePtr e(nullptr, kz_engine_destroy);
+        if (tap_engine(fn, model, device, max_batch, tap_dtype, Profile::taps, batch, e)) return 1;
+        e->tap_geometry_batch = batch;
+        // the host loop reads a site's rows strided, as the engine keeps them (the widened channels are not returned), and transposes
+        const size_t hw = (size_t)src.h * src.w, ld8 = (size_t)e->tap_image_ld(), ld16 = (size_t)e->tap_stream_ld(), channels = (size_t)e->out_channels;
+        std::vector<int8_t> h8((size_t)e->tap_boards * hw * ld8);
+        std::vector<_Float16> h16((size_t)e->tap_boards * hw * ld16);
+        for (int lo = 0; lo < batch; lo += e->tap_boards) {
+            const int nb = std::min(e->tap_boards, batch - lo);
+            if (tap_pass(e.get(), bits + (size_t)lo * bits_stride, bits_stride, src.n_scalar ? scalars_in + (size_t)lo * src.n_scalar : nullptr, nb))
+                return fail(fn + ": " + std::string(g_err));
+            const size_t rows = (size_t)nb * hw;
+            for (int si = 0; si < n_sites; si++) {
+                const int site = site_first + si;
+                const bool has_image = site < n - 1, has_stream = site % 2 == 0;
+                const size_t at = (((size_t)si * batch + lo) * channels) * hw;
+                if (image_out && has_image) HIP_TRY(hipMemcpy(h8.data(), e->tap_site(site), rows * ld8, hipMemcpyDeviceToHost));
+                if (stream_out && has_stream) HIP_TRY(hipMemcpy(h16.data(), e->tap_stream(site), rows * ld16 * 2, hipMemcpyDeviceToHost));
+                for (size_t r = 0; r < rows; r++) {
+                    const size_t o = at + (r / hw) * channels * hw + r % hw;
+                    for (size_t c = 0; c < channels; c++) {
+                        if (image_out) image_out[o + c * hw] = has_image ? h8[r * ld8 + c] : (int8_t)0;  // (the last site has no image)
+                        if (stream_out) stream_out[o + c * hw] = has_stream ? (float)h16[r * ld16 + c] : NAN;  // (a mid site no stream)
+                    }
+                }
+            }
+        }
+        return 0;
+    });
+}
+
+static_assert(sizeof(kz_int8_site_error) == 120 && sizeof(kz::Int8SiteDeviation) == sizeof(kz_int8_site_error), "a device record is a kz_int8_site_error");
+KZ_API int kz_model_int8_error_profile(const kz_model *model, int device, int max_batch, int dtype, const uint8_t *bits, size_t bits_stride,
+                                       const float *scalars_in, int batch, void *out) {
+    return guarded("kz_model_int8_error_profile", [&]() -> int {
+        const std::string fn = "kz_model_int8_error_profile";
+        if (!model || !bits || !out) return fail(fn + ": null argument");
+        PathPlan plan;
+        int n = 0, tap_dtype = 0;
+        if (int8_tap_plan(fn, model, max_batch, dtype, plan, n, tap_dtype)) return 1;
+        const Model &src = *model->m;
+        if (tap_arguments(fn, src, max_batch, bits, bits_stride, scalars_in, batch)) return 1;
+        // the references of kz_model_error_profile: the one-launch f32 tower's taps where that kernel takes the shape, else the
+        // per-layer exact-f32 engine, which drives both reductions of a site as it produces it
+        const bool resident = range_profile_resident(src);
+        EnginePtr e(nullptr, kz_engine_destroy), ref(nullptr, kz_engine_destroy);
+        if (tap_engine(fn, model, device, max_batch, tap_dtype, Profile::taps, resident ? batch : std::min(batch, 64), e)) return 1;
+        e->tap_geometry_batch = batch;
+        const int chunk = std::min(batch, e->tap_boards);
+        if (tap_engine(fn, model, device, chunk, KZ_DTYPE_F32, resident ? Profile::taps_reference : Profile::per_layer_deviation, chunk, ref)) return 1;
+        kz::Int8SiteDeviation *dev = nullptr;
+        if (e->dmalloc((void **)&dev, (size_t)n * sizeof(kz::Int8SiteDeviation))) return fail(fn + ": " + std::string(g_err));
+        HIP_TRY(hipMemset(dev, 0, (size_t)n * sizeof(kz::Int8SiteDeviation)));
+        HIP_TRY(hipDeviceSynchronize());  // (the engines' streams do not wait for the null stream)
+        if (!resident) {
+            ref->tap_peer = e.get();
+            ref->deviation8 = dev;
+        }
+        for (int lo = 0; lo < batch; lo += chunk) {
+            const int nb = std::min(chunk, batch - lo);
+            const uint8_t *b = bits + (size_t)lo * bits_stride;
+            const float *sc = src.n_scalar ? scalars_in + (size_t)lo * src.n_scalar : nullptr;
+            if (tap_pass(e.get(), b, bits_stride, sc, nb)) return fail(fn + ": " + std::string(g_err));
+            if (resident) {
+                if (tap_pass(ref.get(), b, bits_stride, sc, nb)) return fail(fn + ": " + std::string(g_err));
+                const Pass p = ref->pass_staged(0);
+                for (int site = 0; site < n; site++)
+                    if (e->tap_deviation8(p, site, reinterpret_cast<const float *>(ref->tap_site(site)), ref->model->channels, nb, dev + site))
+                        return fail(fn + ": " + std::string(g_err));
+                HIP_TRY(hipStreamSynchronize(p.stream));
+            } else {
+                kz_engine::Slot &s = ref->slots[0];
+                ref->stage_boards(s, b, bits_stride, sc, nb);
+                const Pass p = ref->pass_staged(0);
+                if (ref->copy_boards_in(p, s, nb)) return fail(fn + ": " + std::string(g_err));
+                const kz::PackedBoards in = ref->packed_boards(s.d_bits, ref->bits_bytes(), s.d_sin);
+                if (ref->launch(p, "kz_encode_packed", [&] { kz::launch_encode_packed(ref->dtype, in, nb, src.h * src.w, ref->x_in, ref->cin_p, p.stream); }) ||
+                    ref->run_tower(p, nb, s.d_sout + kz_engine::SOUT_HDR, s.d_pol))
+                    return fail(fn + ": " + std::string(g_err));
+                if (ref->range_site != n) return fail(fn + ": internal error: " + std::to_string(ref->range_site) + " sites compared, " + std::to_string(n) + " expected");
+                HIP_TRY(hipStreamSynchronize(p.stream));
+            }
+        }
+        kz_int8_site_error *rec = static_cast<kz_int8_site_error *>(out);
+        HIP_TRY(hipMemcpy(rec, dev, (size_t)n * sizeof(kz_int8_site_error), hipMemcpyDeviceToHost));
+        for (int site = 0; site < n; site++) {
+            rec[site].exponent = site < n - 1 ? e->model->i8_exp[site] : 0;
+            rec[site].reserved = 0;
+        }
         return 0;
     });
 }

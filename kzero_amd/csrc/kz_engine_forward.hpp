@@ -161,7 +161,7 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
         }
         if (tap_out) {  // a tap engine (no heads in its plan): the tap instance of the geometry max_batch plans
             t.taps = taps();
-            t.tap_wide_batch = max_batch;
+            t.tap_wide_batch = i8() ? tap_geometry_batch : max_batch;  // (the int8 launch chooses its level per launch, from its batch)
             range_site = 2 * m.depth + 1;
         }
         const bool f16g = plan.tower == Tower::resident_f16g;
@@ -220,15 +220,21 @@ inline int kz_engine::run_tower(const Pass &p, int batch, float *d_scalars, floa
             b.ld16 = cp; b.boards = batch; b.h = m.h; b.w = m.w; b.cin = l == 0 ? cin_p : C8; b.cout = C8; b.relu = l != 0;
             return launch(p, l == 0 ? "kz_board_conv_i8_stem" : "kz_board_conv_i8", [&] { kz::launch_board_conv_i8(b, p.stream); });
         };
+        // (a tap engine: every layer's image and stream rows to the site's tap tensors behind its launch, on the same stream)
+        const bool tap = tap_out != nullptr;
         if (i8conv(0, x_in, nullptr, act[0], act8[0], false)) return 1;
+        if (tap && tap_copy(p, 0, act8[0], act[0], batch)) return 1;
         int cur = 0;
         for (int i = 1; i <= m.depth; i++) {
             const int nxt = (cur + 1) % 3;
             const bool last = i == m.depth;
             if (i8conv(2 * i - 1, act8[0], nullptr, nullptr, act8[1], false)) return 1;
+            if (tap && tap_copy(p, 2 * i - 1, act8[1], nullptr, batch)) return 1;
             if (i8conv(2 * i, act8[1], act[cur], act[nxt], last ? nullptr : act8[0], last)) return 1;
+            if (tap && tap_copy(p, 2 * i, last ? nullptr : act8[0], act[nxt], batch)) return 1;
             cur = nxt;
         }
+        if (tap) range_site = 2 * m.depth + 1;
         tower_out = cur;
         return 0;
     }

@@ -426,11 +426,55 @@ struct kz_engine {
     // with tap_peer's tap of that site (tap_peer has finished its pass), into deviation [n_sites] in device memory
     const kz_engine *tap_peer = nullptr;
     kz::TapDeviation *deviation = nullptr;
+    kz::Int8SiteDeviation *deviation8 = nullptr;  // instead, where tap_peer is an int8 tap engine (kz_model_int8_error_profile)
+
+    // The int8 taps (kz_model_int8_taps, kz_model_int8_error_profile): a tap engine of resident_i8 or board_conv_i8.  A site's
+    // tensor holds the int8 image at its start and the f16 stream value stored beside it tap_site_bytes() / 2 behind (mid sites
+    // have no stream, the last site no image).  The image part is filled with 0x80 before a pass (tap_fill): -128 is what no
+    // lane wrote.  The one-launch tower's tap instance writes rows of model->channels elements; the per-layer plan's images and
+    // stream rows are copied behind each layer's launch and keep the engine's own strides, C8 bytes and cp halves.
+    // tap_geometry_batch: the batch whose wide level a tap launch runs (the int8 launch chooses its level per launch).
+    int tap_geometry_batch = 0;
+    int tap_image_ld() const { return plan.tower == Tower::board_conv_i8 ? wts->c8 : model->channels; }
+    int tap_stream_ld() const { return plan.tower == Tower::board_conv_i8 ? cp : model->channels; }
+    const unsigned char *tap_stream(int site) const { return tap_site(site) + tap_site_bytes() / 2; }
+    int tap_fill(const Pass &p) {
+        const size_t n = (size_t)(2 * model->depth + 1), sb = tap_site_bytes();
+        if (!i8()) {
+            HIP_TRY(hipMemsetAsync(tap_out, 0xff, n * sb, p.stream));
+            return 0;
+        }
+        for (size_t site = 0; site < n; site++) {
+            HIP_TRY(hipMemsetAsync(tap_out + site * sb, 0x80, sb / 2, p.stream));
+            HIP_TRY(hipMemsetAsync(tap_out + site * sb + sb / 2, 0xff, sb / 2, p.stream));
+        }
+        return 0;
+    }
+    // (board_conv_i8, a tap engine) a layer's image and f16 rows to the site's tensors, behind that layer's launch
+    int tap_copy(const Pass &p, int site, const void *image, const void *stream16, int batch) {
+        const size_t rows = (size_t)batch * model->h * model->w;
+        if (image) HIP_TRY(hipMemcpyAsync(tap_out + (size_t)site * tap_site_bytes(), image, rows * wts->c8, hipMemcpyDeviceToDevice, p.stream));
+        if (stream16)
+            HIP_TRY(hipMemcpyAsync(tap_out + (size_t)site * tap_site_bytes() + tap_site_bytes() / 2, stream16, rows * cp * 2, hipMemcpyDeviceToDevice, p.stream));
+        return 0;
+    }
+    // both reductions of site `site` of this int8 tap engine's last pass against the same rows in exact f32
+    int tap_deviation8(const Pass &p, int site, const float *ref, int ref_ld, int boards, kz::Int8SiteDeviation *out) const {
+        const size_t rows = (size_t)boards * model->h * model->w;
+        const int n = 2 * model->depth + 1;
+        if (site < n - 1)
+            kz::launch_tap_deviation_i8(tap_site(site), tap_image_ld(), model->i8_exp[site], ref, ref_ld, rows, out_channels, out, p.stream);
+        if (site % 2 == 0)
+            kz::launch_tap_deviation(tap_stream(site), kz::TapFormat::f16, 0, tap_stream_ld(), ref, ref_ld, rows, out_channels, &out->stream, p.stream);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    }
 
     int stash(const Pass &p, const std::string &name, const void *src, int batch) {
         if (!plan.keep) return 0;
         if (tap_peer) {
             const int site = range_site++;
+            if (deviation8) return tap_peer->tap_deviation8(p, site, (const float *)src, cp, batch, deviation8 + site);
             return tap_peer->tap_deviation(p, site, (const float *)src, cp, batch, deviation + site);
         }
         if (range_hist) {

@@ -77,7 +77,10 @@ void launch_range_histogram(const float *x, int boards, int hw, int channels, in
 // of the site's element — a lane's four consecutive channels of a pixel are one vector store.  Only rows of real boards are
 // written (the histogram instances' rule).  A (hi, lo) site is two such f16 tensors, lo site_bytes / 2 behind hi.
 // site_bytes = boards the buffer holds * hw * channels * 4, whatever the element.
-enum class TapFormat : int { f32 = 0, f16 = 1, split16 = 2, bf16 = 3 };
+// The int8 towers (kz_model_int8_taps): a site is an int8 image — the q the epilogue stored, 1 byte an element, at the site's
+// start — and the f16 stream value stored beside it, site_bytes / 2 behind it (the place of a pair's lo half); TapFormat::i8
+// names the image, whose value is q * 2^e_s.  The image part is filled with 0x80 before a pass: the contract never produces -128.
+enum class TapFormat : int { f32 = 0, f16 = 1, split16 = 2, bf16 = 3, i8 = 4 };
 struct TapOut {
     unsigned char *base = nullptr;  // nullptr: no taps (the product instance runs)
     size_t site_bytes = 0;
@@ -124,6 +127,19 @@ struct TapDeviation {
 // are compared.  tap_ld and ref_ld are multiples of 8: every load is 16 bytes.
 void launch_tap_deviation(const void *tap, TapFormat format, size_t lo_bytes, int tap_ld, const float *ref, int ref_ld, size_t rows,
                           int channels, TapDeviation *out, hipStream_t stream);
+// One record per site of an int8 tower (kz_model_int8_error_profile), field for field kz_int8_site_error (include/kz_hip.h):
+// the image's deviation (a = q * 2^e_s, exact in f32; q = -128, which no lane wrote, counts as non-finite), the f16 stream's,
+// and the two clamp counts over the image's elements.  `exponent` is the host's to fill.
+struct Int8SiteDeviation {
+    TapDeviation image, stream;
+    unsigned long long at_clamp, ref_beyond;  // |q| == 127; finite r with |r| * 2^-e_s >= 127.5
+    int exponent, reserved;
+};
+static_assert(sizeof(Int8SiteDeviation) == 120, "kz_int8_site_error");
+// the TapFormat::i8 instance: `tap` = rows of tap_ld int8 (a multiple of 8: eight channels are one 8-byte load), a = q * 2^exponent;
+// ADDS the six fields to out->image and the two counts to out->at_clamp / ref_beyond in the same pass
+void launch_tap_deviation_i8(const void *tap, int tap_ld, int exponent, const float *ref, int ref_ld, size_t rows, int channels,
+                             Int8SiteDeviation *out, hipStream_t stream);
 
 // Implicit-GEMM convolution, kernel k in {1,3}, pad k/2, fused epilogue:
 //   v = acc + bias[oc];  if (relu) v = max(v, 0);  if (res) v += res[row][oc];
@@ -542,7 +558,8 @@ bool launch_tower_bf16(const Tower32Args &a, hipStream_t stream, int *nt = nullp
 
 // ---- the one-launch tower on the i8 matrix cores (kz_tower_i8.hip: "tower_resident_i8", dtype 4 on a calibrated model): the
 // plain-f16 launch's tensors — f16 x0 and y behind the float pointers of Tower32Args, or packed boards in — around int8 block
-// convolutions; no tap instance.  `weights` = the stem's k-steps as tower_split_pack_weights packs them
+// convolutions; taps.base set: the tap instance of the tower alone (int8 images and f16 stream values, TapFormat::i8), at the
+// level tap_wide_batch fills.  `weights` = the stem's k-steps as tower_split_pack_weights packs them
 // (stem, split = false), then tower_i8_pack_weights per block convolution; mult [1 + 2*depth][channels] = 2^(e_in + f_oc) beside
 // the bias table (row 0, the stem's, is not read); qscale [2*depth] = 2^-e_s per quantised range site.
 // With Tower32Args::Heads of kind conv ("tower_resident_i8+heads", dtype 5 where tower_i8_conv_heads_supported holds) the conv

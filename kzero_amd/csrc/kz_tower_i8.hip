@@ -187,7 +187,7 @@ struct I8Dev {
     int hc, hs, pc, policy_len, zero_tail, extra;
     const float *sh_b0, *sh_w1t, *sh_b1, *sh_w2, *sh_b2, *p_b1, *pe_bc, *pe_wl, *pe_bl;
     const uint4 *small_w16;  // the two small convolutions as f16 fragments (tower_split_pack_small_weights16)
-    float *scalars, *policy;
+    union { float *scalars; unsigned char *tap_base; }; union { float *policy; size_t tap_site_bytes; };  // (a tap instance — no heads — keeps its buffer in the heads' two output words: kz_kernels.hpp, tap_put)
     int *nonfinite_flag;
     int epoch;
     DecodeDev dec;  // dec.move_offsets set: decode_output inside the launch
@@ -218,9 +218,14 @@ __device__ __forceinline__ int quant4(f32x4 v, float qs) {
 //     beside the tower's 36 depth NT conflict-free ones, accepted;
 //   the two small convolutions are f16 MFMAs on X and YH (row tiles over the waves), the tail kz_conv_heads.hpp with its
 //     scratch behind the launch's own LDS and X as the decode's staging.
-template <int C, int NT, int HEADS = 0>
+// TAP: the tap instance of the tower alone (kz_kernels.hpp, tap_put; kz_model_int8_taps): behind each of the three epilogue
+// stores the four q bytes go to the site's image tensor — one 4-byte store at the site's start — and the f16 quadruple stored
+// beside them to the site's stream tensor, tap_site_bytes / 2 behind it (the place of a split pair's lo half); a mid site has
+// an image only, the last site — the store to a.y — a stream only.  Rows of real boards only.
+template <int C, int NT, int HEADS = 0, bool TAP = false>
 __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
     static_assert(HEADS == 0 || HEADS == 2, "0: the tower alone; 2: conv heads and decode inside");
+    static_assert(!TAP || HEADS == 0, "the tap instance is the tower alone");
     using L = GeoI8<C, NT>;
     constexpr int PF = L::PF, RS = L::RS, XRS = L::XRS, OT = L::OT, G = L::G;
     constexpr int X8 = L::Q_OFF + L::X8, Y8 = L::Q_OFF + L::Y8, Z8 = L::Q_OFF + L::Z8;
@@ -345,6 +350,17 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
     const int oc0 = wave * OT * 16 + kq * 4;
     auto x_off = [&](int ot, int nt) __attribute__((always_inline)) { return (nt * 16 + fr) * XRS + (oc0 + ot * 16) * 2; };
     auto q_off = [&](int ot, int nt) __attribute__((always_inline)) { return (nt * 16 + fr) * RS + L::chan_off(oc0 + ot * 16); };
+    // (TAP) this lane's four channels of a pixel row to the site's tensors: the image's q bytes, the stream's f16 values
+    auto tap_image = [&](int site, int ot, int nt, int q) __attribute__((always_inline)) {
+        tap_put(a, site, nt * 16 + fr < rows_valid, tap_elem(board0, a.hw, nt * 16 + fr, C, oc0 + ot * 16), q);
+    };
+    auto tap_stream = [&](int site, int ot, int nt, h16x4 xh) __attribute__((always_inline)) {
+        tap_put(a, site, nt * 16 + fr < rows_valid, tap_elem(board0, a.hw, nt * 16 + fr, C, oc0 + ot * 16), xh, a.tap_site_bytes / 2);
+    };
+    auto tap_site = [&](int site, int ot, int nt, int q, h16x4 xh) __attribute__((always_inline)) {
+        tap_image(site, ot, nt, q);
+        tap_stream(site, ot, nt, xh);
+    };
 
     // ---- stem in f16, exactly as the plain-f16 launch: 9 sc k-steps over the 32 sc (padded) input channels; conv + bias, no
     // activation (post_act.py:205).  Its epilogue writes X and X8 = quant(v, e_0) ----
@@ -387,6 +403,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
                 const f32x4 v = sacc[ot][nt];
                 *reinterpret_cast<h16x4 *>(lds + x_off(ot, nt)) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
                 *reinterpret_cast<int *>(lds + X8 + q_off(ot, nt)) = quant4(v, qs);
+                if constexpr (TAP) tap_site(0, ot, nt, quant4(v, qs), h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]});
             }
     }
     __syncthreads();
@@ -555,6 +572,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
                 }
                 if (!is_b) {
                     *reinterpret_cast<int *>(lds + Y8 + q_off(ot, nt)) = quant4(v, qs);
+                    if constexpr (TAP) tap_image(layer, ot, nt, quant4(v, qs));
                     continue;
                 }
                 const h16x4 rx = *reinterpret_cast<const h16x4 *>(lds + x_off(ot, nt));
@@ -563,6 +581,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
                 if (layer != layers) {
                     *reinterpret_cast<h16x4 *>(lds + x_off(ot, nt)) = h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
                     *reinterpret_cast<int *>(lds + X8 + q_off(ot, nt)) = quant4(v, qs);
+                    if constexpr (TAP) tap_site(layer, ot, nt, quant4(v, qs), h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]});
                 } else {
                     // last layer: the final BN in f32 -> f16 rows of the tower output in global memory
                     v = v * ps + pt;
@@ -574,6 +593,7 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
                     if (r < rows_valid)
                         *reinterpret_cast<h16x4 *>(a.y + ((size_t)board0 * a.hw + r) * a.ldy + oc0 + ot * 16) =
                             h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]};
+                    if constexpr (TAP) tap_stream(layers, ot, nt, h16x4{(h16)v[0], (h16)v[1], (h16)v[2], (h16)v[3]});  // (the last site: what the launch hands on)
                 }
             }
         }
@@ -658,25 +678,30 @@ __global__ __launch_bounds__(256, 1) void kz_tower_resident_i8(I8Dev a) {
     }
 }
 
-template <int C, int NT, int HEADS = 0>
+template <int C, int NT, int HEADS = 0, bool TAP = false>
 void launch(const I8Dev &d, int grid, hipStream_t stream) {
     static_assert(GeoI8<C, NT>::LDS_BYTES == i8_own_lds_bytes(C, NT), "the host's restatement of the LDS geometry");
     constexpr int LDS = GeoI8<C, NT>::LDS_BYTES + (HEADS == 2 ? i8_tail_scratch_bytes(C, NT) : 0);
     static_assert(LDS <= 160 * 1024, "LDS budget");
-    allow_dynamic_lds<kz_tower_resident_i8<C, NT, HEADS>>(LDS);
-    kz_tower_resident_i8<C, NT, HEADS><<<grid, 256, LDS, stream>>>(d);
+    allow_dynamic_lds<kz_tower_resident_i8<C, NT, HEADS, TAP>>(LDS);
+    kz_tower_resident_i8<C, NT, HEADS, TAP><<<grid, 256, LDS, stream>>>(d);
 }
 
-// The instance of (channels, nt) among I8_ROWS, with the conv heads' tail if asked for: no such row = no launch (false)
+// The instance of (channels, nt) among I8_ROWS, with the conv heads' tail if asked for: no such row = no launch (false).
+// tap: the tap instance, which every plain row has and no other
 template <size_t... I>
-bool launch_row(std::index_sequence<I...>, int channels, int nt, bool conv_heads, const I8Dev &d, int grid, hipStream_t stream) {
+bool launch_row(std::index_sequence<I...>, int channels, int nt, bool conv_heads, bool tap, const I8Dev &d, int grid, hipStream_t stream) {
     return (... || [&] {
         constexpr I8Row R = I8_ROWS[I];
         if (R.c != channels || R.nt != nt) return false;
         if (!conv_heads) {
-            if constexpr (R.plain) launch<R.c, R.nt>(d, grid, stream);
+            if constexpr (R.plain) {
+                if (tap) launch<R.c, R.nt, 0, true>(d, grid, stream);
+                else launch<R.c, R.nt>(d, grid, stream);
+            }
             return R.plain;
         }
+        if (tap) return false;
         if constexpr (R.conv_heads) launch<R.c, R.nt, 2>(d, grid, stream);
         return R.conv_heads;
     }());
@@ -766,7 +791,8 @@ bool launch_tower_i8(const Tower32Args &t, const float *mult, const float *qscal
     d.w_ = t.w;
     d.hw = t.h * t.w;
     d.stem_chunks = (t.c_in + 31) / 32;
-    const int nt = i8_tiles(d.hw, t.channels, t.wide ? t.batch : 0, t.wide_cap);  // (wide_cap != 0: the heads are inside)
+    // (wide_cap != 0: the heads are inside.  A tap launch runs the level of the batch whose geometry is tapped, on however few boards)
+    const int nt = i8_tiles(d.hw, t.channels, t.wide ? (t.taps.base && t.tap_wide_batch ? t.tap_wide_batch : t.batch) : 0, t.wide_cap);
     if (nt_out) *nt_out = nt;
     if (!nt) return false;
     d.nb = nt * 16 / d.hw;
@@ -785,7 +811,12 @@ bool launch_tower_i8(const Tower32Args &t, const float *mult, const float *qscal
         d.nonfinite_flag = hd.nonfinite_flag; d.epoch = hd.epoch;
         d.dec = decode_dev(hd.decode, true, hd.policy_len);
     }
-    return launch_row(std::make_index_sequence<std::size(I8_ROWS)>{}, t.channels, nt, conv_heads, d, grid, stream);
+    if (t.taps.base) {  // (in the words of the heads' two outputs: a tap launch has no heads)
+        if (conv_heads) return false;
+        d.tap_base = t.taps.base;
+        d.tap_site_bytes = t.taps.site_bytes;
+    }
+    return launch_row(std::make_index_sequence<std::size(I8_ROWS)>{}, t.channels, nt, conv_heads, t.taps.base != nullptr, d, grid, stream);
 }
 
 }  // namespace kz

@@ -13,6 +13,11 @@
 // rule, kz_tower_f32.hip): f64 adds for the sums, integer adds for the counts, a 64-bit integer max on the bit pattern of a
 // non-negative f64 for the maxima.  The maxima and the counts do not depend on the order of the waves; the f64 sums do in
 // their last bits (exact where every square is an integer below 2^53).  Bandwidth-bound: every byte is read once.
+//
+// TapFormat::i8 (kz_model_int8_error_profile): the tap is an int8 image of an int8 tower, eight channels one 8-byte load,
+// a = (float)q * 2^e_s (exact); q = -128 — the fill, which the contract never stores — counts as non-finite.  The same pass
+// counts |q| == 127 (at_clamp) and finite r with |r| * 2^-e_s >= 127.5 (ref_beyond: what an ideal int8 image of the exact
+// network would clamp, rne(127.5) = 128) into the two integers behind the site's records.
 #include <algorithm>
 
 #include "kz_kernels.hpp"
@@ -33,6 +38,14 @@ __device__ __forceinline__ void tap_chunk(const unsigned char *__restrict__ tap,
         for (int j = 0; j < 4; j++) {
             a[j] = v0[j];
             a[4 + j] = v1[j];
+        }
+    } else if constexpr (F == TapFormat::i8) {  // q as a float, unscaled; -128 as NaN
+        const uint2 v = *reinterpret_cast<const uint2 *>(tap + elem);
+        const unsigned w[2] = {v.x, v.y};
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const int q = (int)(signed char)((w[j >> 2] >> (8 * (j & 3))) & 0xffu);
+            a[j] = q == -128 ? __uint_as_float(0x7fc00000u) : (float)q;
         }
     } else if constexpr (F == TapFormat::bf16) {  // (a bf16 value is the upper half of its f32)
         const uint4 v = *reinterpret_cast<const uint4 *>(tap + elem * 2);
@@ -57,12 +70,14 @@ __device__ __forceinline__ void tap_chunk(const unsigned char *__restrict__ tap,
 template <TapFormat F>
 __global__ __launch_bounds__(256) void kz_tap_deviation(const unsigned char *__restrict__ tap, size_t lo_bytes, int tap_ld,
                                                         const float *__restrict__ ref, int ref_ld, size_t rows, int channels,
-                                                        TapDeviation *__restrict__ out) {
+                                                        TapDeviation *__restrict__ out, float scale = 1.0f, float inv_scale = 1.0f,
+                                                        unsigned long long *__restrict__ clamp_counts = nullptr) {
     const int used = (channels + 7) / 8;  // chunks of a row that hold a real channel
     const size_t total = rows * used;
     double sum_err = 0.0, sum_ref = 0.0;
     double max_err = 0.0, max_ref = 0.0;
     unsigned count = 0, nonfinite = 0;  // (a lane sees far fewer than 2^32 elements: launch_tap_deviation's grid)
+    unsigned at_clamp = 0, ref_beyond = 0;  // (TapFormat::i8 only)
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
         const size_t row = i / used;
         const int g = (int)(i - row * used), left = channels - g * 8;  // real channels in this chunk: >= 1
@@ -74,6 +89,11 @@ __global__ __launch_bounds__(256) void kz_tap_deviation(const unsigned char *__r
         for (int j = 0; j < 8; j++) {
             if (j >= left) break;
             const float r = j < 4 ? r0[j] : r1[j - 4];
+            if constexpr (F == TapFormat::i8) {
+                at_clamp += fabsf(a[j]) == 127.0f;
+                ref_beyond += (__float_as_uint(r) & 0x7f800000u) != 0x7f800000u && fabsf(r) * inv_scale >= 127.5f;
+                a[j] *= scale;
+            }
             // finite: the exponent field is not all ones
             const bool finite = (__float_as_uint(a[j]) & 0x7f800000u) != 0x7f800000u && (__float_as_uint(r) & 0x7f800000u) != 0x7f800000u;
             if (!finite) {
@@ -96,6 +116,10 @@ __global__ __launch_bounds__(256) void kz_tap_deviation(const unsigned char *__r
         max_ref = fmax(max_ref, __shfl_xor(max_ref, off));
         count += __shfl_xor(count, off);
         nonfinite += __shfl_xor(nonfinite, off);
+        if constexpr (F == TapFormat::i8) {
+            at_clamp += __shfl_xor(at_clamp, off);
+            ref_beyond += __shfl_xor(ref_beyond, off);
+        }
     }
     if ((threadIdx.x & 63) == 0) {
         if (count) {
@@ -106,6 +130,10 @@ __global__ __launch_bounds__(256) void kz_tap_deviation(const unsigned char *__r
             atomicAdd(&out->count, (unsigned long long)count);
         }
         if (nonfinite) atomicAdd(&out->nonfinite, (unsigned long long)nonfinite);
+        if constexpr (F == TapFormat::i8) {
+            if (at_clamp) atomicAdd(&clamp_counts[0], (unsigned long long)at_clamp);
+            if (ref_beyond) atomicAdd(&clamp_counts[1], (unsigned long long)ref_beyond);
+        }
     }
 }
 
@@ -123,7 +151,17 @@ void launch_tap_deviation(const void *tap, TapFormat format, size_t lo_bytes, in
         case TapFormat::f16: kz_tap_deviation<TapFormat::f16><<<grid, 256, 0, stream>>>(t, lo_bytes, tap_ld, ref, ref_ld, rows, channels, out); break;
         case TapFormat::split16: kz_tap_deviation<TapFormat::split16><<<grid, 256, 0, stream>>>(t, lo_bytes, tap_ld, ref, ref_ld, rows, channels, out); break;
         case TapFormat::bf16: kz_tap_deviation<TapFormat::bf16><<<grid, 256, 0, stream>>>(t, lo_bytes, tap_ld, ref, ref_ld, rows, channels, out); break;
+        case TapFormat::i8: break;  // (launch_tap_deviation_i8: it needs the site's exponent and the record's two counts)
     }
+}
+
+void launch_tap_deviation_i8(const void *tap, int tap_ld, int exponent, const float *ref, int ref_ld, size_t rows, int channels,
+                             Int8SiteDeviation *out, hipStream_t stream) {
+    const size_t total = rows * ((channels + 7) / 8);
+    if (!total) return;
+    const int grid = (int)std::min<size_t>((total + 2047) / 2048, 2048);
+    kz_tap_deviation<TapFormat::i8><<<grid, 256, 0, stream>>>(static_cast<const unsigned char *>(tap), 0, tap_ld, ref, ref_ld, rows, channels,
+                                                              &out->image, ldexpf(1.0f, exponent), ldexpf(1.0f, -exponent), &out->at_clamp);
 }
 
 }  // namespace kz

@@ -140,6 +140,11 @@ extern "C" {
     fn kz_model_tower_taps_path(model: *const c_void, max_batch: c_int, dtype: c_int, buf: *mut c_char, len: usize) -> c_int;
     fn kz_model_tower_taps(model: *const c_void, device: c_int, max_batch: c_int, dtype: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, site_first: c_int, n_sites: c_int, out: *mut f32) -> c_int;
     fn kz_model_error_profile(model: *const c_void, device: c_int, max_batch: c_int, dtype: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, out: *mut c_void) -> c_int;
+    // int8 taps and error profile: every stored int8 image of the int8 tower of (max_batch, dtype 4 / 5 / 8), the f16 stream value
+    // beside it, and per site their deviation from exact f32 with the clamp counts, out KzInt8SiteError [n_sites]
+    fn kz_model_int8_taps_path(model: *const c_void, max_batch: c_int, dtype: c_int, buf: *mut c_char, len: usize) -> c_int;
+    fn kz_model_int8_taps(model: *const c_void, device: c_int, max_batch: c_int, dtype: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, site_first: c_int, n_sites: c_int, image_out: *mut c_void, stream_out: *mut f32) -> c_int;
+    fn kz_model_int8_error_profile(model: *const c_void, device: c_int, max_batch: c_int, dtype: c_int, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, out: *mut c_void) -> c_int;
     fn kz_engine_max_batch(engine: *const c_void) -> c_int;
     fn kz_engine_eval_dense(engine: *mut c_void, input_nchw: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
     fn kz_engine_eval_packed(engine: *mut c_void, bits: *const u8, bits_stride: usize, scalars_in: *const f32, batch: c_int, scalars_out: *mut f32, policy_out: *mut f32) -> c_int;
@@ -410,6 +415,37 @@ impl HipModel {
         out
     }
 
+    /// The kernel an int8 tap call runs, "tower_resident_i8" or "board_conv_i8" (`kz_model_int8_taps_path`; no GPU).
+    pub fn int8_taps_path(&self, max_batch: usize, dtype: i32) -> String {
+        let mut buf = [0 as c_char; 64];
+        check(unsafe { kz_model_int8_taps_path(self.ptr, max_batch as c_int, dtype as c_int, buf.as_mut_ptr(), buf.len()) });
+        unsafe { CStr::from_ptr(buf.as_ptr()) }.to_string_lossy().into_owned()
+    }
+
+    /// What the int8 tower of an engine of (max_batch, dtype) stores at the range sites `site_first .. site_first + n_sites` on
+    /// these packed boards (`kz_model_int8_taps`): the images' q and the f16 stream values, `[n_sites][batch][C][H][W]` flat each.
+    pub fn int8_taps(&self, device: HipDevice, max_batch: usize, dtype: i32, bits: &[u8], bits_stride: usize, scalars_in: &[f32], batch: usize, site_first: usize, n_sites: usize) -> (Vec<i8>, Vec<f32>) {
+        assert!(bits.len() >= batch * bits_stride && scalars_in.len() >= batch * self.info.input_scalar_channels.max(0) as usize);
+        let per_site = batch * self.info.tower_channels as usize * self.info.board_h as usize * self.info.board_w as usize;
+        let (mut image, mut stream) = (vec![0i8; n_sites * per_site], vec![0f32; n_sites * per_site]);
+        check(unsafe {
+            kz_model_int8_taps(self.ptr, device.0 as c_int, max_batch as c_int, dtype as c_int, bits.as_ptr(), bits_stride, scalars_in.as_ptr(), batch as c_int, site_first as c_int, n_sites as c_int, image.as_mut_ptr() as *mut c_void, stream.as_mut_ptr())
+        });
+        (image, stream)
+    }
+
+    /// Per range site, the error of that int8 tower's images and stream values against exact f32 and the clamp counts (`kz_model_int8_error_profile`).
+    pub fn int8_error_profile(&self, device: HipDevice, max_batch: usize, dtype: i32, bits: &[u8], bits_stride: usize, scalars_in: &[f32], batch: usize) -> Vec<KzInt8SiteError> {
+        let mut n = 0;
+        check(unsafe { kz_model_range_sites(self.ptr, &mut n) });
+        assert!(bits.len() >= batch * bits_stride && scalars_in.len() >= batch * self.info.input_scalar_channels.max(0) as usize);
+        let mut out = vec![KzInt8SiteError::default(); n as usize];
+        check(unsafe {
+            kz_model_int8_error_profile(self.ptr, device.0 as c_int, max_batch as c_int, dtype as c_int, bits.as_ptr(), bits_stride, scalars_in.as_ptr(), batch as c_int, out.as_mut_ptr() as *mut c_void)
+        });
+        out
+    }
+
     /// Per range site, how far that tower's stored tensors are from exact f32 on these boards (`kz_model_error_profile`).
     pub fn error_profile(&self, device: HipDevice, max_batch: usize, dtype: i32, bits: &[u8], bits_stride: usize, scalars_in: &[f32], batch: usize) -> Vec<KzSiteError> {
         let mut n = 0;
@@ -544,6 +580,18 @@ pub struct KzSiteError {
     pub max_abs_ref: f64,
     pub count: u64,
     pub nonfinite: u64,
+}
+
+/// `kz_int8_site_error` (include/kz_hip.h): one range site of `HipModel::int8_error_profile`, 120 bytes.
+#[repr(C)]
+#[derive(Debug, Default, Copy, Clone, PartialEq)]
+pub struct KzInt8SiteError {
+    pub image: KzSiteError,
+    pub stream: KzSiteError,
+    pub at_clamp: u64,
+    pub ref_beyond: u64,
+    pub exponent: i32,
+    pub reserved: i32,
 }
 
 /// The bins of `HipModel::range_histogram` (include/kz_hip.h): 0 is +-0, 95 inf or NaN, b in 1..=94 the binade E = b - 51
