@@ -398,10 +398,18 @@ def _lin(x, w, spoil=None, mags=True):
 
 
 def _conv(rep, name, x, w, b, spoil=None):
-    """Convolution or, for 2-D w, linear layer, with what the report measures of it.  spoil: {"tap": (dy, dx)} (`_lin`), or
-    {"fragment": (tile, (dy, dx), chunk)}: that weight fragment loses its lo halves."""
+    """Convolution or, for 2-D w, linear layer, with what the report measures of it.  spoil: {"tap": (dy, dx)} (`_lin`),
+    {"fragment": (tile, (dy, dx), chunk)}: that weight fragment loses its lo halves, or {"chunk": k}: what a stale image chunk
+    does in a kernel that stages its input 64 channels at a time — on the board's edge squares channels 64 k .. 64 k + 63 are read
+    from chunk k - 1, for a k that is neither the first chunk nor the last (ValueError where the layer has no such chunk)."""
     w, b = w.astype(np.float64), b.astype(np.float64)
     spoil = spoil or {}
+    if "chunk" in spoil:
+        k, chunks = spoil["chunk"], x.shape[1] // 64
+        if x.ndim != 4 or not 1 <= k <= chunks - 2:
+            raise ValueError(f"{name}: {chunks} chunks of 64 input channels, none at {k} that is neither the first nor the last")
+        x = x.copy()
+        x[:, 64 * k:64 * k + 64] = np.where(_edge(x.shape[2], x.shape[3]), x[:, 64 * k - 64:64 * k], x[:, 64 * k:64 * k + 64])
     if "fragment" in spoil:
         tile, (dy, dx), chunk = spoil["fragment"]
         w = w.copy()
@@ -440,7 +448,11 @@ def reference(t, meta, x, revive=False, spoil=None, exact=True, rounding=None):
     head's intermediates under the oracle's trace names.  revive (the generator's pass): t is changed in place — the bias
     in front of a ReLU is raised by whole units wherever the channel would be positive on too few positions.
     spoil = {"layer": name, "tap": (dy, dx)} or {"layer": name, "fragment": (tile, (dy, dx), chunk)}: one wrong lo address
-    (`_conv`).  exact=False: any network (random weights), nothing measured or asserted.
+    (`_conv`).  Three more, the faults of a kernel that stages 64 input channels at a time and writes 64 output channels per
+    workgroup (tests/board_nets.py): {"layer": name, "chunk": k} (`_conv`); {"block": i, "quarter": q}: block i's residual on
+    output channels 64 q .. 64 q + 63, q >= 2, is read from quarter q - 2; {"block": i, "stale": True}: block i's residual is
+    block i - 1's input, what a rotation of activation buffers that never wraps would leave there.  Each raises ValueError on a
+    network that has no such chunk, quarter or block.  exact=False: any network (random weights), nothing measured or asserted.
     rounding = (sites, fn): what a launch that rounds does (module docstring, "rounding").  At every `store` site named in
     sites the value is replaced by fn(value) and carried on, and so are the weights of every layer named there; fn is one
     function, or {site: function} with None as the key of the rest.  Two more sites exist for the mutants only: "tower.i.branch",
@@ -480,19 +492,37 @@ def reference(t, meta, x, revive=False, spoil=None, exact=True, rounding=None):
     b = x.shape[0]
 
     def conv(p, v):
-        return _conv(rep, p, v, rnd(p, t[p + ".weight"]), t[p + ".bias"], spoil if spoil and spoil["layer"] == p else None)
+        return _conv(rep, p, v, rnd(p, t[p + ".weight"]), t[p + ".bias"], spoil if spoil and spoil.get("layer") == p else None)
 
+    def residual(i, cur, before):
+        """Block i's residual: its input — or what a wrong residual address reads (spoil["block"] == i)."""
+        if not spoil or spoil.get("block") != i:
+            return cur
+        if "quarter" in spoil:
+            q, quarters = spoil["quarter"], cur.shape[1] // 64
+            if not 2 <= q < quarters:
+                raise ValueError(f"block {i}: {quarters} output-channel quarters of 64, none at {q} with a quarter two below it")
+            res = cur.copy()
+            res[:, 64 * q:64 * q + 64] = cur[:, 64 * q - 128:64 * q - 64]
+            return res
+        if before is None:
+            raise ValueError(f"block {i}: no block in front of it whose input a stale buffer could hold")
+        return before
+
+    if spoil and "block" in spoil and not 1 <= spoil["block"] <= depth:
+        raise ValueError(f"block {spoil['block']}: the tower has {depth}")
     x = rnd("input", np.asarray(x, np.float64))
     rep.store("input", x)
     cur = rnd("tower.0", conv("common.tower.0", x))  # stem: no BN, no ReLU
     acts["tower.0"] = cur
     rep.store("tower.0", cur)
+    before = None  # the previous block's input
     for i in range(1, depth + 1):
         p = f"common.tower.{i}.seq."
         mid = rnd(f"tower.{i}.mid", relu(_bn(t, p + "1", conv(p + "0", cur), eps), p + "1.bias"))
         acts[f"tower.{i}.mid"] = mid
         rep.store(f"tower.{i}.mid", mid)
-        cur = rnd(f"tower.{i}", cur + rnd(f"tower.{i}.branch", relu(_bn(t, p + "4", conv(p + "3", mid), eps), p + "4.bias")))  # the residual after the ReLU
+        before, cur = cur, rnd(f"tower.{i}", residual(i, cur, before) + rnd(f"tower.{i}.branch", relu(_bn(t, p + "4", conv(p + "3", mid), eps), p + "4.bias")))  # the residual after the ReLU
         acts[f"tower.{i}"] = cur
         rep.store(f"tower.{i}", cur)
     common = rnd(f"tower.{depth + 1}", _bn(t, f"common.tower.{depth + 1}", cur, eps))

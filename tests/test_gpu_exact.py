@@ -10,6 +10,11 @@ Every engine runs with the fully dense layer at each position of its network and
 halves are all zero on those networks, run the wide family as well, with the exact-f32 engines of the same networks beside them.  Launches are ragged on
 purpose — boards per workgroup x k + 1 boards, and one board alone; the instances that need a full chip before the
 engine picks them get that many boards, the thirteen distinct ones repeated.
+
+The board-tile kernel runs here on three networks of depth 1 and at most 128 channels, Go 13x13 in f16 only: one or two
+chunks, one or two output-channel quarters, one setting of most of its runtime geometry.  tests/test_gpu_board_exact.py holds
+both of its instances to the bit on a table chosen by geometry (tests/board_nets.py), the split16 engines of go9_1x256 and
+go13_1x128 with their wide variants among them.
 """
 import os
 
