@@ -4,6 +4,8 @@
 #pragma once
 #include <cstdint>
 
+#include "kz_tower_mfma_order.hpp"  // the order of a k-step's MFMAs, which part 2 (kz_tower_boundary_body.hpp) walks
+
 #ifdef __HIP__
 #define KZ_BOUNDARY_FN __host__ __device__ inline
 #else

@@ -1,7 +1,9 @@
 // kz_tower_boundary_body.hpp — included INSIDE kz_tower_resident's body (kz_tower.hip), behind conv_3x3_lines: the 3x3
 // layer of the line-tile instances (two boards per workgroup, not PREV, not TAP) with a shorter serial section between
-// two layers.  The k-steps, their order, the MFMA order inside a k-step, the weight stream, the fragment reads and the ring
-// are conv_3x3_lines'; every sum is the same sum in the same order.  What differs is work that stood between two layers
+// two layers.  The k-steps, their order, the weight stream, the fragment reads and the ring are conv_3x3_lines'; every sum
+// is the same sum in the same order.  Inside a k-step the MFMAs walk the tiles in the boustrophedon of
+// kz_tower_mfma_order.hpp (conv_3x3_lines: ascending), which changes fewer operand registers from one MFMA to the next and
+// no sum: every accumulator still receives one MFMA per k-step.  What else differs is work that stood between two layers
 // with the matrix pipe idle:
 //  * no accumulator initialisation.  The first MFMA into an accumulator takes the bias registers as its C operand: in the
 //    first super-step (dx = -1, chunk 0) tiles 1..7 at dy = -1 and tile 0 at dy = 0.  bias + a*b in one instruction is what
@@ -17,6 +19,8 @@
 // v_accvgpr moves in the k-loop: tools/layer_boundary_isa.py).  Unrolled there is neither, the row addresses of a dx are
 // compile-time taps, and the compiler itself starts reading finished accumulators under the last MFMAs.
 constexpr bool LEAN = L::LINE_TILES && !PREV && !TAP;
+// the three tap rows' tile ranges, as the MFMA order takes them
+constexpr kz_mfma_order::Rows ORDER_ROWS{3, {tile_lo(-1), tile_lo(0), tile_lo(1)}, {tile_hi(-1), tile_hi(0), tile_hi(1)}, {-1, 0, 1}};
 int Tl[MT];  // this lane's fragment rows of the coming layer's first dx (dx = -1)
 if constexpr (LEAN) tap_rows(0, -1, L::X_OFF, Tl);
 
@@ -46,15 +50,15 @@ auto conv_3x3_lean = [&](int src_off, int next_off, int next_bias_row) __attribu
                 // this k-step's weight fragments were loaded PF k-steps ago
                 h16x8 af[4];
                 ring_take(stage, af);
-                // (output-channel tile outermost: the weight fragment is held for all pixel tiles)
-#pragma unroll
-                for (int nt = 0; nt < 4; nt++)
-#pragma unroll
-                    for (int mt = 0; mt < MT; mt++)
-                        if (mt >= lo && mt < hi) {
-                            const bool opens = FIRST && (mt == 0 ? i == 1 : i == 0);  // the accumulator's first MFMA
-                            acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[nt], bf[cur][mt + dy], opens ? bias_next[nt] : acc[nt][mt], 0, 0, 0);
-                        }
+                // (output-channel tile outermost: the weight fragment is held for all pixel tiles; the tiles in the
+                // boustrophedon of kz_tower_mfma_order.hpp, so that one MFMA and the next differ in one operand register)
+                static_for<0, 4 * nt_>([&](auto j_tag) __attribute__((always_inline)) {
+                    constexpr kz_mfma_order::Pos p = kz_mfma_order::at(ORDER_ROWS, i, decltype(j_tag)::value);
+                    constexpr int nt = p.nt, mt = p.mt;
+                    constexpr bool opens = FIRST && (mt == 0 ? i == 1 : i == 0);  // the accumulator's first MFMA, wherever it stands in the order
+                    if constexpr (LEAN)  // (the other instances never call this layer; their tiles are not lines)
+                        acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[nt], bf[cur][mt + dy], opens ? bias_next[nt] : acc[nt][mt], 0, 0, 0);
+                });
                 constexpr int n_bias = FIRST && i == 2 ? 4 : 0;
                 if constexpr (n_bias != 0) fetch_bias(next_bias_row);
                 // issue order: the 4 ring refills (and the 4 bias loads) behind the first MFMAs of the k-step; the 8
